@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the DSV2 encode hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: it sets up, warms up, times exactly K steps, writes the last step's outputs
+when --dump-outputs is given, and prints the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = the mean
+wall time of one timed step).  Its pictures are made on the GPU (benchparts/synth_gpu.py, the bytes of the package's
+generator).  Everything else described below -- the parity checks, the stage-timing pass and its roofline, the CPU
+baselines, the decoder, the other configurations and legs -- runs only with --full.
 
 Headline workload (BASELINE.json north star): synthetic 1920x1080 4:2:0, -qp=60 -gop=48, CRF, effort 10
 (quarter-pel + EPRM + in-loop filters).  Every rank drives S independent closed-GOP streams on its GPU -- the
@@ -17,11 +23,11 @@ finished packets in host memory.  The streams' GOP phases are staggered (stream 
 before the others, in an untimed pre-roll), so every step -- and any window of steps -- carries the
 steady-state share of intra pictures (1/48 of the streams per step) instead of one all-intra step per GOP.
 
-Bit-exactness is checked inside the run: a number of streams (two per lockstep group) are re-encoded by the
+With --full, bit-exactness is checked inside the run: a number of streams (two per lockstep group) are re-encoded by the
 real reference (oracle/_ref, CPU) and compared byte for byte, and every stream has a twin with identical
 input in ANOTHER lockstep group whose packets must be identical over the whole run.  A mismatch is fatal.
 
-One JSON line is printed by rank 0: frames/s aggregated over all ranks (weak scaling), the roofline object of
+One JSON line is printed by rank 0: frames/s aggregated over all ranks (weak scaling) and, with --full, the roofline object of
 the dominant kernel (HIP-event stage spans measured in a short extra pass of the same configuration), the CPU
 baselines (the real reference on one thread, and 8 processes on closed-GOP streams as in
 parallel_encode_yuv.sh) and -- at N=1 -- the other BASELINE.json configurations and the decoder.
@@ -71,8 +77,8 @@ def parse():
     ap.add_argument("--no-phase-align", action="store_true",
                     help="spread every step's intra pictures over all lockstep groups (round 2's layout) instead of giving them to one group")
     ap.add_argument("--host-cores", type=int, default=0,
-                    help="pin this rank to N of its usable cores (sched_setaffinity, after the pictures are generated and before anything "
-                         "touches the GPU) and size the library's worker pool from them: does the host side fit N cores per GPU?")
+                    help="pin this rank to N of its usable cores (sched_setaffinity, after any host-made pictures are generated and before "
+                         "anything touches the GPU) and size the library's worker pool from them: does the host side fit N cores per GPU?")
     ap.add_argument("--no-mix", action="store_true", help="every stream pans (round 2's content): no scene-cut / static / fast-motion classes")
     ap.add_argument("--no-batch-curve", action="store_true", help="skip the small-batch operating points (1 / 8 / 48 / 192 streams)")
     ap.add_argument("--only-batch-curve", action="store_true", help="of the extras, run only the small-batch operating points (experiments)")
@@ -86,12 +92,42 @@ def parse():
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed and run the segment gather even with ONE rank "
                     "(exercises RCCL init + collectives on a single GPU)")
     ap.add_argument("--no-multi-rank", action="store_true", help="skip the 8-ranks-on-one-GPU leg")
-    ap.add_argument("--decode-too", action="store_true", help="with --no-extras: still run the decode leg on the run's packets (the 2-host-core re-run uses it)")
+    ap.add_argument("--decode-too", action="store_true", help="with --full --no-extras: still run the decode leg on the run's packets (the 2-host-core re-run uses it)")
     ap.add_argument("--profile-steps", type=int, default=6)
     ap.add_argument("--gen-procs", type=int, default=-1,
-                    help="helper processes that generate the synthetic pictures (default: the usable cores, 1 under a profiler: "
-                         "forked children of a process with rocprofv3's tool library loaded can hang at exit)")
+                    help="with --full: helper processes that generate the synthetic pictures on the host (default: the usable cores, 1 under "
+                         "a profiler: forked children of a process with rocprofv3's tool library loaded can hang at exit)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the stage-timing pass and its roofline, the twin and reference parity "
+                         "checks, the CPU baselines, the decode leg and (at N=1) the other configurations and legs; the --no-* / --only-* "
+                         "options above choose among them.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed encode returned in its last step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
+
+
+DUMP_SAMPLE_STREAMS = 64      # streams whose packets --dump-outputs writes byte for byte (a fixed, seeded choice)
+DUMP_MAX_BYTES = 15 << 20     # packet bytes written at most (as float32: 60 MB; the rest of the dump is a few kB)
+
+
+def dump_outputs(path, last_step):
+    """--dump-outputs: what the timed encode returned in its last step (rank 0's streams).  last_step[s] = the packets stream s received.
+      packet_bytes_per_stream.npy   float64 [S]   bytes of every stream's packets
+      sample_streams.npy            float64 [k]   the sampled streams (seeded choice of DUMP_SAMPLE_STREAMS, ascending)
+      sample_packet_offsets.npy     float64 [k+1] where each sampled stream's bytes begin in sample_packets.npy
+      sample_packets.npy            float32 [n]   the sampled streams' packets, concatenated, byte values 0..255
+                                                  (cut at DUMP_MAX_BYTES; the offsets still count the full lengths)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    S = len(last_step)
+    per_stream = [b"".join(pk) for pk in last_step]
+    sample = np.sort(np.random.RandomState(20240611).choice(S, min(S, DUMP_SAMPLE_STREAMS), replace=False))
+    blob = b"".join(per_stream[s] for s in sample)
+    offsets = np.concatenate([[0], np.cumsum([len(per_stream[s]) for s in sample])])
+    np.save(os.path.join(path, "packet_bytes_per_stream.npy"), np.array([len(b) for b in per_stream], dtype=np.float64))
+    np.save(os.path.join(path, "sample_streams.npy"), sample.astype(np.float64))
+    np.save(os.path.join(path, "sample_packet_offsets.npy"), offsets.astype(np.float64))
+    np.save(os.path.join(path, "sample_packets.npy"), np.frombuffer(blob[:DUMP_MAX_BYTES], dtype=np.uint8).astype(np.float32))
 
 
 def spawn_ranks(args):
@@ -124,7 +160,7 @@ def main():
     # this rank's cores: those next to its GPU (before the picture generators fork, the pictures are pinned, the runtime starts)
     locality = bind_rank_to_gpu_node(local, world if "DSV2_FORCE_DEVICE" not in os.environ else 1)
     ncpu_box = usable_cpus()
-    extras = not args.no_extras and world == 1
+    extras = args.full and not args.no_extras and world == 1
 
     # ---- pictures first: forked generators must not inherit an initialised GPU runtime ----
     W_, H_, GOP, QP = 1920, 1080, 48, 60
@@ -153,10 +189,15 @@ def main():
         specs += [(3840, 2160, "420", 301 + k, 16) for k in range(2)]
         specs += [(1920, 800, "420", 401 + k, 16) for k in range(2)]
     t_gen = time.perf_counter()
+    # A plain run makes the headline's pictures on the GPU once it is up (benchparts/synth_gpu.py: the same bytes, in a fraction of the
+    # time); --full and a run under a profiler (whose kernel traces must hold the codec's kernels only) make them here, on the host.
+    vids = None
     under_profiler = under_profiler_()
-    gen_procs = args.gen_procs if args.gen_procs > 0 else (1 if under_profiler else max(1, min(16, ncpu_box // (1 if locality["bound"] else max(1, world)))))
-    vids = gen_videos(specs, gen_procs)
+    if args.full or under_profiler:
+        gen_procs = args.gen_procs if args.gen_procs > 0 else (1 if under_profiler else max(1, min(16, ncpu_box // (1 if locality["bound"] else max(1, world)))))
+        vids = gen_videos(specs, gen_procs)
     t_gen = time.perf_counter() - t_gen
+    host_pictures = vids is not None
 
     # ---- the host budget of this rank: pinned BEFORE the GPU runtime and the library's worker pool come up ----
     if args.host_cores > 0:
@@ -194,6 +235,9 @@ def main():
     bind_abi(hip, A)
     from conftest import load_pkg
     pkg = load_pkg()
+    if vids is None:
+        from benchparts.synth_gpu import DeviceVideo
+        vids = [DeviceVideo(*spec, dev=torch.device("cuda", local)) for spec in specs]
 
     S, K, Wm = max(1, args.streams), args.steps, args.warmup
     effort = int(os.environ.get("DSV2_BENCH_EFFORT", "10"))  # (experiments only: the headline is effort 10)
@@ -201,8 +245,10 @@ def main():
     mix = None if args.no_mix else MIX
     torch.cuda.synchronize()
     hbm_free0 = torch.cuda.mem_get_info()[0]
+    t_setup = time.perf_counter()
     run = EncodeRun(hip, A, torch, W_, H_, "420", QP, GOP, effort, S, args.groups, vids[:NV], not args.no_stagger, args.device_resident,
                     seeds=seeds, phase_align=align, mix=mix, timed_from=(GOP if not args.no_stagger else 0) + Wm, timed_steps=K)
+    t_setup = time.perf_counter() - t_setup
     G = run.G
     hip.dsv2hip_prof_enable(0)
     run.run(run.R + Wm)                   # untimed: GOP-phase pre-roll + warm-up (allocations, clocks)
@@ -212,11 +258,12 @@ def main():
     thr0 = thread_cpu() if os.environ.get("DSV2_BENCH_THREADS") else None
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     g_timed = run.step
-    census_on = bool(os.environ.get("DSV2_CENSUS"))
+    census_on = args.full and bool(os.environ.get("DSV2_CENSUS"))
     if census_on:  # a `make census` build (DSV2HIP_LIB): resident wavefront-time per kernel, measured inside the kernels under load
         torch.cuda.synchronize()
         hip.dsv2hip_census_reset()
     elapsed = run.run(K, dist, record=True)   # timed: exactly K steps
+    last_step = [run.out[s][-1] for s in range(S)] if args.dump_outputs else None  # per stream: the packets of the last timed step
     census = census_report(hip, elapsed) if census_on else None
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
     if thr0 is not None:  # where the host CPU of the timed region went, by thread (name, seconds)
@@ -235,7 +282,7 @@ def main():
 
     # stage profile: a few more steps of the SAME configuration with HIP-event stage timing on (not timed)
     stage_ms, stage_launches, stage_units, prof_steps = None, None, None, 0
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         hip.dsv2hip_prof_enable(1)
         run.run(args.profile_steps)
         if rank == 0:
@@ -249,7 +296,7 @@ def main():
         hip.dsv2hip_prof_enable(0)
 
     # ---- parity, part 1 (every rank): twin streams in different lockstep groups produced identical packets ----
-    pairs, bad = run.twins_equal()
+    pairs, bad = run.twins_equal() if args.full else (0, 0)
     if bad:
         sys.stderr.write("[bench] rank %d: %d of %d twin stream pairs DIFFER -- output is not deterministic\n" % (rank, bad, pairs))
         sys.exit(3)
@@ -348,12 +395,16 @@ def main():
                    "final_gather_s": round(gather_s, 3) if gather_s is not None else None, "final_gather_check": gather_ok,
                    "exchange_backend": (args.backend if dist is not None else None),
                    "per_rank": per_rank,
-                   "setup_s": {"generate_pictures": round(t_gen, 1)}},
-        "parity_checked": {"twin_pairs_equal": pairs_total, "twin_pairs": pairs_total,
-                           "note": "twins = same input, different lockstep group (and GOP phase), compared frame by frame over the run"},
+                   "setup_s": ({"generate_pictures": round(t_gen, 1)} if host_pictures else
+                               {"pictures_made_on_gpu_and_encoders": round(t_setup, 1)})},
     }
+    if args.full:
+        result["parity_checked"] = {"twin_pairs_equal": pairs_total, "twin_pairs": pairs_total,
+                                    "note": "twins = same input, different lockstep group (and GOP phase), compared frame by frame over the run"}
     if census is not None:
         result["census"] = census
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step)
     if stage_ms is not None and prof_steps:
         # per stage: span (HIP events on the group's stream) per stream-frame, and the algorithmic
         # bytes of SURVEY.md 8(d) moved in that span
@@ -416,14 +467,14 @@ def main():
 
     # ---- legs whose packets the reference will re-encode (collected now, compared at the end, all at once) ----
     checks = []
-    sel = run.pick_reference_streams(NREF_STREAMS)
+    sel = run.pick_reference_streams(NREF_STREAMS) if args.full else []
     for s in sel:
         checks.append(RefCheck("headline", run, s, NREF_FRAMES))
 
     # ---- the decoder on this run's packets (N = 1 only) ----
     # (the headline above is complete: whatever goes wrong below is reported beside it, never instead of it)
     dec_md5 = {}
-    if (extras or args.decode_too) and not args.only_batch_curve and not args.only_api_legs:
+    if (extras or (args.full and args.decode_too)) and not args.only_batch_curve and not args.only_api_legs:
         try:
             # The decode leg's shape: 256 decoders in 4 groups where the HOST parses the plane sections (16 cores' worth of parsing: more
             # decoders do not help); as many decoders as the run has streams (768) in 8 groups where the DEVICE parses them -- a section is one
@@ -505,7 +556,7 @@ def main():
 
     # ---- parity, part 2 + CPU baselines: the real reference (oracle/_ref) on the host cores ----
     rc = 0
-    if not args.no_cpu_baseline and os.path.exists(A.REF_SO):
+    if args.full and not args.no_cpu_baseline and os.path.exists(A.REF_SO):
         try:
             rc = reference_phase(result, checks, dec_md5, sel)
         except (OSError, AssertionError, ValueError) as e:  # the reference side failed: say so beside the headline

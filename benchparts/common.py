@@ -189,14 +189,26 @@ class EncodeRun:
         self.hip, self.A, self.torch = hip, A, torch
         self.w, self.h, self.fmt, self.qp, self.gop, self.effort = w, h, fmt, qp, gop, effort
         self.S, self.G = S, max(1, min(G, S))
-        self.P = len(videos[0][0])
+        # videos: per video a list of frames (bytes), or a synth_gpu.DeviceVideo that is made on the GPU right here
+        self.P = videos[0].P if hasattr(videos[0], "generate") else len(videos[0][0])
         self.NV, self.NF = len(videos), len(videos[0])
         self.seeds = list(seeds) if seeds is not None else [None] * self.NV
         self.device_resident = device_resident
         # pictures: one pinned host block per video (or, for the kernel-side figure, one HBM tensor)
         self.vbase, self._keep = [], []
         for frames in videos:
-            if device_resident:
+            if hasattr(frames, "generate"):
+                if device_resident:
+                    t = frames.generate(torch).reshape(-1)
+                    self._keep.append(t)
+                    self.vbase.append(t.data_ptr())
+                else:
+                    p = hip.dsv2hip_host_alloc(self.P * self.NF)
+                    assert p, "pinned host allocation failed"
+                    host = torch.frombuffer((C.c_uint8 * (self.P * self.NF)).from_address(p), dtype=torch.uint8)
+                    host.copy_(frames.generate(torch).reshape(-1))
+                    self.vbase.append(p)
+            elif device_resident:
                 import numpy as np
                 t = torch.from_numpy(np.frombuffer(b"".join(frames), dtype=np.uint8).copy()).cuda()
                 self._keep.append(t)
@@ -208,6 +220,8 @@ class EncodeRun:
                     C.memmove(p + i * self.P, fb, self.P)
                 self.vbase.append(p)
         torch.cuda.synchronize()
+        if any(hasattr(v, "generate") for v in videos):
+            torch.cuda.empty_cache()  # (the generator's scratch is not the encoders' HBM)
         G = self.G
         self.video = [(s // 2) % self.NV for s in range(S)]
         self.shift = [2 * (((s // 2) // self.NV) % max(1, self.NF // 2)) for s in range(S)]

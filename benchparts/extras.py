@@ -436,7 +436,7 @@ def multi_rank_one_gpu(args, fps_one_rank):
     every gathered segment verified) with the aggregate beside the one-rank 768-stream figure; (b) ONE rank forced through the
     distributed path on RCCL (--backend nccl): process-group init, all_reduce, all_gather and the gather on the hardware."""
     out = {}
-    base = [sys.executable, BENCH_PY, "--no-extras", "--no-profile", "--no-cpu-baseline"]
+    base = [sys.executable, BENCH_PY, "--full", "--no-extras", "--no-profile", "--no-cpu-baseline"]  # (--full: the twin check)
     env = dict(os.environ)
     env.pop("DSV2_HOST_THREADS", None)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
@@ -471,7 +471,7 @@ def multi_rank_one_gpu(args, fps_one_rank):
 def host_share(args, cores, fps_unrestricted):
     """the headline once more in a fresh process pinned to `cores` host cores (an 8-GPU node's share per rank)"""
     cmd = [sys.executable, BENCH_PY, "--host-cores", str(cores), "--streams", str(args.streams), "--groups", str(args.groups),
-           "--steps", str(min(args.steps, 24)), "--warmup", str(min(args.warmup, 4)), "--no-extras", "--no-cpu-baseline", "--no-profile", "--decode-too"]
+           "--steps", str(min(args.steps, 24)), "--warmup", str(min(args.warmup, 4)), "--full", "--no-extras", "--no-cpu-baseline", "--no-profile", "--decode-too"]
     if args.no_stagger:
         cmd.append("--no-stagger")
     if args.no_phase_align:

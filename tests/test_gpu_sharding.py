@@ -52,7 +52,7 @@ def test_bench_spawns_its_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(A.ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--streams", "8", "--groups", "2",
-                        "--steps", "3", "--warmup", "1", "--no-extras", "--profile-steps", "2"], env=env, stdout=subprocess.PIPE, text=True, timeout=1200)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--profile-steps", "2"], env=env, stdout=subprocess.PIPE, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)

@@ -18,7 +18,7 @@ parts=${PARTS:-trace pmc excl insts occ census}
 L0=k_hme_rows_l0
 for p in $parts; do case $p in
 trace)
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --gen-procs 1 --no-cpu-baseline --no-extras > $out/bench_traced.json 2> $out/trace.err
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --gen-procs 1 --no-cpu-baseline --no-extras > $out/bench_traced.json 2> $out/trace.err
     cp $out/trace/*/*_kernel_stats.csv $out/kernel_stats.csv
     gzip -c $out/trace/*/*_kernel_trace.csv > $out/kernel_trace.csv.gz
     rm -rf $out/trace ;;
@@ -48,6 +48,6 @@ occ)
     for o in digital-subband-video-2_amd/csrc/build/*.hip.o; do tools/codeobj.sh $o; done > $out/kernel_registers.txt 2>/dev/null ;;
 census)
     # residency UNDER LOAD, measured inside the kernels (csrc/prio.h; `make -C digital-subband-video-2_amd/csrc census` beforehand): no profiler, nothing serialised
-    DSV2HIP_LIB=$PWD/digital-subband-video-2_amd/libdsv2hip_census.so DSV2_CENSUS=1 timeout 900 python3 bench.py --no-cpu-baseline --no-extras --no-profile --steps 48 > $out/census.json 2> $out/census.err ;;
+    DSV2HIP_LIB=$PWD/digital-subband-video-2_amd/libdsv2hip_census.so DSV2_CENSUS=1 timeout 900 python3 bench.py --full --no-cpu-baseline --no-extras --no-profile --steps 48 > $out/census.json 2> $out/census.err ;;
 esac; done
 ls -la $out
