@@ -20,9 +20,60 @@ using namespace dsv2;
 
 namespace {
 
+// Device copy of one call's job records: the single-picture entry points run the batch drivers over a table of one record
+// (two for dsv_add_pred, three planes for dsv_extend_frame), so that they run the kernels the codec runs.  put() writes the
+// records on the caller's stream just before the launch that reads them; stream order keeps a later write from overtaking
+// an earlier launch.  One table per stream owner: the seam context (serialised by its mutex) and each plane set.
+struct JobTable {
+    static constexpr size_t kBytes = 1024;
+    void *d = nullptr;
+    template <class T> const T *put(hipStream_t s, const T *jobs, int n = 1)
+    {
+        if (n * sizeof(T) > kBytes) {
+            fatal("seam job table too small", __FILE__, __LINE__);
+        }
+        if (!d) {
+            HIPCHK(hipMalloc(&d, kBytes));
+        }
+        HIPCHK(hipMemcpyAsync(d, jobs, n * sizeof(T), hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
+        return (const T *) d;
+    }
+    void release()
+    {
+        if (d) {
+            HIPCHK(hipFree(d));
+            d = nullptr;
+        }
+    }
+};
+
+// the transform's record of one plane (the scratch images sized for it)
+PlaneJob sbt_job(const DPlane &pic, int32_t *coefs, const SbtScratch &sc, const uint8_t *bd, int q)
+{
+    PlaneJob j{};
+    j.pic = pic;
+    j.coefs = coefs;
+    for (int k = 0; k < 3; k++) {
+        j.t[k] = sc.t[k];
+    }
+    j.bd = bd;
+    j.q = q;
+    return j;
+}
+
+Planes3 planes_of(const DFrame &f)
+{
+    Planes3 p;
+    for (int c = 0; c < 3; c++) {
+        p.p[c] = f.p[c];
+    }
+    return p;
+}
+
 struct SeamCtx {
     std::mutex mu;
     hipStream_t stream = nullptr;
+    JobTable jobs;
     SbtScratch scratch;
     // cached device objects, re-created when the geometry changes
     DFrame frame[3];
@@ -196,12 +247,13 @@ void dsv_fwd_sbt(DSV_PLANE *src, DSV_COEFS *dst, DSV_FMETA *fm)
     DSV_PARAMS *p = fm->params;
     size_t n = (size_t) dst->width * dst->height;
     stage_plane_in(c, src, true);
-    DCoefs dc{c.get_coefs(n), dst->width, dst->height};
+    c.scratch.ensure(n);
     // (rows of the coefficient plane below the picture are taken as zero: they are for every
     // plane the codec creates -- the reference leaves the caller's values there, sbt.c:805)
-    BlockMap bm{c.put_blockdata(fm->blockdata, (size_t) p->nblocks_h * p->nblocks_v), p->nblocks_h, p->nblocks_v};
-    sbt_forward(c.stream, g_pstage.p, dc, c.scratch, fm->cur_plane, fm->isP, p->lossless, bm);
-    HIPCHK(hipMemcpyAsync(dst->data, dc.data, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+    const PlaneJob j = sbt_job(g_pstage.p, c.get_coefs(n), c.scratch, c.put_blockdata(fm->blockdata, (size_t) p->nblocks_h * p->nblocks_v), 0);
+    sbt_forward_jobs(c.stream, c.jobs.put(c.stream, &j), 1, dst->width, dst->height, fm->cur_plane, fm->isP, p->lossless, p->nblocks_h,
+                     p->nblocks_v, j.bd != nullptr);
+    HIPCHK(hipMemcpyAsync(dst->data, j.coefs, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
 }
 
@@ -213,10 +265,11 @@ void dsv_inv_sbt(DSV_PLANE *dst, DSV_COEFS *src, int q, DSV_FMETA *fm)
     DSV_PARAMS *p = fm->params;
     size_t n = (size_t) src->width * src->height;
     stage_plane_in(c, dst, false);
-    DCoefs dc{c.get_coefs(n), src->width, src->height};
-    HIPCHK(hipMemcpyAsync(dc.data, src->data, n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
-    BlockMap bm{c.put_blockdata(fm->blockdata, (size_t) p->nblocks_h * p->nblocks_v), p->nblocks_h, p->nblocks_v};
-    sbt_inverse(c.stream, g_pstage.p, dc, c.scratch, q, fm->cur_plane, fm->isP, p->lossless, bm);
+    c.scratch.ensure(n);
+    const PlaneJob j = sbt_job(g_pstage.p, c.get_coefs(n), c.scratch, c.put_blockdata(fm->blockdata, (size_t) p->nblocks_h * p->nblocks_v), q);
+    HIPCHK(hipMemcpyAsync(j.coefs, src->data, n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+    sbt_inverse_jobs(c.stream, c.jobs.put(c.stream, &j), 1, src->width, src->height, fm->cur_plane, fm->isP, p->lossless, p->nblocks_h,
+                     p->nblocks_v, j.bd != nullptr);
     HIPCHK(hipMemcpy2DAsync(dst->data, dst->stride, g_pstage.p.data, g_pstage.p.stride, dst->w, dst->h,
                             hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -255,12 +308,23 @@ void dsv_encode_plane(DSV_BS *bs, DSV_COEFS *src, int q, DSV_FMETA *fm)
     DCoefs dc{c.get_coefs(n), src->width, src->height};
     HIPCHK(hipMemcpyAsync(dc.data, src->data, n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
     QuantCfg cfg = make_quant_cfg(c, src, fm);
-    int32_t *qv = c.get_qv((size_t) g.base[10]);
-    quant_plane(c.stream, dc, qv, cfg, q);
-    c.comp.run(c.stream, qv, (size_t) g.base[10]);
+    const size_t nscan = (size_t) g.base[10];
+    // the quantiser tallies the nonzeros per tile into the compactor's counters, as in the encoder
+    int32_t *qv = c.get_qv(nscan);
+    const CompactJob cj = c.comp.job(qv, nscan);
+    PlaneJob j{};
+    j.coefs = dc.data;
+    j.qv = qv;
+    j.bd = cfg.bd;
+    j.mvs = cfg.mvs;
+    j.tile_count = cj.tile_count;
+    quant_steps(&j, cfg, q);
+    quant_jobs(c.stream, c.jobs.put(c.stream, &j), 1, cfg);
+    compact_jobs(c.stream, c.jobs.put(c.stream, &cj), 1, nscan);
+    int nsym = 0;
+    HIPCHK(hipMemcpyAsync(&nsym, cj.total, sizeof(int), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(src->data, dc.data, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
-    int nsym = *c.comp.h_total;
     std::vector<uint32_t> pos((size_t) nsym);
     std::vector<int32_t> val((size_t) nsym);
     if (nsym) {
@@ -295,7 +359,17 @@ int dsv_decode_plane(DSV_BS *bs, DSV_COEFS *dst, int q, DSV_FMETA *fm)
     if (nsym) {
         HIPCHK(hipMemcpyAsync(c.sym_pos, pos.data(), (size_t) nsym * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
         HIPCHK(hipMemcpyAsync(c.sym_val, val.data(), (size_t) nsym * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
-        dequant_plane(c.stream, dc, c.sym_pos, c.sym_val, seg_count, dst->data[0], cfg, q); // DC handled below
+        DequantJob j{};
+        j.coefs = dc.data;
+        j.pos = c.sym_pos;
+        j.val = c.sym_val;
+        for (int k = 0; k < 4; k++) {
+            j.seg[k] = seg_count[k];
+        }
+        j.bd = cfg.bd;
+        j.LL = dst->data[0]; // (the decoded DC is planted below)
+        dequant_steps(&j, cfg, q);
+        dequant_jobs(c.stream, c.jobs.put(c.stream, &j), 1, seg_count, cfg);
     }
     HIPCHK(hipMemcpyAsync(dst->data, dc.data, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -330,8 +404,13 @@ void dsv_sub_pred(DSV_MV *mv, DSV_PARAMS *p, DSV_FRAME *pred, DSV_FRAME *resd, D
     dframe_upload_full(dpred, pred, c.stream);
     dframe_upload_full(dres, resd, c.stream);
     dframe_upload_full(dref, ref, c.stream);
-    const DSV_MV *dmv = c.put_mvs(mv, (size_t) p->nblocks_h * p->nblocks_v);
-    mc_sub_pred(c.stream, dmv, make_mc_params(p), *dpred, *dres, *dref);
+    McJob j{};
+    j.mvs = c.put_mvs(mv, (size_t) p->nblocks_h * p->nblocks_v);
+    j.p = make_mc_params(p);
+    j.ref = planes_of(*dref);
+    j.pred = planes_of(*dpred);
+    j.res = planes_of(*dres);
+    mc_sub_pred_batch(c.stream, c.jobs.put(c.stream, &j), 1, j.p.nbh, j.p.nbv, j.p.blk_w, j.p.blk_h, j.p.hshift == 1 && j.p.vshift == 1);
     dframe_download_full(dpred, pred, c.stream);
     dframe_download_full(dres, resd, c.stream);
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -347,8 +426,13 @@ void dsv_add_res(DSV_MV *mv, DSV_FMETA *fm, int q, DSV_FRAME *resd, DSV_FRAME *p
     DFrame *dres = c.get_frame(1, resd->format, resd->width, resd->height);
     dframe_upload_full(dpred, pred, c.stream);
     dframe_upload_full(dres, resd, c.stream);
-    const DSV_MV *dmv = c.put_mvs(mv, (size_t) p->nblocks_h * p->nblocks_v);
-    mc_add_res(c.stream, dmv, make_mc_params(p), q, *dres, *dpred, do_filter, p->vidmeta->inter_sharpen);
+    McJob j{};
+    j.mvs = c.put_mvs(mv, (size_t) p->nblocks_h * p->nblocks_v);
+    j.p = make_mc_params(p);
+    j.f = make_filter_params(j.p, q, do_filter, p->vidmeta->inter_sharpen);
+    j.pred = planes_of(*dpred);
+    j.res = planes_of(*dres);
+    mc_add_res_batch(c.stream, c.jobs.put(c.stream, &j), 1, j.p.nbh, j.p.nbv, !p->lossless, dres->w, dres->h, j.p.blk_w, j.p.blk_h);
     dframe_download_full(dres, resd, c.stream);
     HIPCHK(hipStreamSynchronize(c.stream));
 }
@@ -365,8 +449,18 @@ void dsv_add_pred(DSV_MV *mv, DSV_FMETA *fm, int q, DSV_FRAME *resd, DSV_FRAME *
     dframe_upload_full(dout, out, c.stream);
     dframe_upload_full(dres, resd, c.stream);
     dframe_upload_full(dref, ref, c.stream);
-    const DSV_MV *dmv = c.put_mvs(mv, (size_t) p->nblocks_h * p->nblocks_v);
-    mc_add_pred(c.stream, dmv, make_mc_params(p), q, *dres, *dout, *dref, do_filter, p->vidmeta->inter_sharpen);
+    McJob j[2] = {}; // {ref, pred = out, res = resd}; the filters' {res = out}
+    j[0].mvs = c.put_mvs(mv, (size_t) p->nblocks_h * p->nblocks_v);
+    j[0].p = make_mc_params(p);
+    j[0].f = make_filter_params(j[0].p, q, do_filter, p->vidmeta->inter_sharpen);
+    j[0].ref = planes_of(*dref);
+    j[0].pred = planes_of(*dout);
+    j[0].res = planes_of(*dres);
+    j[1] = j[0];
+    j[1].res = j[1].pred;
+    const McJob *tab = c.jobs.put(c.stream, j, 2);
+    mc_add_pred_batch(c.stream, tab, tab + 1, 1, j[0].p.nbh, j[0].p.nbv, !p->lossless, dout->w, dout->h, j[0].p.blk_w, j[0].p.blk_h,
+                      j[0].p.hshift == 1 && j[0].p.vshift == 1);
     dframe_download_full(dout, out, c.stream);
     HIPCHK(hipStreamSynchronize(c.stream));
 }
@@ -380,8 +474,12 @@ void dsv_intra_filter(int q, DSV_PARAMS *p, DSV_FMETA *fm, int cpl, DSV_PLANE *d
     std::lock_guard<std::mutex> lk(c.mu);
     c.init();
     stage_plane_in(c, dp, true);
-    const uint8_t *dbd = c.put_blockdata(fm->blockdata, (size_t) p->nblocks_h * p->nblocks_v);
-    intra_filter_luma(c.stream, dbd, make_mc_params(p), q, g_pstage.p);
+    McJob j{};
+    j.bd = c.put_blockdata(fm->blockdata, (size_t) p->nblocks_h * p->nblocks_v);
+    j.p = make_mc_params(p);
+    j.f = make_filter_params(j.p, q, 1, 0);
+    j.res.p[0] = g_pstage.p;
+    intra_filter_batch(c.stream, c.jobs.put(c.stream, &j), 1, g_pstage.p.w, g_pstage.p.h);
     HIPCHK(hipMemcpy2DAsync(dp->data, dp->stride, g_pstage.p.data, g_pstage.p.stride, dp->w, dp->h, hipMemcpyDeviceToHost,
                             c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -420,7 +518,8 @@ DSV_MV *dsv_intra_analysis(DSV_FRAME *src, DSV_PARAMS *p)
     ap.scale = 2 * spatial_psy_factor(p->blk_w, p->blk_h, p->nblocks_h, p->nblocks_v, -1);
     DSV_MV *host = (DSV_MV *) dsv_alloc((int) (nb * sizeof(DSV_MV)));
     c.put_mvs(host, nb); // sizes the device field (contents are overwritten by the kernel)
-    intra_analysis(c.stream, *d, ap, c.mvs);
+    const IntraJob j{planes_of(*d), c.mvs};
+    intra_analysis_batch(c.stream, c.jobs.put(c.stream, &j), 1, ap);
     HIPCHK(hipMemcpyAsync(host, c.mvs, nb * sizeof(DSV_MV), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
     return host;
@@ -507,7 +606,7 @@ DSV_FRAME *dsv_extend_frame(DSV_FRAME *frame)
     c.init();
     DFrame *d = c.get_frame(0, frame->format, frame->width, frame->height);
     dframe_upload(d, frame, c.stream);
-    extend_frame(c.stream, *d, false);
+    extend_planes(c.stream, c.jobs.put(c.stream, d->p, 3), 3, d->p[0].w, d->p[0].h); // (luma bounds every plane)
     dframe_download_full(d, frame, c.stream);
     HIPCHK(hipStreamSynchronize(c.stream));
     return frame;
@@ -526,7 +625,7 @@ DSV_FRAME *dsv_extend_frame_luma(DSV_FRAME *frame)
     const DSV_PLANE *hp = &frame->planes[0];
     HIPCHK(hipMemcpy2DAsync(d->p[0].data, d->p[0].stride, hp->data, hp->stride, hp->w, hp->h, hipMemcpyHostToDevice,
                             c.stream));
-    extend_plane(c.stream, d->p[0]);
+    extend_planes(c.stream, c.jobs.put(c.stream, &d->p[0]), 1, d->p[0].w, d->p[0].h);
     HIPCHK(hipMemcpy2DAsync(hp->data - (size_t) hp->stride * kBorder - kBorder, hp->stride, d->alloc + d->plane_off[0],
                             d->p[0].stride, hp->w + 2 * kBorder, hp->h + 2 * kBorder, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -565,7 +664,8 @@ void dsv_ds2x_frame_luma(DSV_FRAME *dst, DSV_FRAME *src)
         HIPCHK(hipMemcpy2DAsync(s->p[0].data, s->p[0].stride, sp->data, sp->stride, sp->w, sp->h, hipMemcpyHostToDevice,
                                 c.stream));
     }
-    ds2x_luma(c.stream, s->p[0], d->p[0]);
+    const PlanePair pp{s->p[0], d->p[0]}; // (both planes from dframe_alloc: the 16-byte alignment k_ds2x4 reads with)
+    ds2x_planes4(c.stream, c.jobs.put(c.stream, &pp), 1, pp.dst.w, pp.dst.h);
     HIPCHK(hipMemcpy2DAsync(dp->data, dp->stride, d->p[0].data, d->p[0].stride, dp->w, dp->h, hipMemcpyDeviceToHost,
                             c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
@@ -575,6 +675,7 @@ void dsv_ds2x_frame_luma(DSV_FRAME *dst, DSV_FRAME *src)
 
 struct dsv2hip_planeset {
     hipStream_t stream;
+    JobTable jobs; // (its own: a plane set's calls run on its stream without the seam's lock)
     DFrame pic;
     int32_t *coefs[3];
     int cw[3], ch[3];
@@ -615,6 +716,7 @@ void dsv2hip_planeset_destroy(dsv2hip_planeset *ps)
         HIPCHK(hipFree(ps->coefs[c]));
     }
     ps->scratch.release();
+    ps->jobs.release();
     if (ps->bd) {
         HIPCHK(hipFree(ps->bd));
     }
@@ -653,15 +755,15 @@ int dsv2hip_planeset_set_blockdata(dsv2hip_planeset *ps, const uint8_t *blockdat
 
 int dsv2hip_planeset_fwd_sbt(dsv2hip_planeset *ps, int c, int isP, int lossless)
 {
-    sbt_forward(ps->stream, ps->pic.p[c], DCoefs{ps->coefs[c], ps->cw[c], ps->ch[c]}, ps->scratch, c, isP, lossless,
-                BlockMap{ps->bd, ps->nbh, ps->nbv});
+    const PlaneJob j = sbt_job(ps->pic.p[c], ps->coefs[c], ps->scratch, ps->bd, 0);
+    sbt_forward_jobs(ps->stream, ps->jobs.put(ps->stream, &j), 1, ps->cw[c], ps->ch[c], c, isP, lossless, ps->nbh, ps->nbv, ps->bd != nullptr);
     return 0;
 }
 
 int dsv2hip_planeset_inv_sbt(dsv2hip_planeset *ps, int c, int q, int isP, int lossless)
 {
-    sbt_inverse(ps->stream, ps->pic.p[c], DCoefs{ps->coefs[c], ps->cw[c], ps->ch[c]}, ps->scratch, q, c, isP, lossless,
-                BlockMap{ps->bd, ps->nbh, ps->nbv});
+    const PlaneJob j = sbt_job(ps->pic.p[c], ps->coefs[c], ps->scratch, ps->bd, q);
+    sbt_inverse_jobs(ps->stream, ps->jobs.put(ps->stream, &j), 1, ps->cw[c], ps->ch[c], c, isP, lossless, ps->nbh, ps->nbv, ps->bd != nullptr);
     return 0;
 }
 

@@ -41,18 +41,8 @@ inline int spatial_psy_factor_host(int bw, int bh, int nbh, int nbv, int sub) { 
 
 FilterParams make_filter_params(const MCParams &p, int q, int do_filter, int inter_sharpen);
 
-// dsv_sub_pred (bmc.c:1058): pred <- MC prediction from ref, resd <- resd - pred
-void mc_sub_pred(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, const DFrame &pred, const DFrame &resd, const DFrame &ref);
-// dsv_add_res (bmc.c:1073): resd <- pred + resd, then in-loop filters
-void mc_add_res(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, int q, const DFrame &resd, const DFrame &pred, int do_filter,
-                int inter_sharpen);
-// dsv_add_pred (bmc.c:1094): out <- MC prediction from ref + resd, then in-loop filters
-void mc_add_pred(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, int q, const DFrame &resd, const DFrame &out, const DFrame &ref,
-                 int do_filter, int inter_sharpen);
-// dsv_intra_filter (bmc.c:391), luma plane only
-void intra_filter_luma(hipStream_t s, const uint8_t *d_bd, const MCParams &p, int q, const DPlane &luma);
-
-// lockstep batches over n streams (job tables resident on the device)
+// lockstep batches over n streams (job tables resident on the device): dsv_sub_pred (bmc.c:1058), dsv_add_res (bmc.c:1073),
+// dsv_add_pred (bmc.c:1094) with the in-loop filters, and dsv_intra_filter (bmc.c:391, luma plane only)
 void mc_sub_pred_batch(hipStream_t s, const McJob *d_tab, int n, int nbh, int nbv, int blk_w, int blk_h, bool c420);
 void mc_add_res_batch(hipStream_t s, const McJob *d_tab, int n, int nbh, int nbv, bool any_filter, int luma_w, int luma_h, int blk_w, int blk_h);
 void mc_add_pred_batch(hipStream_t s, const McJob *d_pred, const McJob *d_filt, int n, int nbh, int nbv, bool any_filter, int luma_w, int luma_h, int blk_w,

@@ -379,10 +379,6 @@ __device__ __forceinline__ int row16_sum_i(int v)
     return v;
 }
 
-#ifndef DSV2_CHROMA_PAIR
-#define DSV2_CHROMA_PAIR 1
-#endif
-constexpr bool kChromaPair = DSV2_CHROMA_PAIR != 0; // (build switch for A/B: make EXTRA=-DDSV2_CHROMA_PAIR=0)
 template <int MODE, bool TILED = false>
 __device__ __forceinline__ void predict_chroma_pair(const McJob &jb, const MCParams &p, const DSV_MV &mv, int i, int j, int ox = 0, int oy = 0)
 {
@@ -533,12 +529,7 @@ template <int MODE, int FORM> __device__ __forceinline__ void predict_block_wave
     const DSV_MV mv = load_mv_uniform(&jb.mvs[i + j * p.nbh]);
     if (FORM == PRED_16 || (FORM == PRED_ANY && p.blk_w == 16 && p.blk_h == 16 && p.hshift == 1 && p.vshift == 1)) { // (uniform over the launch)
         predict_plane<MODE, 0>(jb, p, mv, i, j, L, 0);
-        if (kChromaPair) {
-            predict_chroma_pair<MODE>(jb, p, mv, i, j);
-        } else {
-            predict_plane<MODE, 1>(jb, p, mv, i, j, L, 1);
-            predict_plane<MODE, 2>(jb, p, mv, i, j, L, 2);
-        }
+        predict_chroma_pair<MODE>(jb, p, mv, i, j);
     } else if (TILED && !(mv.flags & (1u << DSV_MV_BIT_INTRA))) {
         predict_plane<MODE, 0, true>(jb, p, mv, i, j, L, 0, ox, oy);
         predict_chroma_pair<MODE, true>(jb, p, mv, i, j, ox, oy);
@@ -561,9 +552,6 @@ template <int MODE, int FORM> __global__ __launch_bounds__(256) void k_predict_w
     // then live in scalar registers)
     const int w = __builtin_amdgcn_readfirstlane((int) threadIdx.x >> 6);
     int i = (int) blockIdx.x * 4 + w, j = blockIdx.y;
-#ifdef DSV2_PRED_PAD // (experiment: the 16 x 16 kernel's code with the general kernel's register allocation)
-    asm volatile("v_mov_b32 v55, 0" ::: "v55");
-#endif
     {
         uint8_t *mine = predict_lds + (unsigned) w * wave_lds_bytes(lds_rows);
         WaveLds L{mine, (int16_t *) (mine + wave_lds_win_bytes(lds_rows))};
@@ -2031,22 +2019,6 @@ __device__ __forceinline__ void ring_sweep2(const DPlane &dp, uint8_t *ring, Cel
     __syncthreads();
 }
 
-// grid = 3 workgroups: luma filter, U chroma filter, V chroma filter
-__global__ __launch_bounds__(256) void k_inter_filters(const DSV_MV *__restrict__ vecs, FilterParams f, Planes3 pl)
-{
-    int c = blockIdx.x;
-    const DPlane dp = pl.p[c];
-    if (f.lossless) {
-        return;
-    }
-    if (c == 0) {
-        int nsbx = dp.w / 4, nsby = dp.h / 4;
-        sweep_fronts(nsbx, nsby, [&](int i, int j) { luma_cell(GlobalView{dp}, dp, f, vecs, i, j, nsbx, nsby); });
-    } else {
-        sweep_fronts(f.nbh, f.nbv, [&](int i, int j) { chroma_block(dp, f, vecs, i, j); });
-    }
-}
-
 // stream-batched filters: grid = (n jobs, 3 planes) / (n jobs).  A luma sweep holds ~70 KB of LDS -- two fit a CU, 512 the
 // chip -- and the launch reserves that for the chroma workgroups too: with the plane as the SLOW grid index all luma sweeps of
 // a 192-picture launch (576 workgroups) are dispatched first and start at once; the short chroma sweeps fill in behind them.
@@ -2255,12 +2227,6 @@ __global__ __launch_bounds__(256) void k_intra_filter_g(const McJob *__restrict_
     sweep_fronts(nsbx, nsby, [&](int i, int j) { intra_cell(GlobalView{dp}, dp, f, bd, i, j, nsbx, nsby); });
 }
 
-__global__ __launch_bounds__(256) void k_intra_filter(const uint8_t *__restrict__ bd, FilterParams f, DPlane dp)
-{
-    int nsbx = dp.w / 4, nsby = dp.h / 4;
-    sweep_fronts(nsbx, nsby, [&](int i, int j) { intra_cell(GlobalView{dp}, dp, f, bd, i, j, nsbx, nsby); });
-}
-
 // decoder-side sharpening (dsv_post_process, bmc.c:340): every 4x4 cell is independent
 __global__ __launch_bounds__(256) void k_post_process(DPlane dp)
 {
@@ -2333,15 +2299,6 @@ FilterParams make_filter_params(const MCParams &p, int q, int do_filter, int int
     return f;
 }
 
-static Planes3 planes_of(const DFrame &f)
-{
-    Planes3 p;
-    for (int c = 0; c < 3; c++) {
-        p.p[c] = f.p[c];
-    }
-    return p;
-}
-
 // Blocks larger than 16 x 16 in 4:2:0 (32 x 32: 2160p; 32 x 16: 1920 x 800, 2560 x 1080) are predicted a 16 x 16 piece per wavefront through
 // the 16 x 16 routine (predict_plane<.., TILED>): tw | th << 8 pieces a block, 0 = a wavefront per block (16 x 16 itself; other formats)
 static int mc_tiles(int blk_w, int blk_h, bool c420)
@@ -2363,63 +2320,6 @@ template <int MODE> static void launch_predict(hipStream_t s, const McJob *d_tab
     } else {
         DSV2_LAUNCH((k_predict_w<MODE, PRED_ANY>), dim3((nbh + 3) / 4, nbv, n), dim3(256), 4 * wave_lds_bytes(rows), s, d_tab, rows, 0);
     }
-}
-// the single-call seam (dsv_sub_pred, dsv_add_pred): the batch kernel over a table of ONE job, so that the stage tests exercise
-// the kernel the encoder and the decoder run.  (The seam serialises its callers and drains the stream before it returns: one
-// table is enough.)
-template <int MODE> static void predict_one(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, const DFrame &ref, const DFrame &pred, const DFrame &resd)
-{
-    static McJob *d_job = nullptr;
-    if (d_job == nullptr) {
-        HIPCHK(hipMalloc(&d_job, sizeof(McJob)));
-    }
-    McJob jb{};
-    jb.mvs = d_mvs;
-    jb.p = p;
-    jb.ref = planes_of(ref);
-    jb.pred = planes_of(pred);
-    jb.res = planes_of(resd);
-    HIPCHK(hipMemcpyAsync(d_job, &jb, sizeof(McJob), hipMemcpyHostToDevice, s)); // (pageable source: staged before the call returns)
-    launch_predict<MODE>(s, d_job, 1, p.nbh, p.nbv, p.blk_w, p.blk_h, p.hshift == 1 && p.vshift == 1);
-}
-
-void mc_sub_pred(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, const DFrame &pred, const DFrame &resd, const DFrame &ref)
-{
-    predict_one<MC_SUBTRACT>(s, d_mvs, p, ref, pred, resd);
-    HIPCHK(hipGetLastError());
-}
-void mc_add_res(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, int q, const DFrame &resd, const DFrame &pred, int do_filter,
-                int inter_sharpen)
-{
-    { // (the batch kernel over a table of one: see predict_one)
-        static McJob *d_job = nullptr;
-        if (d_job == nullptr) {
-            HIPCHK(hipMalloc(&d_job, sizeof(McJob)));
-        }
-        McJob jb{};
-        jb.mvs = d_mvs;
-        jb.p = p;
-        jb.pred = planes_of(pred);
-        jb.res = planes_of(resd);
-        HIPCHK(hipMemcpyAsync(d_job, &jb, sizeof(McJob), hipMemcpyHostToDevice, s));
-        DSV2_LAUNCH(k_reconstruct_w, dim3((p.nbh * p.blk_w / 16 + 63) / 64, (p.nbv * p.blk_h + 4 * kReconRows - 1) / (4 * kReconRows), 3), dim3(256), 0, s, d_job);
-    }
-    if (!p.lossless) {
-        DSV2_LAUNCH(k_inter_filters, dim3(3), dim3(256), 0, s, d_mvs, make_filter_params(p, q, do_filter, inter_sharpen),
-                           planes_of(resd));
-    }
-    HIPCHK(hipGetLastError());
-}
-
-void mc_add_pred(hipStream_t s, const DSV_MV *d_mvs, const MCParams &p, int q, const DFrame &resd, const DFrame &out, const DFrame &ref,
-                 int do_filter, int inter_sharpen)
-{
-    predict_one<MC_RECONSTRUCT>(s, d_mvs, p, ref, out, resd);
-    if (!p.lossless) {
-        DSV2_LAUNCH(k_inter_filters, dim3(3), dim3(256), 0, s, d_mvs, make_filter_params(p, q, do_filter, inter_sharpen),
-                           planes_of(out));
-    }
-    HIPCHK(hipGetLastError());
 }
 
 // dynamic LDS of the plane-resident luma sweep: one 64-byte ring per pixel row + guard rows (0 = the ring does not fit this
@@ -2528,15 +2428,6 @@ void intra_filter_batch(hipStream_t s, const McJob *d_tab, int n, int luma_w, in
             DSV2_LAUNCH(k_intra_filter_b, dim3(n), dim3(256), lds, s, d_tab, lds);
         }
     }
-}
-
-void intra_filter_luma(hipStream_t s, const uint8_t *d_bd, const MCParams &p, int q, const DPlane &luma)
-{
-    if (p.lossless) {
-        return;
-    }
-    DSV2_LAUNCH(k_intra_filter, dim3(1), dim3(256), 0, s, d_bd, make_filter_params(p, q, 1, 0), luma);
-    HIPCHK(hipGetLastError());
 }
 
 } // namespace dsv2

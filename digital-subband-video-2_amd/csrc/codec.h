@@ -48,11 +48,6 @@ bool prof_enabled();
 
 // geometry + buffers that persist for the life of a codec instance
 struct CodecDev {
-    // Created on first request: a lockstep batch runs on the stream of its FIRST instance only, so a GPU with hundreds of
-    // encoder instances holds a handful of streams, not one per instance (the runtime spreads the streams that exist
-    // over a few hardware queues).
-    hipStream_t stream = nullptr;
-    hipStream_t ensure_stream();
     bool alive = false;
     int format = 0, w = 0, h = 0;
     int blk_w = 0, blk_h = 0, nbh = 0, nbv = 0, pyr_levels = 0;

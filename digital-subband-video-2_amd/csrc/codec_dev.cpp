@@ -166,8 +166,7 @@ void CodecDev::init(int format_, int w_, int h_, int blk_w_, int blk_h_, int pyr
     size_t nb = nblocks();
     // encoder: everything this function (and the entropy buffers) allocates on the device comes out of ONE block, sized here
     // from the same formulas the allocations use, plus slack; what does not fit falls back to an allocation of its own
-    constexpr bool use_arena = true;
-    if (encoder && use_arena) {
+    if (encoder) {
         // (the same sizes the allocations below ask for; 256 bytes of alignment for each of the ~100 pieces)
         size_t est = 0;
         est += 2 * (2 * dframe_bytes(format, w, h) + nb * sizeof(DSV_MV));
@@ -197,7 +196,7 @@ void CodecDev::init(int format_, int w_, int h_, int blk_w_, int blk_h_, int pyr
         est += 128 * 256;
         arena.create(est);
     }
-    DevArenaScope arena_scope(encoder && use_arena ? &arena : nullptr);
+    DevArenaScope arena_scope(encoder ? &arena : nullptr);
     for (int i = 0; i < 2; i++) {
         dframe_alloc(&pics[i].recon, format, w, h);
         HIPCHK(dev_alloc((void **) &pics[i].d_final_mvs, nb * sizeof(DSV_MV)));
@@ -302,23 +301,12 @@ void CodecDev::ensure_dev_syms(size_t n)
     sym_cap = cap;
 }
 
-hipStream_t CodecDev::ensure_stream()
-{
-    if (!stream) {
-        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    }
-    return stream;
-}
-
 void CodecDev::destroy()
 {
     if (!alive) {
         return;
     }
     alive = false;
-    if (stream) {
-        HIPCHK(hipStreamSynchronize(stream));
-    }
     prof.destroy();
     for (int i = 0; i < 2; i++) {
         dframe_free(&pics[i].recon);
@@ -376,10 +364,6 @@ void CodecDev::destroy()
     if (h_pos) {
         HIPCHK(hipHostFree(h_pos));
         HIPCHK(hipHostFree(h_val));
-    }
-    if (stream) {
-        HIPCHK(hipStreamDestroy(stream));
-        stream = nullptr;
     }
     arena.destroy(); // (last: the releases above skipped everything that lives inside it)
 }

@@ -522,7 +522,7 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     prof.begin(bs, ST_INV_SBT);
     for (const Slice &sl : slices) {
         for (int c = 0; c < 3; c++) {
-            sbt_inverse_jobs(bs, d_pj[c] + sl.first, sl.count, dv0.cw[c], dv0.ch[c], c, sl.isP, sl.lossless, dv0.nbh, dv0.nbv);
+            sbt_inverse_jobs(bs, d_pj[c] + sl.first, sl.count, dv0.cw[c], dv0.ch[c], c, sl.isP, sl.lossless, dv0.nbh, dv0.nbv, true);
         }
     }
     prof.end(bs, ST_INV_SBT, n);

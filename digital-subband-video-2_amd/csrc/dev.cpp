@@ -194,10 +194,10 @@ void dev_zero(void *p, size_t bytes)
 // ~100 % CPU.  The host threads of the lockstep groups wait most of the time, and host CPU time is the scarce
 // resource once the kernels are fast (a container's CPU quota is shared with the entropy back end).  Here the
 // thread sleeps between completion queries; the added latency is bounded by the sleep (tens of microseconds
-// against waits of several milliseconds).  DSV2_SPIN_WAIT=1 restores the runtime's polling wait.
+// against waits of several milliseconds).
 // Polling interval of the two waits below.  A single stream's step is a chain of latency-bound kernels with a host phase
 // between them, and a wake-up that comes late (up to 120 us on the sparse schedule a multi-millisecond wait ends up in) two or
-// three times per frame is 1 % of its frame: such a caller polls at 20 us throughout (DSV2_WAIT_FINE_MAX, default 1 stream).
+// three times per frame is 1 % of its frame: such a caller (a step of one stream) polls at 20 us throughout.
 // Several lockstep groups polling that finely at once was measured too: 4 x 2 streams lose 9 % (the queries contend with the
 // other groups' launches inside the runtime), so batches keep the sparse schedule -- their host is shared by every rank.
 static thread_local bool t_wait_fine = false;

@@ -46,13 +46,11 @@ struct DPlane {
     int w, h;
 };
 
-// A launch's job record: entry i of the table (the host wrote it before the launch; nothing writes it during) or, for the
-// single-call forms, the copy in the kernel arguments -- BY VALUE, THROUGH THE SCALAR CACHE, into scalar registers.
-// `tab ? tab[i] : one` bound to a reference is a pointer into one of two address spaces: the compiler then fetches every field with a
-// per-lane (flat) load of the same address, the record's pointers and strides live in vector registers, and every address the kernel
-// forms from them is a 64-bit vector multiply-add instead of a scalar base plus a 32-bit lane offset.  (For the small records only --
-// planes, plane pairs, the compaction's job: the 144-byte PlaneJob with its arrays ends up in scratch when copied this way, which costs
-// more than the flat loads did; the transform and quantiser kernels keep the reference.)
+// A launch's job record: entry i of a device table the host wrote before the launch (nothing writes it during) --
+// for the small records (planes, plane pairs, the compaction's job) fetched BY VALUE, THROUGH THE SCALAR CACHE, into scalar
+// registers: the record's pointers and strides then live in scalar registers, and every address the kernel forms from them is a
+// scalar base plus a 32-bit lane offset.  The 144-byte PlaneJob with its arrays ends up in scratch when copied this way; the
+// transform and quantiser kernels bind a reference into the `const __restrict__` table instead.
 #ifdef __HIPCC__
 // a value / pointer every lane holds alike, told to the compiler as such: it moves to scalar registers and what is computed from it
 // (addresses above all) to the scalar unit
@@ -66,11 +64,8 @@ template <class T> __device__ __forceinline__ T *uni_ptr(T *p)
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ DPlane uni(const DPlane &p) { return DPlane{uni_ptr(p.data), uni(p.stride), uni(p.w), uni(p.h)}; }
 
-template <class T> __device__ __forceinline__ T job_of(const T *tab, unsigned i, const T &one)
+template <class T> __device__ __forceinline__ T job_of(const T *tab, unsigned i)
 {
-    if (tab == nullptr) {
-        return one;
-    }
     T j;
     __builtin_memcpy(&j, (const __attribute__((address_space(4))) void *) (tab + i), sizeof(T));
     return j;
@@ -89,12 +84,6 @@ struct DFrame {
 struct DCoefs {
     int32_t *data;
     int w, h;
-};
-
-// per-block geometry + flags needed by adaptive stages
-struct BlockMap {
-    const uint8_t *bd; // device blockdata (may be null when unused)
-    int nbh, nbv;
 };
 
 void dev_zero(void *p, size_t bytes); // synchronous zero fill of device memory (nothing inside an arena scope: the arena is zeroed once)
@@ -119,7 +108,7 @@ long arena_fallbacks(); // allocations an instance arena could not hold so far (
 void dev_release(void *p);
 size_t dframe_bytes(int format, int w, int h); // device bytes dframe_alloc asks for
 void event_wait(hipEvent_t ev);        // ... for a recorded event
-void set_wait_fine(bool fine);         // this thread's waits poll at 20 us (small batches: DSV2_WAIT_FINE_MAX) instead of up to 120 us
+void set_wait_fine(bool fine);         // this thread's waits poll at 20 us (steps of one stream) instead of up to 120 us
 void stream_wait(hipStream_t s);       // host wait for the stream to drain: sleeps between completion queries (dev.cpp: 10 - 120 us apart), no busy spin
 // pinned host blocks the GPU may write (hostutil.cpp): recycled through dsv_free
 void *pinned_pool_take(size_t bytes);
@@ -163,30 +152,20 @@ struct PlaneJob {
     int q;             // frame quantiser
     int qll;           // LL step size
     int qp[3][3];      // detail step sizes [level][subband - 1]
-    int *tile_count;   // quantiser: per-1024-position nonzero counts of the stream's symbol list, or null (counted later)
+    int *tile_count;   // quantiser: per-1024-position nonzero counts of the stream's symbol list
     unsigned qv_base;  // scan position of this plane's first value within that list
 };
 
 // --- subband transform (sbt.hip) ------------------------------------------------
 // forward: u8 plane -> coefs (cw x ch).  inverse: coefs -> u8 plane (coefs preserved).
-void sbt_forward(hipStream_t s, const DPlane &src, DCoefs dst, SbtScratch &sc, int plane_idx, int isP,
-                 int lossless, BlockMap bm);
-void sbt_inverse(hipStream_t s, DPlane dst, DCoefs src, SbtScratch &sc, int q, int plane_idx, int isP,
-                 int lossless, BlockMap bm);
-
-// table forms: n jobs of identical geometry (cw x ch coefficient plane)
+// n jobs of identical geometry (cw x ch coefficient plane); have_bd: the jobs carry block flag bytes (the adaptive filters need them)
 void sbt_forward_jobs(hipStream_t s, const PlaneJob *d_jobs, int n, int cw, int ch, int plane_idx, int isP, int lossless, int nbh,
-                      int nbv);
+                      int nbv, bool have_bd);
 void sbt_inverse_jobs(hipStream_t s, const PlaneJob *d_jobs, int n, int cw, int ch, int plane_idx, int isP, int lossless, int nbh,
-                      int nbv);
+                      int nbv, bool have_bd);
 
 // --- picture helpers (frame.hip) ---------------------------------------------------
-void extend_plane(hipStream_t s, const DPlane &p);
-void extend_frame(hipStream_t s, const DFrame &f, bool luma_only);
-void ds2x_luma(hipStream_t s, const DPlane &src, const DPlane &dst);
-void copy_frame_pixels(hipStream_t s, const DFrame &dst, const DFrame &src);
-void copy_frame_full(hipStream_t s, const DFrame &dst, const DFrame &src);
-// stream-batched forms: one launch works through a device-resident table of jobs
+// one launch works through a device-resident table of jobs
 struct PlanePair {
     DPlane src, dst;
 };
@@ -211,7 +190,6 @@ void to420_batch(hipStream_t s, const To420Job *d_jobs, int n, int max_w, int ma
 void ingest_uyvy_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int h); // src = interleaved UYVY rows
 void planes_to_host_batch(hipStream_t s, const PlaneOutJob *d_jobs, int n, int h);
 void extend_planes(hipStream_t s, const DPlane *d_planes, int n, int max_w, int max_h);
-void ds2x_planes(hipStream_t s, const PlanePair *d_pairs, int n, int dst_w, int dst_h);
 void ds2x_planes4(hipStream_t s, const PlanePair *d_pairs, int n, int dst_w, int dst_h); // planes from dframe_alloc: 4 samples per thread
 void copy_linear_batch(hipStream_t s, const CopyJob *d_jobs, int n, size_t max_bytes);
 void zero_linear_batch(hipStream_t s, const CopyJob *d_jobs, int n, size_t max_bytes); // dst, bytes of each job

@@ -728,16 +728,6 @@ void encode_intra_meta(DSV_ENCODER *enc, const FrameCtl *d, BitWriter &bs, const
 }
 
 // ---- device pipeline pieces -----------------------------------------------------------------
-void build_pyramid_on(hipStream_t s, CodecDev &dv, const DFrame &base, DFrame *pyr) // mk_pyramid, dsv_encoder.c:493
-{
-    const DFrame *prev = &base;
-    for (int l = 0; l < dv.pyr_levels; l++) {
-        ds2x_luma(s, prev->p[0], pyr[l].p[0]);
-        extend_plane(s, pyr[l].p[0]);
-        prev = &pyr[l];
-    }
-}
-
 AnalysisParams analysis_params(const CodecDev &dv, int do_psy)
 {
     AnalysisParams a;
@@ -1014,11 +1004,6 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
 // streams and events -- are never destroyed, so an upload left in flight by one call (EncImpl::staged_ev) can be awaited
 // by the next, from any thread.  A scratch's copy stream and copy_done event travel together: a later re-record of the
 // event on that stream covers every earlier upload on it.
-inline bool use_own_streams()
-{
-    return true;
-}
-
 struct ScratchPool {
     std::mutex mu;
     std::vector<BatchScratch *> idle;
@@ -1036,18 +1021,16 @@ struct ScratchPool {
             // come and go with the encoder instances of a run therefore end up two to a queue sooner or later and two
             // lockstep groups then execute one after the other; a fixed set made up front does not.
             primed = true;
-            if (use_own_streams()) {
-                BatchScratch *first[4];
-                for (int k = 0; k < 4; k++) {
-                    first[k] = new BatchScratch();
-                    first[k]->main_stream();
-                }
-                for (int k = 0; k < 4; k++) {
-                    first[k]->ensure_copy_stream();
-                }
-                for (int k = 3; k >= 0; k--) {
-                    idle.push_back(first[k]);
-                }
+            BatchScratch *first[4];
+            for (int k = 0; k < 4; k++) {
+                first[k] = new BatchScratch();
+                first[k]->main_stream();
+            }
+            for (int k = 0; k < 4; k++) {
+                first[k]->ensure_copy_stream();
+            }
+            for (int k = 3; k >= 0; k--) {
+                idle.push_back(first[k]);
             }
         }
         if (idle.empty()) {
@@ -1522,14 +1505,8 @@ struct SearchTokenGuard { // releases on every way out of the scope that took th
 
 // the plane sections of the packet are assembled on the GPU (DSV2_GPU_ENTROPY=0: the host codes them from the symbol list)
 static const bool kGpuEntropy = !(getenv("DSV2_GPU_ENTROPY") && atoi(getenv("DSV2_GPU_ENTROPY")) == 0);
-// side streams within a step: bit 0 entropy coder, bit 1 intra filter; unset: the entropy kernels of a SMALL batch (fewer than
-// 12 streams: the step is a chain of latency-bound launches on a mostly idle GPU) run beside inverse transform /
-// reconstruction / filters, a large batch keeps one chain (no throughput gain there, more host work)
-static const int kAuxStreamsEnv = -1; // (re-measured in round 6 with 192-picture launches: 1 -> -0.6 %, 3 -> +0.2 %: a group's chain in parallel with itself buys nothing)
 static const bool kEntForceFallback = getenv("DSV2_GPU_ENTROPY_FORCE_FALLBACK") && atoi(getenv("DSV2_GPU_ENTROPY_FORCE_FALLBACK")) != 0; // (tests)
-// the quantiser tallies nonzeros per compaction tile while it writes the values (DSV2_FUSED_COUNT=0: separate pass)
 static std::atomic<long> g_list_growths{0}; // pictures that had more symbols than their stream's compaction lists (dsv2hip_enc_list_growths)
-static const bool kFusedCount = true;
 
 // tests: fail the next step of this process on purpose (dsv2hip_test_fail_next_step): 1 = as a search that did not deliver its
 // counters (thrown behind H1a, the search drained), 2 = as a search token that never came (thrown with the step's ingest,
@@ -1569,7 +1546,11 @@ static void enc_batch_step(Job *jobs, int n)
         constexpr int fine_max = 1;
         set_wait_fine(n <= fine_max);
     }
-    const int kAuxStreams = kAuxStreamsEnv >= 0 ? kAuxStreamsEnv : (n < 12 ? 1 : 0);
+    // side streams within the step: bit 0 entropy coder, bit 1 intra filter.  The entropy kernels of a SMALL batch (fewer than
+    // 12 streams: the step is a chain of latency-bound launches on a mostly idle GPU) run beside inverse transform /
+    // reconstruction / filters, a large batch keeps one chain (no throughput gain there, more host work; re-measured in round 6
+    // with 192-picture launches: 1 -> -0.6 %, 3 -> +0.2 %: a group's chain in parallel with itself buys nothing)
+    const int kAuxStreams = n < 12 ? 1 : 0;
     static bool first_step = true; // (DSV2_TRACE=1 only; a benign race)
     const bool trace_startup = first_step;
     first_step = false;
@@ -1607,8 +1588,8 @@ static void enc_batch_step(Job *jobs, int n)
     }
     // The step's kernels run on a stream that belongs to the batch scratch (made once, see ScratchPool::acquire), not on one
     // of the encoders': a step starts and ends with that stream drained, so which stream carried an encoder's previous step
-    // does not matter.  (DSV2_SCRATCH_STREAM=0: the first encoder's stream, created with the instance: A/B.)
-    hipStream_t bs = use_own_streams() ? sc.main_stream() : jobs[0].im->dev.ensure_stream();
+    // does not matter.
+    hipStream_t bs = sc.main_stream();
     sc.ensure(n);
     const int nbh = jobs[0].im->dev.nbh, nbv = jobs[0].im->dev.nbv;
 
@@ -1648,7 +1629,6 @@ static void enc_batch_step(Job *jobs, int n)
         const size_t pbytes = (size_t) f0.p[0].w * f0.p[0].h + (size_t) f0.p[1].w * f0.p[1].h + (size_t) f0.p[2].w * f0.p[2].h;
         hipEvent_t waited[4] = {nullptr, nullptr, nullptr, nullptr};
         int nwaited = 0;
-        bool any_next = false;
         for (int k = 0; k < n; k++) {
             Job &jb = jobs[k];
             EncImpl *im = jb.im;
@@ -1679,7 +1659,7 @@ static void enc_batch_step(Job *jobs, int n)
         }
         // the next step's pictures go up on the copy stream under this step's kernels.  The calls themselves -- one per stream --
         // cost the host several milliseconds for a large batch: they are made once this step's pre-search work and its search
-        // have been handed to the GPU (DSV2_UPLOAD_EARLY=1: before anything else of the step, as up to round 3)
+        // have been handed to the GPU
         upload_next = [&jobs, n, pbytes, &sc] {
             bool any = false;
             for (int k = 0; k < n; k++) {
@@ -1696,12 +1676,6 @@ static void enc_batch_step(Job *jobs, int n)
                 HIPCHK(hipEventRecord(sc.copy_done, sc.copy_stream));
             }
         };
-        constexpr bool upload_early = false;
-        if (upload_early) {
-            upload_next();
-            upload_next = nullptr;
-        }
-        (void) any_next;
     }
     for (int k = 0; k < n; k++) {
         Job &jb = jobs[k];
@@ -2067,7 +2041,7 @@ static void enc_batch_step(Job *jobs, int n)
             }
             pj.bd = d_bd;
             pj.qv = dv.qv + dv.qv_off[c];
-            pj.tile_count = kFusedCount ? dv.comp.tile_count : nullptr;
+            pj.tile_count = dv.comp.tile_count;
             pj.qv_base = (unsigned) dv.qv_off[c];
             pj.mvs = cur.d_final_mvs;
             quant_steps(&pj, dv.quant_cfg(c, p->has_ref, p->lossless, p->do_psy, nullptr), jb.d.quant);
@@ -2117,8 +2091,8 @@ static void enc_batch_step(Job *jobs, int n)
     const int do_psy = jobs[0].d.params.do_psy;
     prof.begin(bs, ST_FWD_SBT);
     for (const Slice &sl : slices) {
-        sbt_forward_jobs(bs, d_py + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv);
-        sbt_forward_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv);
+        sbt_forward_jobs(bs, d_py + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv, true);
+        sbt_forward_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv, true);
     }
     prof.end(bs, ST_FWD_SBT, n);
     prof.begin(bs, ST_QUANT);
@@ -2128,7 +2102,7 @@ static void enc_batch_step(Job *jobs, int n)
         quant_jobs(bs, d_py + sl.first, sl.count, dv0.quant_cfg(0, sl.isP, sl.lossless, do_psy, nullptr));
         quant_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.quant_cfg(1, sl.isP, sl.lossless, do_psy, nullptr));
     }
-    compact_jobs(bs, d_comp, n, dv0.qv_off[3], kFusedCount);
+    compact_jobs(bs, d_comp, n, dv0.qv_off[3]);
     HIPCHK(hipMemcpyAsync(sc.h_totals, sc.d_totals, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, bs));
     if (kGpuEntropy) {
         if (kAuxStreams & 1) {
@@ -2142,8 +2116,8 @@ static void enc_batch_step(Job *jobs, int n)
     prof.end(bs, ST_QUANT, n);
     prof.begin(bs, ST_INV_SBT);
     for (const Slice &sl : slices) {
-        sbt_inverse_jobs(bs, d_py + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv);
-        sbt_inverse_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv);
+        sbt_inverse_jobs(bs, d_py + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv, true);
+        sbt_inverse_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv, true);
     }
     prof.end(bs, ST_INV_SBT, n);
     prof.begin(bs, ST_RECON_FILTER);
@@ -2237,11 +2211,11 @@ static void enc_batch_step(Job *jobs, int n)
             } else {
                 copy_linear_batch(bs, d_c2, 1, cur.src.bytes);
             }
-            sbt_forward_jobs(bs, d_y2, 1, dv.cw[0], dv.ch[0], 0, isP, lossless, nbh, nbv);
-            sbt_forward_jobs(bs, d_uv2, 2, dv.cw[1], dv.ch[1], 1, isP, lossless, nbh, nbv);
+            sbt_forward_jobs(bs, d_y2, 1, dv.cw[0], dv.ch[0], 0, isP, lossless, nbh, nbv, true);
+            sbt_forward_jobs(bs, d_uv2, 2, dv.cw[1], dv.ch[1], 1, isP, lossless, nbh, nbv, true);
             quant_jobs(bs, d_y2, 1, dv.quant_cfg(0, isP, lossless, do_psy, nullptr));
             quant_jobs(bs, d_uv2, 2, dv.quant_cfg(1, isP, lossless, do_psy, nullptr));
-            compact_jobs(bs, d_k2, 1, dv.qv_off[3], kFusedCount);
+            compact_jobs(bs, d_k2, 1, dv.qv_off[3]);
             need_syms = true;
             late_copy = true;
         }

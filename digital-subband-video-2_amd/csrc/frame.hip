@@ -92,24 +92,12 @@ __device__ __forceinline__ void extend_item(const DPlane &pl, int id)
 
 static int extend_items(int w, int h) { return 16 * h + 2 * kBorder * ((w + 3) >> 2) + 4 * kBorder * 8; }
 
-// tab == nullptr: the single plane `one`; otherwise blockIdx.y indexes a device table of planes
-__global__ __launch_bounds__(256) void k_extend(const DPlane *__restrict__ tab, DPlane one)
+// blockIdx.y indexes a device table of planes
+__global__ __launch_bounds__(256) void k_extend(const DPlane *__restrict__ tab)
 {
     DSV2_KERNEL_PRIO();
-    const DPlane pl = job_of(tab, blockIdx.y, one);
+    const DPlane pl = job_of(tab, blockIdx.y);
     extend_item(pl, blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-void extend_plane(hipStream_t s, const DPlane &p)
-{
-    DSV2_LAUNCH(k_extend, dim3((extend_items(p.w, p.h) + 255) / 256), dim3(256), 0, s, nullptr, p);
-}
-
-void extend_frame(hipStream_t s, const DFrame &f, bool luma_only)
-{
-    for (int c = 0; c < (luma_only ? 1 : 3); c++) {
-        extend_plane(s, f.p[c]);
-    }
 }
 
 // n planes (device table d_planes); max_w / max_h bound the largest of them
@@ -118,31 +106,17 @@ void extend_planes(hipStream_t s, const DPlane *d_planes, int n, int max_w, int 
     if (n <= 0) {
         return;
     }
-    DSV2_LAUNCH(k_extend, dim3((extend_items(max_w, max_h) + 255) / 256, n), dim3(256), 0, s, d_planes, DPlane{});
+    DSV2_LAUNCH(k_extend, dim3((extend_items(max_w, max_h) + 255) / 256, n), dim3(256), 0, s, d_planes);
 }
 
-// 2x2 rounded mean decimation of the luma plane (frame.c:211-234)
-__global__ __launch_bounds__(256) void k_ds2x(const PlanePair *__restrict__ tab, PlanePair one)
-{
-    const PlanePair pp = job_of(tab, blockIdx.z, one);
-    int x = blockIdx.x * 64 + threadIdx.x;
-    int y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= pp.dst.w || y >= pp.dst.h) {
-        return;
-    }
-    int sstride = pp.src.stride;
-    const uint8_t *sp = pp.src.data + (size_t) (2 * y) * sstride + 2 * x;
-    pp.dst.data[(size_t) y * pp.dst.stride + x] = (uint8_t) ((sp[0] + sp[1] + sp[sstride] + sp[sstride + 1] + 2) >> 2);
-}
-
-// the same, four output samples per thread: two 8-byte loads (rows 2y, 2y + 1), byte-lane sums, one dword store.
-// Needs 16-byte aligned plane origins and strides (every plane made by dframe_alloc); the last partial group of a row
-// goes sample by sample.
+// 2x2 rounded mean decimation of the luma plane (frame.c:211-234), four output samples per thread: two 8-byte loads (rows 2y,
+// 2y + 1), byte-lane sums, one dword store.  Needs 16-byte aligned plane origins and strides (every plane made by dframe_alloc);
+// the last partial group of a row goes sample by sample.
 constexpr int kDsRows = 4; // output rows per thread (y, y + 4, ...): all eight 8-byte loads issued before the first average
-__global__ __launch_bounds__(256) void k_ds2x4(const PlanePair *__restrict__ tab, PlanePair one)
+__global__ __launch_bounds__(256) void k_ds2x4(const PlanePair *__restrict__ tab)
 {
     DSV2_KERNEL_PRIO();
-    const PlanePair pp = job_of(tab, blockIdx.z, one);
+    const PlanePair pp = job_of(tab, blockIdx.z);
     const int x = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int y0 = blockIdx.y * (4 * kDsRows) + threadIdx.y;
     if (x >= pp.dst.w || y0 >= pp.dst.h) {
@@ -183,41 +157,13 @@ __global__ __launch_bounds__(256) void k_ds2x4(const PlanePair *__restrict__ tab
     }
 }
 
-void ds2x_luma(hipStream_t s, const DPlane &src, const DPlane &dst)
-{
-    DSV2_LAUNCH(k_ds2x, dim3((dst.w + 63) / 64, (dst.h + 3) / 4), dim3(64, 4), 0, s, nullptr, PlanePair{src, dst});
-}
-
-void ds2x_planes(hipStream_t s, const PlanePair *d_pairs, int n, int dst_w, int dst_h)
-{
-    if (n <= 0) {
-        return;
-    }
-    DSV2_LAUNCH(k_ds2x, dim3((dst_w + 63) / 64, (dst_h + 3) / 4, n), dim3(64, 4), 0, s, d_pairs, PlanePair{});
-}
-
 // all planes of the table come from dframe_alloc (16-byte aligned origins and strides): four samples per thread
 void ds2x_planes4(hipStream_t s, const PlanePair *d_pairs, int n, int dst_w, int dst_h)
 {
     if (n <= 0) {
         return;
     }
-    DSV2_LAUNCH(k_ds2x4, dim3((dst_w + 255) / 256, (dst_h + 4 * kDsRows - 1) / (4 * kDsRows), n), dim3(64, 4), 0, s, d_pairs, PlanePair{});
-}
-
-// visible pixels of all planes, device to device (frame.c:186-203 without the extension)
-void copy_frame_pixels(hipStream_t s, const DFrame &dst, const DFrame &src)
-{
-    for (int c = 0; c < 3; c++) {
-        HIPCHK(hipMemcpy2DAsync(dst.p[c].data, dst.p[c].stride, src.p[c].data, src.p[c].stride, src.p[c].w, dst.p[c].h,
-                                hipMemcpyDeviceToDevice, s));
-    }
-}
-
-// whole storage including borders (same geometry required)
-void copy_frame_full(hipStream_t s, const DFrame &dst, const DFrame &src)
-{
-    HIPCHK(hipMemcpyAsync(dst.alloc, src.alloc, src.bytes, hipMemcpyDeviceToDevice, s));
+    DSV2_LAUNCH(k_ds2x4, dim3((dst_w + 255) / 256, (dst_h + 4 * kDsRows - 1) / (4 * kDsRows), n), dim3(64, 4), 0, s, d_pairs);
 }
 
 // ---- batched copies: blockIdx.y indexes a device table --------------------------------------------

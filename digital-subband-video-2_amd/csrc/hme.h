@@ -13,8 +13,7 @@ struct AnalysisParams {
     int scale; // 2 * spatial_psy_factor(-1), hme.c:1851
 };
 
-// dsv_intra_analysis (hme.c:1836): flags-only DSV_MV field for an I frame
-void intra_analysis(hipStream_t s, const DFrame &src, const AnalysisParams &p, DSV_MV *d_out);
+// dsv_intra_analysis (hme.c:1836): flags-only DSV_MV field for an I frame, n pictures
 struct IntraJob {
     Planes3 src;
     DSV_MV *out;
@@ -98,8 +97,5 @@ struct BlockStatsJob {
 };
 void block_stats_batch(hipStream_t s, const BlockStatsJob *d_jobs, int n, int nbh, int nbv);
 
-struct CodecDev;
-struct PicSet;
-int hme_estimate(hipStream_t s, CodecDev &dv, const PicSet &cur, const PicSet &ref, const HmeParams &hp);
 
 } // namespace dsv2

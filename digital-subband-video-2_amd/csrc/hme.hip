@@ -1858,29 +1858,6 @@ void block_stats_batch(hipStream_t s, const BlockStatsJob *d_jobs, int n, int nb
     }
 }
 
-int hme_estimate(hipStream_t s, CodecDev &dv, const PicSet &cur, const PicSet &ref, const HmeParams &hp)
-{
-    HmeFrames f;
-    f.src[0] = cur.src.p[0];
-    f.ref[0] = ref.recon.p[0];
-    f.ogr[0] = ref.src.p[0];
-    for (int l = 0; l < hp.pyr_levels; l++) {
-        f.src[l + 1] = cur.src_pyr[l].p[0];
-        f.ref[l + 1] = ref.recon_pyr[l].p[0];
-        f.ogr[l + 1] = ref.src_pyr[l].p[0];
-    }
-    for (int k = 0; k < 2; k++) {
-        f.srcc[k] = cur.src.p[k + 1];
-        f.refc[k] = ref.recon.p[k + 1];
-    }
-    for (int l = 0; l <= hp.pyr_levels; l++) {
-        f.mvf[l] = dv.d_mvf[l];
-    }
-    f.ref_mvf = ref.has_final_mvs ? ref.d_final_mvs : nullptr;
-    f.counters = dv.d_counters;
-    return hme_run(s, f, hp);
-}
-
 // ---- source statistics ahead of the search (see source_analysis in hme_fast.h) -----------------------------------------
 // grid = (ceil(blocks of level 0 + blocks of level 1, per_wg), streams); one wavefront works through per_wg blocks.
 __global__ __launch_bounds__(64) void k_hme_src_stats_b(const HmeDev *__restrict__ tab, int nb0x, int nb0y, int nb1x, int nb1y, int fb0x, int fb0y,

@@ -12,12 +12,12 @@
 
 namespace dsv2 {
 
-// tab == nullptr: the single picture `one`; otherwise blockIdx.z indexes a device table of pictures
-__global__ __launch_bounds__(64) void k_intra_analysis(const IntraJob *__restrict__ tab, IntraJob one, AnalysisParams p)
+// blockIdx.z indexes a device table of pictures
+__global__ __launch_bounds__(64) void k_intra_analysis(const IntraJob *__restrict__ tab, AnalysisParams p)
 {
     DSV2_CENSUS_SCOPE();
     __shared__ int hist[16];
-    const IntraJob &job = tab ? tab[blockIdx.z] : one;
+    const IntraJob &job = tab[blockIdx.z];
     const Planes3 &src = job.src;
     DSV_MV *out = job.out;
     int i = blockIdx.x, j = blockIdx.y;
@@ -101,22 +101,12 @@ __global__ __launch_bounds__(64) void k_intra_analysis(const IntraJob *__restric
     }
 }
 
-void intra_analysis(hipStream_t s, const DFrame &src, const AnalysisParams &p, DSV_MV *d_out)
-{
-    Planes3 pl;
-    for (int c = 0; c < 3; c++) {
-        pl.p[c] = src.p[c];
-    }
-    DSV2_LAUNCH(k_intra_analysis, dim3(p.nbh, p.nbv), dim3(64), 0, s, nullptr, IntraJob{pl, d_out}, p);
-    HIPCHK(hipGetLastError());
-}
-
 void intra_analysis_batch(hipStream_t s, const IntraJob *d_jobs, int n, const AnalysisParams &p)
 {
     if (n <= 0) {
         return;
     }
-    DSV2_LAUNCH(k_intra_analysis, dim3(p.nbh, p.nbv, n), dim3(64), 0, s, d_jobs, IntraJob{}, p);
+    DSV2_LAUNCH(k_intra_analysis, dim3(p.nbh, p.nbv, n), dim3(64), 0, s, d_jobs, p);
     HIPCHK(hipGetLastError());
 }
 

@@ -23,9 +23,8 @@ struct ScanGeom {
 void make_scan(ScanGeom *g, int w, int h);
 int spatial_psy_factor(int blk_w, int blk_h, int nbh, int nbv, int sub);
 
-// quantise + dequantise `coefs` in place, dense quantised values to qv[scan position]
-void quant_plane(hipStream_t s, DCoefs coefs, int32_t *qv, const QuantCfg &cfg, int q);
-// table form: n PlaneJob records (coefs, qv, bd, mvs and the step sizes filled by quant_steps) sharing `cfg`
+// quantise + dequantise each job's `coefs` in place, dense quantised values to qv[scan position], nonzeros tallied into
+// tile_count: n PlaneJob records (coefs, qv, bd, mvs, tile_count, qv_base and the step sizes filled by quant_steps) sharing `cfg`
 void quant_steps(PlaneJob *job, const QuantCfg &cfg, int q);
 void quant_jobs(hipStream_t s, const PlaneJob *d_jobs, int n, const QuantCfg &cfg);
 
@@ -51,20 +50,16 @@ struct Compactor {
     int *tile_count = nullptr, *tile_base = nullptr, *d_total = nullptr;
     uint32_t *d_pos = nullptr;
     int32_t *d_val = nullptr;
-    int *h_total = nullptr; // pinned
     void ensure(size_t n);
     void release();
-    // after the stream reaches this point *h_total holds the count and d_pos/d_val the symbols
-    void run(hipStream_t s, const int32_t *qv, size_t n);
     CompactJob job(const int32_t *qv, size_t n); // this compactor's buffers as a table entry
 };
-// njobs compactions of n values each in one set of launches; each job's count lands in *job.total
-void compact_jobs(hipStream_t s, const CompactJob *d_jobs, int njobs, size_t n, bool counted = false);
+// njobs compactions of n values each in one set of launches, from the tile counts the quantiser left (zeroed again here);
+// each job's count lands in *job.total
+void compact_jobs(hipStream_t s, const CompactJob *d_jobs, int njobs, size_t n);
 
 // decoder: scatter + dequantise symbols sorted by scan position into a ZEROED coefficient plane;
-// seg_count = {LL, l0, l1, l2}; LL = the separately transmitted DC, stored to coefs[0]
-void dequant_plane(hipStream_t s, DCoefs coefs, const uint32_t *d_pos, const int32_t *d_val, const int seg_count[4], int32_t LL,
-                   const QuantCfg &cfg, int q);
+// seg = {LL, l0, l1, l2}; LL = the separately transmitted DC, stored to coefs[0]
 struct DequantJob {
     int32_t *coefs;
     const uint32_t *pos;
@@ -75,7 +70,7 @@ struct DequantJob {
     int qll, qp[3][3];
 };
 void dequant_steps(DequantJob *job, const QuantCfg &cfg, int q);
-// table form: n jobs sharing `cfg`; max_seg[k] >= every job's seg[k]
+// n jobs sharing `cfg`; max_seg[k] >= every job's seg[k]
 void dequant_jobs(hipStream_t s, const DequantJob *d_jobs, int n, const int max_seg[4], const QuantCfg &cfg);
 
 // ---- host entropy coder (entropy.cpp): bs.c codes + the serial part of hzcc.c ----

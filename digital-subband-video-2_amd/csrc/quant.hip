@@ -249,17 +249,14 @@ __device__ __forceinline__ int quant_detail(const QuantCfg &c, const MvBits &mv,
     }
 }
 
-// Kernels work through PlaneJob records (dev.h): tab == nullptr runs the single job `one`,
-// otherwise a grid dimension indexes a device table whose entries share the geometry in `c`.
+// Kernels work through PlaneJob records (dev.h): a grid dimension indexes a device table whose
+// entries share the geometry in `c`.
 
 // Nonzero bookkeeping for the compaction that follows (saves it a pass over the dense values): the wavefront's
 // nonzeros are tallied per 1024-position tile of the stream's symbol list; a wavefront writes consecutive scan
 // positions, so one atomic per wavefront is the rule and a tile boundary inside it the exception.
 __device__ __forceinline__ void count_nonzero(const PlaneJob &J, size_t pos, int v)
 {
-    if (J.tile_count == nullptr) {
-        return;
-    }
     const bool nz = v != 0;
     const unsigned tile = (unsigned) ((J.qv_base + pos) >> 10);
     const unsigned t0 = (unsigned) __builtin_amdgcn_readfirstlane((int) tile);
@@ -275,10 +272,10 @@ __device__ __forceinline__ void count_nonzero(const PlaneJob &J, size_t pos, int
 }
 
 // LL region: hzcc.c:308-328
-__global__ __launch_bounds__(256) void k_quant_ll(const PlaneJob *__restrict__ tab, PlaneJob one, QuantCfg c, int sw, int sh)
+__global__ __launch_bounds__(256) void k_quant_ll(const PlaneJob *__restrict__ tab, QuantCfg c, int sw, int sh)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = tab ? tab[blockIdx.z] : one;
+    const PlaneJob &J = tab[blockIdx.z];
     int x = blockIdx.x * 64 + threadIdx.x;
     int y = blockIdx.y * 4 + threadIdx.y;
     if (x >= sw || y >= sh) {
@@ -326,12 +323,12 @@ __device__ __forceinline__ bool is_dependent(const LevelArgs &a, int s, int x, i
 }
 
 // phase A of a detail level: every cell that is not a dependent; blockIdx.z = 3 * job + (subband - 1)
-__global__ __launch_bounds__(256) void k_quant_level(const PlaneJob *__restrict__ tab, PlaneJob one, QuantCfg c, LevelArgs a)
+__global__ __launch_bounds__(256) void k_quant_level(const PlaneJob *__restrict__ tab, QuantCfg c, LevelArgs a)
 {
     int x = blockIdx.x * 64 + threadIdx.x;
     int y = blockIdx.y * 4 + threadIdx.y;
     int si = blockIdx.z % 3;
-    const PlaneJob &J = tab ? tab[blockIdx.z / 3] : one;
+    const PlaneJob &J = tab[blockIdx.z / 3];
     if (x >= a.sw || y >= a.sh || is_dependent(a, si + 1, x, y)) {
         return;
     }
@@ -406,30 +403,29 @@ __device__ __forceinline__ void quant_row4(const PlaneJob &J, const QuantCfg &c,
     *cell = make_int4(dq[0], dq[1], dq[2], dq[3]);
     const size_t pos = a.base[si] + (size_t) y * a.sw + x;
     *(int4 *) (J.qv + pos) = make_int4(v[0], v[1], v[2], v[3]);
-    if (J.tile_count != nullptr) { // as count_nonzero, with up to four nonzeros a lane (its four positions share a tile)
-        const unsigned tile = (unsigned) ((J.qv_base + pos) >> 10);
-        const unsigned t0 = (unsigned) __builtin_amdgcn_readfirstlane((int) tile);
-        const bool here = tile == t0;
-        const int sum = __popcll(__ballot(here && (nzc & 1))) + 2 * __popcll(__ballot(here && (nzc & 2))) + 4 * __popcll(__ballot(here && (nzc & 4)));
-        const unsigned long long active = __ballot(true);
-        const int lane = (int) (threadIdx.x + threadIdx.y * blockDim.x) & 63;
-        if (sum && lane == __ffsll((long long) active) - 1) {
-            atomicAdd(&J.tile_count[t0], sum);
-        }
-        if (nzc && !here) {
-            atomicAdd(&J.tile_count[tile], nzc);
-        }
+    // as count_nonzero, with up to four nonzeros a lane (its four positions share a tile)
+    const unsigned tile = (unsigned) ((J.qv_base + pos) >> 10);
+    const unsigned t0 = (unsigned) __builtin_amdgcn_readfirstlane((int) tile);
+    const bool here = tile == t0;
+    const int sum = __popcll(__ballot(here && (nzc & 1))) + 2 * __popcll(__ballot(here && (nzc & 2))) + 4 * __popcll(__ballot(here && (nzc & 4)));
+    const unsigned long long active = __ballot(true);
+    const int lane = (int) (threadIdx.x + threadIdx.y * blockDim.x) & 63;
+    if (sum && lane == __ffsll((long long) active) - 1) {
+        atomicAdd(&J.tile_count[t0], sum);
+    }
+    if (nzc && !here) {
+        atomicAdd(&J.tile_count[tile], nzc);
     }
 }
 
 template <int MODE>
-__global__ __launch_bounds__(256) void k_quant_level4(const PlaneJob *__restrict__ tab, PlaneJob one, QuantCfg c, LevelArgs a)
+__global__ __launch_bounds__(256) void k_quant_level4(const PlaneJob *__restrict__ tab, QuantCfg c, LevelArgs a)
 {
     DSV2_KERNEL_PRIO();
     const int x = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int yb = blockIdx.y * (4 * kQRows) + threadIdx.y;
     const int si = blockIdx.z % 3;
-    const PlaneJob &J = tab ? tab[blockIdx.z / 3] : one;
+    const PlaneJob &J = tab[blockIdx.z / 3];
     if (x >= a.sw || yb >= a.sh) {
         return;
     }
@@ -465,9 +461,9 @@ __global__ __launch_bounds__(256) void k_quant_level4(const PlaneJob *__restrict
 }
 
 // phase B: the dependents (last column, then last row without the shared corner); blockIdx.y = subband - 1
-__global__ __launch_bounds__(256) void k_quant_level_dep(const PlaneJob *__restrict__ tab, PlaneJob one, QuantCfg c, LevelArgs a)
+__global__ __launch_bounds__(256) void k_quant_level_dep(const PlaneJob *__restrict__ tab, QuantCfg c, LevelArgs a)
 {
-    const PlaneJob &J = tab ? tab[blockIdx.z] : one;
+    const PlaneJob &J = tab[blockIdx.z];
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     int si = blockIdx.y;
     int x, y;
@@ -498,13 +494,16 @@ void quant_steps(PlaneJob *job, const QuantCfg &cfg, int q)
     }
 }
 
-static void quant_launch(hipStream_t s, const PlaneJob *tab, const PlaneJob &one, int n, const QuantCfg &cfg)
+void quant_jobs(hipStream_t s, const PlaneJob *tab, int n, const QuantCfg &cfg)
 {
+    if (n <= 0) {
+        return;
+    }
     ScanGeom g;
     make_scan(&g, cfg.w, cfg.h);
     const dim3 blk(64, 4);
-    unsigned nz = tab ? (unsigned) n : 1u;
-    DSV2_LAUNCH(k_quant_ll, dim3((g.sw[0] + 63) / 64, (g.sh[0] + 3) / 4, nz), blk, 0, s, tab, one, cfg, g.sw[0], g.sh[0]);
+    const unsigned nz = (unsigned) n;
+    DSV2_LAUNCH(k_quant_ll, dim3((g.sw[0] + 63) / 64, (g.sh[0] + 3) / 4, nz), blk, 0, s, tab, cfg, g.sw[0], g.sh[0]);
     for (int l = 0; l < 3; l++) {
         LevelArgs a;
         a.l = l;
@@ -527,43 +526,25 @@ static void quant_launch(hipStream_t s, const PlaneJob *tab, const PlaneJob &one
         if (a.vec) {
             const dim3 grid4((a.sw / 4 + 63) / 64, (a.sh + 4 * kQRows - 1) / (4 * kQRows), 3 * nz);
             switch (quant_mode(cfg)) { // (a lossless launch goes cell by cell inside the kernel: any instance will do)
-                case QM_P_PLAIN: DSV2_LAUNCH(k_quant_level4<QM_P_PLAIN>, grid4, blk, 0, s, tab, one, cfg, a); break;
-                case QM_P_PSY: DSV2_LAUNCH(k_quant_level4<QM_P_PSY>, grid4, blk, 0, s, tab, one, cfg, a); break;
-                case QM_I_PSY: DSV2_LAUNCH(k_quant_level4<QM_I_PSY>, grid4, blk, 0, s, tab, one, cfg, a); break;
-                case QM_I_CHROMA: DSV2_LAUNCH(k_quant_level4<QM_I_CHROMA>, grid4, blk, 0, s, tab, one, cfg, a); break;
-                default: DSV2_LAUNCH(k_quant_level4<QM_I_PLAIN>, grid4, blk, 0, s, tab, one, cfg, a); break;
+                case QM_P_PLAIN: DSV2_LAUNCH(k_quant_level4<QM_P_PLAIN>, grid4, blk, 0, s, tab, cfg, a); break;
+                case QM_P_PSY: DSV2_LAUNCH(k_quant_level4<QM_P_PSY>, grid4, blk, 0, s, tab, cfg, a); break;
+                case QM_I_PSY: DSV2_LAUNCH(k_quant_level4<QM_I_PSY>, grid4, blk, 0, s, tab, cfg, a); break;
+                case QM_I_CHROMA: DSV2_LAUNCH(k_quant_level4<QM_I_CHROMA>, grid4, blk, 0, s, tab, cfg, a); break;
+                default: DSV2_LAUNCH(k_quant_level4<QM_I_PLAIN>, grid4, blk, 0, s, tab, cfg, a); break;
             }
         } else {
-            DSV2_LAUNCH(k_quant_level, dim3((a.sw + 63) / 64, (a.sh + 3) / 4, 3 * nz), blk, 0, s, tab, one, cfg, a);
+            DSV2_LAUNCH(k_quant_level, dim3((a.sw + 63) / 64, (a.sh + 3) / 4, 3 * nz), blk, 0, s, tab, cfg, a);
         }
         if (a.xdep || a.ydep) {
-            DSV2_LAUNCH(k_quant_level_dep, dim3((a.sw + a.sh + 255) / 256, 3, nz), dim3(256), 0, s, tab, one, cfg, a);
+            DSV2_LAUNCH(k_quant_level_dep, dim3((a.sw + a.sh + 255) / 256, 3, nz), dim3(256), 0, s, tab, cfg, a);
         }
     }
     HIPCHK(hipGetLastError());
 }
 
-void quant_plane(hipStream_t s, DCoefs coefs, int32_t *qv, const QuantCfg &cfg, int q)
-{
-    PlaneJob one = {};
-    one.coefs = coefs.data;
-    one.qv = qv;
-    one.bd = cfg.bd;
-    one.mvs = cfg.mvs;
-    quant_steps(&one, cfg, q);
-    quant_launch(s, nullptr, one, 1, cfg);
-}
-
-void quant_jobs(hipStream_t s, const PlaneJob *d_jobs, int n, const QuantCfg &cfg)
-{
-    if (n > 0) {
-        quant_launch(s, d_jobs, PlaneJob{}, n, cfg);
-    }
-}
-
 // ---- ordered compaction of the nonzero symbols ---------------------------------------
-// three small kernels: per-tile counts, one-workgroup exclusive scan of the tile counts,
-// ordered scatter.  Tiles are 1024 consecutive scan positions handled by 256 threads.
+// two small kernels after the quantiser's per-tile nonzero counts (count_nonzero): one-workgroup exclusive scan of the
+// tile counts, ordered scatter.  Tiles are 1024 consecutive scan positions handled by 256 threads.
 constexpr int kTile = 1024;
 
 __device__ __forceinline__ int wave_incl_scan(int v, int lane)
@@ -578,40 +559,15 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_count(const CompactJob *__restrict__ tab, CompactJob one)
-{
-    __shared__ int wsum[4];
-    const CompactJob J = job_of(tab, blockIdx.y, one);
-    const int32_t *qv = J.qv;
-    int n = J.n;
-    int *tile_count = J.tile_count;
-    int base = blockIdx.x * kTile;
-    int cnt = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        int i = base + threadIdx.x * 4 + j;
-        cnt += (i < n && qv[i] != 0);
-    }
-    int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = wave_incl_scan(cnt, lane);
-    if (lane == 63) {
-        wsum[wv] = inc;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        tile_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
-}
-
 // exclusive scan of up to 1024*ntile_per_thread tile counts by one workgroup; also emits the total
 // one workgroup of 256 per job (a 1024-thread workgroup needs sixteen free wavefront slots on ONE compute unit at once: beside
 // the search's resident wavefronts its placement alone took ~1 ms in the four-group bench)
 constexpr int kScanThreads = 256;
-__global__ __launch_bounds__(kScanThreads) void k_scan_tiles(const CompactJob *__restrict__ tab, CompactJob one, int reset)
+__global__ __launch_bounds__(kScanThreads) void k_scan_tiles(const CompactJob *__restrict__ tab)
 {
     DSV2_KERNEL_PRIO();
     __shared__ int wsum[kScanThreads / 64];
-    const CompactJob J = job_of(tab, blockIdx.y, one);
+    const CompactJob J = job_of(tab, blockIdx.y);
     const int *tile_count = J.tile_count;
     int ntiles = (J.n + kTile - 1) / kTile;
     int *tile_base = J.tile_base, *total = J.total;
@@ -624,7 +580,7 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_tiles(const CompactJob *_
     for (int start = 0; start < ntiles; start += kScanThreads) {
         int i = start + threadIdx.x;
         int v = i < ntiles ? tile_count[i] : 0;
-        if (reset && i < ntiles) {
+        if (i < ntiles) {
             J.tile_count[i] = 0; // the quantiser of the next frame accumulates into it
         }
         int inc = wave_incl_scan(v, lane);
@@ -655,14 +611,14 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_tiles(const CompactJob *_
 // round trips that tell it so (kernel arguments, job record, two tile bases) -- 3 038 workgroups a picture, 9 x slower under load than
 // alone (round 6).  Now the first nine threads fetch the nine bases of eight tiles at once and the workgroup walks the tiles that hold something.
 constexpr int kScatterTiles = 8;
-__global__ __launch_bounds__(256) void k_scatter(const CompactJob *__restrict__ tab, CompactJob one)
+__global__ __launch_bounds__(256) void k_scatter(const CompactJob *__restrict__ tab)
 {
     DSV2_KERNEL_PRIO();
     __shared__ int wsum[4];
     __shared__ uint32_t spos[kTile];
     __shared__ int32_t sval[kTile];
     __shared__ int tbs[kScatterTiles + 1];
-    const CompactJob J = job_of(tab, blockIdx.y, one);
+    const CompactJob J = job_of(tab, blockIdx.y);
     const int32_t *qv = J.qv;
     int n = J.n;
     uint32_t *out_pos = J.pos;
@@ -755,7 +711,6 @@ void Compactor::ensure_lists(size_t n, size_t symbols)
     HIPCHK(dev_alloc((void **) &d_total, sizeof(int)));
     HIPCHK(dev_alloc((void **) &d_pos, symbols * sizeof(uint32_t)));
     HIPCHK(dev_alloc((void **) &d_val, symbols * sizeof(int32_t)));
-    HIPCHK(hipHostMalloc((void **) &h_total, sizeof(int), hipHostMallocDefault));
     cap = n;
     list_cap = symbols;
 }
@@ -783,7 +738,6 @@ void Compactor::release()
     dev_release(d_total);
     dev_release(d_pos);
     dev_release(d_val);
-    HIPCHK(hipHostFree(h_total));
     cap = 0;
 }
 
@@ -793,34 +747,20 @@ CompactJob Compactor::job(const int32_t *qv, size_t n)
     return CompactJob{qv, (int) n, tile_count, tile_base, d_total, d_pos, d_val, nullptr, nullptr, 0, (int) list_cap};
 }
 
-void Compactor::run(hipStream_t s, const int32_t *qv, size_t n)
-{
-    CompactJob one = job(qv, n);
-    int ntiles = (int) ((n + kTile - 1) / kTile);
-    DSV2_LAUNCH(k_count, dim3(ntiles), dim3(256), 0, s, nullptr, one);
-    DSV2_LAUNCH(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, s, nullptr, one, 1); // counts always left at zero
-    DSV2_LAUNCH(k_scatter, dim3((ntiles + kScatterTiles - 1) / kScatterTiles), dim3(256), 0, s, nullptr, one);
-    HIPCHK(hipMemcpyAsync(h_total, d_total, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipGetLastError());
-}
-
-void compact_jobs(hipStream_t s, const CompactJob *d_jobs, int njobs, size_t n, bool counted)
+void compact_jobs(hipStream_t s, const CompactJob *d_jobs, int njobs, size_t n)
 {
     if (njobs <= 0) {
         return;
     }
     int ntiles = (int) ((n + kTile - 1) / kTile);
-    if (!counted) { // else the quantiser tallied the tiles while writing the values (count_nonzero)
-        DSV2_LAUNCH(k_count, dim3(ntiles, njobs), dim3(256), 0, s, d_jobs, CompactJob{});
-    }
-    DSV2_LAUNCH(k_scan_tiles, dim3(1, njobs), dim3(kScanThreads), 0, s, d_jobs, CompactJob{}, counted ? 1 : 0);
-    DSV2_LAUNCH(k_scatter, dim3((ntiles + kScatterTiles - 1) / kScatterTiles, njobs), dim3(256), 0, s, d_jobs, CompactJob{});
+    DSV2_LAUNCH(k_scan_tiles, dim3(1, njobs), dim3(kScanThreads), 0, s, d_jobs);
+    DSV2_LAUNCH(k_scatter, dim3((ntiles + kScatterTiles - 1) / kScatterTiles, njobs), dim3(256), 0, s, d_jobs);
     HIPCHK(hipGetLastError());
 }
 
 // ---- decoder side: scatter decoded symbols and dequantise (hzcc.c:451-583) -------------------
 // One DequantJob per plane (and stream): its symbol list sorted by scan position, split by seg[] into
-// {LL, level 0, level 1, level 2}.  tab == nullptr: the single job `one`; else blockIdx.y indexes the table.
+// {LL, level 0, level 1, level 2}.  blockIdx.y indexes the table.
 struct DequantArgs {
     int l;
     int sw, sh, dbx, dby;
@@ -828,9 +768,9 @@ struct DequantArgs {
 };
 
 // LL symbols: dequantL (hzcc.c:530); thread 0 also plants the separately transmitted DC (hzcc.c:599-602)
-__global__ __launch_bounds__(256) void k_dequant_ll(const DequantJob *__restrict__ tab, DequantJob one, QuantCfg c, int sw)
+__global__ __launch_bounds__(256) void k_dequant_ll(const DequantJob *__restrict__ tab, QuantCfg c, int sw)
 {
-    const DequantJob &J = tab ? tab[blockIdx.y] : one;
+    const DequantJob &J = tab[blockIdx.y];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) {
         J.coefs[0] = J.LL;
@@ -846,10 +786,10 @@ __global__ __launch_bounds__(256) void k_dequant_ll(const DequantJob *__restrict
 }
 
 // detail symbols of one level; `dep` selects the dependents phase (see header comment)
-__global__ __launch_bounds__(256) void k_dequant_level(const DequantJob *__restrict__ tab, DequantJob one, QuantCfg c, DequantArgs a,
+__global__ __launch_bounds__(256) void k_dequant_level(const DequantJob *__restrict__ tab, QuantCfg c, DequantArgs a,
                                                        int xdep, int ydep, int dep)
 {
-    const DequantJob &J = tab ? tab[blockIdx.y] : one;
+    const DequantJob &J = tab[blockIdx.y];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= J.seg[1 + a.l]) {
         return;
@@ -890,12 +830,15 @@ void dequant_steps(DequantJob *job, const QuantCfg &cfg, int q)
 }
 
 // max_seg[k] bounds seg[k] over the jobs (grid size)
-static void dequant_launch(hipStream_t s, const DequantJob *tab, const DequantJob &one, int n, const int max_seg[4], const QuantCfg &cfg)
+void dequant_jobs(hipStream_t s, const DequantJob *tab, int n, const int max_seg[4], const QuantCfg &cfg)
 {
+    if (n <= 0) {
+        return;
+    }
     ScanGeom g;
     make_scan(&g, cfg.w, cfg.h);
-    unsigned ny = tab ? (unsigned) n : 1u;
-    DSV2_LAUNCH(k_dequant_ll, dim3((unsigned) (max_seg[0] + 255) / 256 + (max_seg[0] == 0), ny), dim3(256), 0, s, tab, one, cfg, g.sw[0]);
+    const unsigned ny = (unsigned) n;
+    DSV2_LAUNCH(k_dequant_ll, dim3((unsigned) (max_seg[0] + 255) / 256 + (max_seg[0] == 0), ny), dim3(256), 0, s, tab, cfg, g.sw[0]);
     for (int l = 0; l < 3; l++) {
         int nmax = max_seg[1 + l];
         if (nmax <= 0) {
@@ -913,35 +856,12 @@ static void dequant_launch(hipStream_t s, const DequantJob *tab, const DequantJo
             a.base[si] = g.base[1 + 3 * l + si];
             a.par[si] = h_subband_off(l - 1, si + 1, cfg.w, cfg.h);
         }
-        DSV2_LAUNCH(k_dequant_level, dim3((unsigned) (nmax + 255) / 256, ny), dim3(256), 0, s, tab, one, cfg, a, xdep, ydep, 0);
+        DSV2_LAUNCH(k_dequant_level, dim3((unsigned) (nmax + 255) / 256, ny), dim3(256), 0, s, tab, cfg, a, xdep, ydep, 0);
         if (xdep || ydep) {
-            DSV2_LAUNCH(k_dequant_level, dim3((unsigned) (nmax + 255) / 256, ny), dim3(256), 0, s, tab, one, cfg, a, xdep, ydep, 1);
+            DSV2_LAUNCH(k_dequant_level, dim3((unsigned) (nmax + 255) / 256, ny), dim3(256), 0, s, tab, cfg, a, xdep, ydep, 1);
         }
     }
     HIPCHK(hipGetLastError());
-}
-
-void dequant_plane(hipStream_t s, DCoefs coefs, const uint32_t *d_pos, const int32_t *d_val, const int seg_count[4], int32_t LL,
-                   const QuantCfg &cfg, int q)
-{
-    DequantJob one = {};
-    one.coefs = coefs.data;
-    one.pos = d_pos;
-    one.val = d_val;
-    for (int k = 0; k < 4; k++) {
-        one.seg[k] = seg_count[k];
-    }
-    one.bd = cfg.bd;
-    one.LL = LL;
-    dequant_steps(&one, cfg, q);
-    dequant_launch(s, nullptr, one, 1, seg_count, cfg);
-}
-
-void dequant_jobs(hipStream_t s, const DequantJob *d_jobs, int n, const int max_seg[4], const QuantCfg &cfg)
-{
-    if (n > 0) {
-        dequant_launch(s, d_jobs, DequantJob{}, n, max_seg, cfg);
-    }
 }
 
 } // namespace dsv2

@@ -264,9 +264,8 @@ template <int F> __device__ __forceinline__ void synthesis_pair(const Syn &v, co
 }
 
 // ---- kernels ----------------------------------------------------------------------
-// Every kernel works through PlaneJob records: tab == nullptr runs the single job `one`, otherwise
-// blockIdx.z indexes a device table (one entry per stream and plane of a lockstep batch; all entries
-// share the geometry `g`).  Images are named by selector: 0..2 = the job's scratch images, 3 = its
+// Every kernel works through PlaneJob records: blockIdx.z indexes a device table (one entry per stream
+// and plane of a lockstep batch; all entries share the geometry `g`).  Images are named by selector: 0..2 = the job's scratch images, 3 = its
 // coefficient plane.
 struct LevelGeom {
     int w;      // row stride of every int32 image (= coefficient plane width)
@@ -279,17 +278,13 @@ struct LevelGeom {
 
 enum { IMG_COEFS = 3 };
 
-__device__ __forceinline__ const PlaneJob &pick_job(const PlaneJob *tab, const PlaneJob &one)
-{
-    return tab ? tab[blockIdx.z] : one;
-}
 __device__ __forceinline__ int32_t *img(const PlaneJob &J, int sel) { return sel == IMG_COEFS ? J.coefs : J.t[sel]; }
 
 template <int F, bool U8>
-__global__ __launch_bounds__(256) void k_fwd_rows(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int s_sel)
+__global__ __launch_bounds__(256) void k_fwd_rows(const PlaneJob *__restrict__ tab, LevelGeom g, int s_sel)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int k = blockIdx.x * 64 + threadIdx.x;
     int j = blockIdx.y * 4 + threadIdx.y;
     if (k >= g.hw || j >= g.sh) {
@@ -312,10 +307,10 @@ __global__ __launch_bounds__(256) void k_fwd_rows(const PlaneJob *__restrict__ t
 }
 
 template <int F>
-__global__ __launch_bounds__(256) void k_fwd_cols(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int d_sel)
+__global__ __launch_bounds__(256) void k_fwd_cols(const PlaneJob *__restrict__ tab, LevelGeom g, int d_sel)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int i = blockIdx.x * 64 + threadIdx.x;
     int k = blockIdx.y * 4 + threadIdx.y;
     if (i >= g.sw || k >= g.hh) {
@@ -390,11 +385,11 @@ __device__ __forceinline__ void fwd_haar_quad(const PlaneJob &J, const LevelGeom
 }
 
 template <bool U8>
-__global__ __launch_bounds__(256) void k_fwd_haar(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int s_sel,
+__global__ __launch_bounds__(256) void k_fwd_haar(const PlaneJob *__restrict__ tab, LevelGeom g, int s_sel,
                                                   int d_sel, int ovf)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int idx = blockIdx.x * 64 + threadIdx.x;
     int jy = blockIdx.y * 4 + threadIdx.y;
     if (idx >= g.hw || jy >= g.hh) {
@@ -408,10 +403,10 @@ __global__ __launch_bounds__(256) void k_fwd_haar(const PlaneJob *__restrict__ t
 // at a third of level 1's work the levels 2 .. 3 took as long under load.  Launched when the level's half width and the row
 // stride are multiples of four; edge threads and unaligned jobs go quad by quad.
 constexpr int kHaarRowsI = 1;
-__global__ __launch_bounds__(256) void k_fwd_haar_i32x4(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int s_sel, int d_sel, int ovf)
+__global__ __launch_bounds__(256) void k_fwd_haar_i32x4(const PlaneJob *__restrict__ tab, LevelGeom g, int s_sel, int d_sel, int ovf)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     const int idx = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int jy0 = blockIdx.y * (4 * kHaarRowsI) + threadIdx.y;
     if (idx >= g.hw || jy0 >= g.hh) {
@@ -467,10 +462,10 @@ __global__ __launch_bounds__(256) void k_fwd_haar_i32x4(const PlaneJob *__restri
 // stores (one per band).  Launched when the level's half width and the row stride are multiples of four; threads at the
 // picture's right / bottom edge, and jobs whose images are not 16-byte aligned, go quad by quad.
 constexpr int kHaarRows = 2; // output rows per thread (jy, jy + 4): both row pairs' loads are issued before the first is used (four rows: 60 registers, a wavefront per SIMD fewer under load, no faster)
-__global__ __launch_bounds__(256) void k_fwd_haar_u8x4(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int d_sel, int ovf)
+__global__ __launch_bounds__(256) void k_fwd_haar_u8x4(const PlaneJob *__restrict__ tab, LevelGeom g, int d_sel, int ovf)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     const int idx = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int jy0 = blockIdx.y * (4 * kHaarRows) + threadIdx.y;
     if (idx >= g.hw || jy0 >= g.hh) {
@@ -630,11 +625,11 @@ __device__ __forceinline__ void inv_haar_quad(const PlaneJob &J, const LevelGeom
 }
 
 template <bool OUT_U8>
-__global__ __launch_bounds__(256) void k_inv_haar(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int ll_sel,
+__global__ __launch_bounds__(256) void k_inv_haar(const PlaneJob *__restrict__ tab, LevelGeom g, int ll_sel,
                                                   int d_sel, int ovf, int filtered, int hdiv)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int idx = blockIdx.x * 64 + threadIdx.x;
     int jy = blockIdx.y * 4 + threadIdx.y;
     if (idx >= g.hw || jy >= g.hh) {
@@ -645,11 +640,11 @@ __global__ __launch_bounds__(256) void k_inv_haar(const PlaneJob *__restrict__ t
 
 // level 1 to the 8-bit picture, four quads per thread: 16-byte loads of the four bands (and of the LL rows above and
 // below for the smoothing), two 8-byte pixel stores.  Interior threads only; the rest goes quad by quad.
-__global__ __launch_bounds__(256) void k_inv_haar_u8x4(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int ll_sel, int ovf,
+__global__ __launch_bounds__(256) void k_inv_haar_u8x4(const PlaneJob *__restrict__ tab, LevelGeom g, int ll_sel, int ovf,
                                                        int filtered, int hdiv)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     const int idx = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int jy = blockIdx.y * 4 + threadIdx.y;
     if (idx >= g.hw || jy >= g.hh) {
@@ -699,11 +694,11 @@ __global__ __launch_bounds__(256) void k_inv_haar_u8x4(const PlaneJob *__restric
 
 // levels above 1, four quads per thread to the int32 image (round 6): k_inv_haar_u8x4's loads, four 16-byte stores.  Interior
 // threads only; the rest goes quad by quad.
-__global__ __launch_bounds__(256) void k_inv_haar_i32x4(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int ll_sel, int d_sel, int ovf,
+__global__ __launch_bounds__(256) void k_inv_haar_i32x4(const PlaneJob *__restrict__ tab, LevelGeom g, int ll_sel, int d_sel, int ovf,
                                                         int filtered, int hdiv)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     const int idx = (blockIdx.x * 64 + threadIdx.x) * 4;
     const int jy = blockIdx.y * 4 + threadIdx.y;
     if (idx >= g.hw || jy >= g.hh) {
@@ -798,12 +793,12 @@ __device__ __forceinline__ void fwd_haar_quad_p(const int32_t *src, int ss, int3
     }
 }
 
-__global__ __launch_bounds__(256) void k_fwd_haar_tail(const PlaneJob *__restrict__ tab, PlaneJob one, int cw, int ch, int l0, int lvls, int lossless,
+__global__ __launch_bounds__(256) void k_fwd_haar_tail(const PlaneJob *__restrict__ tab, int cw, int ch, int l0, int lvls, int lossless,
                                                        int cap_a)
 {
     DSV2_KERNEL_PRIO();
     extern __shared__ int32_t tail_lds[];
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int32_t *C = J.coefs;
     const int32_t *src = img(J, l0 & 1); // written by level l0 - 1
     int ss = cw;
@@ -874,12 +869,12 @@ __device__ __forceinline__ void inv_haar_quad_p(const int32_t *LLp, int ls, cons
     }
 }
 
-__global__ __launch_bounds__(256) void k_inv_haar_tail(const PlaneJob *__restrict__ tab, PlaneJob one, int cw, int ch, int l0, int lvls, int lossless,
+__global__ __launch_bounds__(256) void k_inv_haar_tail(const PlaneJob *__restrict__ tab, int cw, int ch, int l0, int lvls, int lossless,
                                                        int plane_idx, int isP, int cap_a)
 {
     DSV2_KERNEL_PRIO();
     extern __shared__ int32_t tail_lds[];
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     const int32_t *C = J.coefs;
     const int32_t *LLp = C;
     int ls = cw;
@@ -906,10 +901,10 @@ __global__ __launch_bounds__(256) void k_inv_haar_tail(const PlaneJob *__restric
 
 // columns first (sbt.c:467-469): packed column i of the Mallat image -> full column in scratch image 2
 template <int F>
-__global__ __launch_bounds__(256) void k_inv_cols(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int ll_sel)
+__global__ __launch_bounds__(256) void k_inv_cols(const PlaneJob *__restrict__ tab, LevelGeom g, int ll_sel)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int i = blockIdx.x * 64 + threadIdx.x;
     int k = blockIdx.y * 4 + threadIdx.y;
     if (i >= g.sw || k >= g.hh) {
@@ -928,10 +923,10 @@ __global__ __launch_bounds__(256) void k_inv_cols(const PlaneJob *__restrict__ t
 }
 
 template <int F, bool OUT_U8>
-__global__ __launch_bounds__(256) void k_inv_rows(const PlaneJob *__restrict__ tab, PlaneJob one, LevelGeom g, int d_sel)
+__global__ __launch_bounds__(256) void k_inv_rows(const PlaneJob *__restrict__ tab, LevelGeom g, int d_sel)
 {
     DSV2_KERNEL_PRIO();
-    const PlaneJob &J = pick_job(tab, one);
+    const PlaneJob &J = tab[blockIdx.z];
     int k = blockIdx.x * 64 + threadIdx.x;
     int j = blockIdx.y * 4 + threadIdx.y;
     if (k >= g.hw || j >= g.sh) {
@@ -963,31 +958,30 @@ __global__ __launch_bounds__(256) void k_inv_rows(const PlaneJob *__restrict__ t
 }
 
 // ---- host drivers -------------------------------------------------------------------
-struct Batch { // what a launch iterates over: a device table of n jobs, or the one job passed by value
+struct Batch { // what a launch iterates over: a device table of n jobs
     const PlaneJob *tab;
-    PlaneJob one;
     int n;
 };
-static dim3 grid3(int nx, int ny, const Batch &b) { return dim3((nx + 63) / 64, (ny + 3) / 4, b.tab ? b.n : 1); }
+static dim3 grid3(int nx, int ny, const Batch &b) { return dim3((nx + 63) / 64, (ny + 3) / 4, b.n); }
 static const dim3 kBlk(64, 4);
 
 template <int F> static void launch_fwd_sep(hipStream_t s, const Batch &b, bool u8, const LevelGeom &g, int s_sel, int d_sel)
 {
     if (u8) {
-        DSV2_LAUNCH((k_fwd_rows<F, true>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, b.one, g, s_sel);
+        DSV2_LAUNCH((k_fwd_rows<F, true>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, g, s_sel);
     } else {
-        DSV2_LAUNCH((k_fwd_rows<F, false>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, b.one, g, s_sel);
+        DSV2_LAUNCH((k_fwd_rows<F, false>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, g, s_sel);
     }
-    DSV2_LAUNCH((k_fwd_cols<F>), grid3(g.sw, g.hh, b), kBlk, 0, s, b.tab, b.one, g, d_sel);
+    DSV2_LAUNCH((k_fwd_cols<F>), grid3(g.sw, g.hh, b), kBlk, 0, s, b.tab, g, d_sel);
 }
 
 template <int F> static void launch_inv_sep(hipStream_t s, const Batch &b, bool u8, const LevelGeom &g, int ll_sel, int d_sel)
 {
-    DSV2_LAUNCH((k_inv_cols<F>), grid3(g.sw, g.hh, b), kBlk, 0, s, b.tab, b.one, g, ll_sel);
+    DSV2_LAUNCH((k_inv_cols<F>), grid3(g.sw, g.hh, b), kBlk, 0, s, b.tab, g, ll_sel);
     if (u8) {
-        DSV2_LAUNCH((k_inv_rows<F, true>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, b.one, g, d_sel);
+        DSV2_LAUNCH((k_inv_rows<F, true>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, g, d_sel);
     } else {
-        DSV2_LAUNCH((k_inv_rows<F, false>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, b.one, g, d_sel);
+        DSV2_LAUNCH((k_inv_rows<F, false>), grid3(g.hw, g.sh, b), kBlk, 0, s, b.tab, g, d_sel);
     }
 }
 
@@ -1018,12 +1012,8 @@ static LevelGeom level_geom(int cw, int ch, int l, int filter, int nbh, int nbv,
 constexpr int kTailLdsInts = 12 * 1024;
 static int tail_first_level(int cw, int ch, int plane_idx, int isP, int lossless, int lvls, int *cap_a)
 {
-    constexpr bool on = true;
     int l0 = lvls + 1;
     *cap_a = 0;
-    if (!on) {
-        return l0;
-    }
     for (int l = lvls; l >= 2; l--) { // (level 1 reads / writes the 8-bit picture: never part of the tail)
         int hw = (rshift_up(cw, l - 1) + 1) / 2, hh = (rshift_up(ch, l - 1) + 1) / 2;
         int hw2 = (hw + 1) / 2, hh2 = (hh + 1) / 2;
@@ -1044,7 +1034,7 @@ static void fwd_levels(hipStream_t s, const Batch &b, int cw, int ch, int plane_
     const int tail0 = tail_first_level(cw, ch, plane_idx, isP, lossless, lvls, &cap_a);
     for (int l = 1; l <= lvls; l++) {
         if (l == tail0) {
-            DSV2_LAUNCH(k_fwd_haar_tail, dim3(1, 1, b.tab ? b.n : 1), dim3(256), (size_t) kTailLdsInts * sizeof(int32_t), s, b.tab, b.one, cw, ch, tail0,
+            DSV2_LAUNCH(k_fwd_haar_tail, dim3(1, 1, b.n), dim3(256), (size_t) kTailLdsInts * sizeof(int32_t), s, b.tab, cw, ch, tail0,
                         lvls, lossless, cap_a);
             break;
         }
@@ -1058,13 +1048,13 @@ static void fwd_levels(hipStream_t s, const Batch &b, int cw, int ch, int plane_
         switch (filter) {
             case F_HAAR:
                 if (u8 && (g.hw & 3) == 0 && (g.w & 3) == 0) {
-                    DSV2_LAUNCH(k_fwd_haar_u8x4, grid3(g.hw / 4, (g.hh + kHaarRows - 1) / kHaarRows, b), kBlk, 0, s, b.tab, b.one, g, d_sel, ovf);
+                    DSV2_LAUNCH(k_fwd_haar_u8x4, grid3(g.hw / 4, (g.hh + kHaarRows - 1) / kHaarRows, b), kBlk, 0, s, b.tab, g, d_sel, ovf);
                 } else if (u8) {
-                    DSV2_LAUNCH((k_fwd_haar<true>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, b.one, g, s_sel, d_sel, ovf);
+                    DSV2_LAUNCH((k_fwd_haar<true>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, g, s_sel, d_sel, ovf);
                 } else if ((g.hw & 3) == 0 && (g.w & 3) == 0) {
-                    DSV2_LAUNCH(k_fwd_haar_i32x4, grid3(g.hw / 4, (g.hh + kHaarRowsI - 1) / kHaarRowsI, b), kBlk, 0, s, b.tab, b.one, g, s_sel, d_sel, ovf);
+                    DSV2_LAUNCH(k_fwd_haar_i32x4, grid3(g.hw / 4, (g.hh + kHaarRowsI - 1) / kHaarRowsI, b), kBlk, 0, s, b.tab, g, s_sel, d_sel, ovf);
                 } else {
-                    DSV2_LAUNCH((k_fwd_haar<false>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, b.one, g, s_sel, d_sel, ovf);
+                    DSV2_LAUNCH((k_fwd_haar<false>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, g, s_sel, d_sel, ovf);
                 }
                 break;
             case F_LLI: launch_fwd_sep<F_LLI>(s, b, u8, g, s_sel, d_sel); break;
@@ -1086,7 +1076,7 @@ static void inv_levels(hipStream_t s, const Batch &b, int cw, int ch, int plane_
     int cap_a = 0, top = lvls;
     const int tail0 = tail_first_level(cw, ch, plane_idx, isP, lossless, lvls, &cap_a);
     if (tail0 <= lvls) {
-        DSV2_LAUNCH(k_inv_haar_tail, dim3(1, 1, b.tab ? b.n : 1), dim3(256), (size_t) kTailLdsInts * sizeof(int32_t), s, b.tab, b.one, cw, ch, tail0, lvls,
+        DSV2_LAUNCH(k_inv_haar_tail, dim3(1, 1, b.n), dim3(256), (size_t) kTailLdsInts * sizeof(int32_t), s, b.tab, cw, ch, tail0, lvls,
                     lossless, plane_idx, isP, cap_a);
         ll_sel = (lvls - tail0) & 1; // where the level loop would have left level tail0's picture
         d_sel = ll_sel ^ 1;
@@ -1102,14 +1092,14 @@ static void inv_levels(hipStream_t s, const Batch &b, int cw, int ch, int plane_
                 int hdiv = (plane_idx == 0) ? (isP ? 14 : (l > 4 ? 2 : 8)) : 2;   // sbt.c:903
                 int filtered = !lossless && (plane_idx == 0 || !isP);               // sbt.c:925
                 if (u8 && (g.hw & 3) == 0 && (g.w & 3) == 0) {
-                    DSV2_LAUNCH(k_inv_haar_u8x4, grid3(g.hw / 4, g.hh, b), kBlk, 0, s, b.tab, b.one, g, ll_sel, ovf, filtered, hdiv);
+                    DSV2_LAUNCH(k_inv_haar_u8x4, grid3(g.hw / 4, g.hh, b), kBlk, 0, s, b.tab, g, ll_sel, ovf, filtered, hdiv);
                 } else if (u8) {
-                    DSV2_LAUNCH((k_inv_haar<true>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, b.one, g, ll_sel, d_sel, ovf,
+                    DSV2_LAUNCH((k_inv_haar<true>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, g, ll_sel, d_sel, ovf,
                                        filtered, hdiv);
                 } else if ((g.hw & 3) == 0 && (g.w & 3) == 0) {
-                    DSV2_LAUNCH(k_inv_haar_i32x4, grid3(g.hw / 4, g.hh, b), kBlk, 0, s, b.tab, b.one, g, ll_sel, d_sel, ovf, filtered, hdiv);
+                    DSV2_LAUNCH(k_inv_haar_i32x4, grid3(g.hw / 4, g.hh, b), kBlk, 0, s, b.tab, g, ll_sel, d_sel, ovf, filtered, hdiv);
                 } else {
-                    DSV2_LAUNCH((k_inv_haar<false>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, b.one, g, ll_sel, d_sel, ovf,
+                    DSV2_LAUNCH((k_inv_haar<false>), grid3(g.hw, g.hh, b), kBlk, 0, s, b.tab, g, ll_sel, d_sel, ovf,
                                        filtered, hdiv);
                 }
                 break;
@@ -1127,48 +1117,19 @@ static void inv_levels(hipStream_t s, const Batch &b, int cw, int ch, int plane_
     HIPCHK(hipGetLastError());
 }
 
-void sbt_forward(hipStream_t s, const DPlane &src, DCoefs dst, SbtScratch &sc, int plane_idx, int isP, int lossless,
-                 BlockMap bm)
-{
-    sc.ensure((size_t) dst.w * dst.h);
-    Batch b{nullptr, PlaneJob{}, 1};
-    b.one.pic = src;
-    b.one.coefs = dst.data;
-    for (int k = 0; k < 3; k++) {
-        b.one.t[k] = sc.t[k];
-    }
-    b.one.bd = bm.bd;
-    fwd_levels(s, b, dst.w, dst.h, plane_idx, isP, lossless, bm.nbh, bm.nbv, bm.bd != nullptr);
-}
-
-void sbt_inverse(hipStream_t s, DPlane dst, DCoefs src, SbtScratch &sc, int q, int plane_idx, int isP, int lossless,
-                 BlockMap bm)
-{
-    sc.ensure((size_t) src.w * src.h);
-    Batch b{nullptr, PlaneJob{}, 1};
-    b.one.pic = dst;
-    b.one.coefs = src.data;
-    for (int k = 0; k < 3; k++) {
-        b.one.t[k] = sc.t[k];
-    }
-    b.one.bd = bm.bd;
-    b.one.q = q;
-    inv_levels(s, b, src.w, src.h, plane_idx, isP, lossless, bm.nbh, bm.nbv, bm.bd != nullptr);
-}
-
 void sbt_forward_jobs(hipStream_t s, const PlaneJob *d_jobs, int n, int cw, int ch, int plane_idx, int isP, int lossless, int nbh,
-                      int nbv)
+                      int nbv, bool have_bd)
 {
     if (n > 0) {
-        fwd_levels(s, Batch{d_jobs, PlaneJob{}, n}, cw, ch, plane_idx, isP, lossless, nbh, nbv, true);
+        fwd_levels(s, Batch{d_jobs, n}, cw, ch, plane_idx, isP, lossless, nbh, nbv, have_bd);
     }
 }
 
 void sbt_inverse_jobs(hipStream_t s, const PlaneJob *d_jobs, int n, int cw, int ch, int plane_idx, int isP, int lossless, int nbh,
-                      int nbv)
+                      int nbv, bool have_bd)
 {
     if (n > 0) {
-        inv_levels(s, Batch{d_jobs, PlaneJob{}, n}, cw, ch, plane_idx, isP, lossless, nbh, nbv, true);
+        inv_levels(s, Batch{d_jobs, n}, cw, ch, plane_idx, isP, lossless, nbh, nbv, have_bd);
     }
 }
 
