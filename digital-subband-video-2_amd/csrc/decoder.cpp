@@ -562,10 +562,7 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
 
 void dec_batch(DecJob *jobs, int n)
 {
-    {
-        constexpr int fine_max = 1;
-        set_wait_fine(n <= fine_max); // (dev.cpp: a few streams are a latency chain, their waits poll finely)
-    }
+    set_wait_fine(n <= 1); // (dev.cpp: a single stream is a latency chain, its waits poll finely)
     bind_device();
     t_dec_clock.start();
     parallel_for(n, [&](int k) { dec_parse(jobs[k]); });

@@ -18,7 +18,6 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -914,31 +913,28 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
     // uploads of the NEXT step's host pictures run on a stream of their own, under this step's kernels
     hipStream_t copy_stream = nullptr;
     hipEvent_t copy_done = nullptr;
-    // side streams of a step: work that does not depend on the main chain runs beside it (the plane sections are
-    // assembled while the inverse transform / reconstruction / in-loop filters run; the intra pictures' filter sweeps
-    // beside the inter pictures')
-    hipStream_t aux[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork[2], ev_join[2];
+    // the side stream of a step: work that does not depend on the main chain runs beside it (the plane sections are
+    // assembled while the inverse transform / reconstruction / in-loop filters run)
+    hipStream_t aux = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     void ensure_aux()
     {
-        if (!aux[0]) {
-            for (int i = 0; i < 2; i++) {
-                HIPCHK(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
-                HIPCHK(hipEventCreateWithFlags(&ev_fork[i], hipEventDisableTiming));
-                HIPCHK(hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming));
-            }
+        if (!aux) {
+            HIPCHK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
+            HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
         }
     }
-    // the rest of `side` happens after everything enqueued on `main` so far
-    void fork(hipStream_t main, int i)
+    // what follows on `aux` happens after everything enqueued on `main` so far
+    void fork(hipStream_t main)
     {
-        HIPCHK(hipEventRecord(ev_fork[i], main));
-        HIPCHK(hipStreamWaitEvent(aux[i], ev_fork[i], 0));
+        HIPCHK(hipEventRecord(ev_fork, main));
+        HIPCHK(hipStreamWaitEvent(aux, ev_fork, 0));
     }
-    void join(hipStream_t main, int i)
+    void join(hipStream_t main)
     {
-        HIPCHK(hipEventRecord(ev_join[i], aux[i]));
-        HIPCHK(hipStreamWaitEvent(main, ev_join[i], 0));
+        HIPCHK(hipEventRecord(ev_join, aux));
+        HIPCHK(hipStreamWaitEvent(main, ev_join, 0));
     }
     void ensure_copy_stream()
     {
@@ -947,7 +943,7 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
             HIPCHK(hipEventCreateWithFlags(&copy_done, hipEventDisableTiming));
         }
     }
-    // working picture of a picture whose symbols are worked out a second time (redo_overflow: its compaction lists were too short)
+    // working picture of a picture whose symbols are worked out a second time (redo_overflowed_picture: its compaction lists were too short)
     DFrame redo;
     DFrame &redo_frame(int format, int w, int h)
     {
@@ -963,7 +959,7 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
     int cap = 0;
     void ensure(int n)
     {
-        tabs.reserve((size_t) n * 12288 + 65536); // (the last 4 KB a stream: the tables of a redone picture, enc_batch)
+        tabs.reserve((size_t) n * 12288 + 65536); // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture)
         if (n <= cap) {
             return;
         }
@@ -1065,7 +1061,7 @@ struct ScratchLease {
         // drain is never handed out again (leaked on purpose: its owner's encoders are dead, the process is not).
         if (std::uncaught_exceptions() > unwinding) {
             bool ok = true;
-            for (hipStream_t s : {sc->main, sc->aux[0], sc->aux[1], sc->copy_stream}) {
+            for (hipStream_t s : {sc->main, sc->aux, sc->copy_stream}) {
                 ok = ok && (!s || hipStreamSynchronize(s) == hipSuccess);
             }
             if (!ok) {
@@ -1077,6 +1073,12 @@ struct ScratchLease {
         g_scratch_pool.release(sc);
     }
 };
+
+static long env_int(const char *name, long dflt) // a DSV2_* switch; each is read where it was always read (once, per instance, per step)
+{
+    const char *v = getenv(name);
+    return v ? atol(v) : dflt;
+}
 
 // A step that cannot finish (the search token never comes, a search reports a time-out) fails the CALLS that are part of it --
 // every job of the step returns no packets, its encoder is marked dead -- not the process: the library lives inside somebody
@@ -1149,7 +1151,7 @@ void ensure_ready(DSV_ENCODER *enc, EncImpl *im)
     // is a symbol.  DSV2_COMPACT_CAP (symbols) forces a figure (tests: so small that pictures overflow and take the redo path).
     size_t list_syms = 0;
     if (enc->quality != DSV_RC_QUAL_MAX) {
-        const long forced = getenv("DSV2_COMPACT_CAP") ? atol(getenv("DSV2_COMPACT_CAP")) : -1; // (read per instance: tests set it)
+        const long forced = env_int("DSV2_COMPACT_CAP", -1); // (read per instance: tests set it)
         const int fmt = enc->vidmeta.subsamp;
         const size_t ncoef = (size_t) w * h + 2 * (size_t) ((w + (1 << DSV_FORMAT_H_SHIFT(fmt)) - 1) >> DSV_FORMAT_H_SHIFT(fmt)) * ((h + (1 << DSV_FORMAT_V_SHIFT(fmt)) - 1) >> DSV_FORMAT_V_SHIFT(fmt));
         list_syms = forced >= 0 ? (size_t) forced : std::max<size_t>(65536, ncoef / 2);
@@ -1306,7 +1308,7 @@ void phase_h1b(Job &jb)
     bs.put_bits(DSV_MAX_QP_BITS, (unsigned) d->quant);
     bs.put_bit(0);
     bs.align();
-    static const bool side_fallback = getenv("DSV2_SIDE_FORCE_FALLBACK") && atoi(getenv("DSV2_SIDE_FORCE_FALLBACK")) != 0; // (tests)
+    static const bool side_fallback = env_int("DSV2_SIDE_FORCE_FALLBACK", 0) != 0; // (tests)
     if (isP && jb.side_out && jb.side_info[0] == 0 && !side_fallback) {
         // the six sub-streams arrive coded (k_side_info); what stays here of encode_stable_blocks (dsv_encoder.c:797) is the
         // stability accumulator of the temporal AQ, which the next intra picture reads on the host
@@ -1504,8 +1506,8 @@ struct SearchTokenGuard { // releases on every way out of the scope that took th
 };
 
 // the plane sections of the packet are assembled on the GPU (DSV2_GPU_ENTROPY=0: the host codes them from the symbol list)
-static const bool kGpuEntropy = !(getenv("DSV2_GPU_ENTROPY") && atoi(getenv("DSV2_GPU_ENTROPY")) == 0);
-static const bool kEntForceFallback = getenv("DSV2_GPU_ENTROPY_FORCE_FALLBACK") && atoi(getenv("DSV2_GPU_ENTROPY_FORCE_FALLBACK")) != 0; // (tests)
+static const bool kGpuEntropy = env_int("DSV2_GPU_ENTROPY", 1) != 0;
+static const bool kEntForceFallback = env_int("DSV2_GPU_ENTROPY_FORCE_FALLBACK", 0) != 0; // (tests)
 static std::atomic<long> g_list_growths{0}; // pictures that had more symbols than their stream's compaction lists (dsv2hip_enc_list_growths)
 
 // tests: fail the next step of this process on purpose (dsv2hip_test_fail_next_step): 1 = as a search that did not deliver its
@@ -1514,7 +1516,7 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 static std::atomic<int> g_fail_next_step{0};
 
 // workgroups per (picture, plane) of the entropy coder's chunk kernels; each walks its share of the plane's 1 024-symbol chunks
-static const int kEntSlots = getenv("DSV2_ENT_SLOTS") ? atoi(getenv("DSV2_ENT_SLOTS")) : 32; // (192 until round 6: four in five of those workgroups found no chunk)
+static const int kEntSlots = (int) env_int("DSV2_ENT_SLOTS", 32); // (192 until round 6: four in five of those workgroups found no chunk)
 
 static void enc_batch_step(Job *jobs, int n);
 bool enc_batch_ok(Job *jobs, int n)
@@ -1540,27 +1542,86 @@ bool enc_batch_ok(Job *jobs, int n)
 }
 void enc_batch(Job *jobs, int n) { (void) enc_batch_ok(jobs, n); }
 
-static void enc_batch_step(Job *jobs, int n)
+// ---- one lockstep step: the phases of the comment above struct Job, as functions over one Step ----
+
+template <class T> struct Tab { // a job table in the step's arena: filled through h, handed to the kernels as d
+    T *h = nullptr;
+    const T *d = nullptr;
+    Tab() = default;
+    Tab(BatchScratch &sc, size_t count) { h = sc.tabs.take<T>(count, &d); }
+};
+
+struct Slice { // a run of G2's sorted order with one (frame type, lossless) class: one set of transform / quantiser launches
+    int first, count, isP, lossless;
+};
+
+static void first_step_mark(bool first, const char *what) // (DSV2_TRACE=1)
 {
+    if (first) {
+        startup_mark(what);
+    }
+}
+
+struct Step { // what outlives a phase; made behind P0, left behind H2 or by a StepFailed
+    Job *const jobs;
+    const int n;
+    const bool trace_startup;
+    StageProf &prof;
+    ScratchLease lease; // (a failed step's streams drain before another group may overwrite its tables)
+    BatchScratch &sc = *lease.sc;
+    // The step's kernels run on a stream that belongs to the batch scratch (made once, see ScratchPool::acquire), not on one
+    // of the encoders': a step starts and ends with that stream drained, so which stream carried an encoder's previous step
+    // does not matter.
+    hipStream_t bs = nullptr;
+    CodecDev &dv0; // the geometry every encoder of the step shares
+    const int nbh, nbv, do_psy;
+    size_t pbytes; // a packed planar picture as the callers hand it over: Y, U, V rows without padding
+    // The entropy kernels of a SMALL batch (fewer than 12 streams: the step is a chain of latency-bound launches on a mostly
+    // idle GPU) run on the aux stream beside inverse transform / reconstruction / filters, a large batch keeps one chain (no
+    // throughput gain there, more host work; re-measured in round 6 with 192-picture launches: -0.6 %, and with the intra
+    // filter on a second side stream as well +0.2 %: a group's chain in parallel with itself buys nothing)
+    const bool aux_entropy;
+    // G1: the searches of the step (pictures that arrive as P frames), and the controller's sums over their fields
+    std::vector<HmeFrames> hf;
+    std::vector<HmeParams> hp;
+    std::vector<int> searched;
+    Tab<BlockStatsJob> bsj;
+    int n_bsj = 0;
+    // H1: the pictures that stay P frames, and the intra pictures
+    std::vector<int> p_jobs, i_jobs;
+    // G2: streams are ordered by (frame type, lossless): the transform / quantiser kernels are specialised on those, so each
+    // class is one set of launches over its slice of the job tables.  order[slot] = job, slot_of[job] = slot.
+    std::vector<int> order, slot_of;
+    std::vector<Slice> slices;
+    Tab<CopyJob> copy, mvcopy;
+    Tab<PlaneJob> py, pc;
+    Tab<CompactJob> comp;
+    Tab<EntJob> ent;
+    Tab<DPlane> rext_y, rext_c;
+    size_t mv_bytes = 0, slot = 0; // one motion field; a staging slot: one picture's flag bytes
+    int nP = 0, nI = 0, n_rext = 0, n_mvcopy = 0, n_slots = 0, n_copy = 0;
+    bool any_filter = false;
+
+    Step(Job *jobs_, int n_, bool trace_startup_)
+        : jobs(jobs_), n(n_), trace_startup(trace_startup_), prof(jobs_[0].im->dev.prof), dv0(jobs_[0].im->dev), nbh(dv0.nbh), nbv(dv0.nbv),
+          do_psy(jobs_[0].d.params.do_psy), aux_entropy(n_ < 12)
     {
-        constexpr int fine_max = 1;
-        set_wait_fine(n <= fine_max);
+        first_step_mark(trace_startup, "batch scratch + streams ready");
+        bs = sc.main_stream();
+        sc.ensure(n);
+        const DFrame &f0 = dv0.pics[0].src;
+        pbytes = (size_t) f0.p[0].w * f0.p[0].h + (size_t) f0.p[1].w * f0.p[1].h + (size_t) f0.p[2].w * f0.p[2].h;
     }
-    // side streams within the step: bit 0 entropy coder, bit 1 intra filter.  The entropy kernels of a SMALL batch (fewer than
-    // 12 streams: the step is a chain of latency-bound launches on a mostly idle GPU) run beside inverse transform /
-    // reconstruction / filters, a large batch keeps one chain (no throughput gain there, more host work; re-measured in round 6
-    // with 192-picture launches: 1 -> -0.6 %, 3 -> +0.2 %: a group's chain in parallel with itself buys nothing)
-    const int kAuxStreams = n < 12 ? 1 : 0;
-    static bool first_step = true; // (DSV2_TRACE=1 only; a benign race)
-    const bool trace_startup = first_step;
-    first_step = false;
-    if (trace_startup) {
-        startup_mark("first step entered");
-    }
+};
+
+static bool is_420(int format) { return DSV_FORMAT_H_SHIFT(format) == 1 && DSV_FORMAT_V_SHIFT(format) == 1; }
+
+static void step_p0(Job *jobs, int n, bool trace_startup)
+{
+    set_wait_fine(n <= 1); // (dev.cpp: a single stream is a latency chain, its waits poll finely)
+    first_step_mark(trace_startup, "first step entered");
     bind_device();
-    if (trace_startup) {
-        startup_mark("device bound (HIP runtime up)");
-    }
+    first_step_mark(trace_startup, "device bound (HIP runtime up)");
     t_clock.start();
     for (int k = 0; k < n; k++) {
         Job &jb = jobs[k];
@@ -1577,134 +1638,115 @@ static void enc_batch_step(Job *jobs, int n)
         phase_p0(jb);
     }
     t_clock.lap(0);
-    if (trace_startup) {
-        startup_mark("encoder instances allocated");
-    }
-    StageProf &prof = jobs[0].im->dev.prof;
-    ScratchLease lease;
-    BatchScratch &sc = *lease.sc;
-    if (trace_startup) {
-        startup_mark("batch scratch + streams ready");
-    }
-    // The step's kernels run on a stream that belongs to the batch scratch (made once, see ScratchPool::acquire), not on one
-    // of the encoders': a step starts and ends with that stream drained, so which stream carried an encoder's previous step
-    // does not matter.
-    hipStream_t bs = sc.main_stream();
-    sc.ensure(n);
-    const int nbh = jobs[0].im->dev.nbh, nbv = jobs[0].im->dev.nbv;
+    first_step_mark(trace_startup, "encoder instances allocated");
+}
 
-    // ---- G1 ----
-    // every per-picture helper runs ONCE for the whole batch over a device table of jobs
-    CodecDev &dv0 = jobs[0].im->dev;
-    const int L = dv0.pyr_levels;
-    prof.begin(bs, ST_INGEST);
-    std::vector<HmeFrames> hf;
-    std::vector<HmeParams> hp;
-    std::vector<int> pjobs;
-    const IngestJob *d_ing, *d_ingu;
-    IngestJob *h_ing = sc.tabs.take<IngestJob>((size_t) n, &d_ing), *h_ingu = sc.tabs.take<IngestJob>((size_t) n, &d_ingu);
-    int n_ingu = 0;
-    const DPlane *d_ext_y, *d_ext_c;
-    DPlane *h_ext_y = sc.tabs.take<DPlane>((size_t) n, &d_ext_y), *h_ext_c = sc.tabs.take<DPlane>(2 * (size_t) n, &d_ext_c);
-    const PlanePair *d_pair[DSV_MAX_PYRAMID_LEVELS];
-    PlanePair *h_pair[DSV_MAX_PYRAMID_LEVELS];
-    const DPlane *d_pext[DSV_MAX_PYRAMID_LEVELS];
-    DPlane *h_pext[DSV_MAX_PYRAMID_LEVELS];
-    for (int l = 0; l < L; l++) {
-        h_pair[l] = sc.tabs.take<PlanePair>(2 * (size_t) n, &d_pair[l]);
-        h_pext[l] = sc.tabs.take<DPlane>(2 * (size_t) n, &d_pext[l]);
-    }
-    const IntraJob *d_intra;
-    IntraJob *h_intra = sc.tabs.take<IntraJob>((size_t) n, &d_intra);
-    const PlaneOutJob *d_small;
-    PlaneOutJob *h_small = sc.tabs.take<PlaneOutJob>((size_t) n, &d_small);
-    const BlockStatsJob *d_bsj;
-    BlockStatsJob *h_bsj = sc.tabs.take<BlockStatsJob>((size_t) n, &d_bsj);
-    int n_ing = 0, n_pyr = 0, n_intra = 0, n_bsj = 0;
-    std::function<void()> upload_next;
-    {
-        // pictures that arrive in host memory: this step's either came up during the previous step (prefetched
-        // through host_next) or is uploaded now; the next step's goes up on the copy stream under this step's kernels
-        const DFrame &f0 = dv0.pics[0].src;
-        const size_t pbytes = (size_t) f0.p[0].w * f0.p[0].h + (size_t) f0.p[1].w * f0.p[1].h + (size_t) f0.p[2].w * f0.p[2].h;
-        hipEvent_t waited[4] = {nullptr, nullptr, nullptr, nullptr};
-        int nwaited = 0;
-        for (int k = 0; k < n; k++) {
-            Job &jb = jobs[k];
-            EncImpl *im = jb.im;
-            if (!jb.host_planar) {
-                continue;
-            }
-            if (!im->d_stage[0]) {
-                HIPCHK(hipMalloc((void **) &im->d_stage[0], pbytes));
-                HIPCHK(hipMalloc((void **) &im->d_stage[1], pbytes));
-            }
-            if (im->staged_src == (const void *) jb.host_planar) {
-                im->stage_cur ^= 1;
-                bool seen = false;
-                for (int e = 0; e < nwaited; e++) {
-                    seen = seen || waited[e] == im->staged_ev;
-                }
-                if (!seen) {
-                    HIPCHK(hipStreamWaitEvent(bs, im->staged_ev, 0));
-                    if (nwaited < 4) {
-                        waited[nwaited++] = im->staged_ev;
-                    }
-                }
-            } else {
-                HIPCHK(hipMemcpyAsync(im->d_stage[im->stage_cur], jb.host_planar, pbytes, hipMemcpyHostToDevice, bs));
-            }
-            im->staged_src = nullptr;
-            jb.dev_planar = im->d_stage[im->stage_cur];
+// pictures that arrive in host memory: this step's either came up during the previous step (prefetched through host_next)
+// or is uploaded now
+static void g1_stage_inputs(Step &st)
+{
+    hipEvent_t waited[4] = {nullptr, nullptr, nullptr, nullptr};
+    int nwaited = 0;
+    for (int k = 0; k < st.n; k++) {
+        Job &jb = st.jobs[k];
+        EncImpl *im = jb.im;
+        if (!jb.host_planar) {
+            continue;
         }
-        // the next step's pictures go up on the copy stream under this step's kernels.  The calls themselves -- one per stream --
-        // cost the host several milliseconds for a large batch: they are made once this step's pre-search work and its search
-        // have been handed to the GPU
-        upload_next = [&jobs, n, pbytes, &sc] {
-            bool any = false;
-            for (int k = 0; k < n; k++) {
-                Job &jb = jobs[k];
-                if (jb.host_planar && jb.host_next) {
-                    sc.ensure_copy_stream();
-                    HIPCHK(hipMemcpyAsync(jb.im->d_stage[jb.im->stage_cur ^ 1], jb.host_next, pbytes, hipMemcpyHostToDevice, sc.copy_stream));
-                    jb.im->staged_src = jb.host_next;
-                    jb.im->staged_ev = sc.copy_done;
-                    any = true;
+        if (!im->d_stage[0]) {
+            HIPCHK(hipMalloc((void **) &im->d_stage[0], st.pbytes));
+            HIPCHK(hipMalloc((void **) &im->d_stage[1], st.pbytes));
+        }
+        if (im->staged_src == (const void *) jb.host_planar) {
+            im->stage_cur ^= 1;
+            bool seen = false;
+            for (int e = 0; e < nwaited; e++) {
+                seen = seen || waited[e] == im->staged_ev;
+            }
+            if (!seen) {
+                HIPCHK(hipStreamWaitEvent(st.bs, im->staged_ev, 0));
+                if (nwaited < 4) {
+                    waited[nwaited++] = im->staged_ev;
                 }
             }
-            if (any) {
-                HIPCHK(hipEventRecord(sc.copy_done, sc.copy_stream));
-            }
-        };
+        } else {
+            HIPCHK(hipMemcpyAsync(im->d_stage[im->stage_cur], jb.host_planar, st.pbytes, hipMemcpyHostToDevice, st.bs));
+        }
+        im->staged_src = nullptr;
+        jb.dev_planar = im->d_stage[im->stage_cur];
     }
+}
+
+// The next step's host pictures go up on the copy stream under this step's kernels.  The calls themselves -- one per stream --
+// cost the host several milliseconds for a large batch: they are made once this step's pre-search work and its search have
+// been handed to the GPU.
+static void upload_next(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    bool any = false;
+    for (int k = 0; k < st.n; k++) {
+        Job &jb = st.jobs[k];
+        if (jb.host_planar && jb.host_next) {
+            sc.ensure_copy_stream();
+            HIPCHK(hipMemcpyAsync(jb.im->d_stage[jb.im->stage_cur ^ 1], jb.host_next, st.pbytes, hipMemcpyHostToDevice, sc.copy_stream));
+            jb.im->staged_src = jb.host_next;
+            jb.im->staged_ev = sc.copy_done;
+            any = true;
+        }
+    }
+    if (any) {
+        HIPCHK(hipEventRecord(sc.copy_done, sc.copy_stream));
+    }
+}
+
+// ingest, border extension, pyramids, the coarsest level's read-back, the intra pictures' block analysis: every per-picture
+// helper runs ONCE for the whole batch over a device table of jobs
+static void g1_enqueue(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    hipStream_t bs = st.bs;
+    const CodecDev &dv0 = st.dv0;
+    const int n = st.n, L = dv0.pyr_levels;
+    Tab<IngestJob> ing(sc, (size_t) n), ingu(sc, (size_t) n);
+    Tab<DPlane> ext_y(sc, (size_t) n), ext_c(sc, 2 * (size_t) n);
+    Tab<PlanePair> pair[DSV_MAX_PYRAMID_LEVELS];
+    Tab<DPlane> pext[DSV_MAX_PYRAMID_LEVELS];
+    for (int l = 0; l < L; l++) {
+        pair[l] = Tab<PlanePair>(sc, 2 * (size_t) n);
+        pext[l] = Tab<DPlane>(sc, 2 * (size_t) n);
+    }
+    Tab<IntraJob> intra(sc, (size_t) n);
+    Tab<PlaneOutJob> small(sc, (size_t) n);
+    st.bsj = Tab<BlockStatsJob>(sc, (size_t) n);
+    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0;
     for (int k = 0; k < n; k++) {
-        Job &jb = jobs[k];
+        Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
         PicSet &cur = dv.pics[jb.im->cur], &ref = dv.pics[jb.im->cur ^ 1];
-        if (jb.d.params.do_psy != jobs[0].d.params.do_psy) {
+        if (jb.d.params.do_psy != st.do_psy) {
             fatal("dsv2hip_enc_batch: all encoders of a batch must share one do_psy setting", __FILE__, __LINE__);
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
         } else {
-            IngestJob &ij = jb.im->input_uyvy && !jb.from_frame ? h_ingu[n_ingu++] : h_ing[n_ing++];
+            IngestJob &ij = jb.im->input_uyvy && !jb.from_frame ? ingu.h[n_ingu++] : ing.h[n_ing++];
             ij.src = jb.dev_planar;
             for (int c = 0; c < 3; c++) {
                 ij.dst[c] = cur.src.p[c];
             }
         }
-        h_ext_y[k] = cur.src.p[0];
-        h_ext_c[2 * k] = cur.src.p[1];
-        h_ext_c[2 * k + 1] = cur.src.p[2];
+        ext_y.h[k] = cur.src.p[0];
+        ext_c.h[2 * k] = cur.src.p[1];
+        ext_c.h[2 * k + 1] = cur.src.p[2];
         for (int l = 0; l < L; l++) { // mk_pyramid, dsv_encoder.c:493
-            h_pair[l][n_pyr] = PlanePair{l ? cur.src_pyr[l - 1].p[0] : cur.src.p[0], cur.src_pyr[l].p[0]};
-            h_pext[l][n_pyr] = cur.src_pyr[l].p[0];
+            pair[l].h[n_pyr] = PlanePair{l ? cur.src_pyr[l - 1].p[0] : cur.src.p[0], cur.src_pyr[l].p[0]};
+            pext[l].h[n_pyr] = cur.src_pyr[l].p[0];
         }
         n_pyr++;
         if (jb.d.params.has_ref && !ref.recon_pyr_valid) {
             for (int l = 0; l < L; l++) {
-                h_pair[l][n_pyr] = PlanePair{l ? ref.recon_pyr[l - 1].p[0] : ref.recon.p[0], ref.recon_pyr[l].p[0]};
-                h_pext[l][n_pyr] = ref.recon_pyr[l].p[0];
+                pair[l].h[n_pyr] = PlanePair{l ? ref.recon_pyr[l - 1].p[0] : ref.recon.p[0], ref.recon_pyr[l].p[0]};
+                pext[l].h[n_pyr] = ref.recon_pyr[l].p[0];
             }
             n_pyr++;
             ref.recon_pyr_valid = true;
@@ -1713,99 +1755,110 @@ static void enc_batch_step(Job *jobs, int n)
         // frame that H1 flips to intra gets its analysis then)
         if (!jb.d.params.has_ref) {
             for (int c = 0; c < 3; c++) {
-                h_intra[n_intra].src.p[c] = cur.src.p[c];
+                intra.h[n_intra].src.p[c] = cur.src.p[c];
             }
-            h_intra[n_intra].out = dv.h_intra;
+            intra.h[n_intra].out = dv.h_intra;
             n_intra++;
         }
-        h_small[k] = PlaneOutJob{cur.src_pyr[L - 1].p[0], dv.h_small};
+        small.h[k] = PlaneOutJob{cur.src_pyr[L - 1].p[0], dv.h_small};
         jb.bstats = nullptr;
         if (jb.d.params.has_ref) { // the controller's sums over the field this step's search is about to produce
-            BlockStatsJob &bj = h_bsj[n_bsj];
+            BlockStatsJob &bj = st.bsj.h[st.n_bsj];
             bj.mvs = dv.d_mvf[0];
             bj.counters = dv.d_counters;
             bj.map_in = jb.im->map_valid ? dv.d_intra_map[jb.im->map_cur] : nullptr;
             bj.map_out = dv.d_intra_map[jb.im->map_cur ^ 1];
             bj.host_mvs = dv.h_mvs;
-            bj.out = sc.d_bstats + (size_t) n_bsj * BS_WORDS;
+            bj.out = sc.d_bstats + (size_t) st.n_bsj * BS_WORDS;
             bj.b2sr = mv_cost_b2sr(&jb.d.params, jb.enc->prev_quant);
             bj.rc_mode = jb.enc->rc_mode;
-            jb.bstats = sc.h_bstats + (size_t) n_bsj * BS_WORDS;
-            n_bsj++;
+            jb.bstats = sc.h_bstats + (size_t) st.n_bsj * BS_WORDS;
+            st.n_bsj++;
         }
     }
+    const DFrame &f0 = dv0.pics[0].src;
     sc.tabs.upload(bs);
-    {
-        const DFrame &f0 = dv0.pics[0].src;
-        {
-            bool wide = f0.p[0].w <= 2048 && (f0.p[0].w % 16) == 0 && (f0.p[1].w % 16) == 0 && (f0.p[2].w % 16) == 0 &&
-                        (((size_t) f0.p[0].w * f0.p[0].h) % 16) == 0 && (((size_t) f0.p[1].w * f0.p[1].h) % 16) == 0;
-            for (int k = 0; k < n_ing && wide; k++) {
-                wide = ((uintptr_t) h_ing[k].src % 16) == 0;
-            }
-            if (wide) {
-                ingest_batch16(bs, d_ing, n_ing, f0.p[0].h + f0.p[1].h + f0.p[2].h);
-            } else {
-                ingest_batch(bs, d_ing, n_ing, f0.p[0].w, f0.p[0].h + f0.p[1].h + f0.p[2].h);
-            }
-        }
-        ingest_uyvy_batch(bs, d_ingu, n_ingu, f0.p[0].w, f0.p[0].h);
-        extend_planes(bs, d_ext_y, n, f0.p[0].w, f0.p[0].h);
-        extend_planes(bs, d_ext_c, 2 * n, f0.p[1].w, f0.p[1].h);
-        for (int l = 0; l < L; l++) {
-            const DPlane &lp = dv0.pics[0].src_pyr[l].p[0];
-            ds2x_planes4(bs, d_pair[l], n_pyr, lp.w, lp.h); // (picture sets are dframe_alloc'd: aligned)
-            extend_planes(bs, d_pext[l], n_pyr, lp.w, lp.h);
-        }
-        planes_to_host_batch(bs, d_small, n, dv0.pics[0].src_pyr[L - 1].p[0].h);
-        intra_analysis_batch(bs, d_intra, n_intra, analysis_params(dv0, jobs[0].d.params.do_psy));
+    bool wide = f0.p[0].w <= 2048 && (f0.p[0].w % 16) == 0 && (f0.p[1].w % 16) == 0 && (f0.p[2].w % 16) == 0 &&
+                (((size_t) f0.p[0].w * f0.p[0].h) % 16) == 0 && (((size_t) f0.p[1].w * f0.p[1].h) % 16) == 0;
+    for (int k = 0; k < n_ing && wide; k++) {
+        wide = ((uintptr_t) ing.h[k].src % 16) == 0;
     }
-    for (int k = 0; k < n; k++) {
-        Job &jb = jobs[k];
+    if (wide) {
+        ingest_batch16(bs, ing.d, n_ing, f0.p[0].h + f0.p[1].h + f0.p[2].h);
+    } else {
+        ingest_batch(bs, ing.d, n_ing, f0.p[0].w, f0.p[0].h + f0.p[1].h + f0.p[2].h);
+    }
+    ingest_uyvy_batch(bs, ingu.d, n_ingu, f0.p[0].w, f0.p[0].h);
+    extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
+    extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
+    for (int l = 0; l < L; l++) {
+        const DPlane &lp = dv0.pics[0].src_pyr[l].p[0];
+        ds2x_planes4(bs, pair[l].d, n_pyr, lp.w, lp.h); // (picture sets are dframe_alloc'd: aligned)
+        extend_planes(bs, pext[l].d, n_pyr, lp.w, lp.h);
+    }
+    planes_to_host_batch(bs, small.d, n, dv0.pics[0].src_pyr[L - 1].p[0].h);
+    intra_analysis_batch(bs, intra.d, n_intra, analysis_params(dv0, st.do_psy));
+}
+
+// motion_est (dsv_encoder.c:653) of the pictures that arrive as P frames, as far as it needs no search slots: job table,
+// clears, the source blocks' statistics -- nothing the token is for
+static void g1_prepare_search(Step &st)
+{
+    for (int k = 0; k < st.n; k++) {
+        Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
         PicSet &cur = dv.pics[jb.im->cur], &ref = dv.pics[jb.im->cur ^ 1];
-        if (jb.d.params.has_ref) { // motion_est (dsv_encoder.c:653)
-            HmeFrames f;
-            f.src[0] = cur.src.p[0];
-            f.ref[0] = ref.recon.p[0];
-            f.ogr[0] = ref.src.p[0];
-            for (int l = 0; l < dv.pyr_levels; l++) {
-                f.src[l + 1] = cur.src_pyr[l].p[0];
-                f.ref[l + 1] = ref.recon_pyr[l].p[0];
-                f.ogr[l + 1] = ref.src_pyr[l].p[0];
-            }
-            for (int c = 0; c < 2; c++) {
-                f.srcc[c] = cur.src.p[c + 1];
-                f.refc[c] = ref.recon.p[c + 1];
-            }
-            for (int l = 0; l <= dv.pyr_levels; l++) {
-                f.mvf[l] = dv.d_mvf[l];
-            }
-            f.ref_mvf = ref.has_final_mvs ? ref.d_final_mvs : nullptr;
-            f.counters = dv.d_counters;
-            f.src_stats = dv.d_src_stats;
-            f.l0_pre = dv.d_l0_pre;
-            f.host_mvs = nullptr; // (the field reaches the host through k_block_stats_b right behind the search: BlockStatsJob::host_mvs)
-            f.host_counters = dv.h_counters;
-            dv.h_counters[7] = -1; // overwritten with 0 by the search's last row (1: a row timed out); -1 left = it never finished
-            dv.h_counters[kHmeHostTailWord] = 0;
-            HmeParams h;
-            h.a = analysis_params(dv, jb.d.params.do_psy);
-            h.effort = jb.d.params.effort;
-            h.lossless = jb.d.params.lossless;
-            h.quant = jb.enc->prev_quant;
-            h.skip_block_thresh = jb.enc->skip_block_thresh;
-            h.pyr_levels = dv.pyr_levels;
-            hf.push_back(f);
-            hp.push_back(h);
-            pjobs.push_back(k);
-            jb.ran_hme = 1;
+        if (!jb.d.params.has_ref) {
+            continue;
         }
+        HmeFrames f;
+        f.src[0] = cur.src.p[0];
+        f.ref[0] = ref.recon.p[0];
+        f.ogr[0] = ref.src.p[0];
+        for (int l = 0; l < dv.pyr_levels; l++) {
+            f.src[l + 1] = cur.src_pyr[l].p[0];
+            f.ref[l + 1] = ref.recon_pyr[l].p[0];
+            f.ogr[l + 1] = ref.src_pyr[l].p[0];
+        }
+        for (int c = 0; c < 2; c++) {
+            f.srcc[c] = cur.src.p[c + 1];
+            f.refc[c] = ref.recon.p[c + 1];
+        }
+        for (int l = 0; l <= dv.pyr_levels; l++) {
+            f.mvf[l] = dv.d_mvf[l];
+        }
+        f.ref_mvf = ref.has_final_mvs ? ref.d_final_mvs : nullptr;
+        f.counters = dv.d_counters;
+        f.src_stats = dv.d_src_stats;
+        f.l0_pre = dv.d_l0_pre;
+        f.host_mvs = nullptr; // (the field reaches the host through k_block_stats_b right behind the search: BlockStatsJob::host_mvs)
+        f.host_counters = dv.h_counters;
+        dv.h_counters[7] = -1; // overwritten with 0 by the search's last row (1: a row timed out); -1 left = it never finished
+        dv.h_counters[kHmeHostTailWord] = 0;
+        HmeParams h;
+        h.a = analysis_params(dv, jb.d.params.do_psy);
+        h.effort = jb.d.params.effort;
+        h.lossless = jb.d.params.lossless;
+        h.quant = jb.enc->prev_quant;
+        h.skip_block_thresh = jb.enc->skip_block_thresh;
+        h.pyr_levels = dv.pyr_levels;
+        st.hf.push_back(f);
+        st.hp.push_back(h);
+        st.searched.push_back(k);
+        jb.ran_hme = 1;
     }
-    if (!pjobs.empty()) { // job table, clears, the source blocks' statistics: nothing the token is for
-        hme_run_batch(bs, hf.data(), hp.data(), (int) pjobs.size(), sc.h_hme, sc.d_hme, nullptr, -1, 0, HME_PREPARE);
+    if (!st.searched.empty()) {
+        hme_run_batch(st.bs, st.hf.data(), st.hp.data(), (int) st.searched.size(), st.sc.h_hme, st.sc.d_hme, nullptr, HME_PREPARE);
     }
-    prof.end(bs, ST_INGEST, n);
+}
+
+// The levels of the search, the controller's sums over its result, and -- for a search large enough -- the token protocol
+// around them.  The token is local to this phase: every way out of it, a StepFailed included, lets go of it.
+static void search_under_token(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    hipStream_t bs = st.bs;
+    const int nsearch = (int) st.searched.size();
     // (only launches that keep the chip's search slots -- 3 072 persistent workers -- full for most of their length take the token: a row-pipelined
     // launch ramps up and down over one picture's critical path, ~2 ms whatever the batch, and launches of a few dozen
     // pictures hide each other's ramps when they overlap)
@@ -1813,7 +1866,7 @@ static void enc_batch_step(Job *jobs, int n)
     // streams -- gain 3 % from the token, 6 880 -> 7 090 frames/s, 4 groups of 6 528 rows 3.4 %; at 2 176 rows a group the token
     // costs 3 %, at 816 it makes no difference.  3 072 rows it is: one set of the persistent workers.)
     constexpr int min_rows = 3072;
-    const bool searching = !pjobs.empty() && (int) pjobs.size() * nbv >= min_rows;
+    const bool searching = nsearch > 0 && nsearch * st.nbv >= min_rows;
     SearchTokenGuard token;
     if (g_fail_next_step.load() == 2 && g_fail_next_step.exchange(0) == 2) {
         throw StepFailed{"search token not released (test hook)"};
@@ -1821,401 +1874,414 @@ static void enc_batch_step(Job *jobs, int n)
     if (searching) {
         // the token is for the search alone: what precedes it on the stream (this step's upload, ingest, pyramids) is waited
         // for BEFORE taking it, or the holder would sit on the token while its own pictures are still crossing PCIe.
-        // (Running the coarse levels -- launches that cannot fill the slots -- outside the token, beside another group's
-        // level-0 launch, was tried: hme_run_batch takes a level range for it; no gain, they slow the holder's launch.)
+        // (Coarse levels outside the token, beside another group's level-0 launch: tried, no gain, round 5.)
         stream_wait(bs);
-        t_clock.mark("pre-search-drained", n);
+        t_clock.mark("pre-search-drained", st.n);
+        token.acquire(); // (released once the search has handed out its last row, below)
+        t_clock.mark("token", st.n);
     }
-    // DSV2_COARSE_OUTSIDE: the coarse levels -- five launches that are dependency chains and cannot fill the chip -- run BEFORE the
-    // token is taken, beside whatever level-0 launch holds it; the token then covers the level-0 launch alone.  1: queue for the
-    // token at once (the level-0 launch follows the coarse levels on the stream); 2: when the coarse levels have finished.
-    constexpr int coarse_outside = 0;
-    const bool split_levels = searching && coarse_outside && dv0.pyr_levels >= 1;
-    int nfronts_coarse = 0;
-    if (split_levels) {
-        prof.begin(bs, ST_HME);
-        nfronts_coarse = hme_run_batch(bs, hf.data(), hp.data(), (int) pjobs.size(), sc.h_hme, sc.d_hme, &prof, -1, 1, HME_LEVELS);
-        if (coarse_outside >= 2) {
-            stream_wait(bs);
-        }
-        t_clock.mark("coarse-levels", n);
+    if (nsearch) {
+        st.prof.begin(bs, ST_HME);
+        int nfronts = hme_run_batch(bs, st.hf.data(), st.hp.data(), nsearch, sc.h_hme, sc.d_hme, &st.prof, HME_LEVELS);
+        st.prof.end(bs, ST_HME, nsearch, nfronts); // launches = the per-level search kernels
+        HIPCHK(hipMemsetAsync(sc.d_bstats, 0, (size_t) st.n_bsj * BS_WORDS * sizeof(int), bs));
+        block_stats_batch(bs, st.bsj.d, st.n_bsj, st.nbh, st.nbv);
+        HIPCHK(hipMemcpyAsync(sc.h_bstats, sc.d_bstats, (size_t) st.n_bsj * BS_WORDS * sizeof(int), hipMemcpyDeviceToHost, bs));
     }
-    if (searching) {
-        token.acquire(); // (released once the search has drained, below)
-        t_clock.mark("token", n);
-    }
-    if (!pjobs.empty()) {
-        if (!split_levels) {
-            prof.begin(bs, ST_HME);
-        }
-        int nfronts = nfronts_coarse + hme_run_batch(bs, hf.data(), hp.data(), (int) pjobs.size(), sc.h_hme, sc.d_hme, &prof, split_levels ? 0 : -1, 0, HME_LEVELS);
-        prof.end(bs, ST_HME, (int) pjobs.size(), nfronts); // launches = the per-level search kernels
-        HIPCHK(hipMemsetAsync(sc.d_bstats, 0, (size_t) n_bsj * BS_WORDS * sizeof(int), bs));
-        block_stats_batch(bs, d_bsj, n_bsj, nbh, nbv);
-        HIPCHK(hipMemcpyAsync(sc.h_bstats, sc.d_bstats, (size_t) n_bsj * BS_WORDS * sizeof(int), hipMemcpyDeviceToHost, bs));
-    }
-    if (upload_next) {
-        upload_next();
-    }
+    upload_next(st);
     t_clock.lap(1);
     if (searching) {
         // The token is passed on when the level-0 launch has handed out its last block row (the kernel says so in the first
         // stream's pinned counter block): what is left of it is a tail of draining wavefronts -- one row's walk, ~2 ms --
         // whose freed slots the next group's search can take.  (Launch-per-front form, or a launch that ends first: the
         // stream's completion.)
-        volatile int *tail = &jobs[pjobs[0]].im->dev.h_counters[kHmeHostTailWord];
-        // DSV2_SEARCH_EARLY_RELEASE: 1 (default) at the tail; 0 when the launch has finished; 2 right after it was enqueued
-        constexpr int early = 1;
-        if (early == 0) {
-            stream_wait(bs);
-        } else if (early == 1) {
-            while (!*tail && hipStreamQuery(bs) == hipErrorNotReady) {
-                timespec ts = {0, 100000};
-                nanosleep(&ts, nullptr);
-            }
+        volatile int *tail = &st.jobs[st.searched[0]].im->dev.h_counters[kHmeHostTailWord];
+        while (!*tail && hipStreamQuery(bs) == hipErrorNotReady) {
+            timespec ts = {0, 100000};
+            nanosleep(&ts, nullptr);
         }
         token.release();
-        t_clock.mark("token-released", n);
+        t_clock.mark("token-released", st.n);
     }
-    stream_wait(bs);
+}
+
+// P frames flipped to intra by the scene-change test: their block analysis is due now
+static void late_intra_analysis(Step &st)
+{
+    Tab<IntraJob> late(st.sc, (size_t) st.n);
+    int n_late = 0;
+    for (int k = 0; k < st.n; k++) {
+        Job &jb = st.jobs[k];
+        if (jb.ran_hme && !jb.d.params.has_ref) {
+            PicSet &cur = jb.im->dev.pics[jb.im->cur];
+            for (int c = 0; c < 3; c++) {
+                late.h[n_late].src.p[c] = cur.src.p[c];
+            }
+            late.h[n_late].out = jb.im->dev.h_intra;
+            n_late++;
+        }
+    }
+    if (n_late) {
+        st.sc.tabs.upload(st.bs);
+        intra_analysis_batch(st.bs, late.d, n_late, analysis_params(st.dv0, st.do_psy));
+        stream_wait(st.bs);
+    }
+}
+
+// The pictures that stay P frames: their side information is coded on the device (k_side_info), which also finalises
+// the motion field and forms the block flag bytes in HBM for G2.  It is enqueued now, G2 right behind it; the host
+// assembles the P packets' heads (H1b) from the pinned sub-streams while G2 runs.  Intra pictures (1 in a GOP) keep
+// the host coders, whose flag bytes G2 needs: their H1b runs before G2 is built.
+static void enqueue_side_info(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    for (int k = 0; k < st.n; k++) {
+        st.jobs[k].side_out = nullptr;
+        st.jobs[k].side_info = nullptr;
+        (st.jobs[k].d.params.has_ref ? st.p_jobs : st.i_jobs).push_back(k);
+    }
+    if (st.p_jobs.empty()) {
+        return;
+    }
+    Tab<SideJob> side(sc, st.p_jobs.size());
+    for (size_t q = 0; q < st.p_jobs.size(); q++) {
+        Job &jb = st.jobs[st.p_jobs[q]];
+        CodecDev &dv = jb.im->dev;
+        SideJob &sj = side.h[q];
+        sj.raw = dv.d_mvf[0];
+        sj.final_mvs = dv.pics[jb.im->cur].d_final_mvs;
+        sj.bd = dv.d_blockdata;
+        sj.out = sc.h_side + q * SIDE_IMG_BYTES;
+        sj.info = sc.h_side_info + q * SIDE_INFO_WORDS;
+        sj.inv_stable = jb.stats[ST_STABLE] != 0;
+        sj.inv_mode = jb.stats[ST_MODE] != 0;
+        sj.inv_eprm = jb.stats[ST_EPRM] != 0;
+        jb.side_out = sj.out;
+        jb.side_info = sj.info;
+    }
+    sc.tabs.upload(st.bs);
+    side_info_batch(st.bs, side.d, (int) st.p_jobs.size(), st.nbh, st.nbv);
+    HIPCHK(hipEventRecord(sc.ev_side, st.bs));
+}
+
+// G1 is awaited; then H1a, the late intra analysis, the side information, H1b of the I pictures
+static void h1(Step &st)
+{
+    Job *jobs = st.jobs;
+    stream_wait(st.bs);
     t_clock.lap(2);
-    for (int k = 0; k < n; k++) {
+    for (int k = 0; k < st.n; k++) {
         if (jobs[k].frame) {
             dsv_frame_ref_dec(jobs[k].frame); // the caller's pixels are in HBM now (dsv_encoder.c:1457)
             jobs[k].frame = nullptr;
         }
     }
-
-    // ---- H1 ----
-    parallel_for(n, [&](int k) { g_task_cpu.run(0, [&] { phase_h1a(jobs[k]); }); });
+    parallel_for(st.n, [&](int k) { g_task_cpu.run(0, [&] { phase_h1a(jobs[k]); }); });
     if (g_fail_next_step.load() == 1 && g_fail_next_step.exchange(0) == 1) {
         jobs[0].failed = 2;
     }
-    for (int k = 0; k < n; k++) {
+    for (int k = 0; k < st.n; k++) {
         if (jobs[k].failed) {
             throw StepFailed{jobs[k].failed == 1 ? "motion estimation row pipeline timed out (a row waited > 4 s for the row above)"
                                                  : "motion estimation did not deliver its counters (search incomplete)"};
         }
     }
-    {
-        // P frames flipped to intra by the scene-change test: their block analysis is due now
-        const IntraJob *d_late;
-        IntraJob *h_late = sc.tabs.take<IntraJob>((size_t) n, &d_late);
-        int n_late = 0;
-        for (int k = 0; k < n; k++) {
-            Job &jb = jobs[k];
-            if (jb.ran_hme && !jb.d.params.has_ref) {
-                PicSet &cur = jb.im->dev.pics[jb.im->cur];
-                for (int c = 0; c < 3; c++) {
-                    h_late[n_late].src.p[c] = cur.src.p[c];
-                }
-                h_late[n_late].out = jb.im->dev.h_intra;
-                n_late++;
-            }
-        }
-        if (n_late) {
-            sc.tabs.upload(bs);
-            intra_analysis_batch(bs, d_late, n_late, analysis_params(dv0, jobs[0].d.params.do_psy));
-            stream_wait(bs);
-        }
-    }
-    // The pictures that stay P frames: their side information is coded on the device (k_side_info), which also finalises
-    // the motion field and forms the block flag bytes in HBM for G2.  It is enqueued now, G2 right behind it; the host
-    // assembles the P packets' heads (H1b) from the pinned sub-streams while G2 runs.  Intra pictures (1 in a GOP) keep
-    // the host coders, whose flag bytes G2 needs: their H1b runs before G2 is built.
-    std::vector<int> p_jobs, i_jobs;
-    for (int k = 0; k < n; k++) {
-        jobs[k].side_out = nullptr;
-        jobs[k].side_info = nullptr;
-        (jobs[k].d.params.has_ref ? p_jobs : i_jobs).push_back(k);
-    }
-    if (!p_jobs.empty()) {
-        const SideJob *d_side;
-        SideJob *h_sj = sc.tabs.take<SideJob>(p_jobs.size(), &d_side);
-        for (size_t q = 0; q < p_jobs.size(); q++) {
-            Job &jb = jobs[p_jobs[q]];
-            CodecDev &dv = jb.im->dev;
-            SideJob &sj = h_sj[q];
-            sj.raw = dv.d_mvf[0];
-            sj.final_mvs = dv.pics[jb.im->cur].d_final_mvs;
-            sj.bd = dv.d_blockdata;
-            sj.out = sc.h_side + q * SIDE_IMG_BYTES;
-            sj.info = sc.h_side_info + q * SIDE_INFO_WORDS;
-            sj.inv_stable = jb.stats[ST_STABLE] != 0;
-            sj.inv_mode = jb.stats[ST_MODE] != 0;
-            sj.inv_eprm = jb.stats[ST_EPRM] != 0;
-            jb.side_out = sj.out;
-            jb.side_info = sj.info;
-        }
-        sc.tabs.upload(bs);
-        side_info_batch(bs, d_side, (int) p_jobs.size(), nbh, nbv);
-        HIPCHK(hipEventRecord(sc.ev_side, bs));
-    }
-    parallel_for((int) i_jobs.size(), [&](int q) { g_task_cpu.run(1, [&] { phase_h1b(jobs[i_jobs[(size_t) q]]); }); });
+    late_intra_analysis(st);
+    enqueue_side_info(st);
+    parallel_for((int) st.i_jobs.size(), [&](int q) { g_task_cpu.run(1, [&] { phase_h1b(jobs[st.i_jobs[(size_t) q]]); }); });
     t_clock.lap(3);
+}
 
-    // ---- G2 ----
-    // streams are ordered by (frame type, lossless): the transform / quantiser kernels are specialised
-    // on those, so each class is one set of launches over its slice of the job tables
-    std::vector<int> order((size_t) n);
-    for (int k = 0; k < n; k++) {
-        order[(size_t) k] = k;
+// the G2 table entries of the picture in slot i of the sorted order
+static void g2_fill_picture(Step &st, int i)
+{
+    BatchScratch &sc = st.sc;
+    Job &jb = st.jobs[st.order[(size_t) i]];
+    CodecDev &dv = jb.im->dev;
+    PicSet &cur = dv.pics[jb.im->cur], &ref = dv.pics[jb.im->cur ^ 1];
+    const DSV_PARAMS *p = &jb.d.params;
+    // the working ("residual") picture starts as a copy of the padded source (dsv_encoder.c:1292) -- of an INTRA picture:
+    // its forward transform reads the working picture.  A P picture's predict + subtract reads the source itself and
+    // writes the residual over every block of the working picture (McJob::src), so nothing needs copying there.
+    if (!p->has_ref) {
+        st.copy.h[st.n_copy++] = CopyJob{cur.src.alloc, cur.recon.alloc, cur.src.bytes};
     }
-    auto cls = [&](int k) { return jobs[k].d.params.has_ref * 2 + jobs[k].d.params.lossless; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cls(a) > cls(b); });
-    const CopyJob *d_copy;
-    CopyJob *h_copy = sc.tabs.take<CopyJob>((size_t) n, &d_copy);
-    const PlaneJob *d_py, *d_pc;
-    PlaneJob *h_py = sc.tabs.take<PlaneJob>((size_t) n, &d_py), *h_pc = sc.tabs.take<PlaneJob>(2 * (size_t) n, &d_pc);
-    const CompactJob *d_comp;
-    CompactJob *h_comp = sc.tabs.take<CompactJob>((size_t) n, &d_comp);
-    const EntJob *d_ent;
-    EntJob *h_ent = sc.tabs.take<EntJob>((size_t) n, &d_ent);
-    const DPlane *d_rext_y, *d_rext_c;
-    DPlane *h_rext_y = sc.tabs.take<DPlane>((size_t) n, &d_rext_y), *h_rext_c = sc.tabs.take<DPlane>(2 * (size_t) n, &d_rext_c);
-    // host -> device hand-over of what H1 decided: per stream the transmitted motion field and the
-    // block flag bytes, packed into ONE pinned buffer and shipped with one copy
-    const size_t nb0 = dv0.nblocks();
-    const size_t mv_bytes = nb0 * sizeof(DSV_MV), slot = (nb0 + 15) & ~(size_t) 15; // (a staging slot: one picture's flag bytes)
-    sc.ensure_stage(slot * (i_jobs.size() + 1));
-    const CopyJob *d_mvcopy;
-    CopyJob *h_mvcopy = sc.tabs.take<CopyJob>((size_t) n, &d_mvcopy);
-    int nP = 0, nI = 0, n_rext = 0, n_mvcopy = 0, n_slots = 0, n_copy = 0;
-    bool any_filter = false;
-    for (int i = 0; i < n; i++) {
-        int k = order[(size_t) i];
-        Job &jb = jobs[k];
-        CodecDev &dv = jb.im->dev;
-        PicSet &cur = dv.pics[jb.im->cur], &ref = dv.pics[jb.im->cur ^ 1];
-        const DSV_PARAMS *p = &jb.d.params;
-        size_t nb = dv.nblocks();
-        // the working ("residual") picture starts as a copy of the padded source (dsv_encoder.c:1292) -- of an INTRA picture:
-        // its forward transform reads the working picture.  A P picture's predict + subtract reads the source itself and
-        // writes the residual over every block of the working picture (McJob::src), so nothing needs copying there.
-        if (!p->has_ref) {
-            h_copy[n_copy++] = CopyJob{cur.src.alloc, cur.recon.alloc, cur.src.bytes};
+    cur.recon_pyr_valid = false;
+    const uint8_t *d_bd = dv.d_blockdata; // P: formed on the device (k_side_info)
+    if (!p->has_ref) {                      // I: the host coders' flag bytes, staged and shipped with one copy
+        uint8_t *h_slot = sc.h_stage + st.slot * (size_t) st.n_slots;
+        d_bd = sc.d_stage + st.slot * (size_t) st.n_slots;
+        memcpy(h_slot, jb.enc->blockdata, dv.nblocks());
+        st.n_slots++;
+    }
+    McJob mj;
+    mj.mvs = cur.d_final_mvs;
+    mj.bd = d_bd;
+    mj.p = dv.mc_params(p->temporal_mc, p->lossless);
+    for (int c = 0; c < 3; c++) {
+        mj.ref.p[c] = ref.recon.p[c];
+        mj.pred.p[c] = dv.pred.p[c];
+        mj.res.p[c] = cur.recon.p[c];
+        mj.src[c] = cur.src.p[c].data;
+    }
+    if (p->has_ref) {
+        // the motion field as transmitted (written into cur.d_final_mvs by k_side_info): used by MC now and as temporal
+        // candidates of the next frame
+        cur.has_final_mvs = true;
+        mj.f = make_filter_params(mj.p, jb.d.quant, jb.inter_filter, jb.enc->vidmeta.inter_sharpen);
+        st.any_filter = st.any_filter || !p->lossless;
+        sc.h_mc[st.nP++] = mj;
+    } else {
+        mj.f = make_filter_params(mj.p, jb.d.quant, 1, 0);
+        if (jb.enc->do_intra_filter && !p->lossless) {
+            sc.h_mc[st.n + st.nI++] = mj;
         }
-        cur.recon_pyr_valid = false;
-        const uint8_t *d_bd = dv.d_blockdata; // P: formed on the device (k_side_info)
-        if (!p->has_ref) {                      // I: the host coders' flag bytes, staged and shipped with one copy
-            uint8_t *h_slot = sc.h_stage + slot * (size_t) n_slots;
-            d_bd = sc.d_stage + slot * (size_t) n_slots;
-            memcpy(h_slot, jb.enc->blockdata, nb);
-            n_slots++;
-        }
-        McJob mj;
-        mj.mvs = cur.d_final_mvs;
-        mj.bd = d_bd;
-        mj.p = dv.mc_params(p->temporal_mc, p->lossless);
-        for (int c = 0; c < 3; c++) {
-            mj.ref.p[c] = ref.recon.p[c];
-            mj.pred.p[c] = dv.pred.p[c];
-            mj.res.p[c] = cur.recon.p[c];
-            mj.src[c] = cur.src.p[c].data;
-        }
-        if (p->has_ref) {
-            // the motion field as transmitted (written into cur.d_final_mvs by k_side_info): used by MC now and as temporal
-            // candidates of the next frame
+        if (jb.ran_hme) {
+            // the search result of a frame that H1 flipped to intra still serves as the next frame's
+            // temporal candidates (dsv_encoder.c:680, hme.c:1651)
+            st.mvcopy.h[st.n_mvcopy++] = CopyJob{dv.d_mvf[0], cur.d_final_mvs, st.mv_bytes};
             cur.has_final_mvs = true;
-            mj.f = make_filter_params(mj.p, jb.d.quant, jb.inter_filter, jb.enc->vidmeta.inter_sharpen);
-            any_filter = any_filter || !p->lossless;
-            sc.h_mc[nP++] = mj;
-        } else {
-            mj.f = make_filter_params(mj.p, jb.d.quant, 1, 0);
-            if (jb.enc->do_intra_filter && !p->lossless) {
-                sc.h_mc[n + nI++] = mj;
-            }
-            if (jb.ran_hme) {
-                // the search result of a frame that H1 flipped to intra still serves as the next frame's
-                // temporal candidates (dsv_encoder.c:680, hme.c:1651)
-                h_mvcopy[n_mvcopy++] = CopyJob{dv.d_mvf[0], cur.d_final_mvs, mv_bytes};
-                cur.has_final_mvs = true;
-            }
-        }
-        for (int c = 0; c < 3; c++) {
-            PlaneJob &pj = c ? h_pc[2 * i + c - 1] : h_py[i];
-            pj.pic = cur.recon.p[c];
-            pj.coefs = dv.coefs[c];
-            for (int t = 0; t < 3; t++) {
-                pj.t[t] = c ? dv.scratch_uv[c - 1].t[t] : dv.scratch.t[t];
-            }
-            pj.bd = d_bd;
-            pj.qv = dv.qv + dv.qv_off[c];
-            pj.tile_count = dv.comp.tile_count;
-            pj.qv_base = (unsigned) dv.qv_off[c];
-            pj.mvs = cur.d_final_mvs;
-            quant_steps(&pj, dv.quant_cfg(c, p->has_ref, p->lossless, p->do_psy, nullptr), jb.d.quant);
-        }
-        h_comp[i] = dv.comp.job(dv.qv, dv.qv_off[3]);
-        h_comp[i].total = sc.d_totals + i;
-        if (kGpuEntropy) {
-            // the symbols stay in HBM; what comes back is the finished plane sections (pinned mirror: 1 MB, far above
-            // any 1080p picture at sane quality -- larger ones are fetched by a copy)
-            dv.ent.ensure(dv.comp.list_cap, 4u << 20, 1u << 20);
-            h_ent[i] = dv.ent.job(dv.comp.d_pos, dv.comp.d_val, sc.d_totals + i, sc.d_ll + 3 * i, dv.comp.list_cap);
-        } else {
-            dv.ensure_host_syms(dv.qv_off[3] / 8); // P pictures fit; the first intra picture grows it (one fallback copy)
-            h_comp[i].host_pos = dv.h_pos;
-            h_comp[i].host_val = dv.h_val;
-            h_comp[i].host_cap = (int) dv.h_sym_cap;
-        }
-        if (jb.enc->frame_callback || (p->is_ref && jb.enc->gop != DSV_GOP_INTRA)) {
-            h_rext_y[n_rext] = cur.recon.p[0];
-            h_rext_c[2 * n_rext] = cur.recon.p[1];
-            h_rext_c[2 * n_rext + 1] = cur.recon.p[2];
-            n_rext++;
         }
     }
-    sc.tabs.upload(bs);
-    HIPCHK(hipMemcpyAsync(sc.d_mc, sc.h_mc, 2 * (size_t) n * sizeof(McJob), hipMemcpyHostToDevice, bs));
-    if (n_slots) {
-        HIPCHK(hipMemcpyAsync(sc.d_stage, sc.h_stage, slot * (size_t) n_slots, hipMemcpyHostToDevice, bs));
+    for (int c = 0; c < 3; c++) {
+        PlaneJob &pj = c ? st.pc.h[2 * i + c - 1] : st.py.h[i];
+        pj.pic = cur.recon.p[c];
+        pj.coefs = dv.coefs[c];
+        for (int t = 0; t < 3; t++) {
+            pj.t[t] = c ? dv.scratch_uv[c - 1].t[t] : dv.scratch.t[t];
+        }
+        pj.bd = d_bd;
+        pj.qv = dv.qv + dv.qv_off[c];
+        pj.tile_count = dv.comp.tile_count;
+        pj.qv_base = (unsigned) dv.qv_off[c];
+        pj.mvs = cur.d_final_mvs;
+        quant_steps(&pj, dv.quant_cfg(c, p->has_ref, p->lossless, p->do_psy, nullptr), jb.d.quant);
     }
-    copy_linear_batch(bs, d_mvcopy, n_mvcopy, mv_bytes);
-    copy_linear_batch(bs, d_copy, n_copy, dv0.pics[0].src.bytes);
-    prof.begin(bs, ST_PREDICT);
-    mc_sub_pred_batch(bs, sc.d_mc, nP, nbh, nbv, dv0.blk_w, dv0.blk_h, DSV_FORMAT_H_SHIFT(dv0.format) == 1 && DSV_FORMAT_V_SHIFT(dv0.format) == 1);
-    prof.end(bs, ST_PREDICT, nP);
-    struct Slice {
-        int first, count, isP, lossless;
-    };
-    std::vector<Slice> slices;
+    st.comp.h[i] = dv.comp.job(dv.qv, dv.qv_off[3]);
+    st.comp.h[i].total = sc.d_totals + i;
+    if (kGpuEntropy) {
+        // the symbols stay in HBM; what comes back is the finished plane sections (pinned mirror: 1 MB, far above
+        // any 1080p picture at sane quality -- larger ones are fetched by a copy)
+        dv.ent.ensure(dv.comp.list_cap, 4u << 20, 1u << 20);
+        st.ent.h[i] = dv.ent.job(dv.comp.d_pos, dv.comp.d_val, sc.d_totals + i, sc.d_ll + 3 * i, dv.comp.list_cap);
+    } else {
+        dv.ensure_host_syms(dv.qv_off[3] / 8); // P pictures fit; the first intra picture grows it (one fallback copy)
+        st.comp.h[i].host_pos = dv.h_pos;
+        st.comp.h[i].host_val = dv.h_val;
+        st.comp.h[i].host_cap = (int) dv.h_sym_cap;
+    }
+    if (jb.enc->frame_callback || (p->is_ref && jb.enc->gop != DSV_GOP_INTRA)) {
+        st.rext_y.h[st.n_rext] = cur.recon.p[0];
+        st.rext_c.h[2 * st.n_rext] = cur.recon.p[1];
+        st.rext_c.h[2 * st.n_rext + 1] = cur.recon.p[2];
+        st.n_rext++;
+    }
+}
+
+static void g2_build_tables(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    const int n = st.n;
+    Job *jobs = st.jobs;
+    auto cls = [&](int k) { return jobs[k].d.params.has_ref * 2 + jobs[k].d.params.lossless; };
+    st.order.resize((size_t) n);
+    for (int k = 0; k < n; k++) {
+        st.order[(size_t) k] = k;
+    }
+    std::stable_sort(st.order.begin(), st.order.end(), [&](int a, int b) { return cls(a) > cls(b); });
+    st.slot_of.resize((size_t) n);
+    for (int i = 0; i < n; i++) {
+        st.slot_of[(size_t) st.order[(size_t) i]] = i;
+    }
     for (int i = 0; i < n;) {
         int j = i;
-        while (j < n && cls(order[(size_t) j]) == cls(order[(size_t) i])) {
+        while (j < n && cls(st.order[(size_t) j]) == cls(st.order[(size_t) i])) {
             j++;
         }
-        slices.push_back(Slice{i, j - i, jobs[order[(size_t) i]].d.params.has_ref, jobs[order[(size_t) i]].d.params.lossless});
+        st.slices.push_back(Slice{i, j - i, jobs[st.order[(size_t) i]].d.params.has_ref, jobs[st.order[(size_t) i]].d.params.lossless});
         i = j;
     }
-    const int do_psy = jobs[0].d.params.do_psy;
+    st.copy = Tab<CopyJob>(sc, (size_t) n);
+    st.py = Tab<PlaneJob>(sc, (size_t) n);
+    st.pc = Tab<PlaneJob>(sc, 2 * (size_t) n);
+    st.comp = Tab<CompactJob>(sc, (size_t) n);
+    st.ent = Tab<EntJob>(sc, (size_t) n);
+    st.rext_y = Tab<DPlane>(sc, (size_t) n);
+    st.rext_c = Tab<DPlane>(sc, 2 * (size_t) n);
+    // host -> device hand-over of what H1 decided: per stream the transmitted motion field and the
+    // block flag bytes, packed into ONE pinned buffer and shipped with one copy
+    const size_t nb0 = st.dv0.nblocks();
+    st.mv_bytes = nb0 * sizeof(DSV_MV);
+    st.slot = (nb0 + 15) & ~(size_t) 15;
+    sc.ensure_stage(st.slot * (st.i_jobs.size() + 1));
+    st.mvcopy = Tab<CopyJob>(sc, (size_t) n);
+    for (int i = 0; i < n; i++) {
+        g2_fill_picture(st, i);
+    }
+}
+
+// "residual -> symbols" of one class of pictures, in the two halves G2 keeps apart (the DC grab sits between them): shared
+// by G2 and by the redo of a picture whose lists overflowed, which must run the same kernels on the same operands
+static void forward_slice(hipStream_t s, const CodecDev &dv, const PlaneJob *d_y, const PlaneJob *d_uv, int count, int isP, int lossless)
+{
+    sbt_forward_jobs(s, d_y, count, dv.cw[0], dv.ch[0], 0, isP, lossless, dv.nbh, dv.nbv, true);
+    sbt_forward_jobs(s, d_uv, 2 * count, dv.cw[1], dv.ch[1], 1, isP, lossless, dv.nbh, dv.nbv, true);
+}
+static void quant_slice(hipStream_t s, const CodecDev &dv, const PlaneJob *d_y, const PlaneJob *d_uv, int count, int isP, int lossless, int do_psy)
+{
+    quant_jobs(s, d_y, count, dv.quant_cfg(0, isP, lossless, do_psy, nullptr));
+    quant_jobs(s, d_uv, 2 * count, dv.quant_cfg(1, isP, lossless, do_psy, nullptr));
+}
+
+static void g2_enqueue(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    hipStream_t bs = st.bs;
+    StageProf &prof = st.prof;
+    const CodecDev &dv0 = st.dv0;
+    const int n = st.n, nbh = st.nbh, nbv = st.nbv, nP = st.nP, nI = st.nI;
+    sc.tabs.upload(bs);
+    HIPCHK(hipMemcpyAsync(sc.d_mc, sc.h_mc, 2 * (size_t) n * sizeof(McJob), hipMemcpyHostToDevice, bs));
+    if (st.n_slots) {
+        HIPCHK(hipMemcpyAsync(sc.d_stage, sc.h_stage, st.slot * (size_t) st.n_slots, hipMemcpyHostToDevice, bs));
+    }
+    copy_linear_batch(bs, st.mvcopy.d, st.n_mvcopy, st.mv_bytes);
+    copy_linear_batch(bs, st.copy.d, st.n_copy, dv0.pics[0].src.bytes);
+    prof.begin(bs, ST_PREDICT);
+    mc_sub_pred_batch(bs, sc.d_mc, nP, nbh, nbv, dv0.blk_w, dv0.blk_h, is_420(dv0.format));
+    prof.end(bs, ST_PREDICT, nP);
     prof.begin(bs, ST_FWD_SBT);
-    for (const Slice &sl : slices) {
-        sbt_forward_jobs(bs, d_py + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv, true);
-        sbt_forward_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv, true);
+    for (const Slice &sl : st.slices) {
+        forward_slice(bs, dv0, st.py.d + sl.first, st.pc.d + 2 * sl.first, sl.count, sl.isP, sl.lossless);
     }
     prof.end(bs, ST_FWD_SBT, n);
     prof.begin(bs, ST_QUANT);
-    DSV2_LAUNCH(k_grab_ll, dim3((n + 63) / 64), dim3(64), 0, bs, d_py, d_pc, n, sc.d_ll);
+    DSV2_LAUNCH(k_grab_ll, dim3((n + 63) / 64), dim3(64), 0, bs, st.py.d, st.pc.d, n, sc.d_ll);
     HIPCHK(hipMemcpyAsync(sc.h_ll, sc.d_ll, 3 * (size_t) n * sizeof(int32_t), hipMemcpyDeviceToHost, bs));
-    for (const Slice &sl : slices) {
-        quant_jobs(bs, d_py + sl.first, sl.count, dv0.quant_cfg(0, sl.isP, sl.lossless, do_psy, nullptr));
-        quant_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.quant_cfg(1, sl.isP, sl.lossless, do_psy, nullptr));
+    for (const Slice &sl : st.slices) {
+        quant_slice(bs, dv0, st.py.d + sl.first, st.pc.d + 2 * sl.first, sl.count, sl.isP, sl.lossless, st.do_psy);
     }
-    compact_jobs(bs, d_comp, n, dv0.qv_off[3]);
+    compact_jobs(bs, st.comp.d, n, dv0.qv_off[3]);
     HIPCHK(hipMemcpyAsync(sc.h_totals, sc.d_totals, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, bs));
     if (kGpuEntropy) {
-        if (kAuxStreams & 1) {
+        if (st.aux_entropy) {
             sc.ensure_aux();
-            sc.fork(bs, 0);
-            entropy_gpu_jobs(sc.aux[0], d_ent, n, ent_geom(dv0.qv_off, dv0.scan), kEntSlots);
+            sc.fork(bs);
+            entropy_gpu_jobs(sc.aux, st.ent.d, n, ent_geom(dv0.qv_off, dv0.scan), kEntSlots);
         } else {
-            entropy_gpu_jobs(bs, d_ent, n, ent_geom(dv0.qv_off, dv0.scan), kEntSlots);
+            entropy_gpu_jobs(bs, st.ent.d, n, ent_geom(dv0.qv_off, dv0.scan), kEntSlots);
         }
     }
     prof.end(bs, ST_QUANT, n);
     prof.begin(bs, ST_INV_SBT);
-    for (const Slice &sl : slices) {
-        sbt_inverse_jobs(bs, d_py + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv, true);
-        sbt_inverse_jobs(bs, d_pc + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv, true);
+    for (const Slice &sl : st.slices) {
+        sbt_inverse_jobs(bs, st.py.d + sl.first, sl.count, dv0.cw[0], dv0.ch[0], 0, sl.isP, sl.lossless, nbh, nbv, true);
+        sbt_inverse_jobs(bs, st.pc.d + 2 * sl.first, 2 * sl.count, dv0.cw[1], dv0.ch[1], 1, sl.isP, sl.lossless, nbh, nbv, true);
     }
     prof.end(bs, ST_INV_SBT, n);
     prof.begin(bs, ST_RECON_FILTER);
-    const bool side_intra = (kAuxStreams & 2) && nI > 0 && nP > 0; // two latency-bound sweeps over disjoint pictures: side by side
-    if (side_intra) {
-        sc.ensure_aux();
-        sc.fork(bs, 1);
-        intra_filter_batch(sc.aux[1], sc.d_mc + n, nI, dv0.w, dv0.h);
-    } else {
-        intra_filter_batch(bs, sc.d_mc + n, nI, dv0.w, dv0.h);
-    }
-    mc_add_res_batch(bs, sc.d_mc, nP, nbh, nbv, any_filter, dv0.w, dv0.h, dv0.blk_w, dv0.blk_h);
-    if (side_intra) {
-        sc.join(bs, 1);
-    }
+    intra_filter_batch(bs, sc.d_mc + n, nI, dv0.w, dv0.h);
+    mc_add_res_batch(bs, sc.d_mc, nP, nbh, nbv, st.any_filter, dv0.w, dv0.h, dv0.blk_w, dv0.blk_h);
     prof.end(bs, ST_RECON_FILTER, nP + nI);
     prof.begin(bs, ST_EXTEND);
-    extend_planes(bs, d_rext_y, n_rext, dv0.pics[0].recon.p[0].w, dv0.pics[0].recon.p[0].h);
-    extend_planes(bs, d_rext_c, 2 * n_rext, dv0.pics[0].recon.p[1].w, dv0.pics[0].recon.p[1].h);
-    prof.end(bs, ST_EXTEND, n_rext);
-    if (kGpuEntropy && (kAuxStreams & 1)) {
-        sc.join(bs, 0);
+    extend_planes(bs, st.rext_y.d, st.n_rext, dv0.pics[0].recon.p[0].w, dv0.pics[0].recon.p[0].h);
+    extend_planes(bs, st.rext_c.d, 2 * st.n_rext, dv0.pics[0].recon.p[1].w, dv0.pics[0].recon.p[1].h);
+    prof.end(bs, ST_EXTEND, st.n_rext);
+    if (kGpuEntropy && st.aux_entropy) {
+        sc.join(bs);
     }
     t_clock.lap(4);
-    if (!p_jobs.empty()) { // H1b of the P pictures, under G2's kernels: header + the sub-streams the device coded
-        event_wait(sc.ev_side);
-        parallel_for((int) p_jobs.size(), [&](int q) { g_task_cpu.run(1, [&] { phase_h1b(jobs[p_jobs[(size_t) q]]); }); });
+}
+
+// H1b of the P pictures, under G2's kernels: header + the sub-streams the device coded
+static void h1b_of_p_under_g2(Step &st)
+{
+    if (!st.p_jobs.empty()) {
+        event_wait(st.sc.ev_side);
+        parallel_for((int) st.p_jobs.size(), [&](int q) { g_task_cpu.run(1, [&] { phase_h1b(st.jobs[st.p_jobs[(size_t) q]]); }); });
     }
     t_clock.lap(8);
-    stream_wait(bs);
+    stream_wait(st.bs);
     t_clock.lap(5);
+}
+
+// More symbols than this stream's compaction lists hold (they start at half the worst case, at least 65 536 symbols:
+// ensure_ready): the lists are enlarged to the worst case for good, and this picture's symbols worked out again -- predict +
+// subtract (or the source copy of an intra picture) into a spare working picture, forward transform, quantiser, compaction:
+// the same kernels on the same operands, so the same symbols -- which the host then codes.  The reconstruction is untouched.
+static void redo_overflowed_picture(Step &st, int k)
+{
+    BatchScratch &sc = st.sc;
+    hipStream_t bs = st.bs;
+    Job &jb = st.jobs[k];
+    CodecDev &dv = jb.im->dev;
+    const int ti = st.slot_of[(size_t) k];
+    if (trace_mode() & 2) {
+        fprintf(stderr, "[batch] stream %d: %d symbols > compaction lists of %zu: redone\n", k, jb.nsym, dv.comp.list_cap);
+    }
+    const bool isP = jb.d.params.has_ref, lossless = jb.d.params.lossless;
+    PicSet &cur = dv.pics[jb.im->cur];
+    g_list_growths += (size_t) jb.nsym > dv.comp.list_cap;
+    dv.comp.grow_lists(dv.qv_off[3]);
+    if (kGpuEntropy) {
+        dv.ent.ensure(dv.comp.list_cap, 4u << 20, 1u << 20);
+    }
+    DFrame &tmp = sc.redo_frame(dv.format, dv.w, dv.h);
+    static_assert(sizeof(McJob) + sizeof(CopyJob) + 3 * sizeof(PlaneJob) + sizeof(CompactJob) + 6 * 16 <= 4096,
+                  "a redone picture's tables outgrow the 4 KB a stream BatchScratch::ensure sets aside for them");
+    Tab<McJob> m2(sc, 1);
+    Tab<CopyJob> c2(sc, 1);
+    Tab<PlaneJob> y2(sc, 1), uv2(sc, 2);
+    Tab<CompactJob> k2(sc, 1);
+    if (isP) {
+        *m2.h = sc.h_mc[ti]; // (P pictures lead the sorted order: slot_of = index among the P jobs)
+        for (int c = 0; c < 3; c++) {
+            m2.h->res.p[c] = tmp.p[c];
+        }
+    } else {
+        *c2.h = CopyJob{cur.src.alloc, tmp.alloc, cur.src.bytes};
+    }
+    *y2.h = st.py.h[ti];
+    y2.h->pic = tmp.p[0];
+    for (int c = 1; c < 3; c++) {
+        uv2.h[c - 1] = st.pc.h[2 * ti + c - 1];
+        uv2.h[c - 1].pic = tmp.p[c];
+    }
+    dv.ensure_host_syms((size_t) jb.nsym);
+    *k2.h = dv.comp.job(dv.qv, dv.qv_off[3]);
+    k2.h->total = sc.d_totals + ti;
+    sc.tabs.upload(bs);
+    if (isP) {
+        mc_sub_pred_batch(bs, m2.d, 1, st.nbh, st.nbv, st.dv0.blk_w, st.dv0.blk_h, is_420(st.dv0.format));
+    } else {
+        copy_linear_batch(bs, c2.d, 1, cur.src.bytes);
+    }
+    forward_slice(bs, dv, y2.d, uv2.d, 1, isP, lossless);
+    quant_slice(bs, dv, y2.d, uv2.d, 1, isP, lossless, st.do_psy);
+    compact_jobs(bs, k2.d, 1, dv.qv_off[3]);
+}
+
+// what G2 left for each picture: symbol count and DC coefficients, then either the plane sections the GPU assembled or -- GPU
+// coder off, fallen back, or lists overflowed -- the symbol list for the host coder
+static void collect_symbols(Step &st)
+{
+    BatchScratch &sc = st.sc;
+    hipStream_t bs = st.bs;
     bool late_copy = false;
-    const bool force_redo = getenv("DSV2_COMPACT_REDO") && atoi(getenv("DSV2_COMPACT_REDO"));
-    for (int k = 0; k < n; k++) {
-        Job &jb = jobs[k];
+    const bool force_redo = env_int("DSV2_COMPACT_REDO", 0) != 0; // (every picture takes the redo path: a test switch, read per step)
+    for (int k = 0; k < st.n; k++) {
+        Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
-        int ti = (int) (std::find(order.begin(), order.end(), k) - order.begin()); // this stream's table slot
+        const int ti = st.slot_of[(size_t) k];
         jb.nsym = sc.h_totals[ti];
         for (int c = 0; c < 3; c++) {
             dv.h_ll[c] = sc.h_ll[3 * ti + c];
         }
         jb.gpu_bytes = nullptr;
         bool need_syms = !kGpuEntropy;
-        // More symbols than this stream's compaction lists hold (they start at half the worst case, at least 65 536 symbols: ensure_ready): the lists are
-        // enlarged to the worst case for good, and this picture's symbols worked out again -- predict + subtract (or the source
-        // copy of an intra picture) into a spare working picture, forward transform, quantiser, compaction: the same kernels
-        // on the same operands, so the same symbols -- which the host then codes.  The reconstruction is untouched.
-        const bool overflow = (size_t) jb.nsym > dv.comp.list_cap || force_redo; // (DSV2_COMPACT_REDO=1: every picture, a test switch)
+        const bool overflow = (size_t) jb.nsym > dv.comp.list_cap || force_redo;
         if (overflow) {
-            if (trace_mode() & 2) {
-                fprintf(stderr, "[batch] stream %d: %d symbols > compaction lists of %zu: redone\n", k, jb.nsym, dv.comp.list_cap);
-            }
-            const bool isP = jb.d.params.has_ref, lossless = jb.d.params.lossless;
-            PicSet &cur = dv.pics[jb.im->cur];
-            g_list_growths += (size_t) jb.nsym > dv.comp.list_cap;
-            dv.comp.grow_lists(dv.qv_off[3]);
-            if (kGpuEntropy) {
-                dv.ent.ensure(dv.comp.list_cap, 4u << 20, 1u << 20);
-            }
-            DFrame &tmp = sc.redo_frame(dv.format, dv.w, dv.h);
-            static_assert(sizeof(McJob) + sizeof(CopyJob) + 3 * sizeof(PlaneJob) + sizeof(CompactJob) + 6 * 16 <= 4096,
-                          "a redone picture's tables outgrow the 4 KB a stream BatchScratch::ensure sets aside for them");
-            const McJob *d_m2;
-            McJob *h_m2 = sc.tabs.take<McJob>(1, &d_m2);
-            const CopyJob *d_c2;
-            CopyJob *h_c2 = sc.tabs.take<CopyJob>(1, &d_c2);
-            const PlaneJob *d_y2, *d_uv2;
-            PlaneJob *h_y2 = sc.tabs.take<PlaneJob>(1, &d_y2), *h_uv2 = sc.tabs.take<PlaneJob>(2, &d_uv2);
-            const CompactJob *d_k2;
-            CompactJob *h_k2 = sc.tabs.take<CompactJob>(1, &d_k2);
-            if (isP) {
-                *h_m2 = sc.h_mc[ti]; // (P pictures lead the sorted order: table slot = index among the P jobs)
-                for (int c = 0; c < 3; c++) {
-                    h_m2->res.p[c] = tmp.p[c];
-                }
-            } else {
-                *h_c2 = CopyJob{cur.src.alloc, tmp.alloc, cur.src.bytes};
-            }
-            *h_y2 = h_py[ti];
-            h_y2->pic = tmp.p[0];
-            for (int c = 1; c < 3; c++) {
-                h_uv2[c - 1] = h_pc[2 * ti + c - 1];
-                h_uv2[c - 1].pic = tmp.p[c];
-            }
-            dv.ensure_host_syms((size_t) jb.nsym);
-            *h_k2 = dv.comp.job(dv.qv, dv.qv_off[3]);
-            h_k2->total = sc.d_totals + ti;
-            sc.tabs.upload(bs);
-            if (isP) {
-                mc_sub_pred_batch(bs, d_m2, 1, nbh, nbv, dv0.blk_w, dv0.blk_h, DSV_FORMAT_H_SHIFT(dv0.format) == 1 && DSV_FORMAT_V_SHIFT(dv0.format) == 1);
-            } else {
-                copy_linear_batch(bs, d_c2, 1, cur.src.bytes);
-            }
-            sbt_forward_jobs(bs, d_y2, 1, dv.cw[0], dv.ch[0], 0, isP, lossless, nbh, nbv, true);
-            sbt_forward_jobs(bs, d_uv2, 2, dv.cw[1], dv.ch[1], 1, isP, lossless, nbh, nbv, true);
-            quant_jobs(bs, d_y2, 1, dv.quant_cfg(0, isP, lossless, do_psy, nullptr));
-            quant_jobs(bs, d_uv2, 2, dv.quant_cfg(1, isP, lossless, do_psy, nullptr));
-            compact_jobs(bs, d_k2, 1, dv.qv_off[3]);
+            redo_overflowed_picture(st, k);
             need_syms = true;
             late_copy = true;
         }
@@ -2255,29 +2321,50 @@ static void enc_batch_step(Job *jobs, int n)
         stream_wait(bs);
     }
     t_clock.lap(6);
-    prof.collect();
+    st.prof.collect();
+}
 
-    // ---- H2 ----
-    for (int k = 0; k < n; k++) {
-        Job &jb = jobs[k];
+static void h2(Step &st)
+{
+    for (int k = 0; k < st.n; k++) {
+        Job &jb = st.jobs[k];
         if (jb.enc->frame_callback) { // before the picture sets swap
             CodecDev &dv = jb.im->dev;
             PicSet &cur = dv.pics[jb.im->cur];
             DSV_FRAME *orig = dsv_mk_frame(dv.format, dv.w, dv.h, 1), *rec = dsv_mk_frame(dv.format, dv.w, dv.h, 1);
-            dframe_download_full(&cur.src, orig, bs);
-            dframe_download_full(&cur.recon, rec, bs);
-            stream_wait(bs);
+            dframe_download_full(&cur.src, orig, st.bs);
+            dframe_download_full(&cur.recon, rec, st.bs);
+            stream_wait(st.bs);
             jb.enc->frame_callback(&jb.enc->vidmeta, orig, rec);
             dsv_frame_ref_dec(orig);
             dsv_frame_ref_dec(rec);
         }
     }
-    parallel_for(n, [&](int k) { g_task_cpu.run(2, [&] { phase_h2(jobs[k]); }); });
-    if (trace_startup) {
-        startup_mark("first step done");
-    }
+    parallel_for(st.n, [&](int k) { g_task_cpu.run(2, [&] { phase_h2(st.jobs[k]); }); });
+    first_step_mark(st.trace_startup, "first step done");
     t_clock.lap(7);
-    t_clock.done(n);
+    t_clock.done(st.n);
+}
+
+static void enc_batch_step(Job *jobs, int n)
+{
+    static bool first_step = true; // (DSV2_TRACE=1 only; a benign race)
+    const bool trace_startup = first_step;
+    first_step = false;
+    step_p0(jobs, n, trace_startup); // P0
+    Step st(jobs, n, trace_startup);
+    st.prof.begin(st.bs, ST_INGEST); // G1
+    g1_stage_inputs(st);
+    g1_enqueue(st);
+    g1_prepare_search(st);
+    st.prof.end(st.bs, ST_INGEST, n);
+    search_under_token(st);
+    h1(st); // H1: H1a, late intra analysis, side information, H1b of the I pictures
+    g2_build_tables(st); // G2
+    g2_enqueue(st);
+    h1b_of_p_under_g2(st);
+    collect_symbols(st);
+    h2(st); // H2
 }
 
 Coalescer<Job> g_enc_queue; // dsv_enc callers share lockstep steps (batch.h)

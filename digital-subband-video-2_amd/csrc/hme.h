@@ -57,14 +57,12 @@ int hme_run(hipStream_t s, const HmeFrames &f, const HmeParams &hp); // returns 
 size_t hme_table_bytes(int n);
 struct StageProf;
 // prof (optional): HIP events around the level-0 launch alone (stage ST_HME_L0), for the roofline of the dominant kernel
-// level_hi .. level_lo: the pyramid levels this call runs (default: all, coarse to fine); a search may be split over calls --
-// the one that starts at the coarsest level also ships the job table and clears the hand-off words
 // phases: HME_PREPARE = what needs neither the reference's search slots nor any order -- the job table, the clears and the
-// source pre-pass (k_hme_src_stats_b) --, HME_LEVELS = the levels' launches; a caller that serialises searches (the
-// encoder's search token) prepares before it queues for its turn
+// source pre-pass (k_hme_src_stats_b) --, HME_LEVELS = the levels' launches, all of them, coarse to fine; a caller that
+// serialises searches (the encoder's search token) prepares before it queues for its turn
 enum { HME_PREPARE = 1, HME_LEVELS = 2 };
 int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n, void *h_table, void *d_table, StageProf *prof = nullptr,
-                  int level_hi = -1, int level_lo = 0, int phases = HME_PREPARE | HME_LEVELS);
+                  int phases = HME_PREPARE | HME_LEVELS);
 
 // ---- per-frame block statistics of the finished level-0 field (host controller inputs) -------------------------
 // What the reference's controller sums over the motion field of a P frame before it decides anything

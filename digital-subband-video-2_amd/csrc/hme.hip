@@ -2150,8 +2150,7 @@ static void fill_hme_dev(HmeDev &c, const HmeFrames &f, const HmeParams &hp)
 size_t hme_table_bytes(int n) { return (size_t) n * sizeof(HmeDev); }
 
 // n independent streams of identical geometry in lockstep: every level is ONE launch for all of them
-int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n, void *h_table, void *d_table, StageProf *prof, int level_hi,
-                  int level_lo, int phases)
+int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n, void *h_table, void *d_table, StageProf *prof, int phases)
 {
     if (n <= 0) {
         return 0;
@@ -2160,13 +2159,9 @@ int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n,
     if (g.a.blk_w > 32 || g.a.blk_h > 32) { // (the general block routine stages its operand blocks in LDS: GenLds)
         fatal("motion search: blocks larger than 32 x 32 (dsv_encoder.c:1203-1211 makes 16 or 32)", __FILE__, __LINE__);
     }
-    // a call that starts the search: job table, clears, source pre-pass
-    const bool from_top = (phases & HME_PREPARE) && (level_hi < 0 || level_hi >= g.pyr_levels);
-    if (level_hi < 0 || level_hi > g.pyr_levels) {
-        level_hi = g.pyr_levels;
-    }
+    const bool prepare = (phases & HME_PREPARE) != 0; // job table, clears, source pre-pass
     HmeDev *ht = (HmeDev *) h_table;
-    if (from_top) {
+    if (prepare) {
         for (int k = 0; k < n; k++) {
             fill_hme_dev(ht[k], f[k], hp[k]);
         }
@@ -2184,7 +2179,7 @@ int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n,
     auto fast_level = [&](int level) { return fast && level_all_fast(g.a, f[0].src[level], level); };
     const bool c422 = g.a.hshift == 1 && g.a.vshift == 0;
     const bool split = b16 && !c422 && fast_level(0) && (g_hme_split >= 0 ? g_hme_split != 0 : n * g.a.nbv <= kSplitMaxRows);
-    if (from_top) {
+    if (prepare) {
         const int nb0x = g.a.nbh, nb0y = g.a.nbv, nb1x = g.pyr_levels >= 1 ? (g.a.nbh + 1) / 2 : 0, nb1y = g.pyr_levels >= 1 ? (g.a.nbv + 1) / 2 : 0;
         if (fast) {
             for (int k = 0; k < n; k++) {
@@ -2228,7 +2223,7 @@ int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n,
         DSV2_LAUNCH(k_hme_clear_b, dim3((nwords + 2047) / 2048, n, g.pyr_levels + 1), dim3(256), 0, s, tab, -1, nwords, 1);
     }
     const int parts = n < 8 ? n : 8; // ticket partitions (take_row): 8 XCDs on MI355X
-    for (int level = level_hi; (phases & HME_LEVELS) && level >= level_lo; level--) {
+    for (int level = g.pyr_levels; (phases & HME_LEVELS) && level >= 0; level--) {
         const int step = 1 << level;
         const int nbx = (g.a.nbh + step - 1) / step, nby = (g.a.nbv + step - 1) / step;
         // (three workers per SIMD for the kernels whose wavefronts are small enough to share a SIMD with the other groups' kernels;
@@ -2257,8 +2252,7 @@ int hme_run_batch(hipStream_t s, const HmeFrames *f, const HmeParams *hp, int n,
         }
         nlaunch++;
         // what of level 0 does not depend on the order of its blocks (hme_fast.h: hme_l0_pre_block): needs level 1's field and its
-        // global motion, nothing else -- so it belongs to the call that runs level 1 (a caller that serialises level-0 launches --
-        // the encoder's search token -- may run the coarser levels, and this with them, outside that)
+        // global motion, nothing else -- so it follows level 1 at once
         if (level == 1 && split) {
             const int per_wg = 2;
             DSV2_LAUNCH(k_hme_l0_pre_b, dim3((g.a.nbh * g.a.nbv + per_wg - 1) / per_wg, n), dim3(64), 0, s, tab, g.a.nbh, g.a.nbv, per_wg);
