@@ -18,6 +18,7 @@
 #include "codec.h"
 #include "dec_parse.h"
 #include "dec_parse_dev.h"
+#include "overlay.h"
 
 using namespace dsv2;
 using namespace dsv2::decparse;
@@ -66,6 +67,7 @@ struct DecJob {
     int cap[3] = {0, 0, 0};          // ... into lists of this many entries (min(header count, coefficients of the plane))
     size_t pkt_off = 0;              // ... out of the packet as staged at this offset of the round's stage block
     DSV_FRAME *of = nullptr; // output picture: a bordered frame on pinned memory the device writes directly
+    int draw = 0;            // the decoder's draw_info when the packet was handed in: non-zero = overlay on the luma of `of` (overlay.hip)
 };
 
 struct DecScratch { // held by ONE device round at a time (pool below); owns the stream the round's kernels run on
@@ -194,6 +196,7 @@ void dec_parse(DecJob &jb)
     DSV_DECODER *d = jb.d;
     DSV_BUF *buffer = jb.buf;
     *jb.fn = (DSV_FNUM) -1;
+    jb.draw = d->draw_info;
     // parse from a private copy with zeroed slack behind it, so that codes can be read through a 64-bit window
     static thread_local std::vector<uint8_t> copy;
     if (buffer->len > (1u << 28)) { // (bit positions are 32-bit)
@@ -288,7 +291,11 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     hipStream_t bs = sc.main_stream(); // (a stream of the scratch pool, made once: see the encoder's ScratchPool)
     const size_t nb = dv0.nblocks();
     const size_t mv_bytes = nb * sizeof(DSV_MV), bd_bytes = (nb + 15) & ~(size_t) 15;
-    sc.tabs.reserve((size_t) n * 8192 + 65536);
+    int n_draw = 0; // pictures of this round that get the draw_info overlay (none: no table, no launch)
+    for (int i = 0; i < n; i++) {
+        n_draw += jobs[ids[(size_t) i]].draw != 0;
+    }
+    sc.tabs.reserve((size_t) n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob));
 
     // stage layout: per stream {motion field, block flags}
     // stage layout: per stream {motion field, block flags}, then -- for pictures whose sections the device parses -- the packets,
@@ -363,6 +370,10 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     CopyJob *h_zcond = sc.tabs.take<CopyJob>(3 * (size_t) n, &d_zcond);
     const int *d_fail;
     int *h_fail = sc.tabs.take<int>(3 * (size_t) n, &d_fail);
+    const OverlayJob *d_ov = nullptr;
+    OverlayJob *h_ov = n_draw ? sc.tabs.take<OverlayJob>((size_t) n_draw, &d_ov) : nullptr;
+    int n_ov = 0;
+    bool ov_vectors = false;
     int n_parse = 0;
     int nP = 0, nI = 0, nIf = 0, n_ext = 0, n_zfail = 0, n_out = 0, n_to420 = 0;
     size_t max_plane_bytes = 0;
@@ -495,6 +506,11 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
         } else {
             h_out[n_out++] = CopyJob{cur.recon.alloc, jb.of->alloc, cur.recon.bytes};
         }
+        if (jb.draw) { // drawn on the frame the caller receives only: cur.recon, which the next P picture reads, stays as decoded (dsv_decoder.c:555-561)
+            const DSV_PLANE &op = jb.of->planes[0];
+            h_ov[n_ov++] = OverlayJob{DPlane{op.data, op.stride, op.w, op.h}, d_mvs, d_bd, dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref};
+            ov_vectors = ov_vectors || (jb.has_ref && (jb.draw & DSV_DRAW_MOVECS));
+        }
     }
 
     // (stage spans for bench.py's decode roofline: HIP events on this step's stream when dsv2hip_prof_enable(1) is on -- the
@@ -541,6 +557,7 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     }
     copy_linear_batch(bs, d_out, n_out, dv0.pics[0].recon.bytes);
     to420_batch(bs, d_to420, n_to420, dv0.w, dv0.h);
+    overlay_batch(bs, d_ov, n_ov, dv0.h, dv0.nbh, dv0.nbv, ov_vectors);
     prof.end(bs, ST_EXTEND, n);
     t_dec_clock.lap(2);
     stream_wait(bs);

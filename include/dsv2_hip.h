@@ -281,6 +281,10 @@ void dsv_enc_end_of_stream(DSV_ENCODER *enc, DSV_BUF *bufs); /* dsv_encoder.h:19
 typedef struct { /* dsv_decoder.h:39-45; zero-initialised by the caller */
     DSV_META vidmeta;
     void *ref; /* reference: DSV_IMAGE*; here: opaque device decoder context */
+    /* DSV_DRAW_* bits, read by every dsv_dec call; honoured as in dsv_decoder.c:240-350, :555-561: any non-zero value draws
+     * the block grid on the luma of the returned picture, the bits add dashes, vectors and intra marks; the picture later
+     * P pictures predict from is never drawn on.  The reference stores the intra marks without a bounds check (:326-346);
+     * here a mark that falls outside the luma plane (clipped last block row / column) is dropped. */
     int draw_info;
     int got_metadata;
 } DSV_DECODER;

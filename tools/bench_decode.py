@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--steps", type=int, default=48)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--draw-info", type=int, default=0, help="DSV_DECODER.draw_info of every decoder (0: no overlay)")
     args = ap.parse_args()
     import dsvabi as A
     from codec_run import decode_stream, encode_stream
@@ -47,6 +48,8 @@ def main():
         pk = encode_stream(hip, frames, W_, H_, A.SUBSAMP_420, eos=False, qp=QP, gop=GOP, effort=10)[0]
         vids.append(pk)  # [meta, pic0, pic1, ...] (one metadata packet per GOP start)
     decs = [A.DECODER() for _ in range(S)]
+    for d in decs:
+        d.draw_info = args.draw_info
     group_of = [list(range(g, S, G)) for g in range(G)]
 
     def make_bufs(ids, t):
@@ -105,7 +108,7 @@ def main():
               "unit": "frames/s", "n_gpus": 1, "steps": npk - first, "ms_per_step": round(1e3 * elapsed / max(1, npk - first), 3),
               "higher_is_better": True, "dtype": "u8/int32", "data": "synthetic",
               "config": {"workload": "1920x1080 4:2:0 -qp=60 -gop=48, %d decoder instances in %d lockstep groups, frames delivered to host memory" % (S, G),
-                         "streams_per_gpu": S, "groups": G, "frames": nframes, "mpix_per_s": round(fps * W_ * H_ / 1e6, 1)}}
+                         "streams_per_gpu": S, "groups": G, "draw_info": args.draw_info, "frames": nframes, "mpix_per_s": round(fps * W_ * H_ / 1e6, 1)}}
     if not args.no_cpu_baseline and os.path.exists(A.REF_SO):
         ref = A.load_ref()
         pk = vids[0][:25]
