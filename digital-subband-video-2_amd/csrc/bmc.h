@@ -52,4 +52,10 @@ void intra_filter_batch(hipStream_t s, const McJob *d_tab, int n, int luma_w, in
 // dsv_post_process (bmc.c:340): de-gradient sharpen of every interior 4x4 cell
 void post_process_plane(hipStream_t s, const DPlane &dp);
 
+// decoder egress: n planes (device table) copied out of the reconstruction into the delivered picture, the sharpened ones
+// through dsv_post_process on the way.  wide: every job's width is a multiple of 16 and its destination and destination
+// stride are 16-byte aligned (16-byte loads and stores); else any width and alignment.  any_sharp: some job has `sharp` set.
+// max_h: the tallest plane.
+void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool wide, bool any_sharp);
+
 } // namespace dsv2

@@ -2244,6 +2244,102 @@ void post_process_plane(hipStream_t s, const DPlane &dp)
     HIPCHK(hipGetLastError());
 }
 
+// ---- decoder egress: visible pixels of a reconstruction plane into the picture the caller receives ---------------------
+// One job per plane (EgressJob, dev.h), fetched by value through the scalar cache.  A thread moves VEC bytes of FOUR
+// consecutive rows -- one row of 4x4 cells -- and a workgroup (64 x 4 threads) 16 rows of the plane, every load issued before
+// the first store.  VEC = 16, the wide form: the plane's width a multiple of 16, destination and its stride 16-byte aligned
+// (the host picks it per round); VEC = 4, the general form: any width, any destination alignment -- whole dwords are read
+// from the source (its 32-pixel border covers the up to three bytes past the row), the destination is written dword-wise
+// only where the dword is whole and aligned, else byte by byte inside the row: nothing outside [dst, dst + h * dstride) row
+// pieces of w bytes is ever touched.  With `sharp` (luma under dsv2hip_dec_set_postsharp) each cell the reference's
+// dsv_post_process visits -- x + 4 < w and y + 4 < h (bmc.c:350,355) -- goes through degrad16 in registers on the way: the
+// cells are independent and read only their own 16 samples, so this equals the in-place pass over the delivered plane, and
+// the reconstruction the next P picture predicts from stays unsharpened.  SHARP = false is the kernel of rounds without
+// such a job: the copy alone, a third of the registers.
+constexpr int kEgressRows = 16; // plane rows per workgroup
+template <int VEC, bool SHARP> __global__ __launch_bounds__(256) void k_egress(const EgressJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const EgressJob j = job_of(tab, blockIdx.y);
+    const int w = j.src.w, h = j.src.h;
+    const int y0 = ((int) blockIdx.x * 4 + (int) threadIdx.y) * 4;
+    if (y0 >= h) {
+        return;
+    }
+    constexpr int NW = VEC / 4;
+    const bool sharp_row = SHARP && j.sharp && y0 + 4 < h;
+    for (int x = (int) threadIdx.x * VEC; x < w; x += 64 * VEC) {
+        uint32_t v[4][NW];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int y = y0 + r < h ? y0 + r : h - 1; // (rows below the plane: read again from its last row, never stored)
+            const uint8_t *sp = j.src.data + (size_t) y * j.src.stride + x;
+            if constexpr (VEC == 16) {
+                const uint4 q = *(const uint4 *) sp;
+                v[r][0] = q.x, v[r][1] = q.y, v[r][2] = q.z, v[r][3] = q.w;
+            } else {
+                v[r][0] = *(const uint32_t *) sp;
+            }
+        }
+        if (sharp_row) {
+#pragma unroll
+            for (int k = 0; k < NW; k++) {
+                if (x + 4 * k + 4 < w) {
+                    int px[16];
+#pragma unroll
+                    for (int i = 0; i < 16; i++) {
+                        px[i] = (int) ((v[i >> 2][k] >> (8 * (i & 3))) & 0xffu);
+                    }
+                    if (degrad16(px)) {
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            v[r][k] = (uint32_t) px[4 * r] | ((uint32_t) px[4 * r + 1] << 8) | ((uint32_t) px[4 * r + 2] << 16) |
+                                      ((uint32_t) px[4 * r + 3] << 24);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            if (y0 + r >= h) {
+                break;
+            }
+            uint8_t *dp = j.dst + (size_t) (y0 + r) * j.dstride + x;
+            if constexpr (VEC == 16) {
+                *(uint4 *) dp = make_uint4(v[r][0], v[r][1], v[r][2], v[r][3]);
+            } else {
+                if (x + 4 <= w && (((uintptr_t) dp) & 3) == 0) {
+                    *(uint32_t *) dp = v[r][0];
+                } else {
+                    for (int i = 0; i < 4 && x + i < w; i++) {
+                        dp[i] = (uint8_t) (v[r][0] >> (8 * i));
+                    }
+                }
+            }
+        }
+    }
+}
+
+void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool wide, bool any_sharp)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
+    if (wide) {
+        if (any_sharp) {
+            DSV2_LAUNCH((k_egress<16, true>), grid, block, 0, s, d_jobs);
+        } else {
+            DSV2_LAUNCH((k_egress<16, false>), grid, block, 0, s, d_jobs);
+        }
+    } else if (any_sharp) {
+        DSV2_LAUNCH((k_egress<4, true>), grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH((k_egress<4, false>), grid, block, 0, s, d_jobs);
+    }
+}
+
 #ifdef DSV2_FILTER_PROF
 } // namespace dsv2
 #ifdef DSV2_FILTER_PROF

@@ -36,6 +36,7 @@ struct DecImpl {
     std::vector<uint32_t> pos;
     std::vector<int32_t> val;
     bool out420p = false; // deliver every picture as 4:2:0 (the CLI's -out420p, util.c:79-153, done by the GPU on the way out)
+    bool postsharp = false; // dsv_post_process on the luma of every picture handed out (the CLI's -postsharp, dsv_main.c:1084-1089)
 };
 
 // ---- lockstep batch engine ------------------------------------------------------------------------
@@ -44,7 +45,8 @@ struct DecImpl {
 //            serial entropy parse of the three planes into (position, value) symbol lists
 //   B device every picture of the step in one set of launches over job tables: zero + scatter/dequantise
 //            the coefficient planes, inverse transform, intra filter or motion-compensated
-//            reconstruction + in-loop filters, border extension, picture to pinned host memory
+//            reconstruction + in-loop filters, border extension, picture to pinned host memory or (dsv2hip_dec_batch_device)
+//            packed into the caller's device buffer; on that way out: 4:2:0 conversion, draw_info overlay, postsharp
 //   C host   (one pool task per stream) output frame, reference bookkeeping
 // Pictures of a step whose geometry differs from the first one are decoded in a second round.
 struct DecJob {
@@ -67,6 +69,10 @@ struct DecJob {
     int cap[3] = {0, 0, 0};          // ... into lists of this many entries (min(header count, coefficients of the plane))
     size_t pkt_off = 0;              // ... out of the packet as staged at this offset of the round's stage block
     DSV_FRAME *of = nullptr; // output picture: a bordered frame on pinned memory the device writes directly
+    bool to_dev = false;     // ... or (dsv2hip_dec_batch_device) no frame at all: the picture goes, packed, to dev_out
+    uint8_t *dev_out = nullptr;
+    int out_format = 0;      // format of the delivered picture: the stream's, or 4:2:0 under out420p
+    bool sharp = false;      // the decoder's postsharp switch when the packet was handed in
     int draw = 0;            // the decoder's draw_info when the packet was handed in: non-zero = overlay on the luma of `of` (overlay.hip)
 };
 
@@ -277,7 +283,11 @@ void dec_parse(DecJob &jb)
         jb.ret = DSV_DEC_ERROR; /* reference frame not found (dsv_decoder.c:535) */
         return;
     }
-    jb.of = mk_frame_pinned(im->out420p ? DSV_SUBSAMP_420 : meta->subsamp, meta->width, meta->height);
+    jb.out_format = im->out420p ? DSV_SUBSAMP_420 : meta->subsamp;
+    jb.sharp = im->postsharp;
+    if (!jb.to_dev) {
+        jb.of = mk_frame_pinned(jb.out_format, meta->width, meta->height);
+    }
     jb.pic = true;
 }
 
@@ -292,10 +302,12 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     const size_t nb = dv0.nblocks();
     const size_t mv_bytes = nb * sizeof(DSV_MV), bd_bytes = (nb + 15) & ~(size_t) 15;
     int n_draw = 0; // pictures of this round that get the draw_info overlay (none: no table, no launch)
+    int n_egress = 0; // ... that leave through the egress kernel: device delivery, postsharp (none: no table, no launch)
     for (int i = 0; i < n; i++) {
         n_draw += jobs[ids[(size_t) i]].draw != 0;
+        n_egress += jobs[ids[(size_t) i]].to_dev || jobs[ids[(size_t) i]].sharp;
     }
-    sc.tabs.reserve((size_t) n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob));
+    sc.tabs.reserve((size_t) n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob));
 
     // stage layout: per stream {motion field, block flags}
     // stage layout: per stream {motion field, block flags}, then -- for pictures whose sections the device parses -- the packets,
@@ -374,6 +386,12 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     OverlayJob *h_ov = n_draw ? sc.tabs.take<OverlayJob>((size_t) n_draw, &d_ov) : nullptr;
     int n_ov = 0;
     bool ov_vectors = false;
+    const EgressJob *d_eg = nullptr;
+    EgressJob *h_eg = n_egress ? sc.tabs.take<EgressJob>(3 * (size_t) n_egress, &d_eg) : nullptr;
+    int n_eg = 0;
+    bool eg_sharp = false;           // some egress job sharpens
+    bool eg_wide = true;             // every egress job of the round allows the 16-byte form (bmc.hip: k_egress)
+    std::vector<DPlane> sharp_drawn; // delivered luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
     int n_parse = 0;
     int nP = 0, nI = 0, nIf = 0, n_ext = 0, n_zfail = 0, n_out = 0, n_to420 = 0;
     size_t max_plane_bytes = 0;
@@ -495,21 +513,43 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
             }
             n_ext++;
         }
-        if (im->out420p && dv.format != DSV_SUBSAMP_420) {
-            // converted on the way out (dsv_main.c:1030-1048): luma copied, chroma through the reference's pair averages
+        // the planes of the delivered picture: those of the pinned frame, or the packed layout in the caller's device buffer
+        DPlane op[3];
+        if (jb.to_dev) {
+            const int ohs = DSV_FORMAT_H_SHIFT(jb.out_format), ovs = DSV_FORMAT_V_SHIFT(jb.out_format);
+            const int ocw = (dv.w + (1 << ohs) - 1) >> ohs, och = (dv.h + (1 << ovs) - 1) >> ovs; // dsv_mk_frame's plane sizes (frame.c:63-113)
+            op[0] = DPlane{jb.dev_out, dv.w, dv.w, dv.h};
+            op[1] = DPlane{op[0].data + (size_t) dv.w * dv.h, ocw, ocw, och};
+            op[2] = DPlane{op[1].data + (size_t) ocw * och, ocw, ocw, och};
+        } else {
+            for (int c = 0; c < 3; c++) {
+                const DSV_PLANE &fp = jb.of->planes[c];
+                op[c] = DPlane{fp.data, fp.stride, fp.w, fp.h};
+            }
+        }
+        const bool conv = jb.out_format != dv.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
+        const bool sharp_out = jb.sharp && !jb.draw;  // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
+        if (!conv && !jb.to_dev && !sharp_out) {
+            h_out[n_out++] = CopyJob{cur.recon.alloc, jb.of->alloc, cur.recon.bytes};
+        } else {
             const int hs = DSV_FORMAT_H_SHIFT(dv.format), vs = DSV_FORMAT_V_SHIFT(dv.format);
             const int mode = (hs == 0 && vs == 0) ? 1 : (hs == 1 && vs == 0) ? 2 : (hs == 2 && vs == 0) ? 3 : 4;
             for (int c = 0; c < 3; c++) {
-                const DSV_PLANE &op = jb.of->planes[c];
-                h_to420[n_to420++] = To420Job{cur.recon.p[c], DPlane{op.data, op.stride, op.w, op.h}, c ? mode : 0};
+                if (conv && (c || (!jb.to_dev && !sharp_out))) {
+                    h_to420[n_to420++] = To420Job{cur.recon.p[c], op[c], c ? mode : 0};
+                } else {
+                    h_eg[n_eg++] = EgressJob{cur.recon.p[c], op[c].data, op[c].stride, c == 0 && sharp_out};
+                    eg_sharp = eg_sharp || (c == 0 && sharp_out);
+                    eg_wide = eg_wide && op[c].w % 16 == 0 && ((((uintptr_t) op[c].data) | (uintptr_t) op[c].stride) & 15) == 0;
+                }
             }
-        } else {
-            h_out[n_out++] = CopyJob{cur.recon.alloc, jb.of->alloc, cur.recon.bytes};
         }
         if (jb.draw) { // drawn on the frame the caller receives only: cur.recon, which the next P picture reads, stays as decoded (dsv_decoder.c:555-561)
-            const DSV_PLANE &op = jb.of->planes[0];
-            h_ov[n_ov++] = OverlayJob{DPlane{op.data, op.stride, op.w, op.h}, d_mvs, d_bd, dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref};
+            h_ov[n_ov++] = OverlayJob{op[0], d_mvs, d_bd, dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref};
             ov_vectors = ov_vectors || (jb.has_ref && (jb.draw & DSV_DRAW_MOVECS));
+            if (jb.sharp) {
+                sharp_drawn.push_back(op[0]);
+            }
         }
     }
 
@@ -557,14 +597,18 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     }
     copy_linear_batch(bs, d_out, n_out, dv0.pics[0].recon.bytes);
     to420_batch(bs, d_to420, n_to420, dv0.w, dv0.h);
+    egress_batch(bs, d_eg, n_eg, dv0.h, eg_wide, eg_sharp);
     overlay_batch(bs, d_ov, n_ov, dv0.h, dv0.nbh, dv0.nbv, ov_vectors);
+    for (const DPlane &pl : sharp_drawn) { // (a debugging combination: one launch a picture)
+        post_process_plane(bs, pl);
+    }
     prof.end(bs, ST_EXTEND, n);
     t_dec_clock.lap(2);
     stream_wait(bs);
     prof.collect();
     t_dec_clock.lap(3);
 
-    // phase C: the pictures are already in their output frames
+    // phase C: the pictures are already in their output frames / the callers' device buffers
     for (int i = 0; i < n; i++) {
         DecJob &jb = jobs[order[(size_t) i]];
         DecImpl *im = jb.im;
@@ -572,7 +616,9 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
             im->cur ^= 1;
             im->have_ref = true;
         }
-        *jb.out = jb.of;
+        if (!jb.to_dev) {
+            *jb.out = jb.of;
+        }
         jb.ret = DSV_DEC_OK;
     }
 }
@@ -712,6 +758,72 @@ int dsv2hip_dec_batch(int n, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FRAME **out,
         ret[k] = jobs[(size_t) k].ret;
     }
     return n;
+}
+
+/* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out
+ * from now on goes through dsv_post_process -- last, behind the 4:2:0 conversion and the draw_info overlay */
+int dsv2hip_dec_set_postsharp(DSV_DECODER *d, int on)
+{
+    if (!d) {
+        return -1;
+    }
+    if (!d->ref) {
+        d->ref = new DecImpl();
+    }
+    ((DecImpl *) d->ref)->postsharp = on != 0;
+    return 0;
+}
+
+size_t dsv2hip_dec_picture_bytes(DSV_DECODER *d)
+{
+    if (!d || !d->got_metadata) {
+        return 0;
+    }
+    const DSV_META &m = d->vidmeta;
+    const int fmt = (d->ref && ((DecImpl *) d->ref)->out420p) ? DSV_SUBSAMP_420 : m.subsamp;
+    const int hs = DSV_FORMAT_H_SHIFT(fmt), vs = DSV_FORMAT_V_SHIFT(fmt);
+    const size_t cw = (size_t) ((m.width + (1 << hs) - 1) >> hs), ch = (size_t) ((m.height + (1 << vs) - 1) >> vs);
+    return (size_t) m.width * (size_t) m.height + 2 * cw * ch;
+}
+
+// dsv2hip_dec_batch with the pictures delivered, packed, to device memory: nothing is consumed unless every decoder that could
+// yield a picture (it has metadata) brings a buffer that holds one
+int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *const *dev_out, const size_t *dev_cap, DSV_FNUM *fn, int *ret)
+{
+    if (n <= 0 || !decs || !bufs || !dev_out || !dev_cap || !fn || !ret) {
+        return -1;
+    }
+    for (int k = 0; k < n; k++) {
+        if (!decs[k]) {
+            return -1;
+        }
+        if (decs[k]->got_metadata && (!dev_out[k] || dev_cap[k] < dsv2hip_dec_picture_bytes(decs[k]))) {
+            return -1;
+        }
+    }
+    std::vector<DecJob> jobs((size_t) n);
+    for (int k = 0; k < n; k++) {
+        jobs[(size_t) k].d = decs[k];
+        jobs[(size_t) k].buf = &bufs[k];
+        jobs[(size_t) k].out = nullptr;
+        jobs[(size_t) k].fn = &fn[k];
+        jobs[(size_t) k].to_dev = true;
+        jobs[(size_t) k].dev_out = (uint8_t *) dev_out[k];
+    }
+    dec_batch(jobs.data(), n);
+    for (int k = 0; k < n; k++) {
+        ret[k] = jobs[(size_t) k].ret;
+    }
+    return n;
+}
+
+int dsv2hip_dec_device_frame(DSV_DECODER *d, DSV_BUF *buf, void *dev_out, size_t dev_cap, DSV_FNUM *fn)
+{
+    int ret = DSV_DEC_ERROR;
+    if (dsv2hip_dec_batch_device(1, &d, buf, &dev_out, &dev_cap, fn, &ret) != 1) {
+        return -1;
+    }
+    return ret;
 }
 
 } // extern "C"

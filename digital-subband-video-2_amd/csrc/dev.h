@@ -186,6 +186,12 @@ struct To420Job { // one plane of a decoded picture on its way into a 4:2:0 outp
     DPlane src, dst;
     int mode; // 0 copy, 1 from 4:4:4, 2 from 4:2:2, 3 from 4:1:1, 4 from "4:1:0"
 };
+struct EgressJob { // one plane of a decoded picture on its way into the picture the caller receives (bmc.hip: k_egress)
+    DPlane src;   // reconstruction plane (dframe_alloc: bordered, 16-byte aligned origin and stride)
+    uint8_t *dst; // the same w x h pixels: device memory (packed, dstride = w) or a plane of a pinned host frame
+    int dstride;
+    int sharp;    // luma under -postsharp: dsv_post_process (bmc.c:340) applied in registers on the way
+};
 void to420_batch(hipStream_t s, const To420Job *d_jobs, int n, int max_w, int max_h);
 void ingest_uyvy_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int h); // src = interleaved UYVY rows
 void planes_to_host_batch(hipStream_t s, const PlaneOutJob *d_jobs, int n, int h);

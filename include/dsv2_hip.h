@@ -398,6 +398,29 @@ void dsv2hip_host_free(void *p);
  * and fn[k] are exactly what dsv_dec(decs[k], &bufs[k], &out[k], &fn[k]) would have produced (packets are
  * consumed the same way).  All pictures of a step run through one set of kernel launches. */
 int dsv2hip_dec_batch(int n, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FRAME **out, DSV_FNUM *fn, int *ret);
+/* Decoded pictures delivered to DEVICE memory (the mirror image of dsv2hip_enc_device_frame / dsv2hip_enc_batch: decode, processing
+ * and encode can stay in HBM).
+ * dsv2hip_dec_picture_bytes: bytes of one picture as this decoder delivers it to device memory: the packed planar layout
+ * dsv2hip_enc_device_frame accepts (Y, U, V back to back, rows of exactly the plane's width, no padding; plane sizes as dsv_mk_frame
+ * makes them), in the stream's format, or 4:2:0 when dsv2hip_dec_set_out420p is on.  0 before the decoder has seen metadata.
+ * dsv2hip_dec_batch_device: dsv2hip_dec_batch without DSV_FRAMEs -- where dsv_dec would have returned a picture it is in dev_out[k]
+ * (any alignment), complete when the call returns (the step's stream has drained: readable from any stream); ret[k], fn[k], the
+ * packets' consumption and the decoders' state are those of dsv_dec (a picture was delivered where the decoder had metadata before
+ * the call and ret[k] == DSV_DEC_OK); draw_info, out420p and postsharp are honoured as on the host
+ * path.  Returns n, or -1 -- before any packet is touched or any decoder changed -- for n <= 0, a NULL array or decoder, or a decoder
+ * that has metadata and whose dev_out[k] is NULL or dev_cap[k] < dsv2hip_dec_picture_bytes(decs[k]); a decoder without metadata
+ * cannot yield a picture in the call and may pass NULL.
+ * dsv2hip_dec_device_frame: the same for one decoder, as a step of its own (not through the dsv_dec submit queue); returns what
+ * dsv_dec returns, or -1 (the packet untouched) where the batch call would return -1. */
+size_t dsv2hip_dec_picture_bytes(DSV_DECODER *dec);
+int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *const *dev_out, const size_t *dev_cap, DSV_FNUM *fn, int *ret);
+int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size_t dev_cap, DSV_FNUM *fn);
+/* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
+ * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
+ * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the
+ * picture later P pictures predict from are untouched.  May be called on a zero-initialised decoder before the first packet.
+ * 0 on success, -1 for a NULL decoder. */
+int dsv2hip_dec_set_postsharp(DSV_DECODER *dec, int on);
 /* where the decoder parses the plane sections of the pictures it is given from now on (hzcc.c:451-585): 0 on the host (fastest with
  * ~16 host cores per GPU), 1 P pictures on the device (one wavefront per section: ~1.4 host cores per GPU), 2 every picture on the
  * device; -1 (the default when DSV2_DEC_DEVICE_PARSE is unset): by the number of cores the process may use.  Returns the mode in force. */

@@ -3,7 +3,8 @@
 1080p 4:2:0 -qp=60 -gop=48 streams, S decoder instances per GPU in G lockstep groups.  Prints one JSON line.
 The packets are produced on the fly with the GPU encoder (bit-identical to the reference's); every decoded
 picture is delivered to host memory as a DSV_FRAME exactly like dsv_dec does (that D2H copy is part of the
-timed region)."""
+timed region) -- or, with --device-out, through dsv2hip_dec_batch_device into one preallocated device buffer
+per decoder, so that the two deliveries can be compared."""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +27,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--draw-info", type=int, default=0, help="DSV_DECODER.draw_info of every decoder (0: no overlay)")
+    ap.add_argument("--device-out", action="store_true", help="deliver the pictures to device memory (dsv2hip_dec_batch_device)")
+    ap.add_argument("--postsharp", action="store_true", help="dsv2hip_dec_set_postsharp on every decoder")
     args = ap.parse_args()
     import dsvabi as A
     from codec_run import decode_stream, encode_stream
@@ -36,6 +39,11 @@ def main():
     hip.dsv2hip_dec_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(C.POINTER(A.FRAME)),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     hip.dsv2hip_dec_batch.restype = C.c_int
+    if args.device_out:
+        import torch
+        hip.dsv2hip_dec_batch_device.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        hip.dsv2hip_dec_batch_device.restype = C.c_int
     pkg = load_pkg()
     S, G, K, Wm = args.streams, max(1, min(args.groups, args.streams)), args.steps, args.warmup
     nfr = Wm + K
@@ -50,6 +58,13 @@ def main():
     decs = [A.DECODER() for _ in range(S)]
     for d in decs:
         d.draw_info = args.draw_info
+        if args.postsharp:
+            hip.dsv2hip_dec_set_postsharp.argtypes = [C.POINTER(A.DECODER), C.c_int]
+            assert hip.dsv2hip_dec_set_postsharp(C.byref(d), 1) == 0
+    pic_bytes = W_ * H_ * 3 // 2
+    dev_out = [torch.empty(pic_bytes, dtype=torch.uint8, device="cuda") for _ in range(S)] if args.device_out else None
+    if dev_out:
+        torch.cuda.synchronize()
     group_of = [list(range(g, S, G)) for g in range(G)]
 
     def make_bufs(ids, t):
@@ -75,8 +90,16 @@ def main():
         outs = (C.POINTER(A.FRAME) * m)()
         fns = (C.c_uint32 * m)()
         rets = (C.c_int * m)()
+        if dev_out:
+            ptrs = (C.c_void_p * m)(*[dev_out[s].data_ptr() for s in ids])
+            caps = (C.c_size_t * m)(*[pic_bytes] * m)
         bar.wait()
         for t in range(t0, t1):
+            if dev_out:
+                had_meta = [decs[s].got_metadata for s in ids]
+                assert hip.dsv2hip_dec_batch_device(m, decp, plan[g][t], ptrs, caps, fns, rets) == m
+                decoded[g] += sum(1 for i in range(m) if rets[i] == A.DEC_OK and had_meta[i])
+                continue
             hip.dsv2hip_dec_batch(m, decp, plan[g][t], outs, fns, rets)
             for i in range(m):
                 if rets[i] == A.DEC_OK and outs[i]:
@@ -99,7 +122,11 @@ def main():
 
     run(0, first)
     before = sum(decoded)
+    import resource
+    ru0 = resource.getrusage(resource.RUSAGE_SELF)
     elapsed = run(first, npk)
+    ru1 = resource.getrusage(resource.RUSAGE_SELF)
+    host_cpu_s = (ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)
     nframes = sum(decoded) - before
     for d in decs:
         hip.dsv_dec_free(C.byref(d))
@@ -107,8 +134,8 @@ def main():
     result = {"metric": "decoded frames/s, 1080p 4:2:0 qp=60 gop=48 (pictures identical to the reference decoder's)", "value": round(fps, 2),
               "unit": "frames/s", "n_gpus": 1, "steps": npk - first, "ms_per_step": round(1e3 * elapsed / max(1, npk - first), 3),
               "higher_is_better": True, "dtype": "u8/int32", "data": "synthetic",
-              "config": {"workload": "1920x1080 4:2:0 -qp=60 -gop=48, %d decoder instances in %d lockstep groups, frames delivered to host memory" % (S, G),
-                         "streams_per_gpu": S, "groups": G, "draw_info": args.draw_info, "frames": nframes, "mpix_per_s": round(fps * W_ * H_ / 1e6, 1)}}
+              "config": {"workload": "1920x1080 4:2:0 -qp=60 -gop=48, %d decoder instances in %d lockstep groups, frames delivered to %s memory" % (S, G, "device" if args.device_out else "host"),
+                         "streams_per_gpu": S, "groups": G, "draw_info": args.draw_info, "delivery": "device" if args.device_out else "host", "postsharp": args.postsharp, "host_cpu_cores_busy": round(host_cpu_s / elapsed, 2), "frames": nframes, "mpix_per_s": round(fps * W_ * H_ / 1e6, 1)}}
     if not args.no_cpu_baseline and os.path.exists(A.REF_SO):
         ref = A.load_ref()
         pk = vids[0][:25]
