@@ -178,6 +178,14 @@ struct IngestJob {
     const uint8_t *src; // packed planar picture in HBM
     DPlane dst[3];
 };
+struct SurfaceJob { // one SOURCE plane of a caller's surface (dsv2hip_surface) on its way into the bordered source planes (frame.hip:
+                    // k_ingest_surface); 48 bytes, fetched by value through the scalar cache like EgressJob
+    const uint8_t *src; // device memory, any alignment: row y at src + y * pitch
+    size_t pitch;
+    uint8_t *dst, *dst2; // plane(s) from dframe_alloc; dst2 != null: the source rows are U0 V0 U1 V1 ..., U goes to dst, V to dst2
+    int dstride;         // of dst and dst2 (the two chroma planes of a frame share their geometry)
+    int w, h;            // visible pixels of each destination plane: the source row holds w bytes (2 * w with dst2)
+};
 struct PlaneOutJob {
     DPlane src;
     uint8_t *dst; // pinned host memory, w * h bytes
@@ -202,6 +210,12 @@ void zero_linear_batch(hipStream_t s, const CopyJob *d_jobs, int n, size_t max_b
 void copy_planes_batch(hipStream_t s, const PlanePair *d_pairs, int n, int w, int h);  // visible pixels, same-size planes
 void ingest_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int total_rows);
 void ingest_batch16(hipStream_t s, const IngestJob *d_jobs, int n, int total_rows); // all plane widths % 16 == 0, <= 2048, 16-byte aligned sources
+// n source planes of at most max_h rows; wide: every job's source row bytes, pointer and pitch are multiples of 16 (surface_job_wide)
+void ingest_surface_batch(hipStream_t s, const SurfaceJob *d_jobs, int n, int max_h, bool wide);
+inline bool surface_job_wide(const SurfaceJob &j)
+{
+    return ((((uintptr_t) j.src) | j.pitch | (size_t) (j.dst2 ? 2 * j.w : j.w)) & 15) == 0;
+}
 
 void ensure_device();
 void set_default_device(int ordinal);

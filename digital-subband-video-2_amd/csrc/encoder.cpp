@@ -836,6 +836,8 @@ struct Job {
     EncImpl *im;
     DSV_FRAME *frame;          // host picture (dsv_enc) ...
     const uint8_t *dev_planar; // ... or packed planar picture already in HBM
+    dsv2hip_surface surf;      // ... or (has_surf) a pitched planar / semi-planar surface in HBM, by value: the caller's array may go
+    bool has_surf;
     const uint8_t *host_planar; // ... or packed planar picture in host memory, uploaded by the batch engine (pinned: asynchronously)
     const uint8_t *host_next;   // the picture this stream will bring to the NEXT step: uploaded under this step's kernels
     bool from_frame;            // host_planar is a DSV_FRAME packed by dsv_enc: planar whatever the encoder's packed-input format
@@ -959,7 +961,9 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
     int cap = 0;
     void ensure(int n)
     {
-        tabs.reserve((size_t) n * 12288 + 65536); // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture)
+        // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture; behind them the three source planes of a
+        // stream that brings a surface)
+        tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob)) + 65536);
         if (n <= cap) {
             return;
         }
@@ -1514,6 +1518,7 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 // counters (thrown behind H1a, the search drained), 2 = as a search token that never came (thrown with the step's ingest,
 // pyramids and source pre-pass still enqueued on the stream)
 static std::atomic<int> g_fail_next_step{0};
+static std::atomic<unsigned long long> g_surface_steps[2]; // steps whose surface ingest ran in the wide / the general form (dsv2hip_enc_surface_stats)
 
 // workgroups per (picture, plane) of the entropy coder's chunk kernels; each walks its share of the plane's 1 024-symbol chunks
 static const int kEntSlots = (int) env_int("DSV2_ENT_SLOTS", 32); // (192 until round 6: four in five of those workgroups found no chunk)
@@ -1718,7 +1723,15 @@ static void g1_enqueue(Step &st)
     Tab<IntraJob> intra(sc, (size_t) n);
     Tab<PlaneOutJob> small(sc, (size_t) n);
     st.bsj = Tab<BlockStatsJob>(sc, (size_t) n);
-    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0;
+    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0;
+    for (int k = 0; k < n; k++) {
+        n_surf += st.jobs[k].has_surf;
+    }
+    Tab<SurfaceJob> sj; // only a step with surface jobs has this table (behind all the others: theirs lie where they always did)
+    if (n_surf) {
+        sj = Tab<SurfaceJob>(sc, 3 * (size_t) n_surf);
+    }
+    bool surf_wide = true;
     for (int k = 0; k < n; k++) {
         Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
@@ -1728,6 +1741,16 @@ static void g1_enqueue(Step &st)
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
+        } else if (jb.has_surf) {
+            const dsv2hip_surface &sf = jb.surf;
+            const int nsrc = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR ? 2 : 3;
+            for (int c = 0; c < nsrc; c++) {
+                const DPlane &dp = cur.src.p[c];
+                const bool uv = nsrc == 2 && c == 1;
+                SurfaceJob &j = sj.h[n_sj++];
+                j = SurfaceJob{(const uint8_t *) sf.plane[c], sf.pitch[c], dp.data, uv ? cur.src.p[2].data : nullptr, dp.stride, dp.w, dp.h};
+                surf_wide = surf_wide && surface_job_wide(j);
+            }
         } else {
             IngestJob &ij = jb.im->input_uyvy && !jb.from_frame ? ingu.h[n_ingu++] : ing.h[n_ing++];
             ij.src = jb.dev_planar;
@@ -1789,6 +1812,10 @@ static void g1_enqueue(Step &st)
         ingest_batch(bs, ing.d, n_ing, f0.p[0].w, f0.p[0].h + f0.p[1].h + f0.p[2].h);
     }
     ingest_uyvy_batch(bs, ingu.d, n_ingu, f0.p[0].w, f0.p[0].h);
+    if (n_sj) {
+        ingest_surface_batch(bs, sj.d, n_sj, f0.p[0].h, surf_wide);
+        g_surface_steps[surf_wide ? 0 : 1]++;
+    }
     extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
     extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
     for (int l = 0; l < L; l++) {
@@ -2595,6 +2622,79 @@ int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, 
         nbufs[k] = jobs[(size_t) k].nbuf;
     }
     return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
+}
+
+/* a surface the ingest can read, for an encoder that takes one: layout, planes, every pitch at least its row's bytes */
+static bool surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf)
+{
+    if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
+        return false;
+    }
+    if (sf->layout != DSV2HIP_SURFACE_PLANAR && sf->layout != DSV2HIP_SURFACE_SEMIPLANAR) {
+        return false;
+    }
+    const int hs = DSV_FORMAT_H_SHIFT(enc->vidmeta.subsamp);
+    const size_t w = (size_t) enc->vidmeta.width, cw = (w + ((size_t) 1 << hs) - 1) >> hs;
+    if (sf->layout == DSV2HIP_SURFACE_SEMIPLANAR) {
+        return sf->plane[0] && sf->plane[1] && sf->pitch[0] >= w && sf->pitch[1] >= 2 * cw;
+    }
+    return sf->plane[0] && sf->plane[1] && sf->plane[2] && sf->pitch[0] >= w && sf->pitch[1] >= cw && sf->pitch[2] >= cw;
+}
+
+/* dsv2hip_enc_batch for pictures that are pitched surfaces in device memory: planar, or luma + one interleaved UV plane (NV12 with
+ * 4:2:0).  surf[k] is read during the call only.  Refused as a whole with -1, nothing touched, for what dsv2hip_enc_batch refuses,
+ * a surface surface_ok does not pass, or an encoder with UYVY input on. */
+int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs)
+{
+    if (n <= 0 || !encs || !surf || !bufs || !nbufs) {
+        return -1;
+    }
+    for (int k = 0; k < n; k++) {
+        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !surface_ok(encs[k], &surf[k])) {
+            return -1;
+        }
+    }
+    std::vector<Job> jobs((size_t) n);
+    for (int k = 0; k < n; k++) {
+        memset(&jobs[(size_t) k], 0, sizeof(Job));
+        jobs[(size_t) k].enc = encs[k];
+        jobs[(size_t) k].surf = surf[k];
+        jobs[(size_t) k].has_surf = true;
+        jobs[(size_t) k].bufs = bufs + 4 * k;
+    }
+    const bool ok = enc_batch_ok(jobs.data(), n);
+    for (int k = 0; k < n; k++) {
+        nbufs[k] = jobs[(size_t) k].nbuf;
+    }
+    return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
+}
+
+/* dsv2hip_enc_device_frame for one surface: a step of its own; 0 packets where the batch call would return -1 */
+int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs)
+{
+    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !surface_ok(enc, surf)) {
+        return 0;
+    }
+    Job jb;
+    memset(&jb, 0, sizeof(jb));
+    jb.enc = enc;
+    jb.surf = *surf;
+    jb.has_surf = true;
+    jb.bufs = bufs;
+    enc_batch(&jb, 1);
+    return jb.nbuf;
+}
+
+void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset)
+{
+    for (int i = 0; i < 2; i++) {
+        if (out2) {
+            out2[i] = g_surface_steps[i].load();
+        }
+        if (reset) {
+            g_surface_steps[i].store(0);
+        }
+    }
 }
 
 /* the same with the pictures in HOST memory (packed planar Y, U, V).  host_planar[k]: stream k's picture of this

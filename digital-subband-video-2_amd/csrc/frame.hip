@@ -323,6 +323,99 @@ __global__ __launch_bounds__(256) void k_ingest_uyvy(const IngestJob *__restrict
     }
 }
 
+// ---- pitched surfaces (dsv2hip_surface): planar, or luma + one interleaved UV plane (NV12 / NV16 / NV24) ----------------
+// One job per SOURCE plane (SurfaceJob, dev.h), fetched by value through the scalar cache; an interleaved plane's job names
+// both chroma planes.  As k_egress (bmc.hip), the other way round: a thread moves VEC source bytes of FOUR consecutive rows, a
+// workgroup (64 x 4 threads) 16 rows over the whole row width, every load issued before the first store.  VEC = 16, the wide
+// form: the source row's bytes, the source pointer and its pitch are multiples of 16 in every job of the launch (the host
+// picks it per step); a lane's 16 interleaved bytes leave as 8 U + 8 V, two aligned 8-byte stores.  VEC = 4, the general form:
+// any width, pitch and alignment -- a dword is read where it is aligned and lies whole inside the row, single bytes of the
+// row otherwise (no word is touched that holds no byte of the row), and stored dword-wise (2 + 2 bytes for an interleaved
+// piece) where it is whole, else byte by byte inside the plane's w x h: the border is k_extend's.
+constexpr int kSurfaceRows = 16; // source rows per workgroup
+constexpr uint32_t kPermEven = 0x06040200u, kPermOdd = 0x07050301u; // bytes 0, 2 / 1, 3 of (second, first) operand of v_perm_b32
+template <int VEC> __global__ __launch_bounds__(256) void k_ingest_surface(const SurfaceJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    // the record and the wavefront's row (64 x 4 threads: threadIdx.y is one value per wavefront) are the same in every lane, and
+    // said so: the row bases below are scalar, a lane adds its 32-bit sx
+    const SurfaceJob jl = job_of(tab, blockIdx.y);
+    const SurfaceJob j{uni_ptr(jl.src), ((size_t) (unsigned) uni((int) (jl.pitch >> 32)) << 32) | (unsigned) uni((int) jl.pitch), uni_ptr(jl.dst),
+                       uni_ptr(jl.dst2), uni(jl.dstride), uni(jl.w), uni(jl.h)};
+    const int w = j.w, h = j.h;
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= h) {
+        return;
+    }
+    const bool uv = j.dst2 != nullptr;
+    const int sbytes = uv ? 2 * w : w; // of a source row
+    constexpr int NW = VEC / 4;
+    for (int sx = (int) threadIdx.x * VEC; sx < sbytes; sx += 64 * VEC) {
+        uint32_t v[4][NW];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int y = y0 + r < h ? y0 + r : h - 1; // (rows below the plane: read again from its last row, never stored)
+            const uint8_t *sp = j.src + (size_t) y * j.pitch + sx;
+            if constexpr (VEC == 16) {
+                const uint4 q = *(const uint4 *) sp;
+                v[r][0] = q.x, v[r][1] = q.y, v[r][2] = q.z, v[r][3] = q.w;
+            } else if (sx + 4 <= sbytes && (((uintptr_t) sp) & 3) == 0) {
+                v[r][0] = *(const uint32_t *) sp;
+            } else {
+                v[r][0] = 0;
+                for (int i = 0; i < 4 && sx + i < sbytes; i++) {
+                    v[r][0] |= (uint32_t) sp[i] << (8 * i);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            if (y0 + r >= h) {
+                break;
+            }
+            const size_t row = (size_t) (y0 + r) * j.dstride;
+            if (!uv) {
+                uint8_t *dp = j.dst + row + sx;
+                if constexpr (VEC == 16) {
+                    *(uint4 *) dp = make_uint4(v[r][0], v[r][1], v[r][2], v[r][3]);
+                } else if (sx + 4 <= w) {
+                    *(uint32_t *) dp = v[r][0]; // (sx is a multiple of 4, the plane's origin and stride of 16)
+                } else {
+                    for (int i = 0; sx + i < w; i++) {
+                        dp[i] = (uint8_t) (v[r][0] >> (8 * i));
+                    }
+                }
+            } else {
+                uint8_t *du = j.dst + row + (sx >> 1), *dv = j.dst2 + row + (sx >> 1);
+                if constexpr (VEC == 16) {
+                    *(uint2 *) du = make_uint2(__builtin_amdgcn_perm(v[r][1], v[r][0], kPermEven), __builtin_amdgcn_perm(v[r][3], v[r][2], kPermEven));
+                    *(uint2 *) dv = make_uint2(__builtin_amdgcn_perm(v[r][1], v[r][0], kPermOdd), __builtin_amdgcn_perm(v[r][3], v[r][2], kPermOdd));
+                } else if (sx + 4 <= sbytes) { // U0 V0 U1 V1
+                    const uint32_t q = __builtin_amdgcn_perm(0u, v[r][0], 0x03010200u); // U0 U1 V0 V1
+                    *(uint16_t *) du = (uint16_t) q;
+                    *(uint16_t *) dv = (uint16_t) (q >> 16);
+                } else { // the last U V pair of an odd-width plane
+                    du[0] = (uint8_t) v[r][0];
+                    dv[0] = (uint8_t) (v[r][0] >> 8);
+                }
+            }
+        }
+    }
+}
+
+void ingest_surface_batch(hipStream_t s, const SurfaceJob *d_jobs, int n, int max_h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_h + kSurfaceRows - 1) / kSurfaceRows, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_surface<16>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_surface<4>, grid, block, 0, s, d_jobs);
+    }
+}
+
 // ---- decoder egress: chroma planes of a decoded picture converted to 4:2:0 -----------------------------------
 // util.c:79-153 of the reference CLI (-out420p): 4:4:4 -> 4:2:2 -> 4:2:0 (two rounded pair averages, the second
 // operand clamped at the plane edge), 4:2:2 -> 4:2:0, 4:1:1 -> 4:2:0, 4:1:0 -> 4:2:0; one thread per output sample,

@@ -376,6 +376,35 @@ int dsv2hip_enc_device_frame(DSV_ENCODER *enc, const void *dev_planar, DSV_BUF *
  * kernels (motion-estimation fronts, MC, in-loop filters) are launched once for all streams.  bufs has
  * 4 slots per stream; nbufs[k] = packets of stream k.  Output is identical to n separate dsv_enc calls. */
 int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, DSV_BUF *bufs, int *nbufs);
+/* The same step for pictures that are SURFACES with a row pitch in device memory -- what hardware video decoders, capture
+ * pipelines, image libraries and hipMallocPitch hand out -- read in place: no repacking pass, no trip through the host.
+ *   PLANAR:     plane[0..2] = Y, U, V, row y of plane c at plane[c] + y * pitch[c].
+ *   SEMIPLANAR: plane[0] = Y, plane[1] = one interleaved chroma plane, rows of 2 * cw bytes U0 V0 U1 V1 ...; plane[2] and pitch[2]
+ *               are ignored.  Allowed for every chroma format: NV12 with 4:2:0, NV16 with 4:2:2, NV24 with 4:4:4.
+ * Plane sizes are dsv_mk_frame's for the stream's format: luma w x h, chroma cw x ch (the format's shifts, rounded up).  Any pointer
+ * alignment and any pitch >= the row's bytes (w, cw, or 2 * cw for the interleaved plane) is accepted; the surfaces of one step may
+ * differ in layout, pitch and alignment (16-byte aligned pointers and pitches with row bytes a multiple of 16 throughout the step
+ * take the fast form of the ingest).  A packed picture is the planar surface with pitch = {w, cw, cw}.  The surface is only read,
+ * and only inside its rows: padding between rows may hold anything, the last row needs none behind it.  surf[k] itself is
+ * copied: the array need not outlive the call.
+ * dsv2hip_enc_batch_surface: semantics of dsv2hip_enc_batch (bufs: 4 slots per stream, packets identical to dsv_enc on the same
+ * pixels, 0, or -1 with every nbufs[k] = 0 for a failed step).  Refused as a whole with -1 -- before any encoder, frame counter,
+ * device buffer or nbufs entry is touched -- for n <= 0, a NULL array, an unusable encoder, encoders of different geometry, a layout
+ * that is neither value, a NULL plane[0] or plane[1] (PLANAR: or plane[2]), a pitch smaller than its row's bytes, or an encoder
+ * with dsv2hip_enc_set_uyvy_input on.  The encoders stay usable.
+ * dsv2hip_enc_surface_frame: the same for one encoder (dsv2hip_enc_device_frame); returns the packet count, 0 where the batch call
+ * would return -1.
+ * dsv2hip_enc_surface_stats: out2[0] / out2[1] = lockstep steps of this process whose surface ingest ran in the fast / in the
+ * general form so far; reset != 0 clears the counts afterwards. */
+enum { DSV2HIP_SURFACE_PLANAR = 0, DSV2HIP_SURFACE_SEMIPLANAR = 1 };
+typedef struct dsv2hip_surface {
+    const void *plane[3]; /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first), plane[2] ignored */
+    size_t pitch[3];      /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR */
+    int layout;
+} dsv2hip_surface;
+int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs);
+int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs);
+void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset);
 /* the same step with the pictures in HOST memory, as dsv_enc (dsv_encoder.c:1430) receives them: host_planar[k] is
  * stream k's packed planar picture of this step.  host_next (NULL, or NULL entries, allowed) names the picture each
  * stream will bring to the NEXT call: it is uploaded on a copy stream under this step's kernels, and the next call

@@ -1,0 +1,380 @@
+"""Pitched device surfaces as encoder input (dsv2hip_enc_batch_surface, dsv2hip_enc_surface_frame): planar and semi-planar
+(NV12 / NV16 / NV24) surfaces of any pitch and alignment give the reference encoder's packets on the same pixels -- both forms
+of the ingest kernel, rows wider than one workgroup pass, mixed surfaces in one step -- padding is never read as pixels, the
+surface is never written, and a refused call touches nothing."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import dsvabi as A
+from codec_run import configure_encoder, encode_stream
+from test_gpu_formats import FMT, frames as plain_frames
+
+pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
+
+PLANAR, SEMI = 0, 1
+GUARD = 0xA5
+LEAD = 64  # guard bytes in front of and behind every plane
+CFG = dict(qp=60, gop=12)
+
+
+class SURFACE(C.Structure):
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("layout", C.c_int)]
+
+
+def bind(hip):
+    P = C.POINTER
+    hip.dsv2hip_enc_batch_surface.argtypes = [C.c_int, P(P(A.ENCODER)), P(SURFACE), P(A.BUF), P(C.c_int)]
+    hip.dsv2hip_enc_batch_surface.restype = C.c_int
+    hip.dsv2hip_enc_surface_frame.argtypes = [P(A.ENCODER), P(SURFACE), P(A.BUF)]
+    hip.dsv2hip_enc_surface_frame.restype = C.c_int
+    hip.dsv2hip_enc_surface_stats.argtypes = [P(C.c_ulonglong), C.c_int]
+    hip.dsv2hip_enc_surface_stats.restype = None
+    hip.dsv2hip_enc_batch.argtypes = [C.c_int, P(P(A.ENCODER)), P(C.c_void_p), P(A.BUF), P(C.c_int)]
+    hip.dsv2hip_enc_batch.restype = C.c_int
+    hip.dsv2hip_enc_set_uyvy_input.argtypes = [P(A.ENCODER), C.c_int]
+    hip.dsv2hip_enc_set_uyvy_input.restype = C.c_int
+    return hip
+
+
+def dims(w, h, name):
+    """(format code, [(row bytes, rows)] of Y, U, V)"""
+    code, hs, vs = FMT[name]
+    cw, ch = (w + (1 << hs) - 1) >> hs, (h + (1 << vs) - 1) >> vs
+    return code, [(w, h), (cw, ch), (cw, ch)]
+
+
+def row_bytes(w, h, name, layout):
+    """bytes of a row of each source plane of the layout"""
+    _, d = dims(w, h, name)
+    return [d[0][0], 2 * d[1][0]] if layout == SEMI else [p[0] for p in d]
+
+
+@functools.lru_cache(maxsize=None)
+def content(w, h, name, nfr, seed):
+    _, hs, vs = FMT[name]
+    return tuple(plain_frames(w, h, hs, vs, nfr, seed))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(w, h, name, nfr, seed):
+    return tuple(encode_stream(A.load_ref(), list(content(w, h, name, nfr, seed)), w, h, FMT[name][0], eos=False, **CFG)[0])
+
+
+class Surface:
+    """One picture as device tensors, one per source plane: LEAD guard bytes, `offset` more, rows `pitch` apart (the last one
+    without padding), LEAD guard bytes.  Guard and padding hold `fill`; `check_untouched` compares every byte with what was put."""
+
+    def __init__(self, frame, w, h, name, layout, pitches, offsets=(0, 0, 0), fill=GUARD):
+        _, d = dims(w, h, name)
+        flat = np.frombuffer(frame, dtype=np.uint8)
+        planes, at = [], 0
+        for pw, ph in d:
+            planes.append(flat[at:at + pw * ph].reshape(ph, pw))
+            at += pw * ph
+        assert at == flat.size
+        if layout == SEMI:
+            planes = [planes[0], np.stack([planes[1], planes[2]], axis=-1).reshape(d[1][1], 2 * d[1][0])]
+        self.t, self.was = [], []
+        self.c = SURFACE()
+        self.c.layout = layout
+        for i, pl in enumerate(planes):
+            rows, rb = pl.shape
+            assert pitches[i] >= rb
+            start = LEAD + offsets[i]
+            t = torch.full((start + (rows - 1) * pitches[i] + rb + LEAD,), fill, dtype=torch.uint8, device="cuda")
+            assert t.data_ptr() % 16 == 0
+            torch.as_strided(t, (rows, rb), (pitches[i], 1), start).copy_(torch.from_numpy(pl.copy()).cuda())
+            self.t.append(t)
+            self.was.append(t.clone())
+            self.c.plane[i] = t.data_ptr() + start
+            self.c.pitch[i] = pitches[i]
+
+    def check_untouched(self):
+        for t, was in zip(self.t, self.was):
+            assert torch.equal(t, was), "the encoder wrote into a surface"
+
+
+def new_encoders(hip, w, h, name, n):
+    meta = A.mk_meta(w, h, FMT[name][0])
+    encs = [A.ENCODER() for _ in range(n)]
+    for e in encs:
+        configure_encoder(hip, e, meta, **CFG)
+    return encs
+
+
+def take_packets(hip, bufs, nbufs, got):
+    for s in range(len(got)):
+        assert 0 <= nbufs[s] <= 4
+        for i in range(nbufs[s]):
+            b = bufs[4 * s + i]
+            got[s].append(bytes(C.string_at(b.data, b.len)))
+            hip.dsv_buf_free(C.byref(b))
+
+
+def encode_steps(hip, encs, make_surface, nfr):
+    """nfr lockstep steps over encs; make_surface(s, t) builds stream s's surface of step t.  Returns the packets per stream."""
+    n = len(encs)
+    encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(e) for e in encs])
+    bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)()
+    got = [[] for _ in range(n)]
+    for t in range(nfr):
+        surfs = [make_surface(s, t) for s in range(n)]
+        arr = (SURFACE * n)(*[sf.c for sf in surfs])
+        torch.cuda.synchronize()  # (the tensors are built on torch's stream, the encoder runs on its own)
+        assert hip.dsv2hip_enc_batch_surface(n, encp, arr, bufs, nbufs) == 0
+        take_packets(hip, bufs, nbufs, got)
+        for sf in surfs:
+            sf.check_untouched()
+    return got
+
+
+def encode_with(hip, w, h, name, specs, nfr=3, seed0=5):
+    """One encoder per spec = dict(layout, pitches, offsets, fill), stream s encoding content(seed0 + s); frees the encoders."""
+    code = dims(w, h, name)[0]
+    assert code == FMT[name][0]
+    encs = new_encoders(hip, w, h, name, len(specs))
+    got = encode_steps(hip, encs, lambda s, t: Surface(content(w, h, name, nfr, seed0 + s)[t], w, h, name, **specs[s]), nfr)
+    for e in encs:
+        hip.dsv_enc_free(C.byref(e))
+    return got
+
+
+def same_packets(want, got, what=""):
+    assert len(want) == len(got), "%s: %d packets, the reference has %d" % (what, len(got), len(want))
+    for i, (a, b) in enumerate(zip(want, got)):
+        assert a == b, "%s: packet %d differs" % (what, i)
+
+
+def forms(hip, reset=False):
+    out = (C.c_ulonglong * 2)()
+    hip.dsv2hip_enc_surface_stats(out, int(reset))
+    return out[0], out[1]
+
+
+def odd_pitch(rb):
+    return (rb + 3) | 1
+
+
+# ---- 1. parity, wide form ---------------------------------------------------------------------------------------------
+CIF_PLANAR = dict(layout=PLANAR, pitches=(512, 256, 256))
+CIF_NV12 = dict(layout=SEMI, pitches=(512, 512))
+
+
+@pytest.mark.parametrize("spec", [CIF_PLANAR, CIF_NV12], ids=["planar", "nv12"])
+def test_wide_form_equals_reference(spec):
+    """352x288 4:2:0 (chroma rows of 176 bytes, NV12 rows of 352), aligned pointers and pitches: the 16-byte form."""
+    hip = bind(A.load_hip())
+    forms(hip, reset=True)
+    got = encode_with(hip, 352, 288, "420", [spec])
+    same_packets(reference(352, 288, "420", 3, 5), got[0])
+    assert forms(hip) == (3, 0)
+
+
+# ---- 2. parity, general form ------------------------------------------------------------------------------------------
+GENERAL = [(354, 290, "420")] + [(176, 144, name) for name in sorted(FMT)]
+
+
+@pytest.mark.parametrize("layout", [PLANAR, SEMI], ids=["planar", "semiplanar"])
+@pytest.mark.parametrize("w,h,name", GENERAL)
+def test_general_form_equals_reference(w, h, name, layout):
+    """Odd pitches (row bytes + 3, made odd) and plane pointers 1, 2 and 3 bytes behind a 16-byte boundary; 354x290 has
+    177-sample chroma rows (NV12 rows of 354 bytes: the last U V pair of a row is half a dword)."""
+    hip = bind(A.load_hip())
+    forms(hip, reset=True)
+    spec = dict(layout=layout, pitches=tuple(odd_pitch(rb) for rb in row_bytes(w, h, name, layout)), offsets=(1, 2, 3))
+    got = encode_with(hip, w, h, name, [spec])
+    same_packets(reference(w, h, name, 3, 5), got[0])
+    assert forms(hip) == (0, 3)
+
+
+# ---- 3. rows wider than 2048 bytes in the wide form ---------------------------------------------------------------------
+def test_2160p_nv12_takes_the_wide_form():
+    """3840x2160 NV12 with a 4096-byte pitch: every row is several passes of the workgroup (1024 bytes each); the counter of
+    dsv2hip_enc_surface_stats shows that both steps ran the 16-byte form."""
+    hip = bind(A.load_hip())
+    forms(hip, reset=True)
+    got = encode_with(hip, 3840, 2160, "420", [dict(layout=SEMI, pitches=(4096, 4096))], nfr=2)
+    same_packets(reference(3840, 2160, "420", 2, 5), got[0])
+    assert forms(hip) == (2, 0)
+
+
+# ---- 4. padding is not pixels; the surface is not written ----------------------------------------------------------------
+@pytest.mark.parametrize("w,h,spec", [(352, 288, CIF_NV12),
+                                      (354, 290, dict(layout=PLANAR, pitches=(357, 181, 181), offsets=(1, 2, 3)))],
+                         ids=["nv12_wide", "planar_general"])
+def test_padding_is_never_read_and_nothing_is_written(w, h, spec):
+    """The same pixels with the pitch padding and the bytes around the planes holding 0x00, then 0xFF: identical packets, the
+    reference's; every byte of the tensors is afterwards what the test put there (checked after each step: encode_steps)."""
+    hip = bind(A.load_hip())
+    zero = encode_with(hip, w, h, "420", [dict(spec, fill=0x00)])[0]
+    ones = encode_with(hip, w, h, "420", [dict(spec, fill=0xFF)])[0]
+    assert zero == ones
+    same_packets(reference(w, h, "420", 3, 5), zero)
+
+
+# ---- 5. one step, mixed surfaces ----------------------------------------------------------------------------------------
+def packed_batch(hip, w, h, name, frames):
+    """dsv2hip_enc_batch on the packed picture, one stream"""
+    enc = new_encoders(hip, w, h, name, 1)[0]
+    encp = (C.POINTER(A.ENCODER) * 1)(C.pointer(enc))
+    bufs, nbufs = (A.BUF * 4)(), (C.c_int * 1)()
+    got = [[]]
+    for fb in frames:
+        dev = torch.from_numpy(np.frombuffer(fb, dtype=np.uint8).copy()).cuda()
+        torch.cuda.synchronize()
+        assert hip.dsv2hip_enc_batch(1, encp, (C.c_void_p * 1)(dev.data_ptr()), bufs, nbufs) == 0
+        take_packets(hip, bufs, nbufs, got)
+    hip.dsv_enc_free(C.byref(enc))
+    return got[0]
+
+
+@pytest.mark.parametrize("aligned", [False, True], ids=["general_step", "wide_step"])
+def test_mixed_surfaces_in_one_step(aligned):
+    """Five encoders with different content in one call per frame: packed as a surface (pitch = width), planar pitched, NV12,
+    NV12 one byte off a 16-byte boundary and planar with odd pitches -- the last two force the step's general form; with
+    `aligned` they are aligned surfaces of other pitches and the whole step is wide."""
+    hip = bind(A.load_hip())
+    w, h = 352, 288
+    specs = [dict(layout=PLANAR, pitches=(352, 176, 176)), CIF_PLANAR, CIF_NV12,
+             dict(layout=SEMI, pitches=(384, 368)) if aligned else dict(layout=SEMI, pitches=(512, 512), offsets=(1, 1, 0)),
+             dict(layout=PLANAR, pitches=(368, 192, 208)) if aligned else dict(layout=PLANAR, pitches=(355, 179, 181))]
+    forms(hip, reset=True)
+    got = encode_with(hip, w, h, "420", specs, seed0=40)
+    assert forms(hip) == ((3, 0) if aligned else (0, 3))
+    for s in range(len(specs)):
+        same_packets(reference(w, h, "420", 3, 40 + s), got[s], "stream %d" % s)
+    assert got[0] == packed_batch(hip, w, h, "420", content(w, h, "420", 3, 40))
+
+
+# ---- 6. refusals -----------------------------------------------------------------------------------------------------------
+def break_pitch(layout, plane):
+    def f(c, w, h, name):
+        c.pitch[plane] = row_bytes(w, h, name, layout)[plane] - 1
+    return f
+
+
+def null_plane(plane):
+    def f(c, w, h, name):
+        c.plane[plane] = None
+    return f
+
+
+def bad_layout(c, w, h, name):
+    c.layout = 2
+
+
+REFUSALS = ([("pitch_short_planar_%d" % p, PLANAR, break_pitch(PLANAR, p)) for p in range(3)] +
+            [("pitch_short_semiplanar_%d" % p, SEMI, break_pitch(SEMI, p)) for p in range(2)] +
+            [("null_planar_%d" % p, PLANAR, null_plane(p)) for p in range(3)] +
+            [("null_semiplanar_%d" % p, SEMI, null_plane(p)) for p in range(2)] +
+            [("layout_2_planar", PLANAR, bad_layout), ("layout_2_semiplanar", SEMI, bad_layout)])
+
+
+def refused(hip, encs, cs, single=True):
+    """the batch call on surfaces cs returns -1 and leaves nbufs alone; the one-frame call on each pair returns 0"""
+    n = len(encs)
+    encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(e) for e in encs])
+    bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)(*[77 + k for k in range(n)])
+    state = [bytes(C.string_at(C.byref(e), C.sizeof(e))) for e in encs]
+    assert hip.dsv2hip_enc_batch_surface(n, encp, (SURFACE * n)(*cs), bufs, nbufs) == -1
+    assert list(nbufs) == [77 + k for k in range(n)]
+    if single:
+        assert sum(hip.dsv2hip_enc_surface_frame(C.byref(e), C.byref(c), bufs) for e, c in zip(encs, cs)) == 0
+    assert [bytes(C.string_at(C.byref(e), C.sizeof(e))) for e in encs] == state
+    return encp, bufs, nbufs
+
+
+def copy_of(c):
+    d = SURFACE()
+    C.memmove(C.byref(d), C.byref(c), C.sizeof(c))
+    return d
+
+
+@pytest.mark.parametrize("what,layout,spoil", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_refused_surface_touches_nothing(what, layout, spoil):
+    """Two encoders, the second one's surface spoiled: -1 (0 from the one-frame call), nbufs as the test set it; the same
+    encoders then give the reference's packets from frame 0 on."""
+    hip = bind(A.load_hip())
+    w, h, name = 352, 288, "420"
+    spec = CIF_NV12 if layout == SEMI else CIF_PLANAR
+    encs = new_encoders(hip, w, h, name, 2)
+    good = [Surface(content(w, h, name, 3, 5 + s)[0], w, h, name, **spec) for s in range(2)]
+    bad = copy_of(good[1].c)
+    spoil(bad, w, h, name)
+    torch.cuda.synchronize()
+    refused(hip, encs, [good[0].c, bad], single=False)
+    bufs = (A.BUF * 4)()
+    assert hip.dsv2hip_enc_surface_frame(C.byref(encs[1]), C.byref(bad), bufs) == 0
+    got = encode_steps(hip, encs, lambda s, t: Surface(content(w, h, name, 3, 5 + s)[t], w, h, name, **spec), 3)
+    for e in encs:
+        hip.dsv_enc_free(C.byref(e))
+    for s in range(2):
+        same_packets(reference(w, h, name, 3, 5 + s), got[s], "stream %d" % s)
+
+
+def test_refused_arguments():
+    """n <= 0, NULL arrays, a NULL encoder, a NULL surface: refused, and the encoder still starts at frame 0"""
+    hip = bind(A.load_hip())
+    w, h, name = 352, 288, "420"
+    encs = new_encoders(hip, w, h, name, 1)
+    sf = Surface(content(w, h, name, 3, 5)[0], w, h, name, **CIF_NV12)
+    torch.cuda.synchronize()
+    encp, bufs, nbufs = (C.POINTER(A.ENCODER) * 1)(C.pointer(encs[0])), (A.BUF * 4)(), (C.c_int * 1)(77)
+    arr = (SURFACE * 1)(sf.c)
+    assert hip.dsv2hip_enc_batch_surface(0, encp, arr, bufs, nbufs) == -1
+    assert hip.dsv2hip_enc_batch_surface(-1, encp, arr, bufs, nbufs) == -1
+    assert hip.dsv2hip_enc_batch_surface(1, None, arr, bufs, nbufs) == -1
+    assert hip.dsv2hip_enc_batch_surface(1, encp, None, bufs, nbufs) == -1
+    assert hip.dsv2hip_enc_batch_surface(1, encp, arr, None, nbufs) == -1
+    assert hip.dsv2hip_enc_batch_surface(1, encp, arr, bufs, None) == -1
+    assert hip.dsv2hip_enc_batch_surface(1, (C.POINTER(A.ENCODER) * 1)(), arr, bufs, nbufs) == -1
+    assert hip.dsv2hip_enc_surface_frame(None, arr, bufs) == 0
+    assert hip.dsv2hip_enc_surface_frame(C.byref(encs[0]), None, bufs) == 0
+    assert hip.dsv2hip_enc_surface_frame(C.byref(encs[0]), arr, None) == 0
+    assert nbufs[0] == 77
+    # the one-frame call, frame by frame, from frame 0
+    got = [[]]
+    for t in range(3):
+        s = Surface(content(w, h, name, 3, 5)[t], w, h, name, **CIF_NV12)
+        torch.cuda.synchronize()
+        nb = (C.c_int * 1)(hip.dsv2hip_enc_surface_frame(C.byref(encs[0]), C.byref(s.c), bufs))
+        take_packets(hip, bufs, nb, got)
+        s.check_untouched()
+    hip.dsv_enc_free(C.byref(encs[0]))
+    same_packets(reference(w, h, name, 3, 5), got[0])
+
+
+def test_refused_on_a_uyvy_encoder():
+    """An encoder whose packed input is interleaved UYVY takes no surface; with the switch off again it encodes NV16 from
+    frame 0."""
+    hip = bind(A.load_hip())
+    w, h, name = 176, 144, "422"
+    encs = new_encoders(hip, w, h, name, 1)
+    assert hip.dsv2hip_enc_set_uyvy_input(C.byref(encs[0]), 1) == 0
+    spec = dict(layout=SEMI, pitches=(256, 256))
+    sf = Surface(content(w, h, name, 3, 5)[0], w, h, name, **spec)
+    torch.cuda.synchronize()
+    refused(hip, encs, [sf.c])
+    assert hip.dsv2hip_enc_set_uyvy_input(C.byref(encs[0]), 0) == 0
+    got = encode_steps(hip, encs, lambda s, t: Surface(content(w, h, name, 3, 5)[t], w, h, name, **spec), 3)
+    hip.dsv_enc_free(C.byref(encs[0]))
+    same_packets(reference(w, h, name, 3, 5), got[0])
+
+
+def test_refused_with_an_encoder_of_another_geometry():
+    """352x288 and 176x144 in one call: -1; each then encodes on its own from frame 0."""
+    hip = bind(A.load_hip())
+    geo = [(352, 288), (176, 144)]
+    encs = [new_encoders(hip, w, h, "420", 1)[0] for w, h in geo]
+    spec = [CIF_NV12, dict(layout=SEMI, pitches=(256, 256))]
+    first = [Surface(content(w, h, "420", 3, 5)[0], w, h, "420", **spec[k]) for k, (w, h) in enumerate(geo)]
+    torch.cuda.synchronize()
+    refused(hip, encs, [sf.c for sf in first], single=False)
+    for k, (w, h) in enumerate(geo):
+        got = encode_steps(hip, [encs[k]], lambda s, t: Surface(content(w, h, "420", 3, 5)[t], w, h, "420", **spec[k]), 3)
+        hip.dsv_enc_free(C.byref(encs[k]))
+        same_packets(reference(w, h, "420", 3, 5), got[0], "%dx%d" % (w, h))
