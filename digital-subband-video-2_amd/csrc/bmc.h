@@ -57,5 +57,9 @@ void post_process_plane(hipStream_t s, const DPlane &dp);
 // stride are 16-byte aligned (16-byte loads and stores); else any width and alignment.  any_sharp: some job has `sharp` set.
 // max_h: the tallest plane.
 void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool wide, bool any_sharp);
+// ... into a semiplanar surface: n pictures' chroma (device table), U and V interleaved into one plane, converted to 4:2:0 on
+// the way where the job's mode says so.  wide: every job's destination and pitch are multiples of 16 and its cw of 8
+// (uv_job_wide); any_conv: some job has mode != 0.  max_ch: the most rows delivered.
+void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch, bool wide, bool any_conv);
 
 } // namespace dsv2

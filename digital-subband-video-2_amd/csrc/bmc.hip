@@ -19,6 +19,7 @@
 #include "prio.h"
 #include "blockstat.h"
 #include "bmc.h"
+#include "egress_uv.h"
 #include "hme.h"
 
 namespace dsv2 {
@@ -2337,6 +2338,40 @@ void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool
         DSV2_LAUNCH((k_egress<4, true>), grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH((k_egress<4, false>), grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- decoder egress into a semiplanar surface: U and V of a decoded picture interleaved into one plane ---------------------
+// One job per picture (UvEgressJob, dev.h), fetched by value through the scalar cache.  k_egress's shape: a workgroup (64 x 4
+// threads) covers 16 rows of the delivered chroma, a thread VEC (U, V) pairs of four consecutive rows, all loads before the
+// first store.  What a thread does -- both forms, the fused -out420p conversions, the bounds argument -- is egress_uv.h.
+template <int VEC, bool CONV> __global__ __launch_bounds__(256) void k_egress_uv(const UvEgressJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const UvEgressJob j = job_of(tab, blockIdx.y);
+    const int y0 = ((int) blockIdx.x * 4 + (int) threadIdx.y) * 4;
+    if (y0 >= j.ch) {
+        return;
+    }
+    egress_uv_rows<VEC, CONV>(j, y0, (int) threadIdx.x * VEC, 64 * VEC);
+}
+
+void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch, bool wide, bool any_conv)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_ch + kEgressRows - 1) / kEgressRows, n), block(64, 4);
+    if (wide) {
+        if (any_conv) {
+            DSV2_LAUNCH((k_egress_uv<8, true>), grid, block, 0, s, d_jobs);
+        } else {
+            DSV2_LAUNCH((k_egress_uv<8, false>), grid, block, 0, s, d_jobs);
+        }
+    } else if (any_conv) {
+        DSV2_LAUNCH((k_egress_uv<4, true>), grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH((k_egress_uv<4, false>), grid, block, 0, s, d_jobs);
     }
 }
 

@@ -45,8 +45,9 @@ struct DecImpl {
 //            serial entropy parse of the three planes into (position, value) symbol lists
 //   B device every picture of the step in one set of launches over job tables: zero + scatter/dequantise
 //            the coefficient planes, inverse transform, intra filter or motion-compensated
-//            reconstruction + in-loop filters, border extension, picture to pinned host memory or (dsv2hip_dec_batch_device)
-//            packed into the caller's device buffer; on that way out: 4:2:0 conversion, draw_info overlay, postsharp
+//            reconstruction + in-loop filters, border extension, picture to pinned host memory or (dsv2hip_dec_batch_device,
+//            dsv2hip_dec_batch_surface) into the caller's device planes; on that way out: 4:2:0 conversion, chroma interleave,
+//            draw_info overlay, postsharp
 //   C host   (one pool task per stream) output frame, reference bookkeeping
 // Pictures of a step whose geometry differs from the first one are decoded in a second round.
 struct DecJob {
@@ -69,8 +70,10 @@ struct DecJob {
     int cap[3] = {0, 0, 0};          // ... into lists of this many entries (min(header count, coefficients of the plane))
     size_t pkt_off = 0;              // ... out of the packet as staged at this offset of the round's stage block
     DSV_FRAME *of = nullptr; // output picture: a bordered frame on pinned memory the device writes directly
-    bool to_dev = false;     // ... or (dsv2hip_dec_batch_device) no frame at all: the picture goes, packed, to dev_out
-    uint8_t *dev_out = nullptr;
+    bool to_dev = false;     // ... or (dsv2hip_dec_batch_device / _surface) no frame at all: the picture goes to the caller's device planes
+    uint8_t *dst[3] = {nullptr, nullptr, nullptr}; // ... these: Y, U, V (a packed buffer: the planar surface with pitch {w, cw, cw}), or
+    int dpitch[3] = {0, 0, 0};
+    bool semi = false;       // ... Y and one plane of interleaved U V rows (dst[2] unused)
     int out_format = 0;      // format of the delivered picture: the stream's, or 4:2:0 under out420p
     bool sharp = false;      // the decoder's postsharp switch when the packet was handed in
     int draw = 0;            // the decoder's draw_info when the packet was handed in: non-zero = overlay on the luma of `of` (overlay.hip)
@@ -172,6 +175,7 @@ struct DecClock { // DSV2_TRACE=2: wall-clock split of a lockstep decode step, p
     }
 };
 thread_local DecClock t_dec_clock;
+std::atomic<unsigned long long> g_uv_rounds[2]; // device rounds whose chroma interleave ran in the wide / the general form (dsv2hip_dec_surface_stats)
 
 // Where a picture's plane sections are parsed: DSV2_DEC_DEVICE_PARSE = 0: on the host (one pool task per picture: ~2 ms of a
 // core per 1080p P picture -- the fastest decoder while there are ~16 host cores per GPU to burn); 1: P pictures on the device, one
@@ -303,11 +307,14 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     const size_t mv_bytes = nb * sizeof(DSV_MV), bd_bytes = (nb + 15) & ~(size_t) 15;
     int n_draw = 0; // pictures of this round that get the draw_info overlay (none: no table, no launch)
     int n_egress = 0; // ... that leave through the egress kernel: device delivery, postsharp (none: no table, no launch)
+    int n_semi = 0;   // ... whose chroma leaves interleaved, into a semiplanar surface (none: no table, no launch)
     for (int i = 0; i < n; i++) {
         n_draw += jobs[ids[(size_t) i]].draw != 0;
         n_egress += jobs[ids[(size_t) i]].to_dev || jobs[ids[(size_t) i]].sharp;
+        n_semi += jobs[ids[(size_t) i]].to_dev && jobs[ids[(size_t) i]].semi;
     }
-    sc.tabs.reserve((size_t) n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob));
+    sc.tabs.reserve((size_t) n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob) +
+                    (size_t) n_semi * sizeof(UvEgressJob));
 
     // stage layout: per stream {motion field, block flags}
     // stage layout: per stream {motion field, block flags}, then -- for pictures whose sections the device parses -- the packets,
@@ -391,6 +398,11 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     int n_eg = 0;
     bool eg_sharp = false;           // some egress job sharpens
     bool eg_wide = true;             // every egress job of the round allows the 16-byte form (bmc.hip: k_egress)
+    const UvEgressJob *d_uv = nullptr;
+    UvEgressJob *h_uv = n_semi ? sc.tabs.take<UvEgressJob>((size_t) n_semi, &d_uv) : nullptr;
+    int n_uv = 0;
+    int uv_rows = 0;                      // the most chroma rows an interleave job delivers ("4:1:0" to 4:2:0: more than the source has)
+    bool uv_wide = true, uv_conv = false; // every interleave job allows the 16-byte form / some job converts to 4:2:0 (bmc.hip: k_egress_uv)
     std::vector<DPlane> sharp_drawn; // delivered luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
     int n_parse = 0;
     int nP = 0, nI = 0, nIf = 0, n_ext = 0, n_zfail = 0, n_out = 0, n_to420 = 0;
@@ -513,14 +525,15 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
             }
             n_ext++;
         }
-        // the planes of the delivered picture: those of the pinned frame, or the packed layout in the caller's device buffer
+        // the planes of the delivered picture: those of the pinned frame, or the caller's device planes (semiplanar: op[1] is the
+        // interleaved plane, w (U, V) pairs a row; op[2] is not a plane)
         DPlane op[3];
         if (jb.to_dev) {
             const int ohs = DSV_FORMAT_H_SHIFT(jb.out_format), ovs = DSV_FORMAT_V_SHIFT(jb.out_format);
             const int ocw = (dv.w + (1 << ohs) - 1) >> ohs, och = (dv.h + (1 << ovs) - 1) >> ovs; // dsv_mk_frame's plane sizes (frame.c:63-113)
-            op[0] = DPlane{jb.dev_out, dv.w, dv.w, dv.h};
-            op[1] = DPlane{op[0].data + (size_t) dv.w * dv.h, ocw, ocw, och};
-            op[2] = DPlane{op[1].data + (size_t) ocw * och, ocw, ocw, och};
+            op[0] = DPlane{jb.dst[0], jb.dpitch[0], dv.w, dv.h};
+            op[1] = DPlane{jb.dst[1], jb.dpitch[1], ocw, och};
+            op[2] = DPlane{jb.semi ? nullptr : jb.dst[2], jb.semi ? 0 : jb.dpitch[2], ocw, och};
         } else {
             for (int c = 0; c < 3; c++) {
                 const DSV_PLANE &fp = jb.of->planes[c];
@@ -535,7 +548,16 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
             const int hs = DSV_FORMAT_H_SHIFT(dv.format), vs = DSV_FORMAT_V_SHIFT(dv.format);
             const int mode = (hs == 0 && vs == 0) ? 1 : (hs == 1 && vs == 0) ? 2 : (hs == 2 && vs == 0) ? 3 : 4;
             for (int c = 0; c < 3; c++) {
-                if (conv && (c || (!jb.to_dev && !sharp_out))) {
+                if (c && jb.to_dev && jb.semi) { // both chroma planes through one job, converted on the way or not
+                    if (c == 1) {
+                        const DPlane &su = cur.recon.p[1];
+                        h_uv[n_uv] = UvEgressJob{su.data, cur.recon.p[2].data, op[1].data, op[1].stride, su.stride, su.w, su.h, op[1].w, op[1].h, conv ? mode : 0};
+                        uv_wide = uv_wide && uv_job_wide(h_uv[n_uv]);
+                        uv_conv = uv_conv || conv;
+                        uv_rows = std::max(uv_rows, op[1].h);
+                        n_uv++;
+                    }
+                } else if (conv && (c || (!jb.to_dev && !sharp_out))) {
                     h_to420[n_to420++] = To420Job{cur.recon.p[c], op[c], c ? mode : 0};
                 } else {
                     h_eg[n_eg++] = EgressJob{cur.recon.p[c], op[c].data, op[c].stride, c == 0 && sharp_out};
@@ -598,6 +620,10 @@ void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
     copy_linear_batch(bs, d_out, n_out, dv0.pics[0].recon.bytes);
     to420_batch(bs, d_to420, n_to420, dv0.w, dv0.h);
     egress_batch(bs, d_eg, n_eg, dv0.h, eg_wide, eg_sharp);
+    if (n_uv) {
+        egress_uv_batch(bs, d_uv, n_uv, uv_rows, uv_wide, uv_conv);
+        g_uv_rounds[uv_wide ? 0 : 1]++;
+    }
     overlay_batch(bs, d_ov, n_ov, dv0.h, dv0.nbh, dv0.nbv, ov_vectors);
     for (const DPlane &pl : sharp_drawn) { // (a debugging combination: one launch a picture)
         post_process_plane(bs, pl);
@@ -655,6 +681,43 @@ void dec_batch(DecJob *jobs, int n)
 }
 
 Coalescer<DecJob> g_dec_queue; // dsv_dec callers share lockstep steps (batch.h)
+
+// Plane sizes of the picture as this decoder delivers it (dsv_mk_frame's, frame.c:63-113, in the stream's format or 4:2:0 under
+// out420p), as the rows of a surface of `layout`: false before the metadata or for a layout that is neither value
+bool surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], int rows[3])
+{
+    if (!d || !d->got_metadata || (layout != DSV2HIP_SURFACE_PLANAR && layout != DSV2HIP_SURFACE_SEMIPLANAR)) {
+        return false;
+    }
+    const DSV_META &m = d->vidmeta;
+    const int fmt = (d->ref && ((DecImpl *) d->ref)->out420p) ? DSV_SUBSAMP_420 : m.subsamp;
+    const int hs = DSV_FORMAT_H_SHIFT(fmt), vs = DSV_FORMAT_V_SHIFT(fmt);
+    const size_t cw = (size_t) ((m.width + (1 << hs) - 1) >> hs);
+    const int ch = (m.height + (1 << vs) - 1) >> vs;
+    const bool semi = layout == DSV2HIP_SURFACE_SEMIPLANAR;
+    row_bytes[0] = (size_t) m.width, rows[0] = m.height;
+    row_bytes[1] = semi ? 2 * cw : cw, rows[1] = ch;
+    row_bytes[2] = semi ? 0 : cw, rows[2] = semi ? 0 : ch;
+    return true;
+}
+
+// one lockstep step with every picture delivered to the device planes the jobs name
+int dec_batch_to_dev(std::vector<DecJob> &jobs, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FNUM *fn, int *ret)
+{
+    const int n = (int) jobs.size();
+    for (int k = 0; k < n; k++) {
+        jobs[(size_t) k].d = decs[k];
+        jobs[(size_t) k].buf = &bufs[k];
+        jobs[(size_t) k].out = nullptr;
+        jobs[(size_t) k].fn = &fn[k];
+        jobs[(size_t) k].to_dev = true;
+    }
+    dec_batch(jobs.data(), n);
+    for (int k = 0; k < n; k++) {
+        ret[k] = jobs[(size_t) k].ret;
+    }
+    return n;
+}
 
 } // namespace
 
@@ -802,19 +865,19 @@ int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *con
         }
     }
     std::vector<DecJob> jobs((size_t) n);
-    for (int k = 0; k < n; k++) {
-        jobs[(size_t) k].d = decs[k];
-        jobs[(size_t) k].buf = &bufs[k];
-        jobs[(size_t) k].out = nullptr;
-        jobs[(size_t) k].fn = &fn[k];
-        jobs[(size_t) k].to_dev = true;
-        jobs[(size_t) k].dev_out = (uint8_t *) dev_out[k];
+    for (int k = 0; k < n; k++) { // the packed picture is the planar surface with pitch {w, cw, cw}
+        size_t rb[3];
+        int rows[3];
+        if (surface_dims(decs[k], DSV2HIP_SURFACE_PLANAR, rb, rows)) {
+            uint8_t *at = (uint8_t *) dev_out[k];
+            for (int c = 0; c < 3; c++) {
+                jobs[(size_t) k].dst[c] = at;
+                jobs[(size_t) k].dpitch[c] = (int) rb[c];
+                at += rb[c] * (size_t) rows[c];
+            }
+        }
     }
-    dec_batch(jobs.data(), n);
-    for (int k = 0; k < n; k++) {
-        ret[k] = jobs[(size_t) k].ret;
-    }
-    return n;
+    return dec_batch_to_dev(jobs, decs, bufs, fn, ret);
 }
 
 int dsv2hip_dec_device_frame(DSV_DECODER *d, DSV_BUF *buf, void *dev_out, size_t dev_cap, DSV_FNUM *fn)
@@ -824,6 +887,70 @@ int dsv2hip_dec_device_frame(DSV_DECODER *d, DSV_BUF *buf, void *dev_out, size_t
         return -1;
     }
     return ret;
+}
+
+int dsv2hip_dec_surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], int rows[3])
+{
+    if (!row_bytes || !rows) {
+        return -1;
+    }
+    return surface_dims(d, layout, row_bytes, rows) ? 0 : -1;
+}
+
+// dsv2hip_dec_batch_device with a surface per decoder: nothing is consumed unless every decoder that could yield a picture (it
+// has metadata) brings a surface that holds one
+int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, DSV_FNUM *fn, int *ret)
+{
+    if (n <= 0 || !decs || !bufs || !surf || !fn || !ret) {
+        return -1;
+    }
+    std::vector<DecJob> jobs((size_t) n);
+    for (int k = 0; k < n; k++) {
+        if (!decs[k]) {
+            return -1;
+        }
+        if (!decs[k]->got_metadata) {
+            continue;
+        }
+        const dsv2hip_out_surface &sf = surf[k];
+        size_t rb[3];
+        int rows[3];
+        if (!surface_dims(decs[k], sf.layout, rb, rows)) {
+            return -1;
+        }
+        DecJob &jb = jobs[(size_t) k];
+        jb.semi = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR;
+        for (int c = 0; c < (jb.semi ? 2 : 3); c++) {
+            // (the kernels carry a pitch as an int: one beyond INT_MAX is refused)
+            if (!sf.plane[c] || sf.pitch[c] < rb[c] || sf.pitch[c] > (size_t) INT32_MAX || sf.cap[c] < (size_t) (rows[c] - 1) * sf.pitch[c] + rb[c]) {
+                return -1;
+            }
+            jb.dst[c] = (uint8_t *) sf.plane[c];
+            jb.dpitch[c] = (int) sf.pitch[c];
+        }
+    }
+    return dec_batch_to_dev(jobs, decs, bufs, fn, ret);
+}
+
+int dsv2hip_dec_surface_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_surface *surf, DSV_FNUM *fn)
+{
+    int ret = DSV_DEC_ERROR;
+    if (dsv2hip_dec_batch_surface(1, &d, buf, surf, fn, &ret) != 1) {
+        return -1;
+    }
+    return ret;
+}
+
+void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset)
+{
+    for (int i = 0; i < 2; i++) {
+        if (out2) {
+            out2[i] = g_uv_rounds[i].load();
+        }
+        if (reset) {
+            g_uv_rounds[i].store(0);
+        }
+    }
 }
 
 } // extern "C"

@@ -200,6 +200,17 @@ struct EgressJob { // one plane of a decoded picture on its way into the picture
     int dstride;
     int sharp;    // luma under -postsharp: dsv_post_process (bmc.c:340) applied in registers on the way
 };
+struct UvEgressJob { // both chroma planes of a decoded picture on their way into ONE interleaved plane of a caller's surface (dsv2hip_out_surface,
+                     // SEMIPLANAR: rows U0 V0 U1 V1 ...), converted to 4:2:0 on the way or not (bmc.hip: k_egress_uv); 56 bytes, fetched by
+                     // value through the scalar cache like EgressJob.  The two source planes of a frame share their geometry.
+    const uint8_t *su, *sv; // pixel (0,0) of the reconstruction's U and V planes (dframe_alloc: bordered, 16-byte aligned origin and stride)
+    uint8_t *dst;           // device memory, any alignment: row y at dst + y * dpitch, 2 * cw bytes of it written
+    int dpitch;
+    int sstride, sw, sh;    // of both source planes
+    int cw, ch;             // chroma samples per row / rows of the delivered picture (= sw x sh with mode 0)
+    int mode;               // To420Job's: 0 as decoded, 1 from 4:4:4, 2 from 4:2:2, 3 from 4:1:1, 4 from "4:1:0"
+};
+inline bool uv_job_wide(const UvEgressJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && j.cw % 8 == 0; }
 void to420_batch(hipStream_t s, const To420Job *d_jobs, int n, int max_w, int max_h);
 void ingest_uyvy_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int h); // src = interleaved UYVY rows
 void planes_to_host_batch(hipStream_t s, const PlaneOutJob *d_jobs, int n, int h);

@@ -444,6 +444,45 @@ int dsv2hip_dec_batch(int n, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FRAME **out,
 size_t dsv2hip_dec_picture_bytes(DSV_DECODER *dec);
 int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *const *dev_out, const size_t *dev_cap, DSV_FNUM *fn, int *ret);
 int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size_t dev_cap, DSV_FNUM *fn);
+/* Decoded pictures delivered into SURFACES with a row pitch in device memory -- what dsv2hip_enc_batch_surface reads, and what
+ * hardware encoders, display paths, image libraries and hipMallocPitch work on: no repacking pass behind the decoder, and for the
+ * semiplanar layouts (NV12 / NV16 / NV24) the chroma interleave happens on the way out.
+ *   PLANAR:     plane[0..2] = Y, U, V, row y of plane c at plane[c] + y * pitch[c].
+ *   SEMIPLANAR: plane[0] = Y, plane[1] = one interleaved chroma plane, rows of 2 * cw bytes U0 V0 U1 V1 ...; plane[2], pitch[2] and
+ *               cap[2] are ignored.  Allowed for every chroma format.
+ * The picture is the stream's format, or 4:2:0 when dsv2hip_dec_set_out420p is on (NV12 then: the conversion and the interleave
+ * are one kernel, no planar 4:2:0 picture is written in between); plane sizes are dsv_mk_frame's: luma w x h, chroma cw x ch (the
+ * format's shifts, rounded up).  Any pointer alignment and any pitch from the row's bytes up to INT_MAX is accepted; the surfaces
+ * of one step may differ in layout, pitch and alignment.  Only bytes inside the rows are written: the padding between rows, the
+ * bytes behind the last row and plane[2] of a semiplanar surface never are.  cap[c] is what the caller owns from plane[c] on.
+ * Overlapping planes are the caller's error and are not checked.  A packed picture (dsv2hip_dec_batch_device) is the planar
+ * surface with pitch = {w, cw, cw}: one code path serves both.
+ * dsv2hip_dec_surface_dims: row bytes and row count of each plane of the picture as this decoder delivers it, for `layout`
+ * (SEMIPLANAR: entry 1 = 2 * cw x ch, entry 2 = 0 x 0).  0, or -1 for a NULL decoder or array, a decoder that has seen no metadata
+ * yet, or a layout that is neither value.
+ * dsv2hip_dec_batch_surface: dsv2hip_dec_batch_device with surf[k] instead of a packed buffer -- ret[k], fn[k], the packets'
+ * consumption and the decoders' state are those of dsv_dec; a picture is delivered exactly where the packed call would deliver one,
+ * complete when the call returns; draw_info, out420p and postsharp are honoured as on every other delivery.  surf[k] is copied:
+ * the array need not outlive the call.  Returns n, or -1 -- before any packet is touched or any decoder changed -- for n <= 0, a NULL
+ * array or decoder, or a decoder that has metadata and whose surface has a layout that is neither value, a NULL plane[0] or plane[1]
+ * (PLANAR: or plane[2]), a pitch smaller than its row's bytes (or beyond INT_MAX), or cap[c] < (rows[c] - 1) * pitch[c] +
+ * row_bytes[c].  A decoder without metadata cannot yield a picture in the call: its entry may be all zeros.
+ * dsv2hip_dec_surface_frame: the same for one decoder, as a step of its own; returns what dsv_dec returns, or -1 (the packet
+ * untouched) where the batch call would return -1.
+ * dsv2hip_dec_surface_stats: out2[0] / out2[1] = device rounds of this process (one per picture geometry present in a lockstep
+ * step) whose chroma interleave ran in the wide form (every interleaved plane of the round: pointer and pitch multiples of 16,
+ * cw of 8) / in the general form so far; rounds without a semiplanar picture count as neither.  reset != 0 clears the counts
+ * afterwards. */
+typedef struct dsv2hip_out_surface {
+    void *plane[3];  /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first); plane[2] ignored */
+    size_t pitch[3]; /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR */
+    size_t cap[3];   /* bytes the caller owns from plane[c] on; cap[2] ignored for SEMIPLANAR */
+    int layout;      /* DSV2HIP_SURFACE_PLANAR / DSV2HIP_SURFACE_SEMIPLANAR */
+} dsv2hip_out_surface;
+int dsv2hip_dec_surface_dims(DSV_DECODER *dec, int layout, size_t row_bytes[3], int rows[3]);
+int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, DSV_FNUM *fn, int *ret);
+int dsv2hip_dec_surface_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_surface *surf, DSV_FNUM *fn);
+void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset);
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the

@@ -4,7 +4,8 @@
 The packets are produced on the fly with the GPU encoder (bit-identical to the reference's); every decoded
 picture is delivered to host memory as a DSV_FRAME exactly like dsv_dec does (that D2H copy is part of the
 timed region) -- or, with --device-out, through dsv2hip_dec_batch_device into one preallocated device buffer
-per decoder, so that the two deliveries can be compared."""
+per decoder, or, with --surface-out planar / nv12, through dsv2hip_dec_batch_surface into one preallocated pitched surface per
+decoder, so that the deliveries can be compared."""
 import argparse
 import ctypes as C
 import json
@@ -29,7 +30,11 @@ def main():
     ap.add_argument("--draw-info", type=int, default=0, help="DSV_DECODER.draw_info of every decoder (0: no overlay)")
     ap.add_argument("--device-out", action="store_true", help="deliver the pictures to device memory (dsv2hip_dec_batch_device)")
     ap.add_argument("--postsharp", action="store_true", help="dsv2hip_dec_set_postsharp on every decoder")
+    ap.add_argument("--surface-out", choices=["planar", "nv12"], help="deliver the pictures into pitched device surfaces (dsv2hip_dec_batch_surface)")
+    ap.add_argument("--pitch-align", type=int, default=256, help="with --surface-out: every row pitch is the row's bytes rounded up to a multiple of this")
     args = ap.parse_args()
+    assert not (args.device_out and args.surface_out), "--device-out and --surface-out are two deliveries"
+    assert args.pitch_align >= 1
     import dsvabi as A
     from codec_run import decode_stream, encode_stream
     from conftest import load_pkg
@@ -44,6 +49,15 @@ def main():
         hip.dsv2hip_dec_batch_device.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(C.c_void_p),
                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         hip.dsv2hip_dec_batch_device.restype = C.c_int
+    if args.surface_out:
+        import torch
+
+        class OUTSURF(C.Structure):  # dsv2hip_out_surface
+            _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("cap", C.c_size_t * 3), ("layout", C.c_int)]
+
+        hip.dsv2hip_dec_batch_surface.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(OUTSURF),
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        hip.dsv2hip_dec_batch_surface.restype = C.c_int
     pkg = load_pkg()
     S, G, K, Wm = args.streams, max(1, min(args.groups, args.streams)), args.steps, args.warmup
     nfr = Wm + K
@@ -64,6 +78,33 @@ def main():
     pic_bytes = W_ * H_ * 3 // 2
     dev_out = [torch.empty(pic_bytes, dtype=torch.uint8, device="cuda") for _ in range(S)] if args.device_out else None
     if dev_out:
+        torch.cuda.synchronize()
+    surf_out = None
+    if args.surface_out:
+        # one surface per decoder: every plane a tensor of its own, rows `pitch` apart
+        semi = args.surface_out == "nv12"
+        # the planes' sizes from the library: a probe decoder reads the stream's metadata packet, dsv2hip_dec_surface_dims answers
+        hip.dsv2hip_dec_surface_dims.argtypes = [C.POINTER(A.DECODER), C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        hip.dsv2hip_dec_surface_dims.restype = C.c_int
+        probe, pbuf, pfn = A.DECODER(), A.BUF(), C.c_uint32(0)
+        hip.dsv_mk_buf(C.byref(pbuf), len(vids[0][0]) + 64)
+        C.memmove(pbuf.data, vids[0][0], len(vids[0][0]))
+        assert hip.dsv_dec(C.byref(probe), C.byref(pbuf), C.byref(C.POINTER(A.FRAME)()), C.byref(pfn)) == A.DEC_GOT_META
+        rb, nrows = (C.c_size_t * 3)(), (C.c_int * 3)()
+        assert hip.dsv2hip_dec_surface_dims(C.byref(probe), 1 if semi else 0, rb, nrows) == 0
+        hip.dsv_dec_free(C.byref(probe))
+        rows = [(rb[i], nrows[i]) for i in range(3) if nrows[i]]
+        assert sum(b * r for b, r in rows) == pic_bytes
+        surf_out, keep = [], []
+        for _ in range(S):
+            c = OUTSURF()
+            c.layout = 1 if semi else 0
+            for i, (rb, nr) in enumerate(rows):
+                pitch = (rb + args.pitch_align - 1) // args.pitch_align * args.pitch_align
+                t = torch.empty(pitch * nr, dtype=torch.uint8, device="cuda")
+                keep.append(t)
+                c.plane[i], c.pitch[i], c.cap[i] = t.data_ptr(), pitch, pitch * nr
+            surf_out.append(c)
         torch.cuda.synchronize()
     group_of = [list(range(g, S, G)) for g in range(G)]
 
@@ -93,8 +134,15 @@ def main():
         if dev_out:
             ptrs = (C.c_void_p * m)(*[dev_out[s].data_ptr() for s in ids])
             caps = (C.c_size_t * m)(*[pic_bytes] * m)
+        if surf_out:
+            surfs = (OUTSURF * m)(*[surf_out[s] for s in ids])
         bar.wait()
         for t in range(t0, t1):
+            if surf_out:
+                had_meta = [decs[s].got_metadata for s in ids]
+                assert hip.dsv2hip_dec_batch_surface(m, decp, plan[g][t], surfs, fns, rets) == m
+                decoded[g] += sum(1 for i in range(m) if rets[i] == A.DEC_OK and had_meta[i])
+                continue
             if dev_out:
                 had_meta = [decs[s].got_metadata for s in ids]
                 assert hip.dsv2hip_dec_batch_device(m, decp, plan[g][t], ptrs, caps, fns, rets) == m
@@ -131,11 +179,16 @@ def main():
     for d in decs:
         hip.dsv_dec_free(C.byref(d))
     fps = nframes / elapsed
+    delivery = "device" if args.device_out else "host"
+    where = delivery + " memory"
+    if args.surface_out:
+        delivery = "surface-" + args.surface_out
+        where = "%s device surfaces, pitch a multiple of %d" % (args.surface_out, args.pitch_align)
     result = {"metric": "decoded frames/s, 1080p 4:2:0 qp=60 gop=48 (pictures identical to the reference decoder's)", "value": round(fps, 2),
               "unit": "frames/s", "n_gpus": 1, "steps": npk - first, "ms_per_step": round(1e3 * elapsed / max(1, npk - first), 3),
               "higher_is_better": True, "dtype": "u8/int32", "data": "synthetic",
-              "config": {"workload": "1920x1080 4:2:0 -qp=60 -gop=48, %d decoder instances in %d lockstep groups, frames delivered to %s memory" % (S, G, "device" if args.device_out else "host"),
-                         "streams_per_gpu": S, "groups": G, "draw_info": args.draw_info, "delivery": "device" if args.device_out else "host", "postsharp": args.postsharp, "host_cpu_cores_busy": round(host_cpu_s / elapsed, 2), "frames": nframes, "mpix_per_s": round(fps * W_ * H_ / 1e6, 1)}}
+              "config": {"workload": "1920x1080 4:2:0 -qp=60 -gop=48, %d decoder instances in %d lockstep groups, frames delivered to %s" % (S, G, where),
+                         "streams_per_gpu": S, "groups": G, "draw_info": args.draw_info, "delivery": delivery, "postsharp": args.postsharp, "host_cpu_cores_busy": round(host_cpu_s / elapsed, 2), "frames": nframes, "mpix_per_s": round(fps * W_ * H_ / 1e6, 1)}}
     if not args.no_cpu_baseline and os.path.exists(A.REF_SO):
         ref = A.load_ref()
         pk = vids[0][:25]
