@@ -17,6 +17,10 @@ namespace dsv2 {
 __device__ __forceinline__ int strip_value(const uint8_t *p, int step, int n, int k)
 {
     int full = n >> 2;
+    if (k < 0) {
+        return 0; // a line of fewer than 4 pixels has no last full group: the corners then take the byte in front of the reference's
+                  // zero-initialised strip (frame.c:378-380, index n / 4 - 1), which is zero
+    }
     if (k < full) {
         const uint8_t *q = p + (size_t) (4 * k) * step;
         return (q[0] + q[step] + q[2 * step] + q[3 * step] + 2) >> 2;

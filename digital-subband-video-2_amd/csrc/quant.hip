@@ -12,7 +12,9 @@
 //   the "dependent" last column / row of a level whose parent cell lies in the first
 //   column / row of the same level when subband sizes are odd (the reference rounds every
 //   scanned size up, hzcc.c:40-57, so adjacent levels overlap by one line).  Dependents
-//   run as a tiny second launch of the pass.
+//   run as a tiny second launch of the pass.  In a level one row or one column long (a plane dimension of 8 or less: the chroma
+//   of a picture 16 high) the last line is the first: dependents then read dependents -- cell x of such a row its cell x / 2, an
+//   HH cell the HL cell over it -- and the second launch is one thread walking them in scan order.
 #include "dev.h"
 #include "prio.h"
 #include "quant.h"
@@ -482,6 +484,24 @@ __global__ __launch_bounds__(256) void k_quant_level_dep(const PlaneJob *__restr
     quant_cell(J, c, a, si, x, y);
 }
 
+// phase B of a level one row or column long: the dependents in the reference's scan order (subband, row, column), one thread a job
+__global__ __launch_bounds__(64) void k_quant_level_dep_ordered(const PlaneJob *__restrict__ tab, QuantCfg c, LevelArgs a)
+{
+    if (threadIdx.x != 0) {
+        return;
+    }
+    const PlaneJob &J = tab[blockIdx.z];
+    for (int si = 0; si < 3; si++) {
+        for (int y = 0; y < a.sh; y++) {
+            for (int x = 0; x < a.sw; x++) {
+                if (is_dependent(a, si + 1, x, y)) {
+                    quant_cell(J, c, a, si, x, y);
+                }
+            }
+        }
+    }
+}
+
 void quant_steps(PlaneJob *job, const QuantCfg &cfg, int q)
 {
     int qf = q * 3 / 2; // fix_quant, hzcc.c:59
@@ -535,7 +555,9 @@ void quant_jobs(hipStream_t s, const PlaneJob *tab, int n, const QuantCfg &cfg)
         } else {
             DSV2_LAUNCH(k_quant_level, dim3((a.sw + 63) / 64, (a.sh + 3) / 4, 3 * nz), blk, 0, s, tab, cfg, a);
         }
-        if (a.xdep || a.ydep) {
+        if (a.sw == 1 || a.sh == 1) { // (then both flags are set: half of a size of 1, rounded up and doubled, exceeds it)
+            DSV2_LAUNCH(k_quant_level_dep_ordered, dim3(1, 1, nz), dim3(64), 0, s, tab, cfg, a);
+        } else if (a.xdep || a.ydep) {
             DSV2_LAUNCH(k_quant_level_dep, dim3((a.sw + a.sh + 255) / 256, 3, nz), dim3(256), 0, s, tab, cfg, a);
         }
     }
@@ -785,15 +807,9 @@ __global__ __launch_bounds__(256) void k_dequant_ll(const DequantJob *__restrict
     J.coefs[(size_t) y * c.w + x] = out;
 }
 
-// detail symbols of one level; `dep` selects the dependents phase (see header comment)
-__global__ __launch_bounds__(256) void k_dequant_level(const DequantJob *__restrict__ tab, QuantCfg c, DequantArgs a,
-                                                       int xdep, int ydep, int dep)
+// detail symbol i of one level; `dep` selects the dependents phase (see header comment)
+__device__ __forceinline__ void dequant_symbol(const DequantJob &J, const QuantCfg &c, const DequantArgs &a, int xdep, int ydep, int dep, int i)
 {
-    const DequantJob &J = tab[blockIdx.y];
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= J.seg[1 + a.l]) {
-        return;
-    }
     int first = J.seg[0] + (a.l > 0 ? J.seg[1] : 0) + (a.l > 1 ? J.seg[2] : 0);
     int p = (int) J.pos[first + i], v = J.val[first + i];
     int32_t *coefs = J.coefs;
@@ -816,6 +832,31 @@ __global__ __launch_bounds__(256) void k_dequant_level(const DequantJob *__restr
         out = dequant_D(v, (unsigned) tmq);
     }
     coefs[a.off[si] + (size_t) y * c.w + x] = out;
+}
+
+__global__ __launch_bounds__(256) void k_dequant_level(const DequantJob *__restrict__ tab, QuantCfg c, DequantArgs a,
+                                                       int xdep, int ydep, int dep)
+{
+    const DequantJob &J = tab[blockIdx.y];
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= J.seg[1 + a.l]) {
+        return;
+    }
+    dequant_symbol(J, c, a, xdep, ydep, dep, i);
+}
+
+// the dependents of a level one row or column long, which read each other: one thread a job walks the symbols, which are
+// sorted by scan position
+__global__ __launch_bounds__(64) void k_dequant_level_dep_ordered(const DequantJob *__restrict__ tab, QuantCfg c, DequantArgs a,
+                                                                  int xdep, int ydep)
+{
+    if (threadIdx.x != 0) {
+        return;
+    }
+    const DequantJob &J = tab[blockIdx.y];
+    for (int i = 0; i < J.seg[1 + a.l]; i++) {
+        dequant_symbol(J, c, a, xdep, ydep, 1, i);
+    }
 }
 
 void dequant_steps(DequantJob *job, const QuantCfg &cfg, int q)
@@ -857,7 +898,9 @@ void dequant_jobs(hipStream_t s, const DequantJob *tab, int n, const int max_seg
             a.par[si] = h_subband_off(l - 1, si + 1, cfg.w, cfg.h);
         }
         DSV2_LAUNCH(k_dequant_level, dim3((unsigned) (nmax + 255) / 256, ny), dim3(256), 0, s, tab, cfg, a, xdep, ydep, 0);
-        if (xdep || ydep) {
+        if (a.sw == 1 || a.sh == 1) {
+            DSV2_LAUNCH(k_dequant_level_dep_ordered, dim3(1, ny), dim3(64), 0, s, tab, cfg, a, xdep, ydep);
+        } else if (xdep || ydep) {
             DSV2_LAUNCH(k_dequant_level, dim3((unsigned) (nmax + 255) / 256, ny), dim3(256), 0, s, tab, cfg, a, xdep, ydep, 1);
         }
     }

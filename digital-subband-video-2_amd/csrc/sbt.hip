@@ -74,13 +74,20 @@ __device__ __forceinline__ int reflect_idx(int i, int nm1)
 struct VecI { // strided int32 vector
     const int32_t *p;
     int s, n;
+    // n == 1 (a dimension that has collapsed while the other still has levels to go): what the reference's update step
+    // v[0] += v[s] >> 1 (sbt.c:200, 222) reads next to the vector -- the previous level's high band at its final place in the
+    // coefficient plane, beside a row, below a column (for a column the reference finds it in row 1 of its scratch image, left
+    // there by the level that was two rows high)
+    const int32_t *past;
     __device__ __forceinline__ int operator()(int i) const { return p[i * s]; }
+    __device__ __forceinline__ int beyond() const { return *past; }
 };
 struct VecU8 { // row of the u8 picture, centred on zero; rows below the picture are zero
     const uint8_t *p;
     int n;
     bool live;
     __device__ __forceinline__ int operator()(int i) const { return live ? (int) p[i] - 128 : 0; }
+    __device__ __forceinline__ int beyond() const { return 0; } // (level 1 is never one sample long)
 };
 
 // adaptive tap selection walk (sbt.c:227-238, 392-405): flag byte of walk index t
@@ -102,11 +109,14 @@ template <class V> __device__ __forceinline__ int hi3(const V &v, int i)
     return v(i) - v(i - 1);
 }
 
+// the high-pass sample that the first update step reads
+template <class V> __device__ __forceinline__ int first_hi(const V &v) { return v.n > 1 ? hi3(v, 1) : v.beyond(); }
+
 template <class V> __device__ __forceinline__ int lo3(const V &v, int i)
 {
     int even_n = v.n & ~1;
     if (i == 0) {
-        return v(0) + (hi3(v, 1) >> 1);
+        return v(0) + (first_hi(v) >> 1);
     }
     if (i >= even_n) {
         return v(i);
@@ -118,7 +128,7 @@ template <class V> __device__ __forceinline__ int lo5(const V &v, int i, int c0,
 {
     int even_n = v.n & ~1, nm1 = v.n - 1;
     if (i == 0) {
-        return v(0) + (hi3(v, 1) >> 1);
+        return v(0) + (first_hi(v) >> 1);
     }
     if (i >= even_n) {
         return v(i);
@@ -186,6 +196,10 @@ struct Syn {
     const int32_t *lo; // low(k)  = lo[k * s]
     const int32_t *hi; // high(k) = hi[k * s]
     int s, n;
+    // n == 1: what out[0] -= out[s] >> 1 reads, unscaled: the coefficient beside a row, below a column (see VecI.  For a column
+    // the reference reads its scratch image, which holds that coefficient only straight after the forward transform of the same
+    // plane and anything otherwise: tests/edge_cases.py, inverse_reads_stale_scratch)
+    const int32_t *past;
 };
 
 template <int F> __device__ __forceinline__ int even_raw(const Syn &v, int k)
@@ -221,7 +235,7 @@ template <int F> __device__ __forceinline__ int syn_even(const Syn &v, const Rin
     int i = 2 * k, n = v.n, even_n = n & ~1, nm1 = n - 1;
     int e = even_raw<F>(v, k);
     if (i == 0) {
-        return e - (odd_raw<F>(v, 0) >> 1);
+        return e - ((n > 1 ? odd_raw<F>(v, 0) : *v.past) >> 1);
     }
     if (i >= even_n) {
         return e;
@@ -297,7 +311,7 @@ __global__ __launch_bounds__(256) void k_fwd_rows(const PlaneJob *__restrict__ t
         VecU8 v{J.pic.data + (size_t) j * J.pic.stride, g.sw, j < J.pic.h};
         analysis_pair<F>(v, r, k, L, H);
     } else {
-        VecI v{img(J, s_sel) + (size_t) j * g.w, 1, g.sw};
+        VecI v{img(J, s_sel) + (size_t) j * g.w, 1, g.sw, J.coefs + (size_t) j * g.w + 1};
         analysis_pair<F>(v, r, k, L, H);
     }
     R[(size_t) j * g.w + k] = L;
@@ -318,7 +332,7 @@ __global__ __launch_bounds__(256) void k_fwd_cols(const PlaneJob *__restrict__ t
     }
     int32_t *D = img(J, d_sel), *C = J.coefs;
     Ring r{g.use_bd ? J.bd + ((i * g.dbx) >> kBlockP) : nullptr, 2 * g.dby, g.nbh};
-    VecI v{J.t[2] + i, g.w, g.sh};
+    VecI v{J.t[2] + i, g.w, g.sh, C + g.w + i};
     int L, H;
     analysis_pair<F>(v, r, k, L, H);
     if (i < g.hw) {
@@ -913,7 +927,7 @@ __global__ __launch_bounds__(256) void k_inv_cols(const PlaneJob *__restrict__ t
     const int32_t *LLp = img(J, ll_sel), *C = J.coefs;
     int32_t *R = J.t[2];
     Ring r{g.use_bd ? J.bd + ((i * g.dbx) >> kBlockP) : nullptr, 2 * g.dby, g.nbh};
-    Syn v{(i < g.hw) ? LLp + i : C + i, C + (size_t) g.hh * g.w + i, g.w, g.sh};
+    Syn v{(i < g.hw) ? LLp + i : C + i, C + (size_t) g.hh * g.w + i, g.w, g.sh, C + g.w + i};
     int xe, xo;
     synthesis_pair<F>(v, r, k, xe, xo);
     R[(size_t) (2 * k) * g.w + i] = xe;
@@ -934,7 +948,7 @@ __global__ __launch_bounds__(256) void k_inv_rows(const PlaneJob *__restrict__ t
     }
     const int32_t *R = J.t[2];
     Ring r{g.use_bd ? J.bd + ((j * g.dby) >> kBlockP) * g.nbh : nullptr, 2 * g.dbx, 1};
-    Syn v{R + (size_t) j * g.w, R + (size_t) j * g.w + g.hw, 1, g.sw};
+    Syn v{R + (size_t) j * g.w, R + (size_t) j * g.w + g.hw, 1, g.sw, J.coefs + (size_t) j * g.w + 1};
     int xe, xo;
     synthesis_pair<F>(v, r, k, xe, xo);
     if (OUT_U8) {

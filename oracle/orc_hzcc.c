@@ -8,7 +8,10 @@
  *      is independent, except that with odd subband sizes the scanned regions of
  *      adjacent levels overlap by one column / row (hzcc.c:40-57 rounds every size
  *      up), which makes the last column / row of a level depend on its first one:
- *      those "dependent" cells form a second phase of the pass;
+ *      those "dependent" cells form a second phase of the pass, walked in scan order:
+ *      in a level one row or column long the last line is the first, and dependents
+ *      then read dependents (cell x of the row its cell x / 2, an HH cell the HL cell
+ *      over it);
  *   2. each pass writes the quantised value of every scanned coefficient into a
  *      dense array indexed by scan position (LL raster, then level-major,
  *      subband-major rasters: hzcc.c:264-342);

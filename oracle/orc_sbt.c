@@ -64,6 +64,12 @@ typedef struct {
      * sb[((k * delta2) >> 14) * sbs]  (sbt.c:227-238, 392-405) */
     const uint8_t *sb;
     int delta2, sbs;
+    /* n == 1 (a dimension that has collapsed while the other still has levels to go): the reference's update step
+     * v[0] += v[s] >> 1 (sbt.c:200, 222) then reads the sample next to the vector.  Along a row that is the coefficient beside
+     * it in the plane; along a column it is row 1 of the reference's scratch image, which the level that was two rows high left
+     * holding its (unscaled) high-pass output -- the coefficient below it in the plane.  Either way: the previous level's
+     * high band at its final place. */
+    const int32_t *past;
 } vec1d;
 
 #define XV(v, i) ((v)->p[(i) * (v)->s])
@@ -90,13 +96,20 @@ hi3(const vec1d *v, int i)
     return XV(v, i) - XV(v, i - 1); /* last sample of an even-length vector */
 }
 
+/* the high-pass sample that the first update step reads */
+static int
+first_hi(const vec1d *v)
+{
+    return v->n > 1 ? hi3(v, 1) : *v->past;
+}
+
 /* 3-tap update on even position i: sbt.c:199-203 DO_SIMPLE_LO with += */
 static int
 lo3(const vec1d *v, int i)
 {
     int even_n = v->n & ~1;
     if (i == 0) {
-        return XV(v, 0) + (hi3(v, 1) >> 1);
+        return XV(v, 0) + (first_hi(v) >> 1);
     }
     if (i >= even_n) {
         return XV(v, i); /* trailing even sample of an odd-length vector is not lifted */
@@ -111,7 +124,7 @@ lo5(const vec1d *v, int i, int c0, int ca, int cs)
     int even_n = v->n & ~1;
     int nm1 = v->n - 1;
     if (i == 0) {
-        return XV(v, 0) + (hi3(v, 1) >> 1);
+        return XV(v, 0) + (first_hi(v) >> 1);
     }
     if (i >= even_n) {
         return XV(v, i);
@@ -228,6 +241,11 @@ typedef struct {
     int s, n;
     const uint8_t *sb;
     int delta2, sbs;
+    /* n == 1: what out[0] -= out[s] >> 1 (sbt.c:200, 222) reads, unscaled.  Along a row it is the coefficient beside the
+     * vector in the plane, not yet consumed (the inverse of the level below reads it later).  Along a column the reference reads
+     * row 1 of its scratch image, which holds whatever the call before left there: only straight after the forward transform of
+     * the same plane is that the coefficient below the vector, which is what this restatement and the kernels take. */
+    const int32_t *past;
 } syn1d;
 
 static int
@@ -281,7 +299,7 @@ syn_even(int filter, const syn1d *v, int k)
     int e = syn_even_raw(filter, v, k);
 
     if (i == 0) {
-        return e - (odd_at(filter, v, 1) >> 1);
+        return e - ((n > 1 ? odd_at(filter, v, 1) : *v->past) >> 1);
     }
     if (i >= even_n) {
         return e;
@@ -362,6 +380,7 @@ fwd_separable(int filter, const sbt_ctx *c, const int32_t *S, int32_t *R, int32_
         v.sb = c->bd ? c->bd + ((j * dby) >> ORC_BLOCK_P) * c->nbh : NULL;
         v.delta2 = 2 * dbx;
         v.sbs = 1;
+        v.past = C + j * w + 1;
         for (k = 0; k < hw; k++) {
             int L, H;
             analysis_pair(filter, &v, k, &L, &H);
@@ -379,6 +398,7 @@ fwd_separable(int filter, const sbt_ctx *c, const int32_t *S, int32_t *R, int32_
         v.sb = c->bd ? c->bd + ((i * dbx) >> ORC_BLOCK_P) : NULL;
         v.delta2 = 2 * dby;
         v.sbs = c->nbh;
+        v.past = C + w + i;
         for (k = 0; k < hh; k++) {
             int L, H;
             analysis_pair(filter, &v, k, &L, &H);
@@ -581,6 +601,7 @@ inv_separable(int filter, const sbt_ctx *c, const int32_t *LLp, const int32_t *C
         v.sb = c->bd ? c->bd + ((i * dbx) >> ORC_BLOCK_P) : NULL;
         v.delta2 = 2 * dby;
         v.sbs = c->nbh;
+        v.past = C + w + i;
         for (k = 0; k < hh; k++) {
             R[(2 * k) * w + i] = syn_even(filter, &v, k);
             if (2 * k + 1 < sh) {
@@ -597,6 +618,7 @@ inv_separable(int filter, const sbt_ctx *c, const int32_t *LLp, const int32_t *C
         v.sb = c->bd ? c->bd + ((j * dby) >> ORC_BLOCK_P) * c->nbh : NULL;
         v.delta2 = 2 * dbx;
         v.sbs = 1;
+        v.past = C + j * w + 1;
         for (k = 0; k < hw; k++) {
             D[j * w + 2 * k] = syn_even(filter, &v, k);
             if (2 * k + 1 < sw) {

@@ -48,20 +48,27 @@ def build_pyramid(lib, base, levels):
 
 
 class Scene:
-    """src = frame t, ogr = frame t-1 (original), ref = degraded frame t-1 (stands for the reconstruction)."""
+    """src = frame t, ogr = frame t-1 (original), ref = degraded frame t-1 (stands for the reconstruction).
+    `planes` = ((Y, U, V) of the current picture, of the previous one, of the degraded previous one) replaces the synthetic
+    video's pictures by given ones, already on the format's chroma grid."""
 
-    def __init__(self, ref_lib, w, h, subsamp, seed, t=3, with_prev_mvs=True):
-        pkg = load_pkg()
+    def __init__(self, ref_lib, w, h, subsamp, seed, t=3, with_prev_mvs=True, planes=None):
         self.w, self.h, self.subsamp = w, h, subsamp
-        v = pkg.synth.SynthVideo(w, h, "420" if subsamp == A.SUBSAMP_420 else "444", seed=seed)
-        cur, prev = v.frame(t), v.frame(t - 1)
-        if subsamp not in (A.SUBSAMP_420, A.SUBSAMP_444):  # 4:2:2, 4:1:1 ...: the 4:4:4 picture's chroma decimated to the format's grid
+        if planes is None:
+            pkg = load_pkg()
+            v = pkg.synth.SynthVideo(w, h, "420" if subsamp == A.SUBSAMP_420 else "444", seed=seed)
+            cur, prev = v.frame(t), v.frame(t - 1)
+        else:
+            cur, prev = planes[0], planes[1]
+        if planes is None and subsamp not in (A.SUBSAMP_420, A.SUBSAMP_444):  # 4:2:2, 4:1:1 ...: the 4:4:4 picture's chroma decimated to the format's grid
             hs, vs = A.format_shifts(subsamp)
             cur = (cur[0], cur[1][::1 << vs, ::1 << hs].copy(), cur[2][::1 << vs, ::1 << hs].copy())
             prev = (prev[0], prev[1][::1 << vs, ::1 << hs].copy(), prev[2][::1 << vs, ::1 << hs].copy())
         rng = np.random.RandomState(seed)
         deg = [np.clip((p.astype(np.int32) // 6) * 6 + 3 + rng.randint(-1, 2, size=p.shape), 0, 255).astype(np.uint8)
                for p in prev]
+        if planes is not None:
+            deg = planes[2]
         self.src0 = frame_from_planes(subsamp, w, h, cur)
         self.ogr0 = frame_from_planes(subsamp, w, h, prev)
         self.ref0 = frame_from_planes(subsamp, w, h, deg)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import dsvabi as A
+from edge_cases import plane_bitstream_bytes
 from test_oracle_hzcc import CASES, rand_mvs, ref_encode_plane
 from test_oracle_sbt import rand_frame, ref_fwd
 
@@ -13,7 +14,8 @@ pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tes
 
 
 def decode_plane(lib, data, cw, ch, q, plane, isP, params, blockdata):
-    buf = np.concatenate([data, np.zeros(64, dtype=np.uint8)])
+    buf = np.zeros(plane_bitstream_bytes(cw, ch), dtype=np.uint8)
+    buf[:len(data)] = data
     coefs = np.zeros(cw * ch, dtype=np.int32)
     bs = A.BS(A.np_ptr(buf, C.c_uint8), 0)
     cs = A.COEFS(A.np_ptr(coefs, C.c_int32), cw, ch)
@@ -22,6 +24,7 @@ def decode_plane(lib, data, cw, ch, q, plane, isP, params, blockdata):
     fm.blockdata = A.np_ptr(blockdata, C.c_uint8)
     fm.cur_plane, fm.isP = plane, isP
     ok = lib.dsv_decode_plane(C.byref(bs), C.byref(cs), q, C.byref(fm))
+    assert bs.pos // 8 <= len(buf) // 2, "the parse ran past half of its buffer"
     return ok, coefs, bs.pos
 
 

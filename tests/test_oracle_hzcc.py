@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import dsvabi as A
+from edge_cases import plane_bitstream_bytes
 from test_oracle_sbt import rand_frame, ref_fwd
 
 pytestmark = pytest.mark.skipif(not os.path.exists(A.REF_SO), reason="oracle/_ref not built")
@@ -28,7 +29,7 @@ def rand_mvs(rng, nb):
 
 def ref_encode_plane(ref, coefs, cw, ch, q, plane, isP, params, blockdata, mvs):
     cc = coefs.copy()
-    out = np.zeros(cw * ch * 8 + 1024, dtype=np.uint8)
+    out = np.zeros(plane_bitstream_bytes(cw, ch), dtype=np.uint8)
     bs = A.BS(A.np_ptr(out, C.c_uint8), 0)
     cs = A.COEFS(A.np_ptr(cc, C.c_int32), cw, ch)
     fm = A.FMETA()
@@ -37,17 +38,19 @@ def ref_encode_plane(ref, coefs, cw, ch, q, plane, isP, params, blockdata, mvs):
     fm.mvs = C.cast(mvs.ctypes.data, C.POINTER(A.MV))
     fm.cur_plane, fm.isP = plane, isP
     ref.dsv_encode_plane(C.byref(bs), C.byref(cs), q, C.byref(fm))
+    assert bs.pos // 8 <= len(out) // 2, "the plane's bitstream outgrew half of its buffer"
     assert bs.pos % 8 == 0
     return out[:bs.pos // 8].copy(), cc
 
 
 def orc_encode_plane(orc, coefs, cw, ch, q, plane, isP, params, subsamp, blockdata, mvs):
     cc = coefs.copy()
-    out = np.zeros(cw * ch * 8 + 1024, dtype=np.uint8)
+    out = np.zeros(plane_bitstream_bytes(cw, ch), dtype=np.uint8)
     n = orc.orc_encode_plane(A.np_ptr(out, C.c_uint8), 0, A.np_ptr(cc, C.c_int32), cw, ch, q, plane, isP,
                              params.lossless, params.do_psy, (subsamp >> 2) & 3, subsamp & 3,
                              params.blk_w, params.blk_h, params.nblocks_h, params.nblocks_v,
                              A.np_ptr(blockdata, C.c_uint8), C.c_void_p(mvs.ctypes.data))
+    assert n <= len(out) // 2, "the plane's bitstream outgrew half of its buffer"
     return out[:n].copy(), cc
 
 
