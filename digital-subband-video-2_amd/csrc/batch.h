@@ -56,6 +56,12 @@ struct TableArena {
         }
     }
 };
+template <class T> struct Tab { // a job table in a step's arena: filled through h, handed to the kernels as d (no entries: no table)
+    T *h = nullptr;
+    const T *d = nullptr;
+    Tab() = default;
+    Tab(TableArena &a, size_t count) { h = count ? a.take<T>(count, &d) : nullptr; }
+};
 
 // Host phases run one task per stream on a process-wide pool of worker threads (created on first
 // use, sized to the machine); the calling thread works too, and several lockstep groups may share

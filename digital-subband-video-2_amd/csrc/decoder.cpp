@@ -58,15 +58,11 @@ struct DecJob {
     int ret = DSV_DEC_OK;
     bool pic = false; // a picture that takes part in the device phase
     DecImpl *im = nullptr;
-    int has_ref = 0, is_ref = 0, do_filter = 0, quant = 0, lossless = 0;
+    int has_ref = 0, is_ref = 0;
     DSV_FNUM fno = 0;
-    int ok[3] = {0, 0, 0};
-    int seg[3][4];
-    int32_t LL[3] = {0, 0, 0};
-    size_t sym_first[3] = {0, 0, 0}; // first symbol of each plane within the decoder's list
-    size_t nsym = 0, stage_off = 0;
-    bool dev_parse = false;          // the plane sections' symbols are parsed on the device (dec_parse_dev.hip)
-    PlaneHead head[3];               // ... from here
+    PictureBody body;                // what the packet says behind the head (dec_parse.h); sym_first: within the decoder's list
+    size_t stage_off = 0;
+    bool dev_parse = false;          // the plane sections' symbols are parsed on the device (dec_parse_dev.hip) from body.head
     int cap[3] = {0, 0, 0};          // ... into lists of this many entries (min(header count, coefficients of the plane))
     size_t pkt_off = 0;              // ... out of the packet as staged at this offset of the round's stage block
     DSV_FRAME *of = nullptr; // output picture: a bordered frame on pinned memory the device writes directly
@@ -229,7 +225,6 @@ void dec_parse(DecJob &jb)
     jb.has_ref = hd.has_ref;
     jb.is_ref = hd.is_ref;
     jb.fno = hd.fno;
-    const int blk_w = hd.blk_w, blk_h = hd.blk_h;
     bind_device();
     DecImpl *im = (DecImpl *) d->ref;
     if (!im) {
@@ -238,41 +233,28 @@ void dec_parse(DecJob &jb)
     }
     jb.im = im;
     if (im->ready && (im->dev.w != meta->width || im->dev.h != meta->height || im->dev.format != meta->subsamp ||
-                      im->dev.blk_w != blk_w || im->dev.blk_h != blk_h)) {
+                      im->dev.blk_w != hd.blk_w || im->dev.blk_h != hd.blk_h)) {
         im->dev.destroy(); // stream parameters changed: start over
         im->ready = false;
         im->have_ref = false;
     }
     if (!im->ready) {
-        im->dev.init(meta->subsamp, meta->width, meta->height, blk_w, blk_h, 0, false);
+        im->dev.init(meta->subsamp, meta->width, meta->height, hd.blk_w, hd.blk_h, 0, false);
         im->dev.scratch_uv[0].ensure((size_t) im->dev.cw[1] * im->dev.ch[1], sbt_ll_elems(im->dev.cw[1], im->dev.ch[1]));
         im->dev.scratch_uv[1].ensure((size_t) im->dev.cw[2] * im->dev.ch[2], sbt_ll_elems(im->dev.cw[2], im->dev.ch[2]));
         im->ready = true;
     }
     CodecDev &dv = im->dev;
-    PictureBody body;
+    PictureBody &body = jb.body;
     const int dev_mode = g_dev_parse.load(std::memory_order_relaxed);
     jb.dev_parse = dev_mode >= 2 || (dev_mode == 1 && hd.has_ref);
     parse_body(br, pkt, hd.has_ref, dv.nbh, dv.nbv, dv.scan, im->side, im->pos, im->val, body, jb.dev_parse);
-    jb.do_filter = body.do_filter;
-    jb.quant = body.quant;
-    jb.lossless = body.lossless;
-    for (int c = 0; c < 3; c++) {
-        jb.sym_first[c] = body.sym_first[c];
-        jb.LL[c] = body.LL[c];
-        jb.ok[c] = body.ok[c];
-        for (int k = 0; k < 4; k++) {
-            jb.seg[c][k] = body.seg[c][k];
-        }
-    }
-    jb.nsym = body.nsym;
     if (jb.dev_parse) {
         // the symbol lists live in device memory; their sizes come from the (untrusted) header counts, bounded by the planes' coefficient counts
         size_t at = 0;
         for (int c = 0; c < 3; c++) {
-            jb.head[c] = body.head[c];
-            jb.sym_first[c] = at;
-            jb.cap[c] = jb.ok[c] > 0 ? std::min(std::max(body.head[c].runs, 0), dv.scan[c].base[10]) : 0;
+            body.sym_first[c] = at;
+            jb.cap[c] = body.ok[c] > 0 ? std::min(std::max(body.head[c].runs, 0), dv.scan[c].base[10]) : 0;
             at += (size_t) jb.cap[c];
         }
         dv.ensure_dev_syms(at);
@@ -295,358 +277,395 @@ void dec_parse(DecJob &jb)
     jb.pic = true;
 }
 
-// phases B and C for the jobs listed in `ids` (pictures of one geometry)
-void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
-{
-    const int n = (int) ids.size();
+// ---- one device round: phases B and C for the pictures of one geometry, as functions over one Round ----
+struct Slice { // a run of the sorted order with one (frame type, lossless) class: one set of dequantiser / transform launches
+    int first, count, isP, lossless, max_seg[3][4];
+};
+
+struct Round { // what outlives a phase (the decoder's counterpart of the encoder's Step)
+    DecJob *const jobs;
+    const std::vector<int> &ids;
+    const int n;
     DecScratchLease lease; // (the round ends with its stream drained: nothing of the scratch is in use after it)
     DecScratch &sc = *lease.sc;
-    CodecDev &dv0 = jobs[ids[0]].im->dev;
+    CodecDev &dv0; // the geometry every picture of the round shares
     hipStream_t bs = sc.main_stream(); // (a stream of the scratch pool, made once: see the encoder's ScratchPool)
-    const size_t nb = dv0.nblocks();
-    const size_t mv_bytes = nb * sizeof(DSV_MV), bd_bytes = (nb + 15) & ~(size_t) 15;
-    int n_draw = 0; // pictures of this round that get the draw_info overlay (none: no table, no launch)
-    int n_egress = 0; // ... that leave through the egress kernel: device delivery, postsharp (none: no table, no launch)
-    int n_semi = 0;   // ... whose chroma leaves interleaved, into a semiplanar surface (none: no table, no launch)
-    for (int i = 0; i < n; i++) {
-        n_draw += jobs[ids[(size_t) i]].draw != 0;
-        n_egress += jobs[ids[(size_t) i]].to_dev || jobs[ids[(size_t) i]].sharp;
-        n_semi += jobs[ids[(size_t) i]].to_dev && jobs[ids[(size_t) i]].semi;
-    }
-    sc.tabs.reserve((size_t) n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob) +
-                    (size_t) n_semi * sizeof(UvEgressJob));
+    const size_t nb = dv0.nblocks(), mv_bytes = nb * sizeof(DSV_MV), bd_bytes = (nb + 15) & ~(size_t) 15;
+    size_t stage_used = 0;
+    std::vector<int> order; // ids, sorted by (frame type, lossless): the kernels are specialised on those.  order[slot] = job
+    std::vector<Slice> slices;
+    // coefficients.  Device-parsed sections: one parse job each; a damaged one raises its flag and the plane's residual is zeroed
+    // behind the inverse transform (zcond); zfail: the residual planes of sections that the host found damaged
+    Tab<CopyJob> zero, zcond, zfail;
+    Tab<DequantJob> dq[3];
+    Tab<PlaneJob> pj[3];
+    Tab<DecParseJob> parse;
+    Tab<int> fail;
+    int n_parse = 0, n_zfail = 0;
+    size_t max_coef_bytes = 0, max_plane_bytes = 0;
+    // reconstruction
+    Tab<McJob> mc_pred, mc_filt, mc_intra;
+    Tab<PlanePair> icopy[3];
+    Tab<DPlane> ext[3];
+    int nP = 0, nI = 0, nIf = 0, n_ext = 0;
+    bool any_filter = false;
+    // delivery.  ov / eg / uv: only in a round with pictures that are drawn on / leave through the egress kernel (device delivery,
+    // postsharp) / leave with interleaved chroma, into a semiplanar surface (none: no table, no launch)
+    Tab<CopyJob> out;
+    Tab<To420Job> to420;
+    Tab<OverlayJob> ov;
+    Tab<EgressJob> eg;
+    Tab<UvEgressJob> uv;
+    int n_out = 0, n_to420 = 0, n_ov = 0, n_eg = 0, n_uv = 0;
+    int uv_rows = 0;                      // the most chroma rows an interleave job delivers ("4:1:0" to 4:2:0: more than the source has)
+    bool uv_wide = true, uv_conv = false; // every interleave job allows the 16-byte form / some job converts to 4:2:0 (bmc.hip: k_egress_uv)
+    bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
+    bool ov_vectors = false;               // some overlay job draws motion vectors
+    std::vector<DPlane> sharp_drawn; // delivered luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
+    Round(DecJob *jobs_, const std::vector<int> &ids_) : jobs(jobs_), ids(ids_), n((int) ids_.size()), dv0(jobs_[ids_[0]].im->dev), order(ids_) {}
+    const DSV_MV *d_mvs(const DecJob &jb) const { return (const DSV_MV *) (sc.d_stage + jb.stage_off); } // as staged for the kernels
+    const uint8_t *d_bd(const DecJob &jb) const { return sc.d_stage + jb.stage_off + mv_bytes; }
+};
 
-    // stage layout: per stream {motion field, block flags}
-    // stage layout: per stream {motion field, block flags}, then -- for pictures whose sections the device parses -- the packets,
-    // each 16-byte aligned with 64 zero bytes behind it (the parser reads a 2 KB window: the block ends with that much slack)
+// The arena holds every table of the round.  Per picture: the tables below; the 65536 cover the three conditional tables' alignment.
+static_assert(13 * sizeof(CopyJob) + 3 * (sizeof(DequantJob) + sizeof(PlaneJob) + sizeof(McJob) + sizeof(PlanePair) + sizeof(DPlane) +
+                                          sizeof(To420Job) + sizeof(DecParseJob) + sizeof(int)) + 22 * 16 <= 8192,
+              "a picture's share of the round's 22 job tables outgrew the 8192 bytes reserved for it");
+void round_take_tables(Round &r)
+{
+    int n_draw = 0, n_egress = 0, n_semi = 0;
+    for (int k : r.ids) {
+        const DecJob &jb = r.jobs[k];
+        n_draw += jb.draw != 0;
+        n_egress += jb.to_dev || jb.sharp;
+        n_semi += jb.to_dev && jb.semi;
+    }
+    TableArena &tabs = r.sc.tabs;
+    const size_t n = (size_t) r.n;
+    tabs.reserve(n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob) +
+                 (size_t) n_semi * sizeof(UvEgressJob));
+    r.zero = Tab<CopyJob>(tabs, 3 * n);
+    r.out = Tab<CopyJob>(tabs, n);
+    for (int c = 0; c < 3; c++) {
+        r.dq[c] = Tab<DequantJob>(tabs, n);
+        r.pj[c] = Tab<PlaneJob>(tabs, n);
+        r.icopy[c] = Tab<PlanePair>(tabs, n);
+        r.ext[c] = Tab<DPlane>(tabs, n);
+    }
+    r.mc_pred = Tab<McJob>(tabs, n);
+    r.mc_filt = Tab<McJob>(tabs, n);
+    r.mc_intra = Tab<McJob>(tabs, n);
+    r.zfail = Tab<CopyJob>(tabs, 3 * n);
+    r.to420 = Tab<To420Job>(tabs, 3 * n);
+    r.parse = Tab<DecParseJob>(tabs, 3 * n);
+    r.zcond = Tab<CopyJob>(tabs, 3 * n);
+    r.fail = Tab<int>(tabs, 3 * n);
+    r.ov = Tab<OverlayJob>(tabs, (size_t) n_draw);
+    r.eg = Tab<EgressJob>(tabs, 3 * (size_t) n_egress);
+    r.uv = Tab<UvEgressJob>(tabs, (size_t) n_semi);
+}
+
+size_t staged_len(const DSV_BUF *b) { return ((size_t) b->len + 64 + 15) & ~(size_t) 15; } // a packet as staged: 16-byte aligned, 64 zero bytes behind it
+
+// stage layout: per stream {motion field, block flags}, then -- for pictures whose sections the device parses -- the packets
+// (the parser reads a 2 KB window: the block ends with that much slack)
+void round_stage(Round &r)
+{
     size_t total = 0;
     int n_dev = 0;
-    for (int i = 0; i < n; i++) {
-        DecJob &jb = jobs[ids[(size_t) i]];
-        jb.stage_off = total;
-        total += mv_bytes + bd_bytes;
+    for (int k : r.ids) {
+        r.jobs[k].stage_off = total;
+        total += r.mv_bytes + r.bd_bytes;
     }
-    for (int i = 0; i < n; i++) {
-        DecJob &jb = jobs[ids[(size_t) i]];
+    for (int k : r.ids) {
+        DecJob &jb = r.jobs[k];
         if (jb.dev_parse) {
             jb.pkt_off = total;
-            total += ((size_t) jb.buf->len + 64 + 15) & ~(size_t) 15;
+            total += staged_len(jb.buf);
             n_dev++;
         }
     }
-    const size_t stage_used = total;
-    sc.ensure_stage(total + (n_dev ? 4096 : 0));
-    parallel_for(n, [&](int i) {
-        DecJob &jb = jobs[ids[(size_t) i]];
-        DecImpl *im = jb.im;
-        uint8_t *h = sc.h_stage + jb.stage_off;
+    r.stage_used = total;
+    r.sc.ensure_stage(total + (n_dev ? 4096 : 0));
+    parallel_for(r.n, [&](int i) {
+        DecJob &jb = r.jobs[r.ids[(size_t) i]];
+        uint8_t *h = r.sc.h_stage + jb.stage_off;
         if (jb.has_ref) {
-            memcpy(h, im->mvs.data(), mv_bytes);
+            memcpy(h, jb.im->mvs.data(), r.mv_bytes);
         }
-        memcpy(h + mv_bytes, im->blockdata.data(), nb);
+        memcpy(h + r.mv_bytes, jb.im->blockdata.data(), r.nb);
         if (jb.dev_parse) {
-            uint8_t *p = sc.h_stage + jb.pkt_off;
+            uint8_t *p = r.sc.h_stage + jb.pkt_off;
             memcpy(p, jb.buf->data, jb.buf->len);
-            memset(p + jb.buf->len, 0, (((size_t) jb.buf->len + 64 + 15) & ~(size_t) 15) - jb.buf->len);
+            memset(p + jb.buf->len, 0, staged_len(jb.buf) - jb.buf->len);
         }
     });
-
     t_dec_clock.lap(1);
-    // order by (frame type, lossless): the kernels are specialised on those
-    std::vector<int> order(ids);
-    auto cls = [&](int k) { return jobs[k].has_ref * 2 + jobs[k].lossless; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cls(a) > cls(b); });
+}
 
-    const CopyJob *d_zero, *d_out;
-    CopyJob *h_zero = sc.tabs.take<CopyJob>(3 * (size_t) n, &d_zero), *h_out = sc.tabs.take<CopyJob>((size_t) n, &d_out);
-    const DequantJob *d_dq[3];
-    DequantJob *h_dq[3];
-    const PlaneJob *d_pj[3];
-    PlaneJob *h_pj[3];
-    for (int c = 0; c < 3; c++) {
-        h_dq[c] = sc.tabs.take<DequantJob>((size_t) n, &d_dq[c]);
-        h_pj[c] = sc.tabs.take<PlaneJob>((size_t) n, &d_pj[c]);
-    }
-    const McJob *d_mc_pred, *d_mc_filt, *d_mc_intra;
-    McJob *h_mc_pred = sc.tabs.take<McJob>((size_t) n, &d_mc_pred), *h_mc_filt = sc.tabs.take<McJob>((size_t) n, &d_mc_filt),
-          *h_mc_intra = sc.tabs.take<McJob>((size_t) n, &d_mc_intra);
-    const PlanePair *d_icopy[3];
-    PlanePair *h_icopy[3];
-    const DPlane *d_ext[3];
-    DPlane *h_ext[3];
-    for (int c = 0; c < 3; c++) {
-        h_icopy[c] = sc.tabs.take<PlanePair>((size_t) n, &d_icopy[c]);
-        h_ext[c] = sc.tabs.take<DPlane>((size_t) n, &d_ext[c]);
-    }
-    const CopyJob *d_zfail;
-    CopyJob *h_zfail = sc.tabs.take<CopyJob>(3 * (size_t) n, &d_zfail);
-    const To420Job *d_to420;
-    To420Job *h_to420 = sc.tabs.take<To420Job>(3 * (size_t) n, &d_to420);
-    // device-parsed sections: one job each; a damaged one raises its flag and the plane's residual is zeroed behind the inverse transform
-    const DecParseJob *d_parse;
-    DecParseJob *h_parse = sc.tabs.take<DecParseJob>(3 * (size_t) n, &d_parse);
-    const CopyJob *d_zcond;
-    CopyJob *h_zcond = sc.tabs.take<CopyJob>(3 * (size_t) n, &d_zcond);
-    const int *d_fail;
-    int *h_fail = sc.tabs.take<int>(3 * (size_t) n, &d_fail);
-    const OverlayJob *d_ov = nullptr;
-    OverlayJob *h_ov = n_draw ? sc.tabs.take<OverlayJob>((size_t) n_draw, &d_ov) : nullptr;
-    int n_ov = 0;
-    bool ov_vectors = false;
-    const EgressJob *d_eg = nullptr;
-    EgressJob *h_eg = n_egress ? sc.tabs.take<EgressJob>(3 * (size_t) n_egress, &d_eg) : nullptr;
-    int n_eg = 0;
-    bool eg_sharp = false;           // some egress job sharpens
-    bool eg_wide = true;             // every egress job of the round allows the 16-byte form (bmc.hip: k_egress)
-    const UvEgressJob *d_uv = nullptr;
-    UvEgressJob *h_uv = n_semi ? sc.tabs.take<UvEgressJob>((size_t) n_semi, &d_uv) : nullptr;
-    int n_uv = 0;
-    int uv_rows = 0;                      // the most chroma rows an interleave job delivers ("4:1:0" to 4:2:0: more than the source has)
-    bool uv_wide = true, uv_conv = false; // every interleave job allows the 16-byte form / some job converts to 4:2:0 (bmc.hip: k_egress_uv)
-    std::vector<DPlane> sharp_drawn; // delivered luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
-    int n_parse = 0;
-    int nP = 0, nI = 0, nIf = 0, n_ext = 0, n_zfail = 0, n_out = 0, n_to420 = 0;
-    size_t max_plane_bytes = 0;
-    bool any_filter = false;
-    size_t max_coef_bytes = 0;
-    struct Slice {
-        int first, count, isP, lossless, max_seg[3][4];
-    };
-    std::vector<Slice> slices;
-    for (int i = 0; i < n; i++) {
-        DecJob &jb = jobs[order[(size_t) i]];
-        DecImpl *im = jb.im;
-        CodecDev &dv = im->dev;
-        PicSet &cur = dv.pics[im->cur], &ref = dv.pics[im->cur ^ 1];
-        DFrame &resid = dv.pred; // the decoder's residual picture
-        const uint8_t *d_slot = sc.d_stage + jb.stage_off;
-        const DSV_MV *d_mvs = (const DSV_MV *) d_slot;
-        const uint8_t *d_bd = d_slot + mv_bytes;
-        const uint32_t *d_pos = dv.h_pos; // pinned host memory, read in place
-        const int32_t *d_val = dv.h_val;
-        if (slices.empty() || slices.back().isP != jb.has_ref || slices.back().lossless != jb.lossless) {
-            Slice sl = {};
-            sl.first = i;
-            sl.isP = jb.has_ref;
-            sl.lossless = jb.lossless;
-            slices.push_back(sl);
+void round_sort(Round &r)
+{
+    auto cls = [&](int k) { return r.jobs[k].has_ref * 2 + r.jobs[k].body.lossless; };
+    std::stable_sort(r.order.begin(), r.order.end(), [&](int a, int b) { return cls(a) > cls(b); });
+    for (int i = 0; i < r.n; i++) {
+        const DecJob &jb = r.jobs[r.order[(size_t) i]];
+        if (r.slices.empty() || r.slices.back().isP != jb.has_ref || r.slices.back().lossless != jb.body.lossless) {
+            r.slices.push_back(Slice{i, 0, jb.has_ref, jb.body.lossless, {}});
         }
-        Slice &sl = slices.back();
-        sl.count++;
-        MCParams mc = dv.mc_params((int) (jb.fno % 2), jb.lossless);
+        r.slices.back().count++;
+    }
+}
+
+// zero, dequantise and inverse-transform jobs of the picture in slot i of slice sl; its device-parse jobs, its damaged planes
+void fill_coef_jobs(Round &r, Slice &sl, int i, DecJob &jb)
+{
+    CodecDev &dv = jb.im->dev;
+    const PictureBody &b = jb.body;
+    DFrame &resid = dv.pred; // the decoder's residual picture
+    for (int c = 0; c < 3; c++) {
+        size_t cbytes = (size_t) dv.cw[c] * dv.ch[c] * sizeof(int32_t);
+        r.zero.h[3 * i + c] = CopyJob{nullptr, dv.coefs[c], cbytes};
+        r.max_coef_bytes = std::max(r.max_coef_bytes, cbytes);
+        const CopyJob zero_resid = CopyJob{nullptr, resid.alloc + resid.plane_off[c], resid.plane_len[c]};
+        DequantJob &dq = r.dq[c].h[i];
+        dq.coefs = dv.coefs[c];
+        // host-parsed symbols: read in place from pinned host memory; device-parsed: the kernel writes the counts into this record's device copy
+        dq.pos = (jb.dev_parse ? dv.d_sym_pos : dv.h_pos) + b.sym_first[c];
+        dq.val = (jb.dev_parse ? dv.d_sym_val : dv.h_val) + b.sym_first[c];
+        for (int k = 0; k < 4; k++) {
+            dq.seg[k] = jb.dev_parse ? 0 : b.seg[c][k];
+            sl.max_seg[c][k] = std::max(sl.max_seg[c][k], jb.dev_parse ? jb.cap[c] : b.seg[c][k]);
+        }
+        if (jb.dev_parse && b.ok[c] > 0) {
+            DecParseJob &pj = r.parse.h[r.n_parse];
+            pj.pkt = r.sc.d_stage + jb.pkt_off;
+            pj.data_bitpos = b.head[c].data_bitpos;
+            pj.limit_bits = (jb.buf->len + 8) * 8;
+            pj.end_byte = b.head[c].end_byte;
+            pj.runs = b.head[c].runs;
+            pj.cap = jb.cap[c];
+            pj.chroma = c != 0;
+            pj.pos = dv.d_sym_pos + b.sym_first[c];
+            pj.val = dv.d_sym_val + b.sym_first[c];
+            pj.seg_out = const_cast<int *>(r.dq[c].d[i].seg);
+            pj.fail = const_cast<int *>(r.fail.d) + r.n_parse;
+            r.fail.h[r.n_parse] = 0;
+            r.zcond.h[r.n_parse] = zero_resid;
+            r.max_plane_bytes = std::max(r.max_plane_bytes, resid.plane_len[c]);
+            r.n_parse++;
+        }
+        dq.bd = r.d_bd(jb);
+        dq.LL = b.LL[c];
+        dequant_steps(&dq, dv.quant_cfg(c, jb.has_ref, b.lossless, 0, nullptr), b.quant);
+        PlaneJob &pj = r.pj[c].h[i];
+        pj = PlaneJob{};
+        pj.pic = resid.p[c];
+        pj.coefs = dv.coefs[c];
+        for (int t = 0; t < 3; t++) {
+            pj.t[t] = c ? dv.scratch_uv[c - 1].t[t] : dv.scratch.t[t];
+        }
+        pj.bd = r.d_bd(jb);
+        pj.q = b.quant;
+        if (b.ok[c] <= 0) { // "decoding error in plane": its residual plane stays zero (dsv_decoder.c:516-523)
+            r.zfail.h[r.n_zfail++] = zero_resid;
+            r.max_plane_bytes = std::max(r.max_plane_bytes, resid.plane_len[c]);
+        }
+    }
+}
+
+// prediction + in-loop filters or intra copy + intra filter, border extension of a picture that is kept as a reference
+void fill_recon_jobs(Round &r, DecJob &jb)
+{
+    CodecDev &dv = jb.im->dev;
+    PicSet &cur = dv.pics[jb.im->cur], &ref = dv.pics[jb.im->cur ^ 1];
+    DFrame &resid = dv.pred;
+    McJob mj;
+    mj.mvs = r.d_mvs(jb);
+    mj.bd = r.d_bd(jb);
+    mj.p = dv.mc_params((int) (jb.fno % 2), jb.body.lossless);
+    if (jb.has_ref) {
+        mj.f = make_filter_params(mj.p, jb.body.quant, jb.body.do_filter, jb.d->vidmeta.inter_sharpen);
         for (int c = 0; c < 3; c++) {
-            size_t cbytes = (size_t) dv.cw[c] * dv.ch[c] * sizeof(int32_t);
-            h_zero[3 * i + c] = CopyJob{nullptr, dv.coefs[c], cbytes};
-            max_coef_bytes = cbytes > max_coef_bytes ? cbytes : max_coef_bytes;
-            DequantJob &dq = h_dq[c][i];
-            dq.coefs = dv.coefs[c];
-            if (jb.dev_parse) {
-                dq.pos = dv.d_sym_pos + jb.sym_first[c];
-                dq.val = dv.d_sym_val + jb.sym_first[c];
-                for (int k = 0; k < 4; k++) { // (the counts are written into the device copy of this record by the parse kernel)
-                    dq.seg[k] = 0;
-                    sl.max_seg[c][k] = jb.cap[c] > sl.max_seg[c][k] ? jb.cap[c] : sl.max_seg[c][k];
+            mj.ref.p[c] = ref.recon.p[c];
+            mj.pred.p[c] = cur.recon.p[c];
+            mj.res.p[c] = resid.p[c];
+        }
+        r.mc_pred.h[r.nP] = mj;
+        mj.res = mj.pred;
+        r.mc_filt.h[r.nP++] = mj;
+        r.any_filter = r.any_filter || !jb.body.lossless;
+    } else {
+        mj.f = make_filter_params(mj.p, jb.body.quant, 1, 0);
+        for (int c = 0; c < 3; c++) {
+            mj.ref.p[c] = mj.pred.p[c] = mj.res.p[c] = resid.p[c];
+            r.icopy[c].h[r.nI] = PlanePair{resid.p[c], cur.recon.p[c]};
+        }
+        r.nI++;
+        if (jb.body.do_filter && !jb.body.lossless) { // dsv_intra_filter is a no-op for lossless pictures (bmc.c:398)
+            r.mc_intra.h[r.nIf++] = mj;
+        }
+    }
+    if (jb.is_ref || !jb.has_ref) {
+        for (int c = 0; c < 3; c++) {
+            r.ext[c].h[r.n_ext] = cur.recon.p[c];
+        }
+        r.n_ext++;
+    }
+}
+
+// the picture's way out: whole-frame copy, or per plane 4:2:0 conversion / egress / chroma interleave; the overlay behind it
+void fill_delivery_jobs(Round &r, DecJob &jb)
+{
+    CodecDev &dv = jb.im->dev;
+    DFrame &recon = dv.pics[jb.im->cur].recon;
+    // the planes of the delivered picture: those of the pinned frame, or the caller's device planes (semiplanar: op[1] is the
+    // interleaved plane, w (U, V) pairs a row; op[2] is not a plane)
+    DPlane op[3];
+    if (jb.to_dev) {
+        const int ohs = DSV_FORMAT_H_SHIFT(jb.out_format), ovs = DSV_FORMAT_V_SHIFT(jb.out_format);
+        const int ocw = (dv.w + (1 << ohs) - 1) >> ohs, och = (dv.h + (1 << ovs) - 1) >> ovs; // dsv_mk_frame's plane sizes (frame.c:63-113)
+        op[0] = DPlane{jb.dst[0], jb.dpitch[0], dv.w, dv.h};
+        op[1] = DPlane{jb.dst[1], jb.dpitch[1], ocw, och};
+        op[2] = DPlane{jb.semi ? nullptr : jb.dst[2], jb.semi ? 0 : jb.dpitch[2], ocw, och};
+    } else {
+        for (int c = 0; c < 3; c++) {
+            const DSV_PLANE &fp = jb.of->planes[c];
+            op[c] = DPlane{fp.data, fp.stride, fp.w, fp.h};
+        }
+    }
+    const bool conv = jb.out_format != dv.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
+    const bool sharp_out = jb.sharp && !jb.draw;  // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
+    if (!conv && !jb.to_dev && !sharp_out) {
+        r.out.h[r.n_out++] = CopyJob{recon.alloc, jb.of->alloc, recon.bytes};
+    } else {
+        const int hs = DSV_FORMAT_H_SHIFT(dv.format), vs = DSV_FORMAT_V_SHIFT(dv.format);
+        const int mode = (hs == 0 && vs == 0) ? 1 : (hs == 1 && vs == 0) ? 2 : (hs == 2 && vs == 0) ? 3 : 4;
+        for (int c = 0; c < 3; c++) {
+            if (c && jb.to_dev && jb.semi) { // both chroma planes through one job, converted on the way or not
+                if (c == 1) {
+                    const DPlane &su = recon.p[1];
+                    UvEgressJob &uj = r.uv.h[r.n_uv++];
+                    uj = UvEgressJob{su.data, recon.p[2].data, op[1].data, op[1].stride, su.stride, su.w, su.h, op[1].w, op[1].h, conv ? mode : 0};
+                    r.uv_wide = r.uv_wide && uv_job_wide(uj);
+                    r.uv_conv = r.uv_conv || conv;
+                    r.uv_rows = std::max(r.uv_rows, op[1].h);
                 }
-                if (jb.ok[c] > 0) {
-                    DecParseJob &pj = h_parse[n_parse];
-                    pj.pkt = sc.d_stage + jb.pkt_off;
-                    pj.data_bitpos = jb.head[c].data_bitpos;
-                    pj.limit_bits = (jb.buf->len + 8) * 8;
-                    pj.end_byte = jb.head[c].end_byte;
-                    pj.runs = jb.head[c].runs;
-                    pj.cap = jb.cap[c];
-                    pj.chroma = c != 0;
-                    pj.pos = dv.d_sym_pos + jb.sym_first[c];
-                    pj.val = dv.d_sym_val + jb.sym_first[c];
-                    pj.seg_out = (int *) ((uint8_t *) const_cast<DequantJob *>(d_dq[c]) + (size_t) i * sizeof(DequantJob) + offsetof(DequantJob, seg));
-                    pj.fail = const_cast<int *>(d_fail) + n_parse;
-                    h_fail[n_parse] = 0;
-                    h_zcond[n_parse] = CopyJob{nullptr, resid.alloc + resid.plane_off[c], resid.plane_len[c]};
-                    max_plane_bytes = resid.plane_len[c] > max_plane_bytes ? resid.plane_len[c] : max_plane_bytes;
-                    n_parse++;
-                }
+            } else if (conv && (c || (!jb.to_dev && !sharp_out))) {
+                r.to420.h[r.n_to420++] = To420Job{recon.p[c], op[c], c ? mode : 0};
             } else {
-                dq.pos = d_pos + jb.sym_first[c];
-                dq.val = d_val + jb.sym_first[c];
-                for (int k = 0; k < 4; k++) {
-                    dq.seg[k] = jb.seg[c][k];
-                    sl.max_seg[c][k] = jb.seg[c][k] > sl.max_seg[c][k] ? jb.seg[c][k] : sl.max_seg[c][k];
-                }
-            }
-            dq.bd = d_bd;
-            dq.LL = jb.LL[c];
-            dequant_steps(&dq, dv.quant_cfg(c, jb.has_ref, jb.lossless, 0, nullptr), jb.quant);
-            PlaneJob &pj = h_pj[c][i];
-            pj = PlaneJob{};
-            pj.pic = resid.p[c];
-            pj.coefs = dv.coefs[c];
-            for (int t = 0; t < 3; t++) {
-                pj.t[t] = c ? dv.scratch_uv[c - 1].t[t] : dv.scratch.t[t];
-            }
-            pj.bd = d_bd;
-            pj.q = jb.quant;
-            if (jb.ok[c] <= 0) { // "decoding error in plane": its residual plane stays zero (dsv_decoder.c:516-523)
-                h_zfail[n_zfail++] = CopyJob{nullptr, resid.alloc + resid.plane_off[c], resid.plane_len[c]};
-                max_plane_bytes = resid.plane_len[c] > max_plane_bytes ? resid.plane_len[c] : max_plane_bytes;
-            }
-        }
-        McJob mj;
-        mj.mvs = d_mvs;
-        mj.bd = d_bd;
-        mj.p = mc;
-        if (jb.has_ref) {
-            mj.f = make_filter_params(mc, jb.quant, jb.do_filter, jb.d->vidmeta.inter_sharpen);
-            for (int c = 0; c < 3; c++) {
-                mj.ref.p[c] = ref.recon.p[c];
-                mj.pred.p[c] = cur.recon.p[c];
-                mj.res.p[c] = resid.p[c];
-            }
-            h_mc_pred[nP] = mj;
-            for (int c = 0; c < 3; c++) {
-                mj.res.p[c] = cur.recon.p[c];
-            }
-            h_mc_filt[nP] = mj;
-            nP++;
-            any_filter = any_filter || !jb.lossless;
-        } else {
-            mj.f = make_filter_params(mc, jb.quant, 1, 0);
-            for (int c = 0; c < 3; c++) {
-                mj.ref.p[c] = mj.pred.p[c] = mj.res.p[c] = resid.p[c];
-                h_icopy[c][nI] = PlanePair{resid.p[c], cur.recon.p[c]};
-            }
-            nI++;
-            if (jb.do_filter && !jb.lossless) { // dsv_intra_filter is a no-op for lossless pictures (bmc.c:398)
-                h_mc_intra[nIf++] = mj;
-            }
-        }
-        if (jb.is_ref || !jb.has_ref) {
-            for (int c = 0; c < 3; c++) {
-                h_ext[c][n_ext] = cur.recon.p[c];
-            }
-            n_ext++;
-        }
-        // the planes of the delivered picture: those of the pinned frame, or the caller's device planes (semiplanar: op[1] is the
-        // interleaved plane, w (U, V) pairs a row; op[2] is not a plane)
-        DPlane op[3];
-        if (jb.to_dev) {
-            const int ohs = DSV_FORMAT_H_SHIFT(jb.out_format), ovs = DSV_FORMAT_V_SHIFT(jb.out_format);
-            const int ocw = (dv.w + (1 << ohs) - 1) >> ohs, och = (dv.h + (1 << ovs) - 1) >> ovs; // dsv_mk_frame's plane sizes (frame.c:63-113)
-            op[0] = DPlane{jb.dst[0], jb.dpitch[0], dv.w, dv.h};
-            op[1] = DPlane{jb.dst[1], jb.dpitch[1], ocw, och};
-            op[2] = DPlane{jb.semi ? nullptr : jb.dst[2], jb.semi ? 0 : jb.dpitch[2], ocw, och};
-        } else {
-            for (int c = 0; c < 3; c++) {
-                const DSV_PLANE &fp = jb.of->planes[c];
-                op[c] = DPlane{fp.data, fp.stride, fp.w, fp.h};
-            }
-        }
-        const bool conv = jb.out_format != dv.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
-        const bool sharp_out = jb.sharp && !jb.draw;  // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
-        if (!conv && !jb.to_dev && !sharp_out) {
-            h_out[n_out++] = CopyJob{cur.recon.alloc, jb.of->alloc, cur.recon.bytes};
-        } else {
-            const int hs = DSV_FORMAT_H_SHIFT(dv.format), vs = DSV_FORMAT_V_SHIFT(dv.format);
-            const int mode = (hs == 0 && vs == 0) ? 1 : (hs == 1 && vs == 0) ? 2 : (hs == 2 && vs == 0) ? 3 : 4;
-            for (int c = 0; c < 3; c++) {
-                if (c && jb.to_dev && jb.semi) { // both chroma planes through one job, converted on the way or not
-                    if (c == 1) {
-                        const DPlane &su = cur.recon.p[1];
-                        h_uv[n_uv] = UvEgressJob{su.data, cur.recon.p[2].data, op[1].data, op[1].stride, su.stride, su.w, su.h, op[1].w, op[1].h, conv ? mode : 0};
-                        uv_wide = uv_wide && uv_job_wide(h_uv[n_uv]);
-                        uv_conv = uv_conv || conv;
-                        uv_rows = std::max(uv_rows, op[1].h);
-                        n_uv++;
-                    }
-                } else if (conv && (c || (!jb.to_dev && !sharp_out))) {
-                    h_to420[n_to420++] = To420Job{cur.recon.p[c], op[c], c ? mode : 0};
-                } else {
-                    h_eg[n_eg++] = EgressJob{cur.recon.p[c], op[c].data, op[c].stride, c == 0 && sharp_out};
-                    eg_sharp = eg_sharp || (c == 0 && sharp_out);
-                    eg_wide = eg_wide && op[c].w % 16 == 0 && ((((uintptr_t) op[c].data) | (uintptr_t) op[c].stride) & 15) == 0;
-                }
-            }
-        }
-        if (jb.draw) { // drawn on the frame the caller receives only: cur.recon, which the next P picture reads, stays as decoded (dsv_decoder.c:555-561)
-            h_ov[n_ov++] = OverlayJob{op[0], d_mvs, d_bd, dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref};
-            ov_vectors = ov_vectors || (jb.has_ref && (jb.draw & DSV_DRAW_MOVECS));
-            if (jb.sharp) {
-                sharp_drawn.push_back(op[0]);
+                r.eg.h[r.n_eg++] = EgressJob{recon.p[c], op[c].data, op[c].stride, c == 0 && sharp_out};
+                r.eg_sharp = r.eg_sharp || (c == 0 && sharp_out);
+                r.eg_wide = r.eg_wide && op[c].w % 16 == 0 && ((((uintptr_t) op[c].data) | (uintptr_t) op[c].stride) & 15) == 0;
             }
         }
     }
+    if (jb.draw) { // drawn on the frame the caller receives only: cur.recon, which the next P picture reads, stays as decoded (dsv_decoder.c:555-561)
+        r.ov.h[r.n_ov++] = OverlayJob{op[0], r.d_mvs(jb), r.d_bd(jb), dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref};
+        r.ov_vectors = r.ov_vectors || (jb.has_ref && (jb.draw & DSV_DRAW_MOVECS));
+        if (jb.sharp) {
+            r.sharp_drawn.push_back(op[0]);
+        }
+    }
+}
 
-    // (stage spans for bench.py's decode roofline: HIP events on this step's stream when dsv2hip_prof_enable(1) is on -- the
-    // encoder's stage names: QUANT = zero + scatter + dequantise, INV_SBT, RECON_FILTER = intra filter / motion-compensated
-    // reconstruction + in-loop filters, EXTEND = borders + the picture's way into the caller's frame)
-    static thread_local StageProf prof;
-    HIPCHK(hipMemcpyAsync(sc.d_stage, sc.h_stage, stage_used, hipMemcpyHostToDevice, bs));
-    sc.tabs.upload(bs);
+// (stage spans for bench.py's decode roofline: HIP events on this step's stream when dsv2hip_prof_enable(1) is on -- the
+// encoder's stage names: QUANT = zero + scatter + dequantise, INV_SBT, RECON_FILTER = intra filter / motion-compensated
+// reconstruction + in-loop filters, EXTEND = borders + the picture's way into the caller's frame)
+thread_local StageProf t_dec_prof;
+
+void round_enqueue(Round &r)
+{
+    StageProf &prof = t_dec_prof;
+    const CodecDev &dv0 = r.dv0;
+    const hipStream_t bs = r.bs;
+    HIPCHK(hipMemcpyAsync(r.sc.d_stage, r.sc.h_stage, r.stage_used, hipMemcpyHostToDevice, bs));
+    r.sc.tabs.upload(bs);
     prof.begin(bs, ST_QUANT);
-    if (n_parse) {
+    if (r.n_parse) {
         DecScanBases sb_l, sb_c;
         for (int k = 0; k < 11; k++) {
             sb_l.base[k] = dv0.scan[0].base[k];
             sb_c.base[k] = dv0.scan[1].base[k];
         }
-        dec_parse_planes(bs, d_parse, n_parse, sb_l, sb_c);
+        dec_parse_planes(bs, r.parse.d, r.n_parse, sb_l, sb_c);
     }
-    zero_linear_batch(bs, d_zero, 3 * n, max_coef_bytes);
-    for (const Slice &sl : slices) {
+    zero_linear_batch(bs, r.zero.d, 3 * r.n, r.max_coef_bytes);
+    for (const Slice &sl : r.slices) {
         for (int c = 0; c < 3; c++) {
-            dequant_jobs(bs, d_dq[c] + sl.first, sl.count, sl.max_seg[c], dv0.quant_cfg(c, sl.isP, sl.lossless, 0, nullptr));
+            dequant_jobs(bs, r.dq[c].d + sl.first, sl.count, sl.max_seg[c], dv0.quant_cfg(c, sl.isP, sl.lossless, 0, nullptr));
         }
     }
-    prof.end(bs, ST_QUANT, n);
+    prof.end(bs, ST_QUANT, r.n);
     prof.begin(bs, ST_INV_SBT);
-    for (const Slice &sl : slices) {
+    for (const Slice &sl : r.slices) {
         for (int c = 0; c < 3; c++) {
-            sbt_inverse_jobs(bs, d_pj[c] + sl.first, sl.count, dv0.cw[c], dv0.ch[c], c, sl.isP, sl.lossless, dv0.nbh, dv0.nbv, true);
+            sbt_inverse_jobs(bs, r.pj[c].d + sl.first, sl.count, dv0.cw[c], dv0.ch[c], c, sl.isP, sl.lossless, dv0.nbh, dv0.nbv, true);
         }
     }
-    prof.end(bs, ST_INV_SBT, n);
+    prof.end(bs, ST_INV_SBT, r.n);
     prof.begin(bs, ST_RECON_FILTER);
-    zero_linear_batch(bs, d_zfail, n_zfail, max_plane_bytes);
-    zero_linear_if_batch(bs, d_zcond, d_fail, n_parse, max_plane_bytes);
-    intra_filter_batch(bs, d_mc_intra, nIf, dv0.w, dv0.h);
-    mc_add_pred_batch(bs, d_mc_pred, d_mc_filt, nP, dv0.nbh, dv0.nbv, any_filter, dv0.w, dv0.h, dv0.blk_w, dv0.blk_h,
+    zero_linear_batch(bs, r.zfail.d, r.n_zfail, r.max_plane_bytes);
+    zero_linear_if_batch(bs, r.zcond.d, r.fail.d, r.n_parse, r.max_plane_bytes);
+    intra_filter_batch(bs, r.mc_intra.d, r.nIf, dv0.w, dv0.h);
+    mc_add_pred_batch(bs, r.mc_pred.d, r.mc_filt.d, r.nP, dv0.nbh, dv0.nbv, r.any_filter, dv0.w, dv0.h, dv0.blk_w, dv0.blk_h,
                       DSV_FORMAT_H_SHIFT(dv0.format) == 1 && DSV_FORMAT_V_SHIFT(dv0.format) == 1);
-    prof.end(bs, ST_RECON_FILTER, n);
+    prof.end(bs, ST_RECON_FILTER, r.n);
     prof.begin(bs, ST_EXTEND);
     for (int c = 0; c < 3; c++) {
         const DPlane &pl = dv0.pics[0].recon.p[c];
-        copy_planes_batch(bs, d_icopy[c], nI, pl.w, pl.h);
-        extend_planes(bs, d_ext[c], n_ext, pl.w, pl.h);
+        copy_planes_batch(bs, r.icopy[c].d, r.nI, pl.w, pl.h);
+        extend_planes(bs, r.ext[c].d, r.n_ext, pl.w, pl.h);
     }
-    copy_linear_batch(bs, d_out, n_out, dv0.pics[0].recon.bytes);
-    to420_batch(bs, d_to420, n_to420, dv0.w, dv0.h);
-    egress_batch(bs, d_eg, n_eg, dv0.h, eg_wide, eg_sharp);
-    if (n_uv) {
-        egress_uv_batch(bs, d_uv, n_uv, uv_rows, uv_wide, uv_conv);
-        g_uv_rounds[uv_wide ? 0 : 1]++;
+    copy_linear_batch(bs, r.out.d, r.n_out, dv0.pics[0].recon.bytes);
+    to420_batch(bs, r.to420.d, r.n_to420, dv0.w, dv0.h);
+    egress_batch(bs, r.eg.d, r.n_eg, dv0.h, r.eg_wide, r.eg_sharp);
+    if (r.n_uv) {
+        egress_uv_batch(bs, r.uv.d, r.n_uv, r.uv_rows, r.uv_wide, r.uv_conv);
+        g_uv_rounds[r.uv_wide ? 0 : 1]++;
     }
-    overlay_batch(bs, d_ov, n_ov, dv0.h, dv0.nbh, dv0.nbv, ov_vectors);
-    for (const DPlane &pl : sharp_drawn) { // (a debugging combination: one launch a picture)
+    overlay_batch(bs, r.ov.d, r.n_ov, dv0.h, dv0.nbh, dv0.nbv, r.ov_vectors);
+    for (const DPlane &pl : r.sharp_drawn) { // (a debugging combination: one launch a picture)
         post_process_plane(bs, pl);
     }
-    prof.end(bs, ST_EXTEND, n);
+    prof.end(bs, ST_EXTEND, r.n);
     t_dec_clock.lap(2);
-    stream_wait(bs);
-    prof.collect();
-    t_dec_clock.lap(3);
+}
 
+void round_finish(Round &r)
+{
+    stream_wait(r.bs);
+    t_dec_prof.collect();
+    t_dec_clock.lap(3);
     // phase C: the pictures are already in their output frames / the callers' device buffers
-    for (int i = 0; i < n; i++) {
-        DecJob &jb = jobs[order[(size_t) i]];
-        DecImpl *im = jb.im;
+    for (int k : r.order) {
+        DecJob &jb = r.jobs[k];
         if (jb.is_ref) {
-            im->cur ^= 1;
-            im->have_ref = true;
+            jb.im->cur ^= 1;
+            jb.im->have_ref = true;
         }
         if (!jb.to_dev) {
             *jb.out = jb.of;
         }
         jb.ret = DSV_DEC_OK;
     }
+}
+
+void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
+{
+    Round r(jobs, ids);
+    round_take_tables(r);
+    round_stage(r);
+    round_sort(r);
+    for (Slice &sl : r.slices) {
+        for (int i = sl.first; i < sl.first + sl.count; i++) {
+            DecJob &jb = jobs[r.order[(size_t) i]];
+            fill_coef_jobs(r, sl, i, jb);
+            fill_recon_jobs(r, jb);
+            fill_delivery_jobs(r, jb);
+        }
+    }
+    round_enqueue(r);
+    round_finish(r);
 }
 
 void dec_batch(DecJob *jobs, int n)
@@ -701,22 +720,38 @@ bool surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], int rows[3])
     return true;
 }
 
-// one lockstep step with every picture delivered to the device planes the jobs name
-int dec_batch_to_dev(std::vector<DecJob> &jobs, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FNUM *fn, int *ret)
+// one lockstep step with every picture delivered into a frame of out[], or (no out) to the device planes the jobs name
+int dec_batch_run(std::vector<DecJob> &jobs, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FRAME **out, DSV_FNUM *fn, int *ret)
 {
-    const int n = (int) jobs.size();
-    for (int k = 0; k < n; k++) {
-        jobs[(size_t) k].d = decs[k];
-        jobs[(size_t) k].buf = &bufs[k];
-        jobs[(size_t) k].out = nullptr;
-        jobs[(size_t) k].fn = &fn[k];
-        jobs[(size_t) k].to_dev = true;
+    int n = 0;
+    for (DecJob &jb : jobs) {
+        jb.d = decs[n];
+        jb.buf = &bufs[n];
+        jb.out = out ? &out[n] : nullptr;
+        jb.fn = &fn[n];
+        jb.to_dev = !out;
+        if (out) {
+            out[n] = NULL;
+        }
+        n++;
     }
     dec_batch(jobs.data(), n);
     for (int k = 0; k < n; k++) {
         ret[k] = jobs[(size_t) k].ret;
     }
     return n;
+}
+
+int set_switch(DSV_DECODER *d, bool DecImpl::*sw, int on) // (a switch may be set before the first packet made the DecImpl)
+{
+    if (!d) {
+        return -1;
+    }
+    if (!d->ref) {
+        d->ref = new DecImpl();
+    }
+    ((DecImpl *) d->ref)->*sw = on != 0;
+    return 0;
 }
 
 } // namespace
@@ -780,17 +815,7 @@ void dsv2hip_dec_queue_stats(unsigned long long *out4, int reset)
 
 /* every picture this decoder returns from now on is converted to 4:2:0 by the GPU while it is written to the output
  * frame -- what the reference CLI's -out420p does on the host afterwards (dsv_main.c:1030-1048, util.c:79-153) */
-int dsv2hip_dec_set_out420p(DSV_DECODER *d, int on)
-{
-    if (!d) {
-        return -1;
-    }
-    if (!d->ref) {
-        d->ref = new DecImpl();
-    }
-    ((DecImpl *) d->ref)->out420p = on != 0;
-    return 0;
-}
+int dsv2hip_dec_set_out420p(DSV_DECODER *d, int on) { return set_switch(d, &DecImpl::out420p, on); }
 
 int dsv2hip_dec_parse_mode(void) { return g_dev_parse.load(); }
 int dsv2hip_dec_set_parse_mode(int mode)
@@ -809,44 +834,21 @@ int dsv2hip_dec_batch(int n, DSV_DECODER **decs, DSV_BUF *bufs, DSV_FRAME **out,
         return 0;
     }
     std::vector<DecJob> jobs((size_t) n);
-    for (int k = 0; k < n; k++) {
-        jobs[(size_t) k].d = decs[k];
-        jobs[(size_t) k].buf = &bufs[k];
-        jobs[(size_t) k].out = &out[k];
-        jobs[(size_t) k].fn = &fn[k];
-        out[k] = NULL;
-    }
-    dec_batch(jobs.data(), n);
-    for (int k = 0; k < n; k++) {
-        ret[k] = jobs[(size_t) k].ret;
-    }
-    return n;
+    return dec_batch_run(jobs, decs, bufs, out, fn, ret);
 }
 
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out
  * from now on goes through dsv_post_process -- last, behind the 4:2:0 conversion and the draw_info overlay */
-int dsv2hip_dec_set_postsharp(DSV_DECODER *d, int on)
-{
-    if (!d) {
-        return -1;
-    }
-    if (!d->ref) {
-        d->ref = new DecImpl();
-    }
-    ((DecImpl *) d->ref)->postsharp = on != 0;
-    return 0;
-}
+int dsv2hip_dec_set_postsharp(DSV_DECODER *d, int on) { return set_switch(d, &DecImpl::postsharp, on); }
 
 size_t dsv2hip_dec_picture_bytes(DSV_DECODER *d)
 {
-    if (!d || !d->got_metadata) {
+    size_t rb[3]; // the packed picture is the planar surface without padding
+    int rows[3];
+    if (!surface_dims(d, DSV2HIP_SURFACE_PLANAR, rb, rows)) {
         return 0;
     }
-    const DSV_META &m = d->vidmeta;
-    const int fmt = (d->ref && ((DecImpl *) d->ref)->out420p) ? DSV_SUBSAMP_420 : m.subsamp;
-    const int hs = DSV_FORMAT_H_SHIFT(fmt), vs = DSV_FORMAT_V_SHIFT(fmt);
-    const size_t cw = (size_t) ((m.width + (1 << hs) - 1) >> hs), ch = (size_t) ((m.height + (1 << vs) - 1) >> vs);
-    return (size_t) m.width * (size_t) m.height + 2 * cw * ch;
+    return rb[0] * (size_t) rows[0] + rb[1] * (size_t) rows[1] + rb[2] * (size_t) rows[2];
 }
 
 // dsv2hip_dec_batch with the pictures delivered, packed, to device memory: nothing is consumed unless every decoder that could
@@ -857,10 +859,7 @@ int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *con
         return -1;
     }
     for (int k = 0; k < n; k++) {
-        if (!decs[k]) {
-            return -1;
-        }
-        if (decs[k]->got_metadata && (!dev_out[k] || dev_cap[k] < dsv2hip_dec_picture_bytes(decs[k]))) {
+        if (!decs[k] || (decs[k]->got_metadata && (!dev_out[k] || dev_cap[k] < dsv2hip_dec_picture_bytes(decs[k])))) {
             return -1;
         }
     }
@@ -869,15 +868,16 @@ int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *con
         size_t rb[3];
         int rows[3];
         if (surface_dims(decs[k], DSV2HIP_SURFACE_PLANAR, rb, rows)) {
+            DecJob &jb = jobs[(size_t) k];
             uint8_t *at = (uint8_t *) dev_out[k];
             for (int c = 0; c < 3; c++) {
-                jobs[(size_t) k].dst[c] = at;
-                jobs[(size_t) k].dpitch[c] = (int) rb[c];
+                jb.dst[c] = at;
+                jb.dpitch[c] = (int) rb[c];
                 at += rb[c] * (size_t) rows[c];
             }
         }
     }
-    return dec_batch_to_dev(jobs, decs, bufs, fn, ret);
+    return dec_batch_run(jobs, decs, bufs, nullptr, fn, ret);
 }
 
 int dsv2hip_dec_device_frame(DSV_DECODER *d, DSV_BUF *buf, void *dev_out, size_t dev_cap, DSV_FNUM *fn)
@@ -929,7 +929,7 @@ int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const ds
             jb.dpitch[c] = (int) sf.pitch[c];
         }
     }
-    return dec_batch_to_dev(jobs, decs, bufs, fn, ret);
+    return dec_batch_run(jobs, decs, bufs, nullptr, fn, ret);
 }
 
 int dsv2hip_dec_surface_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_surface *surf, DSV_FNUM *fn)

@@ -1549,13 +1549,6 @@ void enc_batch(Job *jobs, int n) { (void) enc_batch_ok(jobs, n); }
 
 // ---- one lockstep step: the phases of the comment above struct Job, as functions over one Step ----
 
-template <class T> struct Tab { // a job table in the step's arena: filled through h, handed to the kernels as d
-    T *h = nullptr;
-    const T *d = nullptr;
-    Tab() = default;
-    Tab(BatchScratch &sc, size_t count) { h = sc.tabs.take<T>(count, &d); }
-};
-
 struct Slice { // a run of G2's sorted order with one (frame type, lossless) class: one set of transform / quantiser launches
     int first, count, isP, lossless;
 };
@@ -1712,24 +1705,24 @@ static void g1_enqueue(Step &st)
     hipStream_t bs = st.bs;
     const CodecDev &dv0 = st.dv0;
     const int n = st.n, L = dv0.pyr_levels;
-    Tab<IngestJob> ing(sc, (size_t) n), ingu(sc, (size_t) n);
-    Tab<DPlane> ext_y(sc, (size_t) n), ext_c(sc, 2 * (size_t) n);
+    Tab<IngestJob> ing(sc.tabs, (size_t) n), ingu(sc.tabs, (size_t) n);
+    Tab<DPlane> ext_y(sc.tabs, (size_t) n), ext_c(sc.tabs, 2 * (size_t) n);
     Tab<PlanePair> pair[DSV_MAX_PYRAMID_LEVELS];
     Tab<DPlane> pext[DSV_MAX_PYRAMID_LEVELS];
     for (int l = 0; l < L; l++) {
-        pair[l] = Tab<PlanePair>(sc, 2 * (size_t) n);
-        pext[l] = Tab<DPlane>(sc, 2 * (size_t) n);
+        pair[l] = Tab<PlanePair>(sc.tabs, 2 * (size_t) n);
+        pext[l] = Tab<DPlane>(sc.tabs, 2 * (size_t) n);
     }
-    Tab<IntraJob> intra(sc, (size_t) n);
-    Tab<PlaneOutJob> small(sc, (size_t) n);
-    st.bsj = Tab<BlockStatsJob>(sc, (size_t) n);
+    Tab<IntraJob> intra(sc.tabs, (size_t) n);
+    Tab<PlaneOutJob> small(sc.tabs, (size_t) n);
+    st.bsj = Tab<BlockStatsJob>(sc.tabs, (size_t) n);
     int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0;
     for (int k = 0; k < n; k++) {
         n_surf += st.jobs[k].has_surf;
     }
     Tab<SurfaceJob> sj; // only a step with surface jobs has this table (behind all the others: theirs lie where they always did)
     if (n_surf) {
-        sj = Tab<SurfaceJob>(sc, 3 * (size_t) n_surf);
+        sj = Tab<SurfaceJob>(sc.tabs, 3 * (size_t) n_surf);
     }
     bool surf_wide = true;
     for (int k = 0; k < n; k++) {
@@ -1935,7 +1928,7 @@ static void search_under_token(Step &st)
 // P frames flipped to intra by the scene-change test: their block analysis is due now
 static void late_intra_analysis(Step &st)
 {
-    Tab<IntraJob> late(st.sc, (size_t) st.n);
+    Tab<IntraJob> late(st.sc.tabs, (size_t) st.n);
     int n_late = 0;
     for (int k = 0; k < st.n; k++) {
         Job &jb = st.jobs[k];
@@ -1970,7 +1963,7 @@ static void enqueue_side_info(Step &st)
     if (st.p_jobs.empty()) {
         return;
     }
-    Tab<SideJob> side(sc, st.p_jobs.size());
+    Tab<SideJob> side(sc.tabs, st.p_jobs.size());
     for (size_t q = 0; q < st.p_jobs.size(); q++) {
         Job &jb = st.jobs[st.p_jobs[q]];
         CodecDev &dv = jb.im->dev;
@@ -2128,20 +2121,20 @@ static void g2_build_tables(Step &st)
         st.slices.push_back(Slice{i, j - i, jobs[st.order[(size_t) i]].d.params.has_ref, jobs[st.order[(size_t) i]].d.params.lossless});
         i = j;
     }
-    st.copy = Tab<CopyJob>(sc, (size_t) n);
-    st.py = Tab<PlaneJob>(sc, (size_t) n);
-    st.pc = Tab<PlaneJob>(sc, 2 * (size_t) n);
-    st.comp = Tab<CompactJob>(sc, (size_t) n);
-    st.ent = Tab<EntJob>(sc, (size_t) n);
-    st.rext_y = Tab<DPlane>(sc, (size_t) n);
-    st.rext_c = Tab<DPlane>(sc, 2 * (size_t) n);
+    st.copy = Tab<CopyJob>(sc.tabs, (size_t) n);
+    st.py = Tab<PlaneJob>(sc.tabs, (size_t) n);
+    st.pc = Tab<PlaneJob>(sc.tabs, 2 * (size_t) n);
+    st.comp = Tab<CompactJob>(sc.tabs, (size_t) n);
+    st.ent = Tab<EntJob>(sc.tabs, (size_t) n);
+    st.rext_y = Tab<DPlane>(sc.tabs, (size_t) n);
+    st.rext_c = Tab<DPlane>(sc.tabs, 2 * (size_t) n);
     // host -> device hand-over of what H1 decided: per stream the transmitted motion field and the
     // block flag bytes, packed into ONE pinned buffer and shipped with one copy
     const size_t nb0 = st.dv0.nblocks();
     st.mv_bytes = nb0 * sizeof(DSV_MV);
     st.slot = (nb0 + 15) & ~(size_t) 15;
     sc.ensure_stage(st.slot * (st.i_jobs.size() + 1));
-    st.mvcopy = Tab<CopyJob>(sc, (size_t) n);
+    st.mvcopy = Tab<CopyJob>(sc.tabs, (size_t) n);
     for (int i = 0; i < n; i++) {
         g2_fill_picture(st, i);
     }
@@ -2256,10 +2249,10 @@ static void redo_overflowed_picture(Step &st, int k)
     DFrame &tmp = sc.redo_frame(dv.format, dv.w, dv.h);
     static_assert(sizeof(McJob) + sizeof(CopyJob) + 3 * sizeof(PlaneJob) + sizeof(CompactJob) + 6 * 16 <= 4096,
                   "a redone picture's tables outgrow the 4 KB a stream BatchScratch::ensure sets aside for them");
-    Tab<McJob> m2(sc, 1);
-    Tab<CopyJob> c2(sc, 1);
-    Tab<PlaneJob> y2(sc, 1), uv2(sc, 2);
-    Tab<CompactJob> k2(sc, 1);
+    Tab<McJob> m2(sc.tabs, 1);
+    Tab<CopyJob> c2(sc.tabs, 1);
+    Tab<PlaneJob> y2(sc.tabs, 1), uv2(sc.tabs, 2);
+    Tab<CompactJob> k2(sc.tabs, 1);
     if (isP) {
         *m2.h = sc.h_mc[ti]; // (P pictures lead the sorted order: slot_of = index among the P jobs)
         for (int c = 0; c < 3; c++) {

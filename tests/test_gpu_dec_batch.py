@@ -1,5 +1,6 @@
 """Lockstep batch decoding (dsv2hip_dec_batch): n packets per step == n independent reference decodes."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -16,6 +17,9 @@ def bind(hip):
     hip.dsv2hip_dec_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(C.POINTER(A.FRAME)),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
     hip.dsv2hip_dec_batch.restype = C.c_int
+    for name in ("dsv2hip_dec_set_out420p", "dsv2hip_dec_set_postsharp"):
+        getattr(hip, name).argtypes = [C.POINTER(A.DECODER), C.c_int]
+        getattr(hip, name).restype = C.c_int
 
 
 def planes_of(fp):
@@ -28,10 +32,17 @@ def planes_of(fp):
     return out
 
 
-def batch_decode(hip, streams):
-    """streams: list of packet lists.  Step t feeds packet t of every stream that still has one."""
+def batch_decode(hip, streams, modes=None, sharp=None, out420p=None):
+    """streams: list of packet lists.  Step t feeds packet t of every stream that still has one.
+    modes / sharp / out420p: per stream, the decoder's draw_info word, postsharp and out420p switches."""
     n = len(streams)
     decs = [A.DECODER() for _ in range(n)]
+    for k, d in enumerate(decs):
+        d.draw_info = modes[k] if modes else 0
+        if sharp and sharp[k]:
+            assert hip.dsv2hip_dec_set_postsharp(C.byref(d), 1) == 0
+        if out420p and out420p[k]:
+            assert hip.dsv2hip_dec_set_out420p(C.byref(d), 1) == 0
     got = [[] for _ in range(n)]
     for t in range(max(len(s) for s in streams)):
         live = [k for k in range(n) if t < len(streams[k])]
@@ -141,3 +152,71 @@ def test_lossless_round_trip_1080p_through_both_batch_engines():
             assert np.array_equal(y.ravel(), raw[:w * h])
             assert np.array_equal(u.ravel(), raw[w * h:w * h + w * h // 4])
             assert np.array_equal(v.ravel(), raw[w * h + w * h // 4:])
+
+
+# ---- one round of every kind -------------------------------------------------------------------------------------------------
+# Ten 4:2:2 streams of three pictures: eight of 80x48 (five by three blocks, width no multiple of 32) and two of 72x40 (a second
+# round in every step; luma width no multiple of 16).  (gop, qp, offset): gop 0 = intra only, qp 100 = lossless; an offset stream
+# starts with a one-picture closed GOP, so its I picture shares a step with the others' P pictures; an intra-only stream has a
+# metadata packet before every picture.  Step 3 holds a picture of every stream: all four (frame type, lossless) classes at 80x48,
+# a lossy P and a lossless I picture at 72x40.
+KINDS = [(80, 48, 48, 60, False), (80, 48, 48, 60, False), (80, 48, 0, 60, False), (80, 48, 48, 100, False), (80, 48, 48, 60, True),
+         (80, 48, 0, 100, False), (80, 48, 48, 100, True), (80, 48, 48, 60, False), (72, 40, 48, 60, False), (72, 40, 0, 100, False)]
+DRAW_ALL = 7  # DSV_DRAW_STABHQ | DSV_DRAW_MOVECS | DSV_DRAW_IBLOCK
+SUBSAMP_422 = 0x4
+# leg A, per stream: (draw_info, postsharp, out420p); the draw_info decoders are 80x48 ones: the reference stores intra marks
+# without a bounds check, so it is compared on block-aligned pictures only (test_gpu_dec_drawinfo.py)
+HOST_OPTS = [(DRAW_ALL, False, False), (0, True, False), (DRAW_ALL, True, False), (0, False, True), (0, True, True)] + [(0, False, False)] * 5
+# leg B: planar and semiplanar surfaces alternate; pitches: row bytes rounded up to 64, one odd (83 / 43 for rows of 80 / 40 bytes)
+SURF_OPTS = [(0, k == 2, k == 3) for k in range(10)]
+
+
+@functools.lru_cache(maxsize=None)
+def kind_stream(k):
+    from test_gpu_formats import frames
+    w, h, gop, qp, offset = KINDS[k]
+    fr = frames(w, h, 1, 0, 3, 30 + k)
+    enc = lambda f, eos: encode_stream(A.load_ref(), f, w, h, SUBSAMP_422, eos=eos, qp=qp, gop=gop)[0]
+    return tuple(enc(fr[:1], False) + enc(fr[1:], True)) if offset else tuple(enc(fr, True))
+
+
+@functools.lru_cache(maxsize=None)
+def kind_want(k, mode, sharp, to420):
+    """the reference decode of stream k with the post-steps applied by the reference / the oracle (shared, never modified)"""
+    from test_gpu_dec_postsharp import expected
+    w, h = KINDS[k][:2]
+    want = expected(A.load_ref(), kind_stream(k), mode=mode, sharp=sharp, to420=(SUBSAMP_422, w, h) if to420 else None)
+    assert sum(1 for r in want if r[2] is not None) == 3
+    return tuple(want)
+
+
+@pytest.mark.parametrize("parse_mode", [0, 1], ids=["host-parse", "P-on-device"])
+def test_one_round_of_every_kind(parse_mode):
+    """Every job table of a device round filled in the same round: I and P, lossy and lossless pictures, host- and (mode 1:
+    the P pictures) device-parsed sections, whole-frame copies, 4:2:0 conversion, egress with and without sharpening, chroma
+    interleave with and without conversion, overlay, overlay + sharpening -- through dsv2hip_dec_batch into host frames (leg A)
+    and through dsv2hip_dec_batch_surface into planar and semiplanar surfaces (leg B).  Every delivered picture equals the
+    reference decode of its stream with the same post-steps.  (No stream carries a damaged plane section: the damaged packets
+    of test_gpu_robustness.py are drawn at random inside its test, so the zfail table stays empty here.)"""
+    import test_gpu_dec_surface as S
+    from test_gpu_dec_device_out import same_results
+    from test_gpu_dec_drawinfo import pictures
+    hip = S.bind(A.load_hip())
+    bind(hip)
+    assert A.block_geometry(80, 48)[2:] == (5, 3) and 80 % A.block_geometry(80, 48)[0] == 0 and 48 % A.block_geometry(80, 48)[1] == 0
+    streams = [kind_stream(k) for k in range(len(KINDS))]
+    kinds = [[r[0] for r in kind_want(k, 0, False, False)] for k in range(len(KINDS))]
+    assert all(k[3] == A.DEC_OK for k in kinds) and len(streams[4]) == len(streams[0]) + 1  # (step 3; an offset stream is one packet longer)
+    S.PITCH.setdefault("align64", lambda rb: (rb + 63) // 64 * 64)
+    specs = [dict(layout=S.SEMI if k % 2 else S.PLANAR, pitch="plus3" if k == 5 else "align64", offset=0) for k in range(len(KINDS))]
+    try:
+        assert hip.dsv2hip_dec_set_parse_mode(parse_mode) == parse_mode
+        got = batch_decode(hip, streams, *zip(*HOST_OPTS))
+        for k, opts in enumerate(HOST_OPTS):
+            check(pictures(kind_want(k, *opts)), got[k])
+        modes, sharp, out420p = zip(*SURF_OPTS)
+        got = S.surface_decode(hip, streams, specs, modes=modes, sharp=sharp, out420p=out420p)
+        for k, opts in enumerate(SURF_OPTS):
+            S.same(kind_want(k, *opts), got[k], specs[k]["layout"])
+    finally:
+        hip.dsv2hip_dec_set_parse_mode(-1)
