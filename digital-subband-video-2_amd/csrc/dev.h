@@ -186,6 +186,19 @@ struct SurfaceJob { // one SOURCE plane of a caller's surface (dsv2hip_surface) 
     int dstride;         // of dst and dst2 (the two chroma planes of a frame share their geometry)
     int w, h;            // visible pixels of each destination plane: the source row holds w bytes (2 * w with dst2)
 };
+struct RgbJob { // one packed four-byte RGB surface (dsv2hip_surface, BGRA / RGBA) on its way into the three bordered source planes, converted
+                // on the way (ingest_rgb.h, frame.hip: k_ingest_rgb); 88 bytes, fetched by value through the scalar cache like SurfaceJob
+    const uint8_t *src; // device memory, any alignment: row y at src + y * pitch, w pixels of 4 bytes
+    size_t pitch;
+    uint8_t *dst[3];      // Y, U, V planes from dframe_alloc
+    int ystride, cstride; // of dst[0]; of dst[1] and dst[2] (the two chroma planes of a frame share their geometry)
+    int w, h;             // of the picture
+    int hs, vs;           // the stream's chroma shifts
+    // The conversion's coefficients as byte quads in the surface's channel order, 0 for alpha -- the byte order lives in these
+    // quads and nowhere else.  Chroma rows: positive coefficients / magnitudes of the negative ones.
+    uint32_t ycoef, upos, uneg, vpos, vneg;
+    uint32_t yoff; // 128 + 256 * ybase
+};
 struct PlaneOutJob {
     DPlane src;
     uint8_t *dst; // pinned host memory, w * h bytes
@@ -227,6 +240,9 @@ inline bool surface_job_wide(const SurfaceJob &j)
 {
     return ((((uintptr_t) j.src) | j.pitch | (size_t) (j.dst2 ? 2 * j.w : j.w)) & 15) == 0;
 }
+// n RGB surfaces of h rows; wide: every job's source pointer and pitch are multiples of 16 and w of 4 (rgb_job_wide)
+void ingest_rgb_batch(hipStream_t s, const RgbJob *d_jobs, int n, int h, bool wide);
+inline bool rgb_job_wide(const RgbJob &j) { return ((((uintptr_t) j.src) | j.pitch) & 15) == 0 && (j.w & 3) == 0; }
 
 void ensure_device();
 void set_default_device(int ordinal);

@@ -962,8 +962,8 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
     void ensure(int n)
     {
         // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture; behind them the three source planes of a
-        // stream that brings a surface)
-        tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob)) + 65536);
+        // stream that brings a surface, or the one record of a stream that brings an RGB surface)
+        tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob) + sizeof(RgbJob)) + 65536);
         if (n <= cap) {
             return;
         }
@@ -1519,6 +1519,34 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 // pyramids and source pre-pass still enqueued on the stream)
 static std::atomic<int> g_fail_next_step{0};
 static std::atomic<unsigned long long> g_surface_steps[2]; // steps whose surface ingest ran in the wide / the general form (dsv2hip_enc_surface_stats)
+static std::atomic<unsigned long long> g_rgb_steps[2];     // the same for the RGB ingest (dsv2hip_enc_rgb_stats)
+
+static bool surface_is_rgb(int layout) { return (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_RGBA; }
+
+// The conversion of include/dsv2_hip.h for an RGB surface of `layout` as k_ingest_rgb takes it: each row of the preset's matrix as
+// byte quads in the surface's channel order (alpha weighs 0), chroma rows split into positive parts and magnitudes of negative ones
+static void rgb_job_coefs(RgbJob &j, int layout)
+{
+    static const int presets[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},   // BT601 (limited)
+                                      {47, 157, 16, -26, -86, 112, 112, -102, -10},  // BT709 (limited)
+                                      {77, 150, 29, -43, -85, 128, 128, -107, -21},  // BT601 | FULL
+                                      {54, 183, 19, -29, -99, 128, 128, -116, -12}}; // BT709 | FULL
+    const bool full = (layout & DSV2HIP_CSC_FULL_RANGE) != 0;
+    const int *m = presets[(full ? 2 : 0) + ((layout & DSV2HIP_CSC_BT709) ? 1 : 0)];
+    const bool bgra = (layout & ~0x300) == DSV2HIP_SURFACE_BGRA;
+    uint32_t q[3][2];
+    for (int row = 0; row < 3; row++) {
+        q[row][0] = q[row][1] = 0;
+        for (int c = 0; c < 3; c++) { // R, G, B
+            const int v = m[3 * row + c], at = 8 * (bgra ? 2 - c : c);
+            q[row][v < 0] |= (uint32_t) (v < 0 ? -v : v) << at;
+        }
+    }
+    j.ycoef = q[0][0];
+    j.upos = q[1][0], j.uneg = q[1][1];
+    j.vpos = q[2][0], j.vneg = q[2][1];
+    j.yoff = 128u + (full ? 0u : 256u * 16u);
+}
 
 // workgroups per (picture, plane) of the entropy coder's chunk kernels; each walks its share of the plane's 1 024-symbol chunks
 static const int kEntSlots = (int) env_int("DSV2_ENT_SLOTS", 32); // (192 until round 6: four in five of those workgroups found no chunk)
@@ -1716,15 +1744,21 @@ static void g1_enqueue(Step &st)
     Tab<IntraJob> intra(sc.tabs, (size_t) n);
     Tab<PlaneOutJob> small(sc.tabs, (size_t) n);
     st.bsj = Tab<BlockStatsJob>(sc.tabs, (size_t) n);
-    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0;
+    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0, n_rgb = 0, n_rj = 0;
     for (int k = 0; k < n; k++) {
-        n_surf += st.jobs[k].has_surf;
+        const bool rgb = st.jobs[k].has_surf && surface_is_rgb(st.jobs[k].surf.layout);
+        n_rgb += rgb;
+        n_surf += st.jobs[k].has_surf && !rgb;
     }
     Tab<SurfaceJob> sj; // only a step with surface jobs has this table (behind all the others: theirs lie where they always did)
     if (n_surf) {
         sj = Tab<SurfaceJob>(sc.tabs, 3 * (size_t) n_surf);
     }
-    bool surf_wide = true;
+    Tab<RgbJob> rj; // only a step with RGB surfaces has this one, behind the SurfaceJob table
+    if (n_rgb) {
+        rj = Tab<RgbJob>(sc.tabs, (size_t) n_rgb);
+    }
+    bool surf_wide = true, rgb_wide = true;
     for (int k = 0; k < n; k++) {
         Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
@@ -1734,6 +1768,14 @@ static void g1_enqueue(Step &st)
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
+        } else if (jb.has_surf && surface_is_rgb(jb.surf.layout)) {
+            const dsv2hip_surface &sf = jb.surf;
+            const DPlane *dp = cur.src.p;
+            RgbJob &j = rj.h[n_rj++];
+            j = RgbJob{(const uint8_t *) sf.plane[0], sf.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h,
+                       DSV_FORMAT_H_SHIFT(cur.src.format), DSV_FORMAT_V_SHIFT(cur.src.format), 0, 0, 0, 0, 0, 0};
+            rgb_job_coefs(j, sf.layout);
+            rgb_wide = rgb_wide && rgb_job_wide(j);
         } else if (jb.has_surf) {
             const dsv2hip_surface &sf = jb.surf;
             const int nsrc = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR ? 2 : 3;
@@ -1808,6 +1850,10 @@ static void g1_enqueue(Step &st)
     if (n_sj) {
         ingest_surface_batch(bs, sj.d, n_sj, f0.p[0].h, surf_wide);
         g_surface_steps[surf_wide ? 0 : 1]++;
+    }
+    if (n_rj) {
+        ingest_rgb_batch(bs, rj.d, n_rj, f0.p[0].h, rgb_wide);
+        g_rgb_steps[rgb_wide ? 0 : 1]++;
     }
     extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
     extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
@@ -2617,17 +2663,23 @@ int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, 
     return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
 }
 
-/* a surface the ingest can read, for an encoder that takes one: layout, planes, every pitch at least its row's bytes */
+/* a surface the ingest can read, for an encoder that takes one: layout, planes, every pitch at least its row's bytes (an RGB surface:
+ * plane[0] and pitch[0] alone, four bytes a pixel) */
 static bool surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf)
 {
     if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
         return false;
     }
+    const int hs = DSV_FORMAT_H_SHIFT(enc->vidmeta.subsamp);
+    const size_t w = (size_t) enc->vidmeta.width, cw = (w + ((size_t) 1 << hs) - 1) >> hs;
+    if (surface_is_rgb(sf->layout)) { // (a stream format outside the five the conversion knows is refused: k_ingest_rgb has no code for it)
+        const int f = enc->vidmeta.subsamp;
+        const bool known = f == DSV_SUBSAMP_444 || f == DSV_SUBSAMP_422 || f == DSV_SUBSAMP_420 || f == DSV_SUBSAMP_411 || f == DSV_SUBSAMP_410;
+        return known && sf->plane[0] && sf->pitch[0] >= 4 * w;
+    }
     if (sf->layout != DSV2HIP_SURFACE_PLANAR && sf->layout != DSV2HIP_SURFACE_SEMIPLANAR) {
         return false;
     }
-    const int hs = DSV_FORMAT_H_SHIFT(enc->vidmeta.subsamp);
-    const size_t w = (size_t) enc->vidmeta.width, cw = (w + ((size_t) 1 << hs) - 1) >> hs;
     if (sf->layout == DSV2HIP_SURFACE_SEMIPLANAR) {
         return sf->plane[0] && sf->plane[1] && sf->pitch[0] >= w && sf->pitch[1] >= 2 * cw;
     }
@@ -2686,6 +2738,18 @@ void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset)
         }
         if (reset) {
             g_surface_steps[i].store(0);
+        }
+    }
+}
+
+void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset)
+{
+    for (int i = 0; i < 2; i++) {
+        if (out2) {
+            out2[i] = g_rgb_steps[i].load();
+        }
+        if (reset) {
+            g_rgb_steps[i].store(0);
         }
     }
 }

@@ -9,6 +9,7 @@
 // truncating mean), replicated across the 32-pixel border; corners average the two
 // adjacent strip ends (frame.c:377-380).
 #include "dev.h"
+#include "ingest_rgb.h"
 #include "prio.h"
 
 namespace dsv2 {
@@ -417,6 +418,49 @@ void ingest_surface_batch(hipStream_t s, const SurfaceJob *d_jobs, int n, int ma
         DSV2_LAUNCH(k_ingest_surface<16>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_ingest_surface<4>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- packed four-byte RGB surfaces (dsv2hip_surface, BGRA / RGBA), converted on the way in ------------------------------------
+// One RgbJob per surface, fetched by value and pinned to scalar registers as above; the thread's work is ingest_rgb.h's
+// ingest_rgb_rows (which tools/ingest_rgb_check.cpp runs on the CPU): 64 x 4 threads cover 16 rows -- every vertical chroma footprint,
+// up to 4 rows, lies inside one thread -- and walk the row in passes of 256 pixels.
+template <int VEC> __global__ __launch_bounds__(256) void k_ingest_rgb(const RgbJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const RgbJob jl = job_of(tab, blockIdx.y);
+    const RgbJob j{uni_ptr(jl.src),
+                   ((size_t) (unsigned) uni((int) (jl.pitch >> 32)) << 32) | (unsigned) uni((int) jl.pitch),
+                   {uni_ptr(jl.dst[0]), uni_ptr(jl.dst[1]), uni_ptr(jl.dst[2])},
+                   uni(jl.ystride),
+                   uni(jl.cstride),
+                   uni(jl.w),
+                   uni(jl.h),
+                   uni(jl.hs),
+                   uni(jl.vs),
+                   (uint32_t) uni((int) jl.ycoef),
+                   (uint32_t) uni((int) jl.upos),
+                   (uint32_t) uni((int) jl.uneg),
+                   (uint32_t) uni((int) jl.vpos),
+                   (uint32_t) uni((int) jl.vneg),
+                   (uint32_t) uni((int) jl.yoff)};
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    ingest_rgb_rows<VEC>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void ingest_rgb_batch(hipStream_t s, const RgbJob *d_jobs, int n, int h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kSurfaceRows - 1) / kSurfaceRows, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_rgb<16>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_rgb<4>, grid, block, 0, s, d_jobs);
     }
 }
 

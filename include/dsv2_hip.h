@@ -397,14 +397,53 @@ int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, 
  * dsv2hip_enc_surface_stats: out2[0] / out2[1] = lockstep steps of this process whose surface ingest ran in the fast / in the
  * general form so far; reset != 0 clears the counts afterwards. */
 enum { DSV2HIP_SURFACE_PLANAR = 0, DSV2HIP_SURFACE_SEMIPLANAR = 1 };
+/* PACKED RGB SURFACES, converted on ingest -- what renderers, screen capture, image libraries and torch image tensors produce: four
+ * bytes a pixel, no conversion kernel, planar intermediate or extra pass over memory on the caller's side.
+ *   BGRA / RGBA: plane[0] = the picture, row y at plane[0] + y * pitch[0], w pixels of 4 bytes in the named byte order;
+ *                pitch[0] >= 4 * w; plane[1..2] and pitch[1..2] are ignored; the alpha byte is ignored.
+ * A valid RGB layout is DSV2HIP_SURFACE_BGRA or DSV2HIP_SURFACE_RGBA or-ed with any subset of DSV2HIP_CSC_BT709 |
+ * DSV2HIP_CSC_FULL_RANGE (DSV2HIP_CSC_BT601 = 0 is the default matrix, limited range the default range); a CSC bit on PLANAR /
+ * SEMIPLANAR, or any other value, is refused.  The layouts go through dsv2hip_enc_batch_surface and dsv2hip_enc_surface_frame and
+ * everything said above holds for them: only read, only inside the rows, surf[k] copied, any alignment and pitch (16-byte aligned
+ * pointers and pitches with w a multiple of 4 throughout the step's RGB surfaces take the fast form of the RGB ingest), layouts
+ * mixed freely within one step -- packed, planar, NV12, BGRA-601, RGBA-709-full ... -- and a refused call touches nothing.  Refused
+ * in addition: plane[0] == NULL, pitch[0] < 4 * w, an encoder with dsv2hip_enc_set_uyvy_input on.  The stream may have any of the five
+ * chroma formats (4:4:4, 4:2:2, 4:2:0, 4:1:1, "4:1:0"); its format decides the subsampling of the conversion.
+ *
+ * THE CONVERSION (the contract: encoding an RGB surface gives exactly the packets dsv_enc gives on the planar picture it defines).
+ * Integer arithmetic with 8-bit coefficients.  With N = 1 << (hs + vs), the pixels per chroma sample of the stream's format:
+ *
+ *   Y(x,y) = (yr*R + yg*G + yb*B + 128 + 256*ybase) >> 8
+ *   U(cx,cy) = min(255, (SUM over the footprint of (ur*R + ug*G + ub*B) + N*32896) >> (8 + hs + vs))
+ *   V likewise with vr, vg, vb
+ *
+ * The footprint of chroma sample (cx, cy) is the pixels (cx<<hs ... +(1<<hs)-1, cy<<vs ... +(1<<vs)-1), with coordinates clamped to
+ * w-1 and h-1.  Edge pixels are repeated where cw or ch was rounded up.  This is a box average, with the chroma sample centred on
+ * its footprint.  ybase is 16 for limited range and 0 for full range.
+ *
+ *   preset            yr  yg  yb    ur  ug  ub    vr   vg  vb
+ *   BT601 (limited)   66 129  25   -38 -74 112   112  -94 -18
+ *   BT709 (limited)   47 157  16   -26 -86 112   112 -102 -10
+ *   BT601 | FULL      77 150  29   -43 -85 128   128 -107 -21
+ *   BT709 | FULL      54 183  19   -29 -99 128   128 -116 -12
+ *
+ * Every chroma row sums to 0, so R = G = B gives U = V = 128; limited range yields Y 16 ... 235 and U, V 16 ... 240 without a clamp;
+ * full range needs the min(255, ...) only for U and V at 128 * 255 (value 256), and Y reaches 255 exactly; every sum is non-negative
+ * before the shift.
+ * dsv2hip_enc_rgb_stats: out2[0] / out2[1] = lockstep steps of this process whose RGB ingest ran in the fast / in the general form
+ * so far; reset != 0 clears the counts afterwards.  dsv2hip_enc_surface_stats keeps counting the steps' YUV surfaces only. */
+enum { DSV2HIP_SURFACE_BGRA = 0x10,   /* bytes in memory: B G R A */
+       DSV2HIP_SURFACE_RGBA = 0x11 }; /* bytes in memory: R G B A */
+enum { DSV2HIP_CSC_BT601 = 0x000, DSV2HIP_CSC_BT709 = 0x100, DSV2HIP_CSC_FULL_RANGE = 0x200 }; /* or-ed into the layout of an RGB surface */
 typedef struct dsv2hip_surface {
-    const void *plane[3]; /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first), plane[2] ignored */
-    size_t pitch[3];      /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR */
+    const void *plane[3]; /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first), plane[2] ignored.  BGRA / RGBA: the picture */
+    size_t pitch[3];      /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR, pitch[1..2] for BGRA / RGBA */
     int layout;
 } dsv2hip_surface;
 int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs);
 int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs);
 void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset);
+void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset);
 /* the same step with the pictures in HOST memory, as dsv_enc (dsv_encoder.c:1430) receives them: host_planar[k] is
  * stream k's packed planar picture of this step.  host_next (NULL, or NULL entries, allowed) names the picture each
  * stream will bring to the NEXT call: it is uploaded on a copy stream under this step's kernels, and the next call
