@@ -61,5 +61,8 @@ void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool
 // the way where the job's mode says so.  wide: every job's destination and pitch are multiples of 16 and its cw of 8
 // (uv_job_wide); any_conv: some job has mode != 0.  max_ch: the most rows delivered.
 void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch, bool wide, bool any_conv);
+// ... into packed four-byte RGB surfaces: n pictures of h rows (device table), converted on the way (egress_rgb.h).  wide: every
+// job's destination and pitch are multiples of 16 and its w of 4 (rgb_out_job_wide).
+void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide);
 
 } // namespace dsv2

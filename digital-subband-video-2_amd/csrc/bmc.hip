@@ -19,6 +19,7 @@
 #include "prio.h"
 #include "blockstat.h"
 #include "bmc.h"
+#include "egress_rgb.h"
 #include "egress_uv.h"
 #include "hme.h"
 
@@ -2372,6 +2373,38 @@ void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch
         DSV2_LAUNCH((k_egress_uv<4, true>), grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH((k_egress_uv<4, false>), grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- decoder egress into a packed four-byte RGB surface (BGRA / RGBA), converted on the way out ----------------------------------
+// One job per picture (RgbOutJob, dev.h), fetched by value and pinned to scalar registers as k_ingest_rgb (frame.hip) does, whose
+// shape this mirrors: 64 x 4 threads cover 16 rows -- every vertical chroma footprint, up to 4 rows, lies inside one thread -- and
+// walk the row in passes of 256 pixels.  The thread's work is egress_rgb.h's egress_rgb_rows (which tools/egress_rgb_check.cpp runs
+// on the CPU).
+template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_rgb(const RgbOutJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const RgbOutJob jl = job_of(tab, blockIdx.y);
+    const RgbOutJob j{uni_ptr(jl.sy), uni_ptr(jl.su), uni_ptr(jl.sv), uni_ptr(jl.dst), uni(jl.ystride), uni(jl.cstride), uni(jl.dpitch),
+                      uni(jl.w),      uni(jl.h),      uni(jl.hs),     uni(jl.vs),      uni(jl.ky),      uni(jl.ybase),   uni(jl.rv),
+                      uni(jl.gu),     uni(jl.gv),     uni(jl.bu),     uni(jl.bgra)};
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    egress_rgb_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_egress_rgb<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_egress_rgb<false>, grid, block, 0, s, d_jobs);
     }
 }
 

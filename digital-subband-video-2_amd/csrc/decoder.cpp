@@ -37,6 +37,24 @@ struct DecImpl {
     std::vector<int32_t> val;
     bool out420p = false; // deliver every picture as 4:2:0 (the CLI's -out420p, util.c:79-153, done by the GPU on the way out)
     bool postsharp = false; // dsv_post_process on the luma of every picture handed out (the CLI's -postsharp, dsv_main.c:1084-1089)
+    // RGB delivery of a drawn-on or sharpened picture: there is no delivered luma plane for the overlay and the sharpening to act on,
+    // so the luma is staged here (w x h, 16-byte aligned origin and stride) and converted from here; made on first use
+    DPlane rgb_luma = {nullptr, 0, 0, 0};
+    const DPlane &staged_luma()
+    {
+        if (!rgb_luma.data) {
+            const int stride = (dev.w + 15) & ~15;
+            HIPCHK(dev_alloc((void **) &rgb_luma.data, (size_t) stride * (size_t) dev.h));
+            rgb_luma.stride = stride, rgb_luma.w = dev.w, rgb_luma.h = dev.h;
+        }
+        return rgb_luma;
+    }
+    void destroy_dev() // the device instance and what was sized by its geometry
+    {
+        dev.destroy();
+        dev_release(rgb_luma.data);
+        rgb_luma = DPlane{nullptr, 0, 0, 0};
+    }
 };
 
 // ---- lockstep batch engine ------------------------------------------------------------------------
@@ -69,7 +87,9 @@ struct DecJob {
     bool to_dev = false;     // ... or (dsv2hip_dec_batch_device / _surface) no frame at all: the picture goes to the caller's device planes
     uint8_t *dst[3] = {nullptr, nullptr, nullptr}; // ... these: Y, U, V (a packed buffer: the planar surface with pitch {w, cw, cw}), or
     int dpitch[3] = {0, 0, 0};
-    bool semi = false;       // ... Y and one plane of interleaved U V rows (dst[2] unused)
+    bool semi = false;       // ... Y and one plane of interleaved U V rows (dst[2] unused), or
+    int rgb = 0;             // ... (non-zero: the surface's layout, DSV2HIP_SURFACE_BGRA / _RGBA with its DSV2HIP_CSC_* bits) one plane of
+                             // four-byte pixels, dst[0], converted on the way out (dst[1..2] unused)
     int out_format = 0;      // format of the delivered picture: the stream's, or 4:2:0 under out420p
     bool sharp = false;      // the decoder's postsharp switch when the packet was handed in
     int draw = 0;            // the decoder's draw_info when the packet was handed in: non-zero = overlay on the luma of `of` (overlay.hip)
@@ -172,6 +192,7 @@ struct DecClock { // DSV2_TRACE=2: wall-clock split of a lockstep decode step, p
 };
 thread_local DecClock t_dec_clock;
 std::atomic<unsigned long long> g_uv_rounds[2]; // device rounds whose chroma interleave ran in the wide / the general form (dsv2hip_dec_surface_stats)
+std::atomic<unsigned long long> g_rgb_rounds[2]; // ... whose RGB egress ran in the wide / the general form (dsv2hip_dec_rgb_stats)
 
 // Where a picture's plane sections are parsed: DSV2_DEC_DEVICE_PARSE = 0: on the host (one pool task per picture: ~2 ms of a
 // core per 1080p P picture -- the fastest decoder while there are ~16 host cores per GPU to burn); 1: P pictures on the device, one
@@ -234,7 +255,7 @@ void dec_parse(DecJob &jb)
     jb.im = im;
     if (im->ready && (im->dev.w != meta->width || im->dev.h != meta->height || im->dev.format != meta->subsamp ||
                       im->dev.blk_w != hd.blk_w || im->dev.blk_h != hd.blk_h)) {
-        im->dev.destroy(); // stream parameters changed: start over
+        im->destroy_dev(); // stream parameters changed: start over
         im->ready = false;
         im->have_ref = false;
     }
@@ -309,17 +330,19 @@ struct Round { // what outlives a phase (the decoder's counterpart of the encode
     Tab<DPlane> ext[3];
     int nP = 0, nI = 0, nIf = 0, n_ext = 0;
     bool any_filter = false;
-    // delivery.  ov / eg / uv: only in a round with pictures that are drawn on / leave through the egress kernel (device delivery,
-    // postsharp) / leave with interleaved chroma, into a semiplanar surface (none: no table, no launch)
+    // delivery.  ov / eg / uv / rgb: only in a round with pictures that are drawn on / leave through the egress kernel (device delivery,
+    // postsharp) / leave with interleaved chroma, into a semiplanar surface / leave as four-byte RGB pixels (none: no table, no launch)
     Tab<CopyJob> out;
     Tab<To420Job> to420;
     Tab<OverlayJob> ov;
     Tab<EgressJob> eg;
     Tab<UvEgressJob> uv;
-    int n_out = 0, n_to420 = 0, n_ov = 0, n_eg = 0, n_uv = 0;
+    Tab<RgbOutJob> rgb;
+    int n_out = 0, n_to420 = 0, n_ov = 0, n_eg = 0, n_uv = 0, n_rgb = 0;
     int uv_rows = 0;                      // the most chroma rows an interleave job delivers ("4:1:0" to 4:2:0: more than the source has)
     bool uv_wide = true, uv_conv = false; // every interleave job allows the 16-byte form / some job converts to 4:2:0 (bmc.hip: k_egress_uv)
     bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
+    bool rgb_wide = true;                  // every RGB job allows the 16-byte form (bmc.hip: k_egress_rgb)
     bool ov_vectors = false;               // some overlay job draws motion vectors
     std::vector<DPlane> sharp_drawn; // delivered luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
     Round(DecJob *jobs_, const std::vector<int> &ids_) : jobs(jobs_), ids(ids_), n((int) ids_.size()), dv0(jobs_[ids_[0]].im->dev), order(ids_) {}
@@ -333,17 +356,18 @@ static_assert(13 * sizeof(CopyJob) + 3 * (sizeof(DequantJob) + sizeof(PlaneJob) 
               "a picture's share of the round's 22 job tables outgrew the 8192 bytes reserved for it");
 void round_take_tables(Round &r)
 {
-    int n_draw = 0, n_egress = 0, n_semi = 0;
+    int n_draw = 0, n_egress = 0, n_semi = 0, n_rgb = 0;
     for (int k : r.ids) {
         const DecJob &jb = r.jobs[k];
         n_draw += jb.draw != 0;
         n_egress += jb.to_dev || jb.sharp;
         n_semi += jb.to_dev && jb.semi;
+        n_rgb += jb.to_dev && jb.rgb;
     }
     TableArena &tabs = r.sc.tabs;
     const size_t n = (size_t) r.n;
     tabs.reserve(n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob) +
-                 (size_t) n_semi * sizeof(UvEgressJob));
+                 (size_t) n_semi * sizeof(UvEgressJob) + (size_t) n_rgb * sizeof(RgbOutJob));
     r.zero = Tab<CopyJob>(tabs, 3 * n);
     r.out = Tab<CopyJob>(tabs, n);
     for (int c = 0; c < 3; c++) {
@@ -363,6 +387,7 @@ void round_take_tables(Round &r)
     r.ov = Tab<OverlayJob>(tabs, (size_t) n_draw);
     r.eg = Tab<EgressJob>(tabs, 3 * (size_t) n_egress);
     r.uv = Tab<UvEgressJob>(tabs, (size_t) n_semi);
+    r.rgb = Tab<RgbOutJob>(tabs, (size_t) n_rgb);
 }
 
 size_t staged_len(const DSV_BUF *b) { return ((size_t) b->len + 64 + 15) & ~(size_t) 15; } // a packet as staged: 16-byte aligned, 64 zero bytes behind it
@@ -513,7 +538,18 @@ void fill_recon_jobs(Round &r, DecJob &jb)
     }
 }
 
-// the picture's way out: whole-frame copy, or per plane 4:2:0 conversion / egress / chroma interleave; the overlay behind it
+// the YUV -> RGB conversion of include/dsv2_hip.h for a layout's DSV2HIP_CSC_* bits: ky, ybase, rv, gu, gv, bu
+void rgb_out_coefs(RgbOutJob &j, int layout)
+{
+    static const int preset[4][6] = {{298, 16, 409, -100, -208, 516},  // BT601 (limited)
+                                     {298, 16, 459, -55, -136, 541},   // BT709 (limited)
+                                     {256, 0, 359, -88, -183, 454},    // BT601 | FULL
+                                     {256, 0, 403, -48, -120, 475}};   // BT709 | FULL
+    const int *p = preset[((layout & DSV2HIP_CSC_FULL_RANGE) ? 2 : 0) + ((layout & DSV2HIP_CSC_BT709) ? 1 : 0)];
+    j.ky = p[0], j.ybase = p[1], j.rv = p[2], j.gu = p[3], j.gv = p[4], j.bu = p[5];
+}
+
+// the picture's way out: whole-frame copy, or per plane 4:2:0 conversion / egress / chroma interleave / RGB conversion; the overlay behind it
 void fill_delivery_jobs(Round &r, DecJob &jb)
 {
     CodecDev &dv = jb.im->dev;
@@ -535,7 +571,23 @@ void fill_delivery_jobs(Round &r, DecJob &jb)
     }
     const bool conv = jb.out_format != dv.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
     const bool sharp_out = jb.sharp && !jb.draw;  // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
-    if (!conv && !jb.to_dev && !sharp_out) {
+    if (jb.to_dev && jb.rgb) {
+        // One job, reading the reconstruction in place.  A sharpened and / or drawn-on picture: its luma goes through the egress
+        // kernel into the decoder's staging plane first, which stands in for the delivered luma plane below (overlay, sharpening
+        // behind the overlay) and is what the conversion then reads; round_enqueue launches the conversion last.
+        DPlane ly = recon.p[0];
+        if (jb.sharp || jb.draw) {
+            ly = op[0] = jb.im->staged_luma();
+            r.eg.h[r.n_eg++] = EgressJob{recon.p[0], ly.data, ly.stride, sharp_out};
+            r.eg_sharp = r.eg_sharp || sharp_out;
+            r.eg_wide = r.eg_wide && ly.w % 16 == 0;
+        }
+        RgbOutJob &rj = r.rgb.h[r.n_rgb++];
+        rj = RgbOutJob{ly.data, recon.p[1].data, recon.p[2].data, jb.dst[0], ly.stride, recon.p[1].stride, jb.dpitch[0], dv.w, dv.h,
+                       DSV_FORMAT_H_SHIFT(dv.format), DSV_FORMAT_V_SHIFT(dv.format), 0, 0, 0, 0, 0, 0, (jb.rgb & 0xff) == DSV2HIP_SURFACE_BGRA};
+        rgb_out_coefs(rj, jb.rgb);
+        r.rgb_wide = r.rgb_wide && rgb_out_job_wide(rj);
+    } else if (!conv && !jb.to_dev && !sharp_out) {
         r.out.h[r.n_out++] = CopyJob{recon.alloc, jb.of->alloc, recon.bytes};
     } else {
         const int hs = DSV_FORMAT_H_SHIFT(dv.format), vs = DSV_FORMAT_V_SHIFT(dv.format);
@@ -627,6 +679,10 @@ void round_enqueue(Round &r)
     for (const DPlane &pl : r.sharp_drawn) { // (a debugging combination: one launch a picture)
         post_process_plane(bs, pl);
     }
+    if (r.n_rgb) { // last: behind the overlay and the sharpening of the luma planes staged for it
+        egress_rgb_batch(bs, r.rgb.d, r.n_rgb, dv0.h, r.rgb_wide);
+        g_rgb_rounds[r.rgb_wide ? 0 : 1]++;
+    }
     prof.end(bs, ST_EXTEND, r.n);
     t_dec_clock.lap(2);
 }
@@ -701,15 +757,33 @@ void dec_batch(DecJob *jobs, int n)
 
 Coalescer<DecJob> g_dec_queue; // dsv_dec callers share lockstep steps (batch.h)
 
+// an RGB layout: BGRA / RGBA or-ed with any subset of the DSV2HIP_CSC_* bits (the bits on PLANAR / SEMIPLANAR are no layout)
+bool is_rgb_layout(int layout)
+{
+    const int order = layout & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE);
+    return order == DSV2HIP_SURFACE_BGRA || order == DSV2HIP_SURFACE_RGBA;
+}
+
 // Plane sizes of the picture as this decoder delivers it (dsv_mk_frame's, frame.c:63-113, in the stream's format or 4:2:0 under
-// out420p), as the rows of a surface of `layout`: false before the metadata or for a layout that is neither value
+// out420p), as the rows of a surface of `layout`: false before the metadata or for a value that is no layout.  An RGB layout is one
+// plane of 4 * w bytes a row, and no layout for a decoder that converts to 4:2:0: an RGB picture has no chroma planes to subsample.
 bool surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], int rows[3])
 {
-    if (!d || !d->got_metadata || (layout != DSV2HIP_SURFACE_PLANAR && layout != DSV2HIP_SURFACE_SEMIPLANAR)) {
+    const bool rgb = is_rgb_layout(layout);
+    if (!d || !d->got_metadata || (layout != DSV2HIP_SURFACE_PLANAR && layout != DSV2HIP_SURFACE_SEMIPLANAR && !rgb)) {
         return false;
     }
     const DSV_META &m = d->vidmeta;
-    const int fmt = (d->ref && ((DecImpl *) d->ref)->out420p) ? DSV_SUBSAMP_420 : m.subsamp;
+    const bool out420p = d->ref && ((DecImpl *) d->ref)->out420p;
+    if (rgb) {
+        if (out420p) {
+            return false;
+        }
+        row_bytes[0] = 4 * (size_t) m.width, rows[0] = m.height;
+        row_bytes[1] = row_bytes[2] = 0, rows[1] = rows[2] = 0;
+        return true;
+    }
+    const int fmt = out420p ? DSV_SUBSAMP_420 : m.subsamp;
     const int hs = DSV_FORMAT_H_SHIFT(fmt), vs = DSV_FORMAT_V_SHIFT(fmt);
     const size_t cw = (size_t) ((m.width + (1 << hs) - 1) >> hs);
     const int ch = (m.height + (1 << vs) - 1) >> vs;
@@ -764,7 +838,7 @@ void dsv_dec_free(DSV_DECODER *d)
     if (d->ref) {
         DecImpl *im = (DecImpl *) d->ref;
         if (im->ready) {
-            im->dev.destroy();
+            im->destroy_dev();
         }
         delete im;
         d->ref = NULL;
@@ -920,7 +994,8 @@ int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const ds
         }
         DecJob &jb = jobs[(size_t) k];
         jb.semi = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR;
-        for (int c = 0; c < (jb.semi ? 2 : 3); c++) {
+        jb.rgb = is_rgb_layout(sf.layout) ? sf.layout : 0;
+        for (int c = 0; c < (jb.rgb ? 1 : jb.semi ? 2 : 3); c++) {
             // (the kernels carry a pitch as an int: one beyond INT_MAX is refused)
             if (!sf.plane[c] || sf.pitch[c] < rb[c] || sf.pitch[c] > (size_t) INT32_MAX || sf.cap[c] < (size_t) (rows[c] - 1) * sf.pitch[c] + rb[c]) {
                 return -1;
@@ -939,6 +1014,18 @@ int dsv2hip_dec_surface_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_su
         return -1;
     }
     return ret;
+}
+
+void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset)
+{
+    for (int i = 0; i < 2; i++) {
+        if (out2) {
+            out2[i] = g_rgb_rounds[i].load();
+        }
+        if (reset) {
+            g_rgb_rounds[i].store(0);
+        }
+    }
 }
 
 void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset)

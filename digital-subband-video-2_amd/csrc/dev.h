@@ -224,6 +224,19 @@ struct UvEgressJob { // both chroma planes of a decoded picture on their way int
     int mode;               // To420Job's: 0 as decoded, 1 from 4:4:4, 2 from 4:2:2, 3 from 4:1:1, 4 from "4:1:0"
 };
 inline bool uv_job_wide(const UvEgressJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && j.cw % 8 == 0; }
+struct RgbOutJob { // one decoded picture on its way into a packed four-byte RGB surface (dsv2hip_out_surface, BGRA / RGBA), converted on the
+                   // way (egress_rgb.h, bmc.hip: k_egress_rgb); 88 bytes, fetched by value through the scalar cache like UvEgressJob
+    const uint8_t *sy, *su, *sv; // pixel (0,0) of the luma and the chroma planes: 16-byte aligned origin and stride, rows readable up to the
+                                 // next multiple of 4 bytes (dframe_alloc's border; the decoder's staged luma: its stride)
+    uint8_t *dst;                // device memory, any alignment: row y at dst + y * dpitch, 4 * w bytes of it written
+    int ystride, cstride;        // of sy; of su and sv (the two chroma planes of a frame share their geometry)
+    int dpitch;
+    int w, h;                    // of the picture
+    int hs, vs;                  // the stream's chroma shifts
+    int ky, ybase, rv, gu, gv, bu; // the conversion of include/dsv2_hip.h
+    int bgra;                    // the surface's byte order: non-zero B G R A, zero R G B A
+};
+inline bool rgb_out_job_wide(const RgbOutJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && (j.w & 3) == 0; }
 void to420_batch(hipStream_t s, const To420Job *d_jobs, int n, int max_w, int max_h);
 void ingest_uyvy_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int h); // src = interleaved UYVY rows
 void planes_to_host_batch(hipStream_t s, const PlaneOutJob *d_jobs, int n, int h);

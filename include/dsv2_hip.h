@@ -511,17 +511,59 @@ int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size
  * dsv2hip_dec_surface_stats: out2[0] / out2[1] = device rounds of this process (one per picture geometry present in a lockstep
  * step) whose chroma interleave ran in the wide form (every interleaved plane of the round: pointer and pitch multiples of 16,
  * cw of 8) / in the general form so far; rounds without a semiplanar picture count as neither.  reset != 0 clears the counts
- * afterwards. */
+ * afterwards.
+ *
+ * PACKED RGB SURFACES, converted on egress -- what display paths, image libraries and torch uint8[h, w, 4] tensors take: four bytes a
+ * pixel, no conversion kernel and no second pass over memory behind the decoder.  The counterpart of the encoder's RGB surfaces
+ * above, with the same constants and the same meaning.
+ *   BGRA / RGBA: plane[0] = the picture, row y at plane[0] + y * pitch[0], w pixels of 4 bytes in the named byte order; the fourth
+ *                byte of every pixel is written as 255; plane[1..2], pitch[1..2] and cap[1..2] are ignored.
+ * A valid RGB layout is DSV2HIP_SURFACE_BGRA or DSV2HIP_SURFACE_RGBA or-ed with any subset of DSV2HIP_CSC_BT709 |
+ * DSV2HIP_CSC_FULL_RANGE; a CSC bit on PLANAR / SEMIPLANAR, or any other value (0x12, 0x410 ...), is no layout.  The layouts go
+ * through dsv2hip_dec_batch_surface and dsv2hip_dec_surface_frame, and everything said above holds for them, applied to plane 0: any
+ * pointer alignment and any pitch from 4 * w up to INT_MAX; only the 4 * w bytes of each of the h rows are ever written, padding
+ * and the bytes behind the last row never; cap[0] >= (h - 1) * pitch[0] + 4 * w; surf[k] copied; layouts mixed freely within one
+ * step and one round -- packed, planar, NV12, BGRA-601, RGBA-709-full ...; a refused call touches nothing.  The stream may have any
+ * of the five chroma formats.  Refused in addition -- as a whole, with -1, for a decoder that has metadata: an RGB layout on a decoder
+ * with dsv2hip_dec_set_out420p on (an RGB picture has no chroma planes to subsample).  dsv2hip_dec_surface_dims gives row_bytes =
+ * {4 * w, 0, 0} and rows = {h, 0, 0} for an RGB layout, and -1 for that pair too.
+ *
+ * THE CONVERSION (the contract: the delivered RGB picture is exactly this function of the planar picture that the same decoder,
+ * with the same draw_info / postsharp settings, delivers through a PLANAR surface).  Integer arithmetic.  hs, vs are the stream's
+ * chroma shifts; the chroma of pixel (x, y) is the sample (x >> hs, y >> vs): replication over exactly the footprint the encoder's
+ * box average uses.  Bilinear or sited chroma upsampling is out of scope.
+ *
+ *   C = ky * (Y - ybase),  D = U - 128,  E = V - 128
+ *   R = clamp((C + rv*E         + 128) >> 8, 0, 255)
+ *   G = clamp((C + gu*D + gv*E  + 128) >> 8, 0, 255)
+ *   B = clamp((C + bu*D         + 128) >> 8, 0, 255)      (>> arithmetic, i.e. floor)
+ *
+ *   preset            ky  ybase   rv    gu    gv    bu
+ *   BT601 (limited)  298    16   409  -100  -208   516
+ *   BT709 (limited)  298    16   459   -55  -136   541
+ *   BT601 | FULL     256     0   359   -88  -183   454
+ *   BT709 | FULL     256     0   403   -48  -120   475
+ *
+ * Over all 2^24 (Y, U, V): C + rv*E, C + gu*D + gv*E and C + bu*D lie within -74 016 ... 139 929 (with the rounding constant: -73 888
+ * ... 140 057 at the shift), so 24-bit signed multiply-adds suffice;
+ * U = V = 128 gives R = G = B; limited range maps Y = 16 to 0 and Y = 235 to 255; full range gives a grey Y back exactly.  Behind
+ * the encoder's conversion at 4:4:4 (above) the round trip R, G, B -> Y, U, V -> R, G, B errs by at most 2, 2, 3 (R, G, B) with the
+ * limited-range presets and 2, 1, 2 with the full-range ones, over all 2^24 colours (tests/test_egress_rgb_cpu.py).
+ * draw_info and postsharp act on the luma the conversion reads, as they act on the luma plane of every other delivery.
+ * dsv2hip_dec_rgb_stats: out2[0] / out2[1] = device rounds of this process whose RGB egress ran in the wide form (every RGB surface
+ * of the round: pointer and pitch multiples of 16, w of 4) / in the general form so far; rounds without an RGB picture count as
+ * neither.  reset != 0 clears the counts afterwards.  dsv2hip_dec_surface_stats keeps counting the chroma interleaves only. */
 typedef struct dsv2hip_out_surface {
-    void *plane[3];  /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first); plane[2] ignored */
-    size_t pitch[3]; /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR */
-    size_t cap[3];   /* bytes the caller owns from plane[c] on; cap[2] ignored for SEMIPLANAR */
-    int layout;      /* DSV2HIP_SURFACE_PLANAR / DSV2HIP_SURFACE_SEMIPLANAR */
+    void *plane[3];  /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first); plane[2] ignored.  BGRA / RGBA: the picture */
+    size_t pitch[3]; /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR, pitch[1..2] for BGRA / RGBA */
+    size_t cap[3];   /* bytes the caller owns from plane[c] on; cap[2] ignored for SEMIPLANAR, cap[1..2] for BGRA / RGBA */
+    int layout;      /* DSV2HIP_SURFACE_PLANAR / _SEMIPLANAR, or DSV2HIP_SURFACE_BGRA / _RGBA or-ed with DSV2HIP_CSC_* bits */
 } dsv2hip_out_surface;
 int dsv2hip_dec_surface_dims(DSV_DECODER *dec, int layout, size_t row_bytes[3], int rows[3]);
 int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, DSV_FNUM *fn, int *ret);
 int dsv2hip_dec_surface_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_surface *surf, DSV_FNUM *fn);
 void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset);
+void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset);
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the
