@@ -1656,6 +1656,8 @@ static void step_p0(Job *jobs, int n, bool trace_startup)
         }
         jb.im = (EncImpl *) jb.enc->ref;
         ensure_ready(jb.enc, jb.im);
+        // (an invariant of the step, not an input check: every public call -- the batch entry points, the submit queue of dsv_enc --
+        // compares step_key() first and refuses or separates what differs, so no caller's arguments reach this line)
         if (k > 0 && (jb.im->dev.w != jobs[0].im->dev.w || jb.im->dev.h != jobs[0].im->dev.h || jb.im->dev.format != jobs[0].im->dev.format ||
                       jb.im->dev.blk_w != jobs[0].im->dev.blk_w || jb.im->dev.blk_h != jobs[0].im->dev.blk_h ||
                       jb.im->dev.pyr_levels != jobs[0].im->dev.pyr_levels)) {
@@ -1763,7 +1765,7 @@ static void g1_enqueue(Step &st)
         Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
         PicSet &cur = dv.pics[jb.im->cur], &ref = dv.pics[jb.im->cur ^ 1];
-        if (jb.d.params.do_psy != st.do_psy) {
+        if (jb.d.params.do_psy != st.do_psy) { // (unreachable from the public calls, as the geometry check of step_p0: do_psy is in step_key())
             fatal("dsv2hip_enc_batch: all encoders of a batch must share one do_psy setting", __FILE__, __LINE__);
         }
         if (jb.frame) {

@@ -374,7 +374,19 @@ int dsv2hip_set_device(int ordinal);
 int dsv2hip_enc_device_frame(DSV_ENCODER *enc, const void *dev_planar, DSV_BUF *bufs);
 /* lockstep step over n independent encoders of identical geometry: one frame each, the latency-bound
  * kernels (motion-estimation fronts, MC, in-loop filters) are launched once for all streams.  bufs has
- * 4 slots per stream; nbufs[k] = packets of stream k.  Output is identical to n separate dsv_enc calls. */
+ * 4 slots per stream; nbufs[k] = packets of stream k.  Output is identical to n separate dsv_enc calls.
+ * WHAT A STEP MUST SHARE (this call, _batch_surface and _batch_host alike; the submit queue behind dsv_enc groups callers by the
+ * same rule): vidmeta.width, .height and .subsamp; block_size_override_x and _y; the pyramid depth the encoder runs with
+ * (pyramid_levels, or what 0 resolves to for the picture: an encoder that says 3 and one that says 0 at a size that resolves to 3
+ * agree); do_psy.  A step whose encoders differ in one of these is refused as a whole with -1 before any encoder, frame counter,
+ * input buffer or nbufs entry is touched; the encoders stay usable, each in steps of its own kind.
+ * EVERYTHING ELSE IS PER STREAM and may differ freely within one step: quality (lossless streams beside lossy ones), effort, gop and
+ * the phase within it, the frame number (streams may join a step group late, leave early, or sit steps out), rc_mode, bitrate and
+ * the quality bounds, skip_block_thresh, do_scd, do_temporal_aq, do_dark_intra_boost, do_intra_filter, do_inter_filter,
+ * variable_i_interval, scene_change_pct, intra_pct_thresh, stable_refresh, and the metadata's fps and inter_sharpen.  An encoder
+ * may also change its company, its slot and its entry point from one picture to the next -- dsv_enc, _enc_device_frame, _enc_batch,
+ * _batch_host and _batch_surface in any order: its packets are those of dsv_enc on its pictures alone
+ * (tests/test_gpu_enc_mixed_steps.py). */
 int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, DSV_BUF *bufs, int *nbufs);
 /* The same step for pictures that are SURFACES with a row pitch in device memory -- what hardware video decoders, capture
  * pipelines, image libraries and hipMallocPitch hand out -- read in place: no repacking pass, no trip through the host.

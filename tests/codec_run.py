@@ -32,9 +32,10 @@ def configure_encoder(lib, enc, meta, qp=60, gop=48, effort=10, rc_mode=0, **ove
     lib.dsv_enc_start(C.byref(enc))
 
 
-def encode_stream(lib, frames, w, h, subsamp, eos=True, **cfg):
-    """frames: list of bytes (planar YUV). Returns (list of packet bytes, encoder struct)."""
-    meta = A.mk_meta(w, h, subsamp)
+def encode_stream(lib, frames, w, h, subsamp, eos=True, meta=None, **cfg):
+    """frames: list of bytes (planar YUV); meta: the stream's metadata where it is not mk_meta's default.  Returns (list of
+    packet bytes, dict of the encoder's final stats)."""
+    meta = A.mk_meta(w, h, subsamp) if meta is None else meta
     enc = A.ENCODER()
     configure_encoder(lib, enc, meta, **cfg)
     packets = []
