@@ -20,6 +20,7 @@
 #include "blockstat.h"
 #include "bmc.h"
 #include "egress_rgb.h"
+#include "egress_scale.h"
 #include "egress_uv.h"
 #include "hme.h"
 
@@ -2405,6 +2406,37 @@ void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool
         DSV2_LAUNCH(k_egress_rgb<true>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_egress_rgb<false>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- decoder egress at half, quarter or eighth size: the box average of include/dsv2_hip.h ------------------------------------------
+// One job per plane (ScaleOutJob, dev.h), fetched by value and pinned to scalar registers.  A workgroup of 8 x 32 threads covers 32
+// OUTPUT rows, a thread one output row: it walks the source rows of its footprint in passes of 8 x 16 = 128 source bytes, so a
+// wavefront's load is eight whole 128-byte lines, one per output row.  The thread's work is egress_scale.h's egress_scale_row (which
+// tools/egress_scale_check.cpp runs on the CPU).
+constexpr int kScaleRows = 32, kScaleLanes = 8; // output rows per workgroup; threads along a row
+template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_scale(const ScaleOutJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const ScaleOutJob jl = job_of(tab, blockIdx.y);
+    const ScaleOutJob j{uni_ptr(jl.src), uni_ptr(jl.dst), uni(jl.sstride), uni(jl.pw), uni(jl.ph), uni(jl.dpitch), uni(jl.shift)};
+    const int oy0 = uni((int) blockIdx.x * kScaleRows);
+    if (oy0 + (int) threadIdx.y >= (j.ph + (1 << j.shift) - 1) >> j.shift) {
+        return;
+    }
+    egress_scale_row<WIDE>(j, oy0, (int) threadIdx.y, (int) threadIdx.x, kScaleLanes);
+}
+
+void egress_scale_batch(hipStream_t s, const ScaleOutJob *d_jobs, int n, int max_oh, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_oh + kScaleRows - 1) / kScaleRows, n), block(kScaleLanes, kScaleRows);
+    if (wide) {
+        DSV2_LAUNCH(k_egress_scale<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_egress_scale<false>, grid, block, 0, s, d_jobs);
     }
 }
 

@@ -49,11 +49,37 @@ struct DecImpl {
         }
         return rgb_luma;
     }
+    // Scaled delivery (DSV2HIP_SCALE_*) into a semiplanar or an RGB surface: the reduced planes that k_egress_uv / k_egress_rgb then
+    // read are staged here.  Sized for half size -- a quarter of a picture -- and laid out once with its strides; a quarter- or eighth-
+    // size picture uses the top left of the same planes.  16-byte aligned origins and strides, so rows are readable (and, by the wide
+    // form of the reduction, writable) up to the next multiple of 16 bytes; made on first use
+    DPlane scaled[3] = {{nullptr, 0, 0, 0}, {nullptr, 0, 0, 0}, {nullptr, 0, 0, 0}};
+    const DPlane *staged_scaled()
+    {
+        if (!scaled[0].data) {
+            size_t off[3], total = 0;
+            for (int c = 0; c < 3; c++) {
+                const DPlane &p = dev.pics[0].recon.p[c];
+                scaled[c].w = (p.w + 1) >> 1, scaled[c].h = (p.h + 1) >> 1;
+                scaled[c].stride = (scaled[c].w + 15) & ~15;
+                off[c] = total;
+                total += (size_t) scaled[c].stride * (size_t) scaled[c].h;
+            }
+            uint8_t *base = nullptr;
+            HIPCHK(dev_alloc((void **) &base, total));
+            for (int c = 0; c < 3; c++) {
+                scaled[c].data = base + off[c];
+            }
+        }
+        return scaled;
+    }
     void destroy_dev() // the device instance and what was sized by its geometry
     {
         dev.destroy();
         dev_release(rgb_luma.data);
         rgb_luma = DPlane{nullptr, 0, 0, 0};
+        dev_release(scaled[0].data);
+        scaled[0].data = nullptr;
     }
 };
 
@@ -90,6 +116,8 @@ struct DecJob {
     bool semi = false;       // ... Y and one plane of interleaved U V rows (dst[2] unused), or
     int rgb = 0;             // ... (non-zero: the surface's layout, DSV2HIP_SURFACE_BGRA / _RGBA with its DSV2HIP_CSC_* bits) one plane of
                              // four-byte pixels, dst[0], converted on the way out (dst[1..2] unused)
+    int scale = 0;           // ... (non-zero: the surface's DSV2HIP_SCALE_* shift, 1 .. 3) every plane at 1 / 2^scale of its size, box-averaged on
+                             // the way out (egress_scale.h)
     int out_format = 0;      // format of the delivered picture: the stream's, or 4:2:0 under out420p
     bool sharp = false;      // the decoder's postsharp switch when the packet was handed in
     int draw = 0;            // the decoder's draw_info when the packet was handed in: non-zero = overlay on the luma of `of` (overlay.hip)
@@ -193,6 +221,7 @@ struct DecClock { // DSV2_TRACE=2: wall-clock split of a lockstep decode step, p
 thread_local DecClock t_dec_clock;
 std::atomic<unsigned long long> g_uv_rounds[2]; // device rounds whose chroma interleave ran in the wide / the general form (dsv2hip_dec_surface_stats)
 std::atomic<unsigned long long> g_rgb_rounds[2]; // ... whose RGB egress ran in the wide / the general form (dsv2hip_dec_rgb_stats)
+std::atomic<unsigned long long> g_scale_rounds[2]; // ... whose reduction ran in the wide / the general form (dsv2hip_dec_scale_stats)
 
 // Where a picture's plane sections are parsed: DSV2_DEC_DEVICE_PARSE = 0: on the host (one pool task per picture: ~2 ms of a
 // core per 1080p P picture -- the fastest decoder while there are ~16 host cores per GPU to burn); 1: P pictures on the device, one
@@ -338,7 +367,10 @@ struct Round { // what outlives a phase (the decoder's counterpart of the encode
     Tab<EgressJob> eg;
     Tab<UvEgressJob> uv;
     Tab<RgbOutJob> rgb;
-    int n_out = 0, n_to420 = 0, n_ov = 0, n_eg = 0, n_uv = 0, n_rgb = 0;
+    Tab<ScaleOutJob> scl; // planes that leave at half, quarter or eighth size (into a caller's plane, or staged for uv / rgb)
+    int n_out = 0, n_to420 = 0, n_ov = 0, n_eg = 0, n_uv = 0, n_rgb = 0, n_scl = 0;
+    int scl_rows = 0;                     // the most rows a reduction job delivers
+    bool scl_wide = true;                 // every reduction job allows the unconditional vector store (bmc.hip: k_egress_scale)
     int uv_rows = 0;                      // the most chroma rows an interleave job delivers ("4:1:0" to 4:2:0: more than the source has)
     bool uv_wide = true, uv_conv = false; // every interleave job allows the 16-byte form / some job converts to 4:2:0 (bmc.hip: k_egress_uv)
     bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
@@ -356,18 +388,20 @@ static_assert(13 * sizeof(CopyJob) + 3 * (sizeof(DequantJob) + sizeof(PlaneJob) 
               "a picture's share of the round's 22 job tables outgrew the 8192 bytes reserved for it");
 void round_take_tables(Round &r)
 {
-    int n_draw = 0, n_egress = 0, n_semi = 0, n_rgb = 0;
+    int n_draw = 0, n_egress = 0, n_semi = 0, n_rgb = 0, n_scaled = 0;
     for (int k : r.ids) {
         const DecJob &jb = r.jobs[k];
         n_draw += jb.draw != 0;
         n_egress += jb.to_dev || jb.sharp;
         n_semi += jb.to_dev && jb.semi;
         n_rgb += jb.to_dev && jb.rgb;
+        n_scaled += jb.to_dev && jb.scale;
     }
     TableArena &tabs = r.sc.tabs;
     const size_t n = (size_t) r.n;
     tabs.reserve(n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob) +
-                 (size_t) n_semi * sizeof(UvEgressJob) + (size_t) n_rgb * sizeof(RgbOutJob));
+                 (size_t) n_semi * sizeof(UvEgressJob) + (size_t) n_rgb * sizeof(RgbOutJob) +
+                 3 * (size_t) n_scaled * sizeof(ScaleOutJob));
     r.zero = Tab<CopyJob>(tabs, 3 * n);
     r.out = Tab<CopyJob>(tabs, n);
     for (int c = 0; c < 3; c++) {
@@ -388,6 +422,7 @@ void round_take_tables(Round &r)
     r.eg = Tab<EgressJob>(tabs, 3 * (size_t) n_egress);
     r.uv = Tab<UvEgressJob>(tabs, (size_t) n_semi);
     r.rgb = Tab<RgbOutJob>(tabs, (size_t) n_rgb);
+    r.scl = Tab<ScaleOutJob>(tabs, 3 * (size_t) n_scaled);
 }
 
 size_t staged_len(const DSV_BUF *b) { return ((size_t) b->len + 64 + 15) & ~(size_t) 15; } // a packet as staged: 16-byte aligned, 64 zero bytes behind it
@@ -571,7 +606,44 @@ void fill_delivery_jobs(Round &r, DecJob &jb)
     }
     const bool conv = jb.out_format != dv.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
     const bool sharp_out = jb.sharp && !jb.draw;  // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
-    if (jb.to_dev && jb.rgb) {
+    if (jb.to_dev && jb.scale) {
+        // Every plane through the reduction (egress_scale.h), reading the reconstruction in place: PLANAR, and the luma of SEMIPLANAR,
+        // straight into the caller's planes; what the interleave or the conversion has yet to read, into the decoder's staging picture,
+        // from which the unchanged k_egress_uv (mode 0) / k_egress_rgb run on the reduced geometry.  A sharpened and / or drawn-on
+        // picture: its full-size luma is staged first, exactly as in the RGB branch below, and the reduction reads from there --
+        // round_enqueue launches it behind the overlay and the sharpening.  (No 4:2:0 conversion here: the surface call refuses the pair.)
+        const int s = jb.scale, up = (1 << s) - 1;
+        DPlane src[3] = {recon.p[0], recon.p[1], recon.p[2]};
+        if (jb.sharp || jb.draw) {
+            src[0] = op[0] = jb.im->staged_luma();
+            r.eg.h[r.n_eg++] = EgressJob{recon.p[0], src[0].data, src[0].stride, sharp_out};
+            r.eg_sharp = r.eg_sharp || sharp_out;
+            r.eg_wide = r.eg_wide && src[0].w % 16 == 0;
+        }
+        const DPlane *st = (jb.semi || jb.rgb) ? jb.im->staged_scaled() : nullptr;
+        DPlane red[3]; // the reduced planes, where they go
+        for (int c = 0; c < 3; c++) {
+            const bool staged = jb.rgb || (jb.semi && c);
+            red[c] = staged ? DPlane{st[c].data, st[c].stride, 0, 0} : DPlane{jb.dst[c], jb.dpitch[c], 0, 0};
+            red[c].w = (src[c].w + up) >> s, red[c].h = (src[c].h + up) >> s;
+            ScaleOutJob &sj = r.scl.h[r.n_scl++];
+            sj = ScaleOutJob{src[c].data, red[c].data, src[c].stride, src[c].w, src[c].h, red[c].stride, s};
+            r.scl_wide = r.scl_wide && scale_job_wide(sj, staged ? red[c].stride : red[c].w);
+            r.scl_rows = std::max(r.scl_rows, red[c].h);
+        }
+        if (jb.semi) {
+            UvEgressJob &uj = r.uv.h[r.n_uv++];
+            uj = UvEgressJob{red[1].data, red[2].data, jb.dst[1], jb.dpitch[1], red[1].stride, red[1].w, red[1].h, red[1].w, red[1].h, 0};
+            r.uv_wide = r.uv_wide && uv_job_wide(uj);
+            r.uv_rows = std::max(r.uv_rows, red[1].h);
+        } else if (jb.rgb) {
+            RgbOutJob &rj = r.rgb.h[r.n_rgb++];
+            rj = RgbOutJob{red[0].data, red[1].data, red[2].data, jb.dst[0], red[0].stride, red[1].stride, jb.dpitch[0], red[0].w, red[0].h,
+                           DSV_FORMAT_H_SHIFT(dv.format), DSV_FORMAT_V_SHIFT(dv.format), 0, 0, 0, 0, 0, 0, (jb.rgb & 0xff) == DSV2HIP_SURFACE_BGRA};
+            rgb_out_coefs(rj, jb.rgb);
+            r.rgb_wide = r.rgb_wide && rgb_out_job_wide(rj);
+        }
+    } else if (jb.to_dev && jb.rgb) {
         // One job, reading the reconstruction in place.  A sharpened and / or drawn-on picture: its luma goes through the egress
         // kernel into the decoder's staging plane first, which stands in for the delivered luma plane below (overlay, sharpening
         // behind the overlay) and is what the conversion then reads; round_enqueue launches the conversion last.
@@ -671,13 +743,17 @@ void round_enqueue(Round &r)
     copy_linear_batch(bs, r.out.d, r.n_out, dv0.pics[0].recon.bytes);
     to420_batch(bs, r.to420.d, r.n_to420, dv0.w, dv0.h);
     egress_batch(bs, r.eg.d, r.n_eg, dv0.h, r.eg_wide, r.eg_sharp);
-    if (r.n_uv) {
-        egress_uv_batch(bs, r.uv.d, r.n_uv, r.uv_rows, r.uv_wide, r.uv_conv);
-        g_uv_rounds[r.uv_wide ? 0 : 1]++;
-    }
     overlay_batch(bs, r.ov.d, r.n_ov, dv0.h, dv0.nbh, dv0.nbv, r.ov_vectors);
     for (const DPlane &pl : r.sharp_drawn) { // (a debugging combination: one launch a picture)
         post_process_plane(bs, pl);
+    }
+    if (r.n_scl) { // behind the overlay and the sharpening of the luma planes staged for it, in front of the two kernels that read what it stages
+        egress_scale_batch(bs, r.scl.d, r.n_scl, r.scl_rows, r.scl_wide);
+        g_scale_rounds[r.scl_wide ? 0 : 1]++;
+    }
+    if (r.n_uv) { // (chroma only: the overlay and the sharpening are none of its business, the reduction of a scaled picture's chroma is)
+        egress_uv_batch(bs, r.uv.d, r.n_uv, r.uv_rows, r.uv_wide, r.uv_conv);
+        g_uv_rounds[r.uv_wide ? 0 : 1]++;
     }
     if (r.n_rgb) { // last: behind the overlay and the sharpening of the luma planes staged for it
         egress_rgb_batch(bs, r.rgb.d, r.n_rgb, dv0.h, r.rgb_wide);
@@ -757,38 +833,53 @@ void dec_batch(DecJob *jobs, int n)
 
 Coalescer<DecJob> g_dec_queue; // dsv_dec callers share lockstep steps (batch.h)
 
-// an RGB layout: BGRA / RGBA or-ed with any subset of the DSV2HIP_CSC_* bits (the bits on PLANAR / SEMIPLANAR are no layout)
+// the shift of an out surface's layout: 0, or 1 .. 3 for DSV2HIP_SCALE_HALF / _QUARTER / _EIGHTH; the layout without it
+constexpr int kScaleMask = DSV2HIP_SCALE_EIGHTH; // (the three values are 1, 2, 3 << 12)
+int layout_shift(int layout) { return (layout & kScaleMask) >> 12; }
+int layout_unscaled(int layout) { return layout & ~kScaleMask; }
+
+// an RGB layout: BGRA / RGBA or-ed with any subset of the DSV2HIP_CSC_* bits (the bits on PLANAR / SEMIPLANAR are no layout) and at
+// most one DSV2HIP_SCALE_* value.  One value is held back: 0x1010, which reads as BGRA | BT601 | limited range | HALF, was refused as
+// "no layout" before the scale values existed, callers and the RGB surface tests probe with it and rely on the refusal, and it stays
+// refused (include/dsv2_hip.h): half-size BGRA takes any other preset (0x1110, 0x1210, 0x1310), or RGBA (0x1011).
 bool is_rgb_layout(int layout)
 {
-    const int order = layout & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE);
+    if (layout == (DSV2HIP_SURFACE_BGRA | DSV2HIP_SCALE_HALF)) {
+        return false;
+    }
+    const int order = layout_unscaled(layout) & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE);
     return order == DSV2HIP_SURFACE_BGRA || order == DSV2HIP_SURFACE_RGBA;
 }
 
 // Plane sizes of the picture as this decoder delivers it (dsv_mk_frame's, frame.c:63-113, in the stream's format or 4:2:0 under
 // out420p), as the rows of a surface of `layout`: false before the metadata or for a value that is no layout.  An RGB layout is one
 // plane of 4 * w bytes a row, and no layout for a decoder that converts to 4:2:0: an RGB picture has no chroma planes to subsample.
+// A layout with a DSV2HIP_SCALE_* value: the sizes of the reduced picture -- dsv_mk_frame's for ceil(w / n) x ceil(h / n), nested
+// round-ups commuting -- and no layout either for a decoder that converts to 4:2:0.
 bool surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], int rows[3])
 {
     const bool rgb = is_rgb_layout(layout);
-    if (!d || !d->got_metadata || (layout != DSV2HIP_SURFACE_PLANAR && layout != DSV2HIP_SURFACE_SEMIPLANAR && !rgb)) {
+    const int shift = layout_shift(layout), plain = layout_unscaled(layout);
+    if (!d || !d->got_metadata || (plain != DSV2HIP_SURFACE_PLANAR && plain != DSV2HIP_SURFACE_SEMIPLANAR && !rgb)) {
         return false;
     }
     const DSV_META &m = d->vidmeta;
     const bool out420p = d->ref && ((DecImpl *) d->ref)->out420p;
+    if (out420p && (rgb || shift)) {
+        return false;
+    }
+    const int width = (m.width + (1 << shift) - 1) >> shift, height = (m.height + (1 << shift) - 1) >> shift;
     if (rgb) {
-        if (out420p) {
-            return false;
-        }
-        row_bytes[0] = 4 * (size_t) m.width, rows[0] = m.height;
+        row_bytes[0] = 4 * (size_t) width, rows[0] = height;
         row_bytes[1] = row_bytes[2] = 0, rows[1] = rows[2] = 0;
         return true;
     }
     const int fmt = out420p ? DSV_SUBSAMP_420 : m.subsamp;
     const int hs = DSV_FORMAT_H_SHIFT(fmt), vs = DSV_FORMAT_V_SHIFT(fmt);
-    const size_t cw = (size_t) ((m.width + (1 << hs) - 1) >> hs);
-    const int ch = (m.height + (1 << vs) - 1) >> vs;
-    const bool semi = layout == DSV2HIP_SURFACE_SEMIPLANAR;
-    row_bytes[0] = (size_t) m.width, rows[0] = m.height;
+    const size_t cw = (size_t) ((width + (1 << hs) - 1) >> hs);
+    const int ch = (height + (1 << vs) - 1) >> vs;
+    const bool semi = plain == DSV2HIP_SURFACE_SEMIPLANAR;
+    row_bytes[0] = (size_t) width, rows[0] = height;
     row_bytes[1] = semi ? 2 * cw : cw, rows[1] = ch;
     row_bytes[2] = semi ? 0 : cw, rows[2] = semi ? 0 : ch;
     return true;
@@ -993,8 +1084,9 @@ int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const ds
             return -1;
         }
         DecJob &jb = jobs[(size_t) k];
-        jb.semi = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR;
-        jb.rgb = is_rgb_layout(sf.layout) ? sf.layout : 0;
+        jb.scale = layout_shift(sf.layout);
+        jb.semi = layout_unscaled(sf.layout) == DSV2HIP_SURFACE_SEMIPLANAR;
+        jb.rgb = is_rgb_layout(sf.layout) ? layout_unscaled(sf.layout) : 0;
         for (int c = 0; c < (jb.rgb ? 1 : jb.semi ? 2 : 3); c++) {
             // (the kernels carry a pitch as an int: one beyond INT_MAX is refused)
             if (!sf.plane[c] || sf.pitch[c] < rb[c] || sf.pitch[c] > (size_t) INT32_MAX || sf.cap[c] < (size_t) (rows[c] - 1) * sf.pitch[c] + rb[c]) {
@@ -1024,6 +1116,18 @@ void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset)
         }
         if (reset) {
             g_rgb_rounds[i].store(0);
+        }
+    }
+}
+
+void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset)
+{
+    for (int i = 0; i < 2; i++) {
+        if (out2) {
+            out2[i] = g_scale_rounds[i].load();
+        }
+        if (reset) {
+            g_scale_rounds[i].store(0);
         }
     }
 }

@@ -237,6 +237,22 @@ struct RgbOutJob { // one decoded picture on its way into a packed four-byte RGB
     int bgra;                    // the surface's byte order: non-zero B G R A, zero R G B A
 };
 inline bool rgb_out_job_wide(const RgbOutJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && (j.w & 3) == 0; }
+struct ScaleOutJob { // one plane of a decoded picture on its way out at half, quarter or eighth size (dsv2hip_out_surface, DSV2HIP_SCALE_*): the box
+                     // average of include/dsv2_hip.h (egress_scale.h, bmc.hip: k_egress_scale) into a plane of the caller's surface, or into the
+                     // decoder's staging picture that k_egress_uv / k_egress_rgb then read; 40 bytes, fetched by value through the scalar cache
+    const uint8_t *src; // pixel (0,0) of the source plane: 16-byte aligned origin and stride, rows readable up to the next multiple of 16 bytes
+                        // (dframe_alloc's border; the decoder's staged luma: its stride)
+    uint8_t *dst;       // device memory, any alignment: row y at dst + y * dpitch, ceil(pw / n) bytes of it written, ceil(ph / n) rows
+    int sstride;
+    int pw, ph;         // of the source plane
+    int dpitch;
+    int shift;          // 1, 2, 3: n = 1 << shift
+};
+// row_room: bytes of a destination row that may be written (a caller's surface: the reduced width; the staging picture: its stride)
+inline bool scale_job_wide(const ScaleOutJob &j, int row_room)
+{
+    return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 7) == 0 && row_room % (16 >> j.shift) == 0;
+}
 void to420_batch(hipStream_t s, const To420Job *d_jobs, int n, int max_w, int max_h);
 void ingest_uyvy_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int h); // src = interleaved UYVY rows
 void planes_to_host_batch(hipStream_t s, const PlaneOutJob *d_jobs, int n, int h);

@@ -564,18 +564,62 @@ int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size
  * draw_info and postsharp act on the luma the conversion reads, as they act on the luma plane of every other delivery.
  * dsv2hip_dec_rgb_stats: out2[0] / out2[1] = device rounds of this process whose RGB egress ran in the wide form (every RGB surface
  * of the round: pointer and pitch multiples of 16, w of 4) / in the general form so far; rounds without an RGB picture count as
- * neither.  reset != 0 clears the counts afterwards.  dsv2hip_dec_surface_stats keeps counting the chroma interleaves only. */
+ * neither.  reset != 0 clears the counts afterwards.  dsv2hip_dec_surface_stats keeps counting the chroma interleaves only.
+ *
+ * HALF, QUARTER AND EIGHTH-SIZE DELIVERY -- thumbnails, scrub strips, proxy renditions (decode 1080p, encode 540p and 270p from the
+ * same step: dsv2hip_enc_batch_surface reads such surfaces in place), model input: the picture arrives at the consumer's size, without
+ * a full-size write and read in between.  The scale belongs to the SURFACE: at most one of DSV2HIP_SCALE_HALF / _QUARTER / _EIGHTH
+ * or-ed into the layout of an out surface, chosen per call and per picture; s = (layout >> 12) & 3 is the shift, n = 1 << s.  A
+ * valid out-surface layout is any layout valid above (PLANAR, SEMIPLANAR, BGRA / RGBA with CSC bits) or-ed with at most one of the
+ * three values; every other bit stays no layout (0x4000, 0x1012 ...).  ONE EXCEPTION: the value 0x1010 -- BGRA with the default
+ * matrix and range at half size -- was documented and tested as "no layout" before the scale values existed, and stays refused by
+ * all three calls; half-size BGRA is available with every other preset (0x1110, 0x1210, 0x1310), half-size BT.601 limited-range
+ * pixels as RGBA (0x1011), and quarter and eighth size (0x2010, 0x3010) are not affected.  The scale goes through dsv2hip_dec_batch_surface,
+ * dsv2hip_dec_surface_frame and dsv2hip_dec_surface_dims; dsv_dec, dsv2hip_dec_batch, dsv2hip_dec_batch_device,
+ * dsv2hip_dec_device_frame and dsv2hip_dec_picture_bytes know nothing of it, and the encoder's surface calls refuse such a layout.
+ * Everything said of out surfaces above holds, applied to the reduced sizes: any pointer alignment, any pitch from the row's bytes
+ * up to INT_MAX, cap[c] >= (rows[c] - 1) * pitch[c] + row_bytes[c], only bytes inside the rows written, surf[k] copied, layouts and
+ * scales mixed freely within one step and one round (full-size NV12 beside quarter-size BGRA beside half-size planar), a refused
+ * call touches nothing.
+ * SIZES.  Each plane is reduced on its own: a plane of pw x ph becomes ow = (pw + n - 1) >> s by oh = (ph + n - 1) >> s.  Nested
+ * round-ups commute, so the reduced picture has exactly dsv_mk_frame's plane sizes for W' = ceil(w / n), H' = ceil(h / n) in the
+ * stream's format (chroma cw' x ch' by the format's shifts, rounded up) and can be handed to an encoder of that geometry.
+ * dsv2hip_dec_surface_dims reports them: PLANAR {W', cw', cw'} by {H', ch', ch'}; SEMIPLANAR {W', 2 * cw', 0} by {H', ch', 0}; RGB
+ * {4 * W', 0, 0} by {H', 0, 0}.
+ * THE REDUCTION (the contract), for every plane P of the full-size picture:
+ *
+ *   out(x, y) = ( SUM j<n, i<n  P(min(x*n + i, pw-1), min(y*n + j, ph-1))  +  (1 << (2*s - 1)) ) >> (2*s)
+ *
+ * A box average with ONE rounding over the whole footprint (not an iterated pairwise one); a footprint that crosses the plane's right
+ * or bottom edge repeats the edge pixel -- the footprint rule of the encoder's RGB ingest above.  The sum is at most 64 * 255 =
+ * 16 320.  For s = 1 on a plane of even size this is the reference's dsv_ds2x_frame_luma (frame.c:211).
+ * The delivered picture is this function of the picture that the same decoder, under the same draw_info and postsharp settings,
+ * delivers through a full-size PLANAR surface: the overlay and the sharpening act on the full-size luma BEFORE the reduction (a
+ * thumbnail of a drawn-on picture is the drawn-on picture reduced).  SEMIPLANAR: the interleave of the reduced U and V planes.  RGB:
+ * THE CONVERSION above applied to the reduced planes -- pixel (x, y) of the reduced picture takes reduced chroma sample (x >> hs,
+ * y >> vs).  The picture later P pictures predict from is never touched.  Arbitrary ratios and other filters are out of scope.
+ * Refused in addition -- as a whole, with -1, for a decoder that has metadata: a scaled layout on a decoder with
+ * dsv2hip_dec_set_out420p on (reducing behind the 4:2:0 conversion is out of scope, as RGB behind it is);
+ * dsv2hip_dec_surface_dims returns -1 for that pair too.
+ * dsv2hip_dec_scale_stats: out2[0] / out2[1] = device rounds of this process whose reduction ran in the wide form (every reduced
+ * plane that goes straight into a caller's surface -- PLANAR: all three, SEMIPLANAR: luma -- has a pointer and a pitch that are
+ * multiples of 8 and a reduced width that is a multiple of 16 >> s, i.e. of 8, 4, 2) / in the general form so far; rounds without a
+ * scaled picture count as neither.  reset != 0 clears the counts afterwards.  The two other counters keep their meaning: a scaled
+ * semiplanar or RGB picture's interleave / conversion counts there as any other. */
+enum { DSV2HIP_SCALE_HALF = 0x1000, DSV2HIP_SCALE_QUARTER = 0x2000, DSV2HIP_SCALE_EIGHTH = 0x3000 }; /* or-ed into the layout of an OUT surface */
 typedef struct dsv2hip_out_surface {
     void *plane[3];  /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first); plane[2] ignored.  BGRA / RGBA: the picture */
     size_t pitch[3]; /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR, pitch[1..2] for BGRA / RGBA */
     size_t cap[3];   /* bytes the caller owns from plane[c] on; cap[2] ignored for SEMIPLANAR, cap[1..2] for BGRA / RGBA */
-    int layout;      /* DSV2HIP_SURFACE_PLANAR / _SEMIPLANAR, or DSV2HIP_SURFACE_BGRA / _RGBA or-ed with DSV2HIP_CSC_* bits */
+    int layout;      /* DSV2HIP_SURFACE_PLANAR / _SEMIPLANAR, or DSV2HIP_SURFACE_BGRA / _RGBA or-ed with DSV2HIP_CSC_* bits; any of them or-ed
+                        with at most one DSV2HIP_SCALE_* value */
 } dsv2hip_out_surface;
 int dsv2hip_dec_surface_dims(DSV_DECODER *dec, int layout, size_t row_bytes[3], int rows[3]);
 int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, DSV_FNUM *fn, int *ret);
 int dsv2hip_dec_surface_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_surface *surf, DSV_FNUM *fn);
 void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset);
 void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset);
+void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset);
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the

@@ -4,8 +4,8 @@
 The packets are produced on the fly with the GPU encoder (bit-identical to the reference's); every decoded
 picture is delivered to host memory as a DSV_FRAME exactly like dsv_dec does (that D2H copy is part of the
 timed region) -- or, with --device-out, through dsv2hip_dec_batch_device into one preallocated device buffer
-per decoder, or, with --surface-out planar / nv12, through dsv2hip_dec_batch_surface into one preallocated pitched surface per
-decoder, so that the deliveries can be compared."""
+per decoder, or, with --surface-out planar / nv12 / bgra, through dsv2hip_dec_batch_surface into one preallocated pitched surface per
+decoder -- with --scale 2 / 4 / 8 at half, quarter or eighth size (DSV2HIP_SCALE_*) --, so that the deliveries can be compared."""
 import argparse
 import ctypes as C
 import json
@@ -30,11 +30,13 @@ def main():
     ap.add_argument("--draw-info", type=int, default=0, help="DSV_DECODER.draw_info of every decoder (0: no overlay)")
     ap.add_argument("--device-out", action="store_true", help="deliver the pictures to device memory (dsv2hip_dec_batch_device)")
     ap.add_argument("--postsharp", action="store_true", help="dsv2hip_dec_set_postsharp on every decoder")
-    ap.add_argument("--surface-out", choices=["planar", "nv12"], help="deliver the pictures into pitched device surfaces (dsv2hip_dec_batch_surface)")
+    ap.add_argument("--surface-out", choices=["planar", "nv12", "bgra"], help="deliver the pictures into pitched device surfaces (dsv2hip_dec_batch_surface)")
+    ap.add_argument("--scale", type=int, choices=[1, 2, 4, 8], default=1, help="with --surface-out: deliver at 1 / scale of the size (DSV2HIP_SCALE_HALF / _QUARTER / _EIGHTH)")
     ap.add_argument("--pitch-align", type=int, default=256, help="with --surface-out: every row pitch is the row's bytes rounded up to a multiple of this")
     args = ap.parse_args()
     assert not (args.device_out and args.surface_out), "--device-out and --surface-out are two deliveries"
     assert args.pitch_align >= 1
+    assert args.scale == 1 or args.surface_out, "--scale belongs to a surface"
     import dsvabi as A
     from codec_run import decode_stream, encode_stream
     from conftest import load_pkg
@@ -82,7 +84,8 @@ def main():
     surf_out = None
     if args.surface_out:
         # one surface per decoder: every plane a tensor of its own, rows `pitch` apart
-        semi = args.surface_out == "nv12"
+        # (bgra: DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709 -- the BT.601 limited-range value at half size, 0x1010, is no layout)
+        layout = {"planar": 0, "nv12": 1, "bgra": 0x110}[args.surface_out] | ({1: 0, 2: 1, 4: 2, 8: 3}[args.scale] << 12)
         # the planes' sizes from the library: a probe decoder reads the stream's metadata packet, dsv2hip_dec_surface_dims answers
         hip.dsv2hip_dec_surface_dims.argtypes = [C.POINTER(A.DECODER), C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         hip.dsv2hip_dec_surface_dims.restype = C.c_int
@@ -91,14 +94,14 @@ def main():
         C.memmove(pbuf.data, vids[0][0], len(vids[0][0]))
         assert hip.dsv_dec(C.byref(probe), C.byref(pbuf), C.byref(C.POINTER(A.FRAME)()), C.byref(pfn)) == A.DEC_GOT_META
         rb, nrows = (C.c_size_t * 3)(), (C.c_int * 3)()
-        assert hip.dsv2hip_dec_surface_dims(C.byref(probe), 1 if semi else 0, rb, nrows) == 0
+        assert hip.dsv2hip_dec_surface_dims(C.byref(probe), layout, rb, nrows) == 0
         hip.dsv_dec_free(C.byref(probe))
         rows = [(rb[i], nrows[i]) for i in range(3) if nrows[i]]
-        assert sum(b * r for b, r in rows) == pic_bytes
+        assert sum(b * r for b, r in rows) == pic_bytes or args.scale > 1 or args.surface_out == "bgra"
         surf_out, keep = [], []
         for _ in range(S):
             c = OUTSURF()
-            c.layout = 1 if semi else 0
+            c.layout = layout
             for i, (rb, nr) in enumerate(rows):
                 pitch = (rb + args.pitch_align - 1) // args.pitch_align * args.pitch_align
                 t = torch.empty(pitch * nr, dtype=torch.uint8, device="cuda")
@@ -182,8 +185,8 @@ def main():
     delivery = "device" if args.device_out else "host"
     where = delivery + " memory"
     if args.surface_out:
-        delivery = "surface-" + args.surface_out
-        where = "%s device surfaces, pitch a multiple of %d" % (args.surface_out, args.pitch_align)
+        delivery = "surface-" + args.surface_out + ("" if args.scale == 1 else "-1/%d" % args.scale)
+        where = "%s device surfaces%s, pitch a multiple of %d" % (args.surface_out, "" if args.scale == 1 else " at 1/%d of the size" % args.scale, args.pitch_align)
     result = {"metric": "decoded frames/s, 1080p 4:2:0 qp=60 gop=48 (pictures identical to the reference decoder's)", "value": round(fps, 2),
               "unit": "frames/s", "n_gpus": 1, "steps": npk - first, "ms_per_step": round(1e3 * elapsed / max(1, npk - first), 3),
               "higher_is_better": True, "dtype": "u8/int32", "data": "synthetic",
