@@ -1,0 +1,235 @@
+// dec_delivery.h -- which kernels a decoded picture leaves through, reading and writing what: planned per picture, free of any device
+// call and of any allocation.  decoder.cpp plans every picture of a round with it before it sizes and fills the round's job
+// tables; tools/dec_delivery_check.cpp compiles it for the host under AddressSanitizer + UndefinedBehaviorSanitizer and sweeps
+// target kind x scale x out420p x postsharp x draw_info x alignment over synthetic addresses (tests/test_dec_delivery_cpu.py).
+#pragma once
+
+#include <stddef.h>
+
+#include "dev.h"
+
+namespace dsv2 {
+namespace delivery {
+
+// ---- the layout word of a dsv2hip_out_surface -------------------------------------------------------------------------------------------
+// the shift of a layout: 0, or 1 .. 3 for DSV2HIP_SCALE_HALF / _QUARTER / _EIGHTH; the layout without it
+constexpr int kScaleMask = DSV2HIP_SCALE_EIGHTH; // (the three values are 1, 2, 3 << 12)
+inline int layout_shift(int layout) { return (layout & kScaleMask) >> 12; }
+inline int layout_unscaled(int layout) { return layout & ~kScaleMask; }
+
+// an RGB layout: BGRA / RGBA or-ed with any subset of the DSV2HIP_CSC_* bits (the bits on PLANAR / SEMIPLANAR are no layout) and at
+// most one DSV2HIP_SCALE_* value.  One value is held back: 0x1010, which reads as BGRA | BT601 | limited range | HALF, was refused as
+// "no layout" before the scale values existed, callers and the RGB surface tests probe with it and rely on the refusal, and it stays
+// refused (include/dsv2_hip.h): half-size BGRA takes any other preset (0x1110, 0x1210, 0x1310), or RGBA (0x1011).
+inline bool is_rgb_layout(int layout)
+{
+    if (layout == (DSV2HIP_SURFACE_BGRA | DSV2HIP_SCALE_HALF)) {
+        return false;
+    }
+    const int order = layout_unscaled(layout) & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE);
+    return order == DSV2HIP_SURFACE_BGRA || order == DSV2HIP_SURFACE_RGBA;
+}
+
+// ---- where a picture goes ---------------------------------------------------------------------------------------------------------------
+struct OutTarget {
+    enum Kind {
+        FRAME,  // a bordered frame on pinned memory the device writes directly: plane[] / pitch[] are its planes, frame_alloc its block
+        PLANAR, // the caller's device planes Y, U, V (a packed buffer: pitch {w, cw, cw})
+        SEMI,   // ... Y and one plane of interleaved U V rows (plane[2] unused)
+        RGB     // ... one plane of four-byte pixels, plane[0], converted on the way out (plane[1..2] unused)
+    } kind = FRAME;
+    uint8_t *plane[3] = {nullptr, nullptr, nullptr};
+    int pitch[3] = {0, 0, 0};
+    int fw[3] = {0, 0, 0}, fh[3] = {0, 0, 0}; // FRAME: the planes' sizes (a device target's follow from the picture's and the shift)
+    void *frame_alloc = nullptr;
+    int shift = 0;  // device targets: every plane at 1 / 2^shift of its size, box-averaged on the way out (egress_scale.h); 0 .. 3
+    int csc = 0;    // RGB: the layout's DSV2HIP_CSC_* bits
+    bool bgra = false; // RGB: bytes in memory B G R A, else R G B A
+    bool device() const { return kind != FRAME; }
+};
+
+inline OutTarget target_frame(const DSV_FRAME *f)
+{
+    OutTarget t;
+    t.frame_alloc = f->alloc;
+    for (int c = 0; c < 3; c++) {
+        t.plane[c] = f->planes[c].data, t.pitch[c] = f->planes[c].stride;
+        t.fw[c] = f->planes[c].w, t.fh[c] = f->planes[c].h;
+    }
+    return t;
+}
+
+// A caller's surface, whose layout dsv2hip_dec_surface_dims accepted with these rows: false for a plane that is missing, whose pitch is
+// below its row bytes or beyond an int (the kernels carry a pitch as an int) or whose capacity does not hold the rows.
+inline bool target_surface(const dsv2hip_out_surface &sf, const size_t row_bytes[3], const int rows[3], OutTarget *out)
+{
+    OutTarget t;
+    const int plain = layout_unscaled(sf.layout);
+    t.shift = layout_shift(sf.layout);
+    t.kind = is_rgb_layout(sf.layout) ? OutTarget::RGB : plain == DSV2HIP_SURFACE_SEMIPLANAR ? OutTarget::SEMI : OutTarget::PLANAR;
+    if (t.kind == OutTarget::RGB) {
+        t.csc = plain & (DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE);
+        t.bgra = (plain & 0xff) == DSV2HIP_SURFACE_BGRA;
+    }
+    for (int c = 0; c < (t.kind == OutTarget::RGB ? 1 : t.kind == OutTarget::SEMI ? 2 : 3); c++) {
+        if (!sf.plane[c] || sf.pitch[c] < row_bytes[c] || sf.pitch[c] > (size_t) INT32_MAX ||
+            sf.cap[c] < (size_t) (rows[c] - 1) * sf.pitch[c] + row_bytes[c]) {
+            return false;
+        }
+        t.plane[c] = (uint8_t *) sf.plane[c];
+        t.pitch[c] = (int) sf.pitch[c];
+    }
+    *out = t;
+    return true;
+}
+
+// the packed buffer of dsv2hip_dec_batch_device: the planar surface with pitch {w, cw, cw}, plane behind plane
+inline OutTarget target_packed(void *buf, const size_t row_bytes[3], const int rows[3])
+{
+    OutTarget t;
+    t.kind = OutTarget::PLANAR;
+    uint8_t *at = (uint8_t *) buf;
+    for (int c = 0; c < 3; c++) {
+        t.plane[c] = at;
+        t.pitch[c] = (int) row_bytes[c];
+        at += row_bytes[c] * (size_t) rows[c];
+    }
+    return t;
+}
+
+// the YUV -> RGB conversion of include/dsv2_hip.h for a layout's DSV2HIP_CSC_* bits: ky, ybase, rv, gu, gv, bu
+inline void rgb_out_coefs(RgbOutJob &j, int csc)
+{
+    static const int preset[4][6] = {{298, 16, 409, -100, -208, 516},  // BT601 (limited)
+                                     {298, 16, 459, -55, -136, 541},   // BT709 (limited)
+                                     {256, 0, 359, -88, -183, 454},    // BT601 | FULL
+                                     {256, 0, 403, -48, -120, 475}};   // BT709 | FULL
+    const int *p = preset[((csc & DSV2HIP_CSC_FULL_RANGE) ? 2 : 0) + ((csc & DSV2HIP_CSC_BT709) ? 1 : 0)];
+    j.ky = p[0], j.ybase = p[1], j.rv = p[2], j.gu = p[3], j.gv = p[4], j.bu = p[5];
+}
+
+// ---- what one picture contributes to a round --------------------------------------------------------------------------------------------
+// The jobs by launch class, in the order the round launches the classes: whole-frame copy, 4:2:0 conversion, egress, overlay, sharpening
+// in place, reduction, chroma interleave, RGB conversion.  A job of a later class may read what a job of an earlier one wrote -- the
+// decoder's two staging areas -- and nothing else is shared between them.
+struct DeliveryPlan {
+    CopyJob copy[1];
+    To420Job to420[3];
+    EgressJob eg[3];
+    ScaleOutJob scl[3];
+    UvEgressJob uv[1];
+    RgbOutJob rgb[1];
+    DPlane overlay[1]; // the luma plane the draw_info overlay goes onto: the delivered one, or the staged one
+    int n_copy = 0, n_to420 = 0, n_eg = 0, n_scl = 0, n_uv = 0, n_rgb = 0, n_overlay = 0;
+    bool sharpen_overlaid = false; // that plane is also sharpened in place, behind the overlay (a drawn-on picture under postsharp)
+    // what the round needs to pick its kernels' forms
+    bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
+    bool scl_wide = true;                  // every reduction job allows the unconditional vector store (bmc.hip: k_egress_scale)
+    int scl_rows = 0;                      // the most rows a reduction job delivers
+    bool uv_wide = true, uv_conv = false;  // the interleave job allows the 16-byte form / converts to 4:2:0 (bmc.hip: k_egress_uv)
+    int uv_rows = 0;                       // the chroma rows it delivers ("4:1:0" to 4:2:0: more than the source has)
+    bool rgb_wide = true;                  // the RGB job allows the 16-byte form (bmc.hip: k_egress_rgb)
+};
+
+// A sharpened and / or drawn-on picture that leaves reduced or as RGB has no delivered full-size luma plane for the overlay and the
+// sharpening to act on: its luma goes through the egress kernel into DecImpl's staged luma plane (w x h, 16-byte aligned origin and stride)
+inline bool needs_staged_luma(const OutTarget &t, bool sharp, int draw)
+{
+    return t.device() && (t.shift || t.kind == OutTarget::RGB) && (sharp || draw);
+}
+// the reduced planes that k_egress_uv / k_egress_rgb then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
+inline bool needs_staged_scaled(const OutTarget &t) { return t.device() && t.shift && t.kind != OutTarget::PLANAR; }
+
+// recon: the picture as decoded (read only; its format is the stream's); out_format: the delivered picture's, the stream's or 4:2:0 under
+// out420p; staged_luma / staged_scaled: the staging areas' planes, looked at only where the predicates above hold
+inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const OutTarget &t, bool sharp, int draw, const DPlane &staged_luma,
+                                  const DPlane *staged_scaled)
+{
+    DeliveryPlan p{};
+    const int hs = DSV_FORMAT_H_SHIFT(recon.format), vs = DSV_FORMAT_V_SHIFT(recon.format);
+    const bool conv = out_format != recon.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
+    const bool sharp_out = sharp && !draw;        // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
+    // the planes of the delivered picture: those of the pinned frame, or the caller's device planes (semiplanar: op[1] is the interleaved
+    // plane, w (U, V) pairs a row; op[2] is not a plane)
+    DPlane op[3];
+    if (t.device()) {
+        const int ohs = DSV_FORMAT_H_SHIFT(out_format), ovs = DSV_FORMAT_V_SHIFT(out_format);
+        const int ocw = (recon.w + (1 << ohs) - 1) >> ohs, och = (recon.h + (1 << ovs) - 1) >> ovs; // dsv_mk_frame's plane sizes (frame.c:63-113)
+        const bool semi = t.kind == OutTarget::SEMI;
+        op[0] = DPlane{t.plane[0], t.pitch[0], recon.w, recon.h};
+        op[1] = DPlane{t.plane[1], t.pitch[1], ocw, och};
+        op[2] = DPlane{semi ? nullptr : t.plane[2], semi ? 0 : t.pitch[2], ocw, och};
+    } else {
+        for (int c = 0; c < 3; c++) {
+            op[c] = DPlane{t.plane[c], t.pitch[c], t.fw[c], t.fh[c]};
+        }
+    }
+    auto egress = [&](const DPlane &src, const DPlane &dst, bool sharpen) {
+        const EgressJob &j = p.eg[p.n_eg++] = EgressJob{src, dst.data, dst.stride, sharpen};
+        p.eg_sharp = p.eg_sharp || sharpen;
+        p.eg_wide = p.eg_wide && egress_job_wide(j, dst.w);
+    };
+    if (t.device() && (t.shift || t.kind == OutTarget::RGB)) {
+        // Every plane is read in place by the reduction (egress_scale.h) and / or the RGB conversion.  A sharpened and / or drawn-on
+        // picture: its full-size luma is staged first, stands in for the delivered luma plane below (overlay, sharpening behind the
+        // overlay) and is what the reduction or the conversion then reads.  (No 4:2:0 conversion here: the surface call refuses the pair.)
+        DPlane src[3] = {recon.p[0], recon.p[1], recon.p[2]};
+        if (needs_staged_luma(t, sharp, draw)) {
+            src[0] = op[0] = staged_luma;
+            egress(recon.p[0], staged_luma, sharp_out);
+        }
+        if (t.shift) {
+            // PLANAR, and the luma of SEMIPLANAR, straight into the caller's planes; what the interleave or the conversion has yet to read,
+            // into the staged scaled picture, from which the unchanged k_egress_uv (mode 0) / k_egress_rgb run on the reduced geometry
+            const int s = t.shift, up = (1 << s) - 1;
+            for (int c = 0; c < 3; c++) {
+                const bool staged = t.kind == OutTarget::RGB || (t.kind == OutTarget::SEMI && c);
+                DPlane red = staged ? staged_scaled[c] : DPlane{t.plane[c], t.pitch[c], 0, 0};
+                red.w = (src[c].w + up) >> s, red.h = (src[c].h + up) >> s;
+                const ScaleOutJob &sj = p.scl[p.n_scl++] = ScaleOutJob{src[c].data, red.data, src[c].stride, src[c].w, src[c].h, red.stride, s};
+                p.scl_wide = p.scl_wide && scale_job_wide(sj, staged ? red.stride : red.w);
+                p.scl_rows = red.h > p.scl_rows ? red.h : p.scl_rows;
+                src[c] = red;
+            }
+        }
+        if (t.kind == OutTarget::SEMI) {
+            const UvEgressJob &uj = p.uv[p.n_uv++] =
+                UvEgressJob{src[1].data, src[2].data, t.plane[1], t.pitch[1], src[1].stride, src[1].w, src[1].h, src[1].w, src[1].h, 0};
+            p.uv_wide = uv_job_wide(uj);
+            p.uv_rows = src[1].h;
+        } else if (t.kind == OutTarget::RGB) {
+            RgbOutJob &rj = p.rgb[p.n_rgb++] = RgbOutJob{src[0].data, src[1].data, src[2].data, t.plane[0], src[0].stride, src[1].stride, t.pitch[0],
+                                                         src[0].w, src[0].h, hs, vs, 0, 0, 0, 0, 0, 0, t.bgra};
+            rgb_out_coefs(rj, t.csc);
+            p.rgb_wide = rgb_out_job_wide(rj);
+        }
+    } else if (!conv && !t.device() && !sharp_out) {
+        p.copy[p.n_copy++] = CopyJob{recon.alloc, t.frame_alloc, recon.bytes};
+    } else {
+        const int mode = (hs == 0 && vs == 0) ? 1 : (hs == 1 && vs == 0) ? 2 : (hs == 2 && vs == 0) ? 3 : 4;
+        for (int c = 0; c < 3; c++) {
+            if (c && t.kind == OutTarget::SEMI) { // both chroma planes through one job, converted on the way or not
+                if (c == 1) {
+                    const DPlane &su = recon.p[1];
+                    const UvEgressJob &uj = p.uv[p.n_uv++] =
+                        UvEgressJob{su.data, recon.p[2].data, op[1].data, op[1].stride, su.stride, su.w, su.h, op[1].w, op[1].h, conv ? mode : 0};
+                    p.uv_wide = uv_job_wide(uj);
+                    p.uv_conv = conv;
+                    p.uv_rows = op[1].h;
+                }
+            } else if (conv && (c || (!t.device() && !sharp_out))) {
+                p.to420[p.n_to420++] = To420Job{recon.p[c], op[c], c ? mode : 0};
+            } else {
+                egress(recon.p[c], op[c], c == 0 && sharp_out);
+            }
+        }
+    }
+    if (draw) { // on the picture the caller receives only: the reconstruction, which the next P picture reads, stays as decoded (dsv_decoder.c:555-561)
+        p.overlay[p.n_overlay++] = op[0];
+        p.sharpen_overlaid = sharp;
+    }
+    return p;
+}
+
+} // namespace delivery
+} // namespace dsv2

@@ -16,12 +16,14 @@
 
 #include "batch.h"
 #include "codec.h"
+#include "dec_delivery.h"
 #include "dec_parse.h"
 #include "dec_parse_dev.h"
 #include "overlay.h"
 
 using namespace dsv2;
 using namespace dsv2::decparse;
+using namespace dsv2::delivery;
 
 namespace {
 
@@ -109,15 +111,8 @@ struct DecJob {
     bool dev_parse = false;          // the plane sections' symbols are parsed on the device (dec_parse_dev.hip) from body.head
     int cap[3] = {0, 0, 0};          // ... into lists of this many entries (min(header count, coefficients of the plane))
     size_t pkt_off = 0;              // ... out of the packet as staged at this offset of the round's stage block
-    DSV_FRAME *of = nullptr; // output picture: a bordered frame on pinned memory the device writes directly
-    bool to_dev = false;     // ... or (dsv2hip_dec_batch_device / _surface) no frame at all: the picture goes to the caller's device planes
-    uint8_t *dst[3] = {nullptr, nullptr, nullptr}; // ... these: Y, U, V (a packed buffer: the planar surface with pitch {w, cw, cw}), or
-    int dpitch[3] = {0, 0, 0};
-    bool semi = false;       // ... Y and one plane of interleaved U V rows (dst[2] unused), or
-    int rgb = 0;             // ... (non-zero: the surface's layout, DSV2HIP_SURFACE_BGRA / _RGBA with its DSV2HIP_CSC_* bits) one plane of
-                             // four-byte pixels, dst[0], converted on the way out (dst[1..2] unused)
-    int scale = 0;           // ... (non-zero: the surface's DSV2HIP_SCALE_* shift, 1 .. 3) every plane at 1 / 2^scale of its size, box-averaged on
-                             // the way out (egress_scale.h)
+    DSV_FRAME *of = nullptr; // output picture: a bordered frame on pinned memory the device writes directly (made in phase A), or none
+    OutTarget target;        // ... where the picture goes: that frame, or (dsv2hip_dec_batch_device / _surface) the caller's device planes
     int out_format = 0;      // format of the delivered picture: the stream's, or 4:2:0 under out420p
     bool sharp = false;      // the decoder's postsharp switch when the packet was handed in
     int draw = 0;            // the decoder's draw_info when the packet was handed in: non-zero = overlay on the luma of `of` (overlay.hip)
@@ -321,8 +316,9 @@ void dec_parse(DecJob &jb)
     }
     jb.out_format = im->out420p ? DSV_SUBSAMP_420 : meta->subsamp;
     jb.sharp = im->postsharp;
-    if (!jb.to_dev) {
+    if (jb.out) {
         jb.of = mk_frame_pinned(jb.out_format, meta->width, meta->height);
+        jb.target = target_frame(jb.of);
     }
     jb.pic = true;
 }
@@ -330,6 +326,95 @@ void dec_parse(DecJob &jb)
 // ---- one device round: phases B and C for the pictures of one geometry, as functions over one Round ----
 struct Slice { // a run of the sorted order with one (frame type, lossless) class: one set of dequantiser / transform launches
     int first, count, isP, lossless, max_seg[3][4];
+};
+
+// The way out of a round's pictures: the jobs of their plans (dec_delivery.h), one table per launch class -- a class that no picture of
+// the round uses has no table and no launch -- and what picks each launch's form.
+struct Delivery {
+    Tab<CopyJob> copy;
+    Tab<To420Job> to420;
+    Tab<EgressJob> eg;
+    Tab<OverlayJob> ov;
+    Tab<ScaleOutJob> scl;
+    Tab<UvEgressJob> uv;
+    Tab<RgbOutJob> rgb;
+    size_t room[7] = {0, 0, 0, 0, 0, 0, 0}; // entries the round's plans need of each table, in the order above
+    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_uv = 0, n_rgb = 0;
+    bool eg_wide = true, eg_sharp = false, scl_wide = true, uv_wide = true, uv_conv = false, rgb_wide = true; // DeliveryPlan's, over the round
+    int scl_rows = 0, uv_rows = 0;
+    bool ov_vectors = false;         // some overlay job draws motion vectors
+    std::vector<DPlane> sharp_drawn; // luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
+    size_t count(const std::vector<DeliveryPlan> &plans) // the arena bytes the tables of these plans take
+    {
+        for (const DeliveryPlan &p : plans) {
+            const int n[7] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_uv, p.n_rgb};
+            for (int k = 0; k < 7; k++) {
+                room[k] += (size_t) n[k];
+            }
+        }
+        return room[0] * sizeof(CopyJob) + room[1] * sizeof(To420Job) + room[2] * sizeof(EgressJob) + room[3] * sizeof(OverlayJob) +
+               room[4] * sizeof(ScaleOutJob) + room[5] * sizeof(UvEgressJob) + room[6] * sizeof(RgbOutJob) + 7 * 16;
+    }
+    void take(TableArena &tabs)
+    {
+        copy = Tab<CopyJob>(tabs, room[0]);
+        to420 = Tab<To420Job>(tabs, room[1]);
+        eg = Tab<EgressJob>(tabs, room[2]);
+        ov = Tab<OverlayJob>(tabs, room[3]);
+        scl = Tab<ScaleOutJob>(tabs, room[4]);
+        uv = Tab<UvEgressJob>(tabs, room[5]);
+        rgb = Tab<RgbOutJob>(tabs, room[6]);
+    }
+    template <class T> static void append(Tab<T> &t, int &n, const T *jobs, int count)
+    {
+        std::copy_n(jobs, count, t.h + n);
+        n += count;
+    }
+    // oj: the picture's overlay job but for its plane
+    void add(const DeliveryPlan &p, OverlayJob oj)
+    {
+        append(copy, n_copy, p.copy, p.n_copy);
+        append(to420, n_to420, p.to420, p.n_to420);
+        append(eg, n_eg, p.eg, p.n_eg);
+        append(scl, n_scl, p.scl, p.n_scl);
+        append(uv, n_uv, p.uv, p.n_uv);
+        append(rgb, n_rgb, p.rgb, p.n_rgb);
+        eg_wide = eg_wide && p.eg_wide, eg_sharp = eg_sharp || p.eg_sharp;
+        scl_wide = scl_wide && p.scl_wide, scl_rows = std::max(scl_rows, p.scl_rows);
+        uv_wide = uv_wide && p.uv_wide, uv_conv = uv_conv || p.uv_conv, uv_rows = std::max(uv_rows, p.uv_rows);
+        rgb_wide = rgb_wide && p.rgb_wide;
+        if (p.n_overlay) {
+            oj.dst = p.overlay[0];
+            ov.h[n_ov++] = oj;
+            ov_vectors = ov_vectors || (oj.isP && (oj.mode & DSV_DRAW_MOVECS));
+            if (p.sharpen_overlaid) {
+                sharp_drawn.push_back(oj.dst);
+            }
+        }
+    }
+    // h: the pictures' height; bytes: their reconstructions'
+    void enqueue(hipStream_t bs, int w, int h, int nbh, int nbv, size_t bytes) const
+    {
+        copy_linear_batch(bs, copy.d, n_copy, bytes);
+        to420_batch(bs, to420.d, n_to420, w, h);
+        egress_batch(bs, eg.d, n_eg, h, eg_wide, eg_sharp);
+        overlay_batch(bs, ov.d, n_ov, h, nbh, nbv, ov_vectors);
+        for (const DPlane &pl : sharp_drawn) { // (a debugging combination: one launch a picture)
+            post_process_plane(bs, pl);
+        }
+        if (n_scl) { // behind the overlay and the sharpening of the luma planes staged for it, in front of the two kernels that read what it stages
+            egress_scale_batch(bs, scl.d, n_scl, scl_rows, scl_wide);
+            g_scale_rounds[scl_wide ? 0 : 1]++;
+        }
+        if (n_uv) { // (chroma only: the overlay and the sharpening are none of its business, the reduction of a scaled picture's chroma is)
+            egress_uv_batch(bs, uv.d, n_uv, uv_rows, uv_wide, uv_conv);
+            g_uv_rounds[uv_wide ? 0 : 1]++;
+        }
+        if (n_rgb) { // last: behind the overlay and the sharpening of the luma planes staged for it
+            egress_rgb_batch(bs, rgb.d, n_rgb, h, rgb_wide);
+            g_rgb_rounds[rgb_wide ? 0 : 1]++;
+        }
+    }
 };
 
 struct Round { // what outlives a phase (the decoder's counterpart of the encoder's Step)
@@ -359,51 +444,25 @@ struct Round { // what outlives a phase (the decoder's counterpart of the encode
     Tab<DPlane> ext[3];
     int nP = 0, nI = 0, nIf = 0, n_ext = 0;
     bool any_filter = false;
-    // delivery.  ov / eg / uv / rgb: only in a round with pictures that are drawn on / leave through the egress kernel (device delivery,
-    // postsharp) / leave with interleaved chroma, into a semiplanar surface / leave as four-byte RGB pixels (none: no table, no launch)
-    Tab<CopyJob> out;
-    Tab<To420Job> to420;
-    Tab<OverlayJob> ov;
-    Tab<EgressJob> eg;
-    Tab<UvEgressJob> uv;
-    Tab<RgbOutJob> rgb;
-    Tab<ScaleOutJob> scl; // planes that leave at half, quarter or eighth size (into a caller's plane, or staged for uv / rgb)
-    int n_out = 0, n_to420 = 0, n_ov = 0, n_eg = 0, n_uv = 0, n_rgb = 0, n_scl = 0;
-    int scl_rows = 0;                     // the most rows a reduction job delivers
-    bool scl_wide = true;                 // every reduction job allows the unconditional vector store (bmc.hip: k_egress_scale)
-    int uv_rows = 0;                      // the most chroma rows an interleave job delivers ("4:1:0" to 4:2:0: more than the source has)
-    bool uv_wide = true, uv_conv = false; // every interleave job allows the 16-byte form / some job converts to 4:2:0 (bmc.hip: k_egress_uv)
-    bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
-    bool rgb_wide = true;                  // every RGB job allows the 16-byte form (bmc.hip: k_egress_rgb)
-    bool ov_vectors = false;               // some overlay job draws motion vectors
-    std::vector<DPlane> sharp_drawn; // delivered luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
+    std::vector<DeliveryPlan> plans; // plans[slot]: the way out of the picture in that slot of `order` (dec_delivery.h)
+    Delivery out;
     Round(DecJob *jobs_, const std::vector<int> &ids_) : jobs(jobs_), ids(ids_), n((int) ids_.size()), dv0(jobs_[ids_[0]].im->dev), order(ids_) {}
     const DSV_MV *d_mvs(const DecJob &jb) const { return (const DSV_MV *) (sc.d_stage + jb.stage_off); } // as staged for the kernels
     const uint8_t *d_bd(const DecJob &jb) const { return sc.d_stage + jb.stage_off + mv_bytes; }
 };
 
-// The arena holds every table of the round.  Per picture: the tables below; the 65536 cover the three conditional tables' alignment.
-static_assert(13 * sizeof(CopyJob) + 3 * (sizeof(DequantJob) + sizeof(PlaneJob) + sizeof(McJob) + sizeof(PlanePair) + sizeof(DPlane) +
-                                          sizeof(To420Job) + sizeof(DecParseJob) + sizeof(int)) + 22 * 16 <= 8192,
-              "a picture's share of the round's 22 job tables outgrew the 8192 bytes reserved for it");
+// The arena holds every table of the round: the fixed tables, of which a picture has the entries below (8192 bytes reserved for them;
+// the 65536 cover the tables' alignment), and on top the delivery tables, sized by the round's plans.  (Taking beyond what was reserved
+// is fatal: TableArena::take.)
+constexpr size_t kFixedEntryBytes = 3 * (3 * sizeof(CopyJob) /* zero, zfail, zcond */ + sizeof(DequantJob) + sizeof(PlaneJob) + sizeof(PlanePair) +
+                                         sizeof(DPlane) + sizeof(McJob) /* mc_pred, mc_filt, mc_intra: one each */ + sizeof(DecParseJob) + sizeof(int));
+static_assert(kFixedEntryBytes <= 8192, "a picture's entries in the round's fixed job tables outgrew the 8192 bytes reserved for them");
 void round_take_tables(Round &r)
 {
-    int n_draw = 0, n_egress = 0, n_semi = 0, n_rgb = 0, n_scaled = 0;
-    for (int k : r.ids) {
-        const DecJob &jb = r.jobs[k];
-        n_draw += jb.draw != 0;
-        n_egress += jb.to_dev || jb.sharp;
-        n_semi += jb.to_dev && jb.semi;
-        n_rgb += jb.to_dev && jb.rgb;
-        n_scaled += jb.to_dev && jb.scale;
-    }
     TableArena &tabs = r.sc.tabs;
     const size_t n = (size_t) r.n;
-    tabs.reserve(n * 8192 + 65536 + (size_t) n_draw * sizeof(OverlayJob) + 3 * (size_t) n_egress * sizeof(EgressJob) +
-                 (size_t) n_semi * sizeof(UvEgressJob) + (size_t) n_rgb * sizeof(RgbOutJob) +
-                 3 * (size_t) n_scaled * sizeof(ScaleOutJob));
+    tabs.reserve(n * 8192 + 65536 + r.out.count(r.plans));
     r.zero = Tab<CopyJob>(tabs, 3 * n);
-    r.out = Tab<CopyJob>(tabs, n);
     for (int c = 0; c < 3; c++) {
         r.dq[c] = Tab<DequantJob>(tabs, n);
         r.pj[c] = Tab<PlaneJob>(tabs, n);
@@ -414,15 +473,10 @@ void round_take_tables(Round &r)
     r.mc_filt = Tab<McJob>(tabs, n);
     r.mc_intra = Tab<McJob>(tabs, n);
     r.zfail = Tab<CopyJob>(tabs, 3 * n);
-    r.to420 = Tab<To420Job>(tabs, 3 * n);
     r.parse = Tab<DecParseJob>(tabs, 3 * n);
     r.zcond = Tab<CopyJob>(tabs, 3 * n);
     r.fail = Tab<int>(tabs, 3 * n);
-    r.ov = Tab<OverlayJob>(tabs, (size_t) n_draw);
-    r.eg = Tab<EgressJob>(tabs, 3 * (size_t) n_egress);
-    r.uv = Tab<UvEgressJob>(tabs, (size_t) n_semi);
-    r.rgb = Tab<RgbOutJob>(tabs, (size_t) n_rgb);
-    r.scl = Tab<ScaleOutJob>(tabs, 3 * (size_t) n_scaled);
+    r.out.take(tabs);
 }
 
 size_t staged_len(const DSV_BUF *b) { return ((size_t) b->len + 64 + 15) & ~(size_t) 15; } // a packet as staged: 16-byte aligned, 64 zero bytes behind it
@@ -573,122 +627,17 @@ void fill_recon_jobs(Round &r, DecJob &jb)
     }
 }
 
-// the YUV -> RGB conversion of include/dsv2_hip.h for a layout's DSV2HIP_CSC_* bits: ky, ybase, rv, gu, gv, bu
-void rgb_out_coefs(RgbOutJob &j, int layout)
+// every picture's way out, planned (dec_delivery.h) before the tables are sized; the staging areas a plan needs are made here
+void round_plan(Round &r)
 {
-    static const int preset[4][6] = {{298, 16, 409, -100, -208, 516},  // BT601 (limited)
-                                     {298, 16, 459, -55, -136, 541},   // BT709 (limited)
-                                     {256, 0, 359, -88, -183, 454},    // BT601 | FULL
-                                     {256, 0, 403, -48, -120, 475}};   // BT709 | FULL
-    const int *p = preset[((layout & DSV2HIP_CSC_FULL_RANGE) ? 2 : 0) + ((layout & DSV2HIP_CSC_BT709) ? 1 : 0)];
-    j.ky = p[0], j.ybase = p[1], j.rv = p[2], j.gu = p[3], j.gv = p[4], j.bu = p[5];
-}
-
-// the picture's way out: whole-frame copy, or per plane 4:2:0 conversion / egress / chroma interleave / RGB conversion; the overlay behind it
-void fill_delivery_jobs(Round &r, DecJob &jb)
-{
-    CodecDev &dv = jb.im->dev;
-    DFrame &recon = dv.pics[jb.im->cur].recon;
-    // the planes of the delivered picture: those of the pinned frame, or the caller's device planes (semiplanar: op[1] is the
-    // interleaved plane, w (U, V) pairs a row; op[2] is not a plane)
-    DPlane op[3];
-    if (jb.to_dev) {
-        const int ohs = DSV_FORMAT_H_SHIFT(jb.out_format), ovs = DSV_FORMAT_V_SHIFT(jb.out_format);
-        const int ocw = (dv.w + (1 << ohs) - 1) >> ohs, och = (dv.h + (1 << ovs) - 1) >> ovs; // dsv_mk_frame's plane sizes (frame.c:63-113)
-        op[0] = DPlane{jb.dst[0], jb.dpitch[0], dv.w, dv.h};
-        op[1] = DPlane{jb.dst[1], jb.dpitch[1], ocw, och};
-        op[2] = DPlane{jb.semi ? nullptr : jb.dst[2], jb.semi ? 0 : jb.dpitch[2], ocw, och};
-    } else {
-        for (int c = 0; c < 3; c++) {
-            const DSV_PLANE &fp = jb.of->planes[c];
-            op[c] = DPlane{fp.data, fp.stride, fp.w, fp.h};
-        }
-    }
-    const bool conv = jb.out_format != dv.format; // converted on the way out (dsv_main.c:1030-1048): chroma through the reference's pair averages
-    const bool sharp_out = jb.sharp && !jb.draw;  // luma sharpened in registers on its way out (a drawn one: in place, behind the overlay)
-    if (jb.to_dev && jb.scale) {
-        // Every plane through the reduction (egress_scale.h), reading the reconstruction in place: PLANAR, and the luma of SEMIPLANAR,
-        // straight into the caller's planes; what the interleave or the conversion has yet to read, into the decoder's staging picture,
-        // from which the unchanged k_egress_uv (mode 0) / k_egress_rgb run on the reduced geometry.  A sharpened and / or drawn-on
-        // picture: its full-size luma is staged first, exactly as in the RGB branch below, and the reduction reads from there --
-        // round_enqueue launches it behind the overlay and the sharpening.  (No 4:2:0 conversion here: the surface call refuses the pair.)
-        const int s = jb.scale, up = (1 << s) - 1;
-        DPlane src[3] = {recon.p[0], recon.p[1], recon.p[2]};
-        if (jb.sharp || jb.draw) {
-            src[0] = op[0] = jb.im->staged_luma();
-            r.eg.h[r.n_eg++] = EgressJob{recon.p[0], src[0].data, src[0].stride, sharp_out};
-            r.eg_sharp = r.eg_sharp || sharp_out;
-            r.eg_wide = r.eg_wide && src[0].w % 16 == 0;
-        }
-        const DPlane *st = (jb.semi || jb.rgb) ? jb.im->staged_scaled() : nullptr;
-        DPlane red[3]; // the reduced planes, where they go
-        for (int c = 0; c < 3; c++) {
-            const bool staged = jb.rgb || (jb.semi && c);
-            red[c] = staged ? DPlane{st[c].data, st[c].stride, 0, 0} : DPlane{jb.dst[c], jb.dpitch[c], 0, 0};
-            red[c].w = (src[c].w + up) >> s, red[c].h = (src[c].h + up) >> s;
-            ScaleOutJob &sj = r.scl.h[r.n_scl++];
-            sj = ScaleOutJob{src[c].data, red[c].data, src[c].stride, src[c].w, src[c].h, red[c].stride, s};
-            r.scl_wide = r.scl_wide && scale_job_wide(sj, staged ? red[c].stride : red[c].w);
-            r.scl_rows = std::max(r.scl_rows, red[c].h);
-        }
-        if (jb.semi) {
-            UvEgressJob &uj = r.uv.h[r.n_uv++];
-            uj = UvEgressJob{red[1].data, red[2].data, jb.dst[1], jb.dpitch[1], red[1].stride, red[1].w, red[1].h, red[1].w, red[1].h, 0};
-            r.uv_wide = r.uv_wide && uv_job_wide(uj);
-            r.uv_rows = std::max(r.uv_rows, red[1].h);
-        } else if (jb.rgb) {
-            RgbOutJob &rj = r.rgb.h[r.n_rgb++];
-            rj = RgbOutJob{red[0].data, red[1].data, red[2].data, jb.dst[0], red[0].stride, red[1].stride, jb.dpitch[0], red[0].w, red[0].h,
-                           DSV_FORMAT_H_SHIFT(dv.format), DSV_FORMAT_V_SHIFT(dv.format), 0, 0, 0, 0, 0, 0, (jb.rgb & 0xff) == DSV2HIP_SURFACE_BGRA};
-            rgb_out_coefs(rj, jb.rgb);
-            r.rgb_wide = r.rgb_wide && rgb_out_job_wide(rj);
-        }
-    } else if (jb.to_dev && jb.rgb) {
-        // One job, reading the reconstruction in place.  A sharpened and / or drawn-on picture: its luma goes through the egress
-        // kernel into the decoder's staging plane first, which stands in for the delivered luma plane below (overlay, sharpening
-        // behind the overlay) and is what the conversion then reads; round_enqueue launches the conversion last.
-        DPlane ly = recon.p[0];
-        if (jb.sharp || jb.draw) {
-            ly = op[0] = jb.im->staged_luma();
-            r.eg.h[r.n_eg++] = EgressJob{recon.p[0], ly.data, ly.stride, sharp_out};
-            r.eg_sharp = r.eg_sharp || sharp_out;
-            r.eg_wide = r.eg_wide && ly.w % 16 == 0;
-        }
-        RgbOutJob &rj = r.rgb.h[r.n_rgb++];
-        rj = RgbOutJob{ly.data, recon.p[1].data, recon.p[2].data, jb.dst[0], ly.stride, recon.p[1].stride, jb.dpitch[0], dv.w, dv.h,
-                       DSV_FORMAT_H_SHIFT(dv.format), DSV_FORMAT_V_SHIFT(dv.format), 0, 0, 0, 0, 0, 0, (jb.rgb & 0xff) == DSV2HIP_SURFACE_BGRA};
-        rgb_out_coefs(rj, jb.rgb);
-        r.rgb_wide = r.rgb_wide && rgb_out_job_wide(rj);
-    } else if (!conv && !jb.to_dev && !sharp_out) {
-        r.out.h[r.n_out++] = CopyJob{recon.alloc, jb.of->alloc, recon.bytes};
-    } else {
-        const int hs = DSV_FORMAT_H_SHIFT(dv.format), vs = DSV_FORMAT_V_SHIFT(dv.format);
-        const int mode = (hs == 0 && vs == 0) ? 1 : (hs == 1 && vs == 0) ? 2 : (hs == 2 && vs == 0) ? 3 : 4;
-        for (int c = 0; c < 3; c++) {
-            if (c && jb.to_dev && jb.semi) { // both chroma planes through one job, converted on the way or not
-                if (c == 1) {
-                    const DPlane &su = recon.p[1];
-                    UvEgressJob &uj = r.uv.h[r.n_uv++];
-                    uj = UvEgressJob{su.data, recon.p[2].data, op[1].data, op[1].stride, su.stride, su.w, su.h, op[1].w, op[1].h, conv ? mode : 0};
-                    r.uv_wide = r.uv_wide && uv_job_wide(uj);
-                    r.uv_conv = r.uv_conv || conv;
-                    r.uv_rows = std::max(r.uv_rows, op[1].h);
-                }
-            } else if (conv && (c || (!jb.to_dev && !sharp_out))) {
-                r.to420.h[r.n_to420++] = To420Job{recon.p[c], op[c], c ? mode : 0};
-            } else {
-                r.eg.h[r.n_eg++] = EgressJob{recon.p[c], op[c].data, op[c].stride, c == 0 && sharp_out};
-                r.eg_sharp = r.eg_sharp || (c == 0 && sharp_out);
-                r.eg_wide = r.eg_wide && op[c].w % 16 == 0 && ((((uintptr_t) op[c].data) | (uintptr_t) op[c].stride) & 15) == 0;
-            }
-        }
-    }
-    if (jb.draw) { // drawn on the frame the caller receives only: cur.recon, which the next P picture reads, stays as decoded (dsv_decoder.c:555-561)
-        r.ov.h[r.n_ov++] = OverlayJob{op[0], r.d_mvs(jb), r.d_bd(jb), dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref};
-        r.ov_vectors = r.ov_vectors || (jb.has_ref && (jb.draw & DSV_DRAW_MOVECS));
-        if (jb.sharp) {
-            r.sharp_drawn.push_back(op[0]);
-        }
+    r.plans.reserve((size_t) r.n);
+    for (int k : r.order) {
+        const DecJob &jb = r.jobs[k];
+        DecImpl &im = *jb.im;
+        static const DPlane none = {nullptr, 0, 0, 0};
+        const DPlane &luma = needs_staged_luma(jb.target, jb.sharp, jb.draw) ? im.staged_luma() : none;
+        const DPlane *scaled = needs_staged_scaled(jb.target) ? im.staged_scaled() : nullptr;
+        r.plans.push_back(plan_delivery(im.dev.pics[im.cur].recon, jb.out_format, jb.target, jb.sharp, jb.draw, luma, scaled));
     }
 }
 
@@ -740,25 +689,7 @@ void round_enqueue(Round &r)
         copy_planes_batch(bs, r.icopy[c].d, r.nI, pl.w, pl.h);
         extend_planes(bs, r.ext[c].d, r.n_ext, pl.w, pl.h);
     }
-    copy_linear_batch(bs, r.out.d, r.n_out, dv0.pics[0].recon.bytes);
-    to420_batch(bs, r.to420.d, r.n_to420, dv0.w, dv0.h);
-    egress_batch(bs, r.eg.d, r.n_eg, dv0.h, r.eg_wide, r.eg_sharp);
-    overlay_batch(bs, r.ov.d, r.n_ov, dv0.h, dv0.nbh, dv0.nbv, r.ov_vectors);
-    for (const DPlane &pl : r.sharp_drawn) { // (a debugging combination: one launch a picture)
-        post_process_plane(bs, pl);
-    }
-    if (r.n_scl) { // behind the overlay and the sharpening of the luma planes staged for it, in front of the two kernels that read what it stages
-        egress_scale_batch(bs, r.scl.d, r.n_scl, r.scl_rows, r.scl_wide);
-        g_scale_rounds[r.scl_wide ? 0 : 1]++;
-    }
-    if (r.n_uv) { // (chroma only: the overlay and the sharpening are none of its business, the reduction of a scaled picture's chroma is)
-        egress_uv_batch(bs, r.uv.d, r.n_uv, r.uv_rows, r.uv_wide, r.uv_conv);
-        g_uv_rounds[r.uv_wide ? 0 : 1]++;
-    }
-    if (r.n_rgb) { // last: behind the overlay and the sharpening of the luma planes staged for it
-        egress_rgb_batch(bs, r.rgb.d, r.n_rgb, dv0.h, r.rgb_wide);
-        g_rgb_rounds[r.rgb_wide ? 0 : 1]++;
-    }
+    r.out.enqueue(bs, dv0.w, dv0.h, dv0.nbh, dv0.nbv, dv0.pics[0].recon.bytes);
     prof.end(bs, ST_EXTEND, r.n);
     t_dec_clock.lap(2);
 }
@@ -775,7 +706,7 @@ void round_finish(Round &r)
             jb.im->cur ^= 1;
             jb.im->have_ref = true;
         }
-        if (!jb.to_dev) {
+        if (jb.of) {
             *jb.out = jb.of;
         }
         jb.ret = DSV_DEC_OK;
@@ -785,15 +716,17 @@ void round_finish(Round &r)
 void dec_device_round(DecJob *jobs, const std::vector<int> &ids)
 {
     Round r(jobs, ids);
+    round_sort(r);
+    round_plan(r);
     round_take_tables(r);
     round_stage(r);
-    round_sort(r);
     for (Slice &sl : r.slices) {
         for (int i = sl.first; i < sl.first + sl.count; i++) {
             DecJob &jb = jobs[r.order[(size_t) i]];
             fill_coef_jobs(r, sl, i, jb);
             fill_recon_jobs(r, jb);
-            fill_delivery_jobs(r, jb);
+            const CodecDev &dv = jb.im->dev;
+            r.out.add(r.plans[(size_t) i], OverlayJob{{}, r.d_mvs(jb), r.d_bd(jb), dv.nbh, dv.nbv, dv.blk_w, dv.blk_h, jb.draw, jb.has_ref});
         }
     }
     round_enqueue(r);
@@ -832,24 +765,6 @@ void dec_batch(DecJob *jobs, int n)
 }
 
 Coalescer<DecJob> g_dec_queue; // dsv_dec callers share lockstep steps (batch.h)
-
-// the shift of an out surface's layout: 0, or 1 .. 3 for DSV2HIP_SCALE_HALF / _QUARTER / _EIGHTH; the layout without it
-constexpr int kScaleMask = DSV2HIP_SCALE_EIGHTH; // (the three values are 1, 2, 3 << 12)
-int layout_shift(int layout) { return (layout & kScaleMask) >> 12; }
-int layout_unscaled(int layout) { return layout & ~kScaleMask; }
-
-// an RGB layout: BGRA / RGBA or-ed with any subset of the DSV2HIP_CSC_* bits (the bits on PLANAR / SEMIPLANAR are no layout) and at
-// most one DSV2HIP_SCALE_* value.  One value is held back: 0x1010, which reads as BGRA | BT601 | limited range | HALF, was refused as
-// "no layout" before the scale values existed, callers and the RGB surface tests probe with it and rely on the refusal, and it stays
-// refused (include/dsv2_hip.h): half-size BGRA takes any other preset (0x1110, 0x1210, 0x1310), or RGBA (0x1011).
-bool is_rgb_layout(int layout)
-{
-    if (layout == (DSV2HIP_SURFACE_BGRA | DSV2HIP_SCALE_HALF)) {
-        return false;
-    }
-    const int order = layout_unscaled(layout) & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE);
-    return order == DSV2HIP_SURFACE_BGRA || order == DSV2HIP_SURFACE_RGBA;
-}
 
 // Plane sizes of the picture as this decoder delivers it (dsv_mk_frame's, frame.c:63-113, in the stream's format or 4:2:0 under
 // out420p), as the rows of a surface of `layout`: false before the metadata or for a value that is no layout.  An RGB layout is one
@@ -894,7 +809,6 @@ int dec_batch_run(std::vector<DecJob> &jobs, DSV_DECODER **decs, DSV_BUF *bufs, 
         jb.buf = &bufs[n];
         jb.out = out ? &out[n] : nullptr;
         jb.fn = &fn[n];
-        jb.to_dev = !out;
         if (out) {
             out[n] = NULL;
         }
@@ -905,6 +819,18 @@ int dec_batch_run(std::vector<DecJob> &jobs, DSV_DECODER **decs, DSV_BUF *bufs, 
         ret[k] = jobs[(size_t) k].ret;
     }
     return n;
+}
+
+void read_rounds(std::atomic<unsigned long long> (&rounds)[2], unsigned long long *out2, int reset) // the dsv2hip_dec_*_stats readers
+{
+    for (int i = 0; i < 2; i++) {
+        if (out2) {
+            out2[i] = rounds[i].load();
+        }
+        if (reset) {
+            rounds[i].store(0);
+        }
+    }
 }
 
 int set_switch(DSV_DECODER *d, bool DecImpl::*sw, int on) // (a switch may be set before the first packet made the DecImpl)
@@ -1029,17 +955,11 @@ int dsv2hip_dec_batch_device(int n, DSV_DECODER **decs, DSV_BUF *bufs, void *con
         }
     }
     std::vector<DecJob> jobs((size_t) n);
-    for (int k = 0; k < n; k++) { // the packed picture is the planar surface with pitch {w, cw, cw}
+    for (int k = 0; k < n; k++) {
         size_t rb[3];
         int rows[3];
         if (surface_dims(decs[k], DSV2HIP_SURFACE_PLANAR, rb, rows)) {
-            DecJob &jb = jobs[(size_t) k];
-            uint8_t *at = (uint8_t *) dev_out[k];
-            for (int c = 0; c < 3; c++) {
-                jb.dst[c] = at;
-                jb.dpitch[c] = (int) rb[c];
-                at += rb[c] * (size_t) rows[c];
-            }
+            jobs[(size_t) k].target = target_packed(dev_out[k], rb, rows);
         }
     }
     return dec_batch_run(jobs, decs, bufs, nullptr, fn, ret);
@@ -1083,17 +1003,8 @@ int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const ds
         if (!surface_dims(decs[k], sf.layout, rb, rows)) {
             return -1;
         }
-        DecJob &jb = jobs[(size_t) k];
-        jb.scale = layout_shift(sf.layout);
-        jb.semi = layout_unscaled(sf.layout) == DSV2HIP_SURFACE_SEMIPLANAR;
-        jb.rgb = is_rgb_layout(sf.layout) ? layout_unscaled(sf.layout) : 0;
-        for (int c = 0; c < (jb.rgb ? 1 : jb.semi ? 2 : 3); c++) {
-            // (the kernels carry a pitch as an int: one beyond INT_MAX is refused)
-            if (!sf.plane[c] || sf.pitch[c] < rb[c] || sf.pitch[c] > (size_t) INT32_MAX || sf.cap[c] < (size_t) (rows[c] - 1) * sf.pitch[c] + rb[c]) {
-                return -1;
-            }
-            jb.dst[c] = (uint8_t *) sf.plane[c];
-            jb.dpitch[c] = (int) sf.pitch[c];
+        if (!target_surface(sf, rb, rows, &jobs[(size_t) k].target)) {
+            return -1;
         }
     }
     return dec_batch_run(jobs, decs, bufs, nullptr, fn, ret);
@@ -1108,40 +1019,8 @@ int dsv2hip_dec_surface_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_su
     return ret;
 }
 
-void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset)
-{
-    for (int i = 0; i < 2; i++) {
-        if (out2) {
-            out2[i] = g_rgb_rounds[i].load();
-        }
-        if (reset) {
-            g_rgb_rounds[i].store(0);
-        }
-    }
-}
-
-void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset)
-{
-    for (int i = 0; i < 2; i++) {
-        if (out2) {
-            out2[i] = g_scale_rounds[i].load();
-        }
-        if (reset) {
-            g_scale_rounds[i].store(0);
-        }
-    }
-}
-
-void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset)
-{
-    for (int i = 0; i < 2; i++) {
-        if (out2) {
-            out2[i] = g_uv_rounds[i].load();
-        }
-        if (reset) {
-            g_uv_rounds[i].store(0);
-        }
-    }
-}
+void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds, out2, reset); }
+void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset) { read_rounds(g_scale_rounds, out2, reset); }
+void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset) { read_rounds(g_uv_rounds, out2, reset); }
 
 } // extern "C"

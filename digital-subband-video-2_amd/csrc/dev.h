@@ -213,6 +213,8 @@ struct EgressJob { // one plane of a decoded picture on its way into the picture
     int dstride;
     int sharp;    // luma under -postsharp: dsv_post_process (bmc.c:340) applied in registers on the way
 };
+// w: the plane's width (the decoder's staged luma, 16-byte aligned origin and stride: w % 16 == 0 decides)
+inline bool egress_job_wide(const EgressJob &j, int w) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dstride) & 15) == 0 && w % 16 == 0; }
 struct UvEgressJob { // both chroma planes of a decoded picture on their way into ONE interleaved plane of a caller's surface (dsv2hip_out_surface,
                      // SEMIPLANAR: rows U0 V0 U1 V1 ...), converted to 4:2:0 on the way or not (bmc.hip: k_egress_uv); 56 bytes, fetched by
                      // value through the scalar cache like EgressJob.  The two source planes of a frame share their geometry.

@@ -500,3 +500,73 @@ def test_transcode_through_surfaces_without_the_host():
     assert code == A.DEC_EOS and [f for f, _ in one] == [r[1] for r in refpics[0]]
     for (_, a), b in zip(one, pics[0]):
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+# ---- 9. every way out side by side -------------------------------------------------------------------------------------------
+def frame_decode(hip, streams, modes, sharp):
+    """dsv2hip_dec_batch over one decoder per stream into pinned frames, draw_info and postsharp per decoder: per stream
+    [(return code, frame number or None, [Y, U, V] or None)] per packet"""
+    from test_gpu_dec_batch import bind as bind_batch, planes_of
+    bind_batch(bind(hip))
+    n = len(streams)
+    decs = [A.DECODER() for _ in range(n)]
+    for d, mode, s in zip(decs, modes, sharp):
+        d.draw_info = mode
+        assert hip.dsv2hip_dec_set_postsharp(C.byref(d), int(s)) == 0
+    decp = (C.POINTER(A.DECODER) * n)(*[C.pointer(d) for d in decs])
+    res = [[] for _ in range(n)]
+    for t in range(len(streams[0])):
+        bufs, outs, fns, rets = (A.BUF * n)(), (C.POINTER(A.FRAME) * n)(), (C.c_uint32 * n)(), (C.c_int * n)()
+        for k in range(n):
+            mk_buf(hip, bufs[k], streams[k][t])
+        assert hip.dsv2hip_dec_batch(n, decp, bufs, outs, fns, rets) == n
+        for k in range(n):
+            planes = None
+            if rets[k] == A.DEC_OK and outs[k]:
+                planes = planes_of(outs[k])
+                hip.dsv_frame_ref_dec(outs[k])
+            res[k].append((rets[k], fns[k] if planes is not None else None, planes))
+    for d in decs:
+        hip.dsv_dec_free(C.byref(d))
+    return res
+
+
+def test_every_delivery_in_one_round():
+    """Ten decoders of one geometry (66x34 4:2:0) on the same I P P stream, one lockstep step per picture, each with another way out:
+    pinned frames (plain, sharpened, drawn on and sharpened), the packed device buffer, a planar surface at an odd pitch and address,
+    NV12, half-size NV12 drawn on and sharpened, BGRA BT.709, sharpened quarter-size RGBA, eighth-size planar.  Every decoder
+    delivers, byte for byte -- the helpers check the guard bytes around every plane after every step --, what a decoder with its
+    settings delivers alone, which the tests above and those of the other ways out pin to the reference.  The ABI has one entry
+    point per kind of destination, so a step is three calls: the three pinned frames share a round, the six surfaces share one,
+    and the packed buffer has its own.  This guards the packing of several pictures' jobs into one round's tables."""
+    from test_gpu_dec_device_out import device_decode
+    from test_gpu_dec_rgb import aligned, plus1, tight
+    from test_gpu_dec_scale import BGRA709, EIGHTH, HALF, QUARTER, decode_steps
+    import yuv_rgb as Q
+    hip = bind(A.load_hip())
+    packets = stream(66, 34, "420", 3, 48, seed=71)
+    assert [pk[5] & 1 for pk in packets if pk[5] & 0x04] == [0, 1, 1]  # (dsv.h: packet type at byte 5, picture = 0x04, bit 0 = predicted)
+    frames = [(0, False), (0, True), (7, True)]  # (draw_info, postsharp)
+    surfaces = [(dict(layout=PLANAR, pitch=plus1, offset=1), 0, False),
+                (dict(layout=SEMI, pitch=aligned, offset=0), 0, False),
+                (dict(layout=SEMI | HALF, pitch=tight, offset=0), 7, True),
+                (dict(layout=BGRA709, pitch=aligned, offset=0), 0, False),
+                (dict(layout=Q.RGBA | QUARTER, pitch=tight, offset=0), 0, True),
+                (dict(layout=PLANAR | EIGHTH, pitch=tight, offset=0), 0, False)]
+
+    def steps(fr, packed, sf):
+        """the three calls of a step sequence over the chosen decoders of each kind"""
+        return (frame_decode(hip, [packets] * len(fr), [m for m, _ in fr], [s for _, s in fr]) if fr else [],
+                device_decode(hip, [packets]) if packed else [],
+                decode_steps(hip, [packets] * len(sf), [spec for spec, _, _ in sf], modes=[m for _, m, _ in sf], sharp=[s for _, _, s in sf]) if sf else [])
+
+    got_frames, got_packed, got_surfaces = steps(frames, True, surfaces)
+    assert all(npics(r) == 3 for r in got_frames + got_packed + got_surfaces)
+    for k, f in enumerate(frames):
+        same_results(steps([f], False, [])[0][0], got_frames[k])
+    same_results(steps([], True, [])[1][0], got_packed[0])
+    for k, s in enumerate(surfaces):
+        alone = steps([], False, [s])[2][0]
+        same_results(alone, got_surfaces[k], planes=range(len(alone[1][2])))
+    # (the settings take effect: the drawn-on, sharpened pictures differ from the plain ones)
+    assert not np.array_equal(got_frames[0][1][2][0], got_frames[1][1][2][0]) and not np.array_equal(got_frames[1][1][2][0], got_frames[2][1][2][0])
