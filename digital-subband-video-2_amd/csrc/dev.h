@@ -274,6 +274,38 @@ inline bool surface_job_wide(const SurfaceJob &j)
 // n RGB surfaces of h rows; wide: every job's source pointer and pitch are multiples of 16 and w of 4 (rgb_job_wide)
 void ingest_rgb_batch(hipStream_t s, const RgbJob *d_jobs, int n, int h, bool wide);
 inline bool rgb_job_wide(const RgbJob &j) { return ((((uintptr_t) j.src) | j.pitch) & 15) == 0 && (j.w & 3) == 0; }
+// Half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled): the records of k_ingest_surface_scaled and
+// k_ingest_rgb_scaled (frame.hip, ingest_scale.h), in tables of their own behind the two above.
+struct ScaledSurfaceJob { // one SOURCE plane of a caller's surface, box-averaged (the decoder's REDUCTION, include/dsv2_hip.h) on its way into a
+                          // bordered source plane of the reduced geometry; 56 bytes, fetched by value through the scalar cache
+    const uint8_t *src; // device memory, any alignment: row y at src + y * pitch
+    size_t pitch;
+    uint8_t *dst, *dst2; // plane(s) from dframe_alloc; dst2 != null: the source rows are U0 V0 U1 V1 ..., reduced U goes to dst, V to dst2
+    int dstride;         // of dst and dst2
+    int pw, ph;          // samples per row and rows of the SOURCE plane (with dst2: U V pairs per row, the row holds 2 * pw bytes)
+    int shift;           // 1, 2, 3: n = 1 << shift; the destination holds ceil(pw / n) x ceil(ph / n)
+};
+struct ScaledRgbJob { // one packed four-byte RGB surface, converted and reduced with one rounding per sample on its way into the three bordered
+                      // source planes of the reduced geometry; 96 bytes, fetched by value through the scalar cache
+    const uint8_t *src; // device memory, any alignment: row y at src + y * pitch, sw pixels of 4 bytes
+    size_t pitch;
+    uint8_t *dst[3];      // Y, U, V planes from dframe_alloc
+    int ystride, cstride; // of dst[0]; of dst[1] and dst[2]
+    int sw, sh;           // of the picture IN THE SURFACE; the encoder's is ceil(sw / n) x ceil(sh / n)
+    int hs, vs;           // the stream's chroma shifts
+    int shift;            // 1, 2, 3
+    uint32_t ycoef, upos, uneg, vpos, vneg; // RgbJob's quads
+    uint32_t yoff;                          // 128 + 256 * ybase
+};
+// n source planes, the widest source row max_row_bytes, the most reduced rows max_rows; wide: the predicate of surface_job_wide on the SOURCE
+void ingest_surface_scaled_batch(hipStream_t s, const ScaledSurfaceJob *d_jobs, int n, int max_row_bytes, int max_rows, bool wide);
+inline bool scaled_surface_job_wide(const ScaledSurfaceJob &j)
+{
+    return ((((uintptr_t) j.src) | j.pitch | (size_t) (j.dst2 ? 2 * j.pw : j.pw)) & 15) == 0;
+}
+// n RGB surfaces, the widest max_sw pixels, the most chroma rows of the reduced picture max_crows; wide: rgb_job_wide's predicate on the SOURCE
+void ingest_rgb_scaled_batch(hipStream_t s, const ScaledRgbJob *d_jobs, int n, int max_sw, int max_crows, bool wide);
+inline bool scaled_rgb_job_wide(const ScaledRgbJob &j) { return ((((uintptr_t) j.src) | j.pitch) & 15) == 0 && (j.sw & 3) == 0; }
 
 void ensure_device();
 void set_default_device(int ordinal);

@@ -25,6 +25,7 @@
 
 #include "batch.h"
 #include "codec.h"
+#include "ingest_scale.h"
 #include "sideinfo.h"
 
 using namespace dsv2;
@@ -838,6 +839,8 @@ struct Job {
     const uint8_t *dev_planar; // ... or packed planar picture already in HBM
     dsv2hip_surface surf;      // ... or (has_surf) a pitched planar / semi-planar surface in HBM, by value: the caller's array may go
     bool has_surf;
+    int src_w, src_h, src_shift; // has_surf through the scaled calls with a scale: the picture IN THE SURFACE is src_w x src_h and is reduced by
+                                 // 1 << src_shift on ingest (ingest_scale.h); surf.layout is then the layout without its scale value.  0: unscaled
     const uint8_t *host_planar; // ... or packed planar picture in host memory, uploaded by the batch engine (pinned: asynchronously)
     const uint8_t *host_next;   // the picture this stream will bring to the NEXT step: uploaded under this step's kernels
     bool from_frame;            // host_planar is a DSV_FRAME packed by dsv_enc: planar whatever the encoder's packed-input format
@@ -962,7 +965,10 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
     void ensure(int n)
     {
         // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture; behind them the three source planes of a
-        // stream that brings a surface, or the one record of a stream that brings an RGB surface)
+        // stream that brings a surface, or the one record of a stream that brings an RGB surface.  A stream brings ONE kind of
+        // picture, so the records of a scaled source lie in the same room: the arena is the size it always was)
+        static_assert(3 * sizeof(ScaledSurfaceJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob) && sizeof(ScaledRgbJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob),
+                      "a scaled source's records fit the room reserved for a stream's surface records");
         tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob) + sizeof(RgbJob)) + 65536);
         if (n <= cap) {
             return;
@@ -1520,12 +1526,13 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 static std::atomic<int> g_fail_next_step{0};
 static std::atomic<unsigned long long> g_surface_steps[2]; // steps whose surface ingest ran in the wide / the general form (dsv2hip_enc_surface_stats)
 static std::atomic<unsigned long long> g_rgb_steps[2];     // the same for the RGB ingest (dsv2hip_enc_rgb_stats)
+static std::atomic<unsigned long long> g_scale_steps[4];   // scaled YUV ingest wide / general, scaled RGB ingest wide / general (dsv2hip_enc_scale_stats)
 
 static bool surface_is_rgb(int layout) { return (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_RGBA; }
 
 // The conversion of include/dsv2_hip.h for an RGB surface of `layout` as k_ingest_rgb takes it: each row of the preset's matrix as
 // byte quads in the surface's channel order (alpha weighs 0), chroma rows split into positive parts and magnitudes of negative ones
-static void rgb_job_coefs(RgbJob &j, int layout)
+template <class RgbJobT> static void rgb_job_coefs(RgbJobT &j, int layout)
 {
     static const int presets[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},   // BT601 (limited)
                                       {47, 157, 16, -26, -86, 112, 112, -102, -10},  // BT709 (limited)
@@ -1747,10 +1754,13 @@ static void g1_enqueue(Step &st)
     Tab<PlaneOutJob> small(sc.tabs, (size_t) n);
     st.bsj = Tab<BlockStatsJob>(sc.tabs, (size_t) n);
     int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0, n_rgb = 0, n_rj = 0;
+    int n_ssurf = 0, n_ssj = 0, n_srgb = 0, n_srj = 0; // the scaled ones (Job::src_shift): tables, forms and launches of their own
     for (int k = 0; k < n; k++) {
-        const bool rgb = st.jobs[k].has_surf && surface_is_rgb(st.jobs[k].surf.layout);
-        n_rgb += rgb;
-        n_surf += st.jobs[k].has_surf && !rgb;
+        const bool rgb = st.jobs[k].has_surf && surface_is_rgb(st.jobs[k].surf.layout), scaled = st.jobs[k].has_surf && st.jobs[k].src_shift;
+        n_rgb += rgb && !scaled;
+        n_surf += st.jobs[k].has_surf && !rgb && !scaled;
+        n_srgb += rgb && scaled;
+        n_ssurf += !rgb && scaled;
     }
     Tab<SurfaceJob> sj; // only a step with surface jobs has this table (behind all the others: theirs lie where they always did)
     if (n_surf) {
@@ -1760,7 +1770,16 @@ static void g1_enqueue(Step &st)
     if (n_rgb) {
         rj = Tab<RgbJob>(sc.tabs, (size_t) n_rgb);
     }
-    bool surf_wide = true, rgb_wide = true;
+    Tab<ScaledSurfaceJob> ssj; // the scaled sources' tables: behind the existing ones, which lie where they always did
+    if (n_ssurf) {
+        ssj = Tab<ScaledSurfaceJob>(sc.tabs, 3 * (size_t) n_ssurf);
+    }
+    Tab<ScaledRgbJob> srj;
+    if (n_srgb) {
+        srj = Tab<ScaledRgbJob>(sc.tabs, (size_t) n_srgb);
+    }
+    bool surf_wide = true, rgb_wide = true, ssurf_wide = true, srgb_wide = true;
+    int ssurf_row_bytes = 0, srgb_sw = 0;
     for (int k = 0; k < n; k++) {
         Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
@@ -1770,6 +1789,29 @@ static void g1_enqueue(Step &st)
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
+        } else if (jb.has_surf && jb.src_shift && surface_is_rgb(jb.surf.layout)) {
+            const dsv2hip_surface &sf = jb.surf;
+            const DPlane *dp = cur.src.p;
+            ScaledRgbJob &j = srj.h[n_srj++];
+            j = ScaledRgbJob{(const uint8_t *) sf.plane[0], sf.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, jb.src_w, jb.src_h,
+                             DSV_FORMAT_H_SHIFT(cur.src.format), DSV_FORMAT_V_SHIFT(cur.src.format), jb.src_shift, 0, 0, 0, 0, 0, 0};
+            rgb_job_coefs(j, sf.layout);
+            srgb_wide = srgb_wide && scaled_rgb_job_wide(j);
+            srgb_sw = std::max(srgb_sw, jb.src_w);
+        } else if (jb.has_surf && jb.src_shift) {
+            const dsv2hip_surface &sf = jb.surf;
+            const int nsrc = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR ? 2 : 3;
+            const int hs = DSV_FORMAT_H_SHIFT(cur.src.format), vs = DSV_FORMAT_V_SHIFT(cur.src.format);
+            const int scw = (jb.src_w + (1 << hs) - 1) >> hs, sch = (jb.src_h + (1 << vs) - 1) >> vs; // dsv_mk_frame's, of the SOURCE
+            for (int c = 0; c < nsrc; c++) {
+                const DPlane &dp = cur.src.p[c];
+                const bool uv = nsrc == 2 && c == 1;
+                ScaledSurfaceJob &j = ssj.h[n_ssj++];
+                j = ScaledSurfaceJob{(const uint8_t *) sf.plane[c], sf.pitch[c], dp.data, uv ? cur.src.p[2].data : nullptr, dp.stride,
+                                     c ? scw : jb.src_w, c ? sch : jb.src_h, jb.src_shift};
+                ssurf_wide = ssurf_wide && scaled_surface_job_wide(j);
+                ssurf_row_bytes = std::max(ssurf_row_bytes, uv ? 2 * j.pw : j.pw);
+            }
         } else if (jb.has_surf && surface_is_rgb(jb.surf.layout)) {
             const dsv2hip_surface &sf = jb.surf;
             const DPlane *dp = cur.src.p;
@@ -1856,6 +1898,14 @@ static void g1_enqueue(Step &st)
     if (n_rj) {
         ingest_rgb_batch(bs, rj.d, n_rj, f0.p[0].h, rgb_wide);
         g_rgb_steps[rgb_wide ? 0 : 1]++;
+    }
+    if (n_ssj) {
+        ingest_surface_scaled_batch(bs, ssj.d, n_ssj, ssurf_row_bytes, f0.p[0].h, ssurf_wide);
+        g_scale_steps[ssurf_wide ? 0 : 1]++;
+    }
+    if (n_srj) {
+        ingest_rgb_scaled_batch(bs, srj.d, n_srj, srgb_sw, f0.p[1].h, srgb_wide);
+        g_scale_steps[srgb_wide ? 2 : 3]++;
     }
     extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
     extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
@@ -2752,6 +2802,93 @@ void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset)
         }
         if (reset) {
             g_rgb_steps[i].store(0);
+        }
+    }
+}
+
+/* ---- half, quarter and eighth-size ingest: a surface of src_w x src_h for an encoder of ceil(src_w / n) x ceil(src_h / n) ----
+ * The rule is ingest_scale.h's device-free one (plan_source, surface_fits); with no scale value in the layout the surface must pass
+ * surface_ok as well, and the step is then the plain call's, job for job. */
+static bool scaled_surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf, int src_w, int src_h, ingest_scale::Source *src)
+{
+    if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
+        return false;
+    }
+    if (!ingest_scale::plan_source(src_w, src_h, enc->vidmeta.subsamp, sf->layout, src) ||
+        !ingest_scale::surface_fits(*src, *sf, enc->vidmeta.width, enc->vidmeta.height)) {
+        return false;
+    }
+    return src->shift != 0 || surface_ok(enc, sf);
+}
+
+static void scaled_job(Job &jb, DSV_ENCODER *enc, const dsv2hip_surface &sf, const ingest_scale::Source &src, int src_w, int src_h, DSV_BUF *bufs)
+{
+    memset(&jb, 0, sizeof(Job));
+    jb.enc = enc;
+    jb.surf = sf;
+    jb.surf.layout = src.plain_layout;
+    jb.has_surf = true;
+    if (src.shift) {
+        jb.src_w = src_w, jb.src_h = src_h, jb.src_shift = src.shift;
+    }
+    jb.bufs = bufs;
+}
+
+int dsv2hip_enc_batch_surface_scaled(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs)
+{
+    if (n <= 0 || !encs || !surf || !src_w || !src_h || !bufs || !nbufs) {
+        return -1;
+    }
+    std::vector<ingest_scale::Source> src((size_t) n);
+    for (int k = 0; k < n; k++) {
+        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !scaled_surface_ok(encs[k], &surf[k], src_w[k], src_h[k], &src[(size_t) k])) {
+            return -1;
+        }
+    }
+    std::vector<Job> jobs((size_t) n);
+    for (int k = 0; k < n; k++) {
+        scaled_job(jobs[(size_t) k], encs[k], surf[k], src[(size_t) k], src_w[k], src_h[k], bufs + 4 * k);
+    }
+    const bool ok = enc_batch_ok(jobs.data(), n);
+    for (int k = 0; k < n; k++) {
+        nbufs[k] = jobs[(size_t) k].nbuf;
+    }
+    return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
+}
+
+int dsv2hip_enc_surface_frame_scaled(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
+{
+    ingest_scale::Source src;
+    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !scaled_surface_ok(enc, surf, src_w, src_h, &src)) {
+        return 0;
+    }
+    Job jb;
+    scaled_job(jb, enc, *surf, src, src_w, src_h, bufs);
+    enc_batch(&jb, 1);
+    return jb.nbuf;
+}
+
+int dsv2hip_enc_scaled_dims(int src_w, int src_h, int subsamp, int layout, int *enc_w, int *enc_h, size_t row_bytes[3], int rows[3])
+{
+    ingest_scale::Source src;
+    if (!enc_w || !enc_h || !row_bytes || !rows || !ingest_scale::plan_source(src_w, src_h, subsamp, layout, &src)) {
+        return -1;
+    }
+    *enc_w = src.enc_w, *enc_h = src.enc_h;
+    for (int c = 0; c < 3; c++) {
+        row_bytes[c] = src.row_bytes[c], rows[c] = src.rows[c];
+    }
+    return 0;
+}
+
+void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset)
+{
+    for (int i = 0; i < 4; i++) {
+        if (out4) {
+            out4[i] = g_scale_steps[i].load();
+        }
+        if (reset) {
+            g_scale_steps[i].store(0);
         }
     }
 }

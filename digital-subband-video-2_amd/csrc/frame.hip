@@ -10,6 +10,7 @@
 // adjacent strip ends (frame.c:377-380).
 #include "dev.h"
 #include "ingest_rgb.h"
+#include "ingest_scale.h"
 #include "prio.h"
 
 namespace dsv2 {
@@ -461,6 +462,81 @@ void ingest_rgb_batch(hipStream_t s, const RgbJob *d_jobs, int n, int h, bool wi
         DSV2_LAUNCH(k_ingest_rgb<16>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_ingest_rgb<4>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled) ---------------------------------------------------
+// The threads' work is ingest_scale.h's (which tools/ingest_scale_check.cpp runs on the CPU); the records are fetched by value and
+// pinned to scalar registers as above.  The passes over a row are workgroups, not a loop: blockIdx.x names the 1024 source bytes
+// (RGB: 256 source pixels) a wavefront takes, and the loop inside the bodies runs again only for rows beyond kScaledGridX of them.
+constexpr int kScaledGridX = 64;
+template <bool WIDE> __global__ __launch_bounds__(256) void k_ingest_surface_scaled(const ScaledSurfaceJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const ScaledSurfaceJob jl = job_of(tab, blockIdx.z);
+    const ScaledSurfaceJob j{uni_ptr(jl.src), ((size_t) (unsigned) uni((int) (jl.pitch >> 32)) << 32) | (unsigned) uni((int) jl.pitch), uni_ptr(jl.dst),
+                             uni_ptr(jl.dst2), uni(jl.dstride), uni(jl.pw), uni(jl.ph), uni(jl.shift)};
+    const int oy = (int) blockIdx.y * 4 + uni((int) threadIdx.y); // one output row per wavefront
+    if (oy >= (j.ph + (1 << j.shift) - 1) >> j.shift) {
+        return;
+    }
+    ingest_scaled_row<WIDE>(j, oy, (int) blockIdx.x * 64 + (int) threadIdx.x, (int) gridDim.x * 64);
+}
+
+void ingest_surface_scaled_batch(hipStream_t s, const ScaledSurfaceJob *d_jobs, int n, int max_row_bytes, int max_rows, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const int gx = (max_row_bytes + 1023) / 1024;
+    const dim3 grid(gx < kScaledGridX ? gx : kScaledGridX, (max_rows + 3) / 4, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_surface_scaled<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_surface_scaled<false>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// a wavefront: one row of chroma samples of the reduced picture over a span of 256 source pixels -- (1 << vs) strips of n source rows
+template <bool WIDE> __global__ __launch_bounds__(256) void k_ingest_rgb_scaled(const ScaledRgbJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const ScaledRgbJob jl = job_of(tab, blockIdx.z);
+    const ScaledRgbJob j{uni_ptr(jl.src),
+                         ((size_t) (unsigned) uni((int) (jl.pitch >> 32)) << 32) | (unsigned) uni((int) jl.pitch),
+                         {uni_ptr(jl.dst[0]), uni_ptr(jl.dst[1]), uni_ptr(jl.dst[2])},
+                         uni(jl.ystride),
+                         uni(jl.cstride),
+                         uni(jl.sw),
+                         uni(jl.sh),
+                         uni(jl.hs),
+                         uni(jl.vs),
+                         uni(jl.shift),
+                         (uint32_t) uni((int) jl.ycoef),
+                         (uint32_t) uni((int) jl.upos),
+                         (uint32_t) uni((int) jl.uneg),
+                         (uint32_t) uni((int) jl.vpos),
+                         (uint32_t) uni((int) jl.vneg),
+                         (uint32_t) uni((int) jl.yoff)};
+    const int cy = (int) blockIdx.y * 4 + uni((int) threadIdx.y);
+    const int up = (1 << (j.shift + j.vs)) - 1;
+    if (cy >= (j.sh + up) >> (j.shift + j.vs)) { // (= ch' of the reduced picture; the whole wavefront leaves or stays)
+        return;
+    }
+    ingest_rgb_scaled_band<WIDE>(j, cy, (int) blockIdx.x * kRgbScaledSpan, (int) gridDim.x * kRgbScaledSpan);
+}
+
+void ingest_rgb_scaled_batch(hipStream_t s, const ScaledRgbJob *d_jobs, int n, int max_sw, int max_crows, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const int gx = (max_sw + kRgbScaledSpan - 1) / kRgbScaledSpan;
+    const dim3 grid(gx < kScaledGridX ? gx : kScaledGridX, (max_crows + 3) / 4, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_rgb_scaled<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_rgb_scaled<false>, grid, block, 0, s, d_jobs);
     }
 }
 

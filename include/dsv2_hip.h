@@ -456,6 +456,67 @@ int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *
 int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs);
 void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset);
 void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset);
+/* HALF, QUARTER AND EIGHTH-SIZE INGEST -- a proxy ladder (1080p + 540p + 270p) from ONE full-size surface of a renderer, a screen
+ * capture, a hardware decoder or a torch image tensor: an encoder of W' x H' reads a surface that holds src_w x src_h with
+ * W' = ceil(src_w / n), H' = ceil(src_h / n), and the picture is reduced in the ingest pass -- one read of the source, no full-size
+ * planar picture in between, no resize kernel on the caller's side.  The counterpart of the decoder's half, quarter and eighth-size
+ * delivery below, with the same values and ONE layout grammar for both directions.
+ * surf[k].layout: any layout dsv2hip_enc_batch_surface takes, or-ed with at most one DSV2HIP_SCALE_* value; s = (layout >> 12) & 3
+ * is the shift, n = 1 << s.  A scaled in-layout is valid exactly when it is a valid out-layout (below): PLANAR, SEMIPLANAR, BGRA /
+ * RGBA with CSC bits, or-ed with at most one of the three values; every other bit is no layout (0x4000, 0x1012 ...), a CSC bit on
+ * PLANAR / SEMIPLANAR is none, and 0x1010 is held back here too (half-size BGRA: 0x1110, 0x1210, 0x1310; BT.601 limited-range pixels
+ * at half size: RGBA, 0x1011).
+ * src_w[k] x src_h[k]: the size of the picture IN THE SURFACE (ceil is not invertible, so the caller says it).  The encoder's
+ * vidmeta.width, .height must equal ceil(src_w / n), ceil(src_h / n).  The source planes are dsv_mk_frame's for src_w x src_h in the
+ * encoder's chroma format, scw x sch the chroma size of THAT picture:
+ *   PLANAR      {src_w, scw, scw} bytes by {src_h, sch, sch} rows
+ *   SEMIPLANAR  {src_w, 2 * scw}  bytes by {src_h, sch}      rows
+ *   BGRA / RGBA {4 * src_w}       bytes by {src_h}           rows
+ * and every pitch must be at least its SOURCE row's bytes.  Nested round-ups commute, so reducing each source plane on its own gives
+ * exactly the encoder's plane sizes.
+ * dsv2hip_enc_batch_surface_scaled / dsv2hip_enc_surface_frame_scaled behave as dsv2hip_enc_batch_surface / _surface_frame in
+ * everything else: one lockstep step, 4 DSV_BUF slots per stream, surf[k] copied, the surface only read and only inside its rows,
+ * any pointer alignment and any pitch; the encoders of a step share a geometry, their surfaces may differ in layout, scale, source
+ * size, pitch and alignment (a plain NV12 beside a quarter-size BGRA beside an eighth-size planar one).  With s = 0 the call does
+ * exactly what the plain call does (src_w, src_h must then equal the encoder's).  The batch call refuses as a whole with -1, before
+ * any encoder, counter, buffer or nbufs entry is touched, and the one-frame call returns 0, for: everything the plain calls refuse;
+ * a NULL src_w / src_h array; a layout outside the grammar; src_w or src_h <= 0; a source whose reduction is not the encoder's
+ * geometry; a pitch below the SOURCE row's bytes; a NULL plane the layout needs; an encoder with dsv2hip_enc_set_uyvy_input on; an RGB
+ * layout on a format outside the five.  dsv2hip_enc_batch_surface and dsv2hip_enc_surface_frame keep refusing a layout with a scale.
+ * dsv2hip_enc_scaled_dims: what an encoder of this source must be (enc_w, enc_h) and what the source planes are (row_bytes, rows;
+ * entries a layout has no plane for are 0), for a chroma format `subsamp` (DSV_SUBSAMP_*): 0, or -1 for a NULL pointer, a layout
+ * outside the grammar, a size <= 0, a format that is none of DSV_SUBSAMP_* (an RGB layout: of the five).
+ *
+ * THE CONTRACT (the packets are exactly dsv_enc's on the planar W' x H' picture defined here).
+ * YUV surfaces: the decoder's REDUCTION (below) applied to each SOURCE plane P, pw x ph, on its own:
+ *
+ *   out(x, y) = ( SUM j<n, i<n  P(min(x*n + i, pw-1), min(y*n + j, ph-1))  +  (1 << (2*s - 1)) ) >> (2*s)
+ *
+ * SEMIPLANAR: the reduced U and V of the de-interleaved plane.  So a picture decoded at full size into a surface and encoded through
+ * the scaled call gives the packets of the same picture decoded at that scale and encoded through the plain call.
+ * RGB surfaces: THE CONVERSION above with every footprint enlarged by the scale and ONE rounding per sample:
+ *
+ *   Y'(x,y)   = ( SUM over n x n of (yr*R + yg*G + yb*B)  +  ((128 + 256*ybase) << 2s) ) >> (8 + 2s)
+ *   U'(cx,cy) = min(255, ( SUM over (n << hs) x (n << vs) of (ur*R + ug*G + ub*B)  +  (32896 << (hs + vs + 2s)) ) >> (8 + hs + vs + 2s))
+ *   V' likewise with vr, vg, vb
+ *
+ * The footprints start at (x*n, y*n) and (cx << (hs + s), cy << (vs + s)), with coordinates clamped to src_w-1 and src_h-1 -- one
+ * clamp, on source coordinates.  The matrices are those of the table above.  For U and V this is the plain formula with hs + s, vs + s
+ * in place of hs, vs; with s = 0 the whole is the plain conversion.  (Converting at full size and reducing, or reducing RGB and
+ * converting, would round two or three times.)  A footprint of equal pixels gives what one pixel gives; limited range stays within
+ * Y 16 ... 235 and U, V 16 ... 240 without a clamp; every sum is non-negative before its shift; the largest accumulator is 1024 pixels
+ * x 255 x 128 = 33 423 360, so plain 32-bit sums suffice (tests/test_ingest_scale_cpu.py, over all 2^24 colours).
+ * dsv2hip_enc_scale_stats: out4[0] / out4[1] = lockstep steps of this process whose scaled YUV ingest ran in the wide form (every
+ * scaled YUV source plane of the step: pointer, pitch and SOURCE row bytes multiples of 16) / in the general form; out4[2] / out4[3]
+ * = the same for the scaled RGB ingest (every scaled RGB surface of the step: pointer and pitch multiples of 16, src_w of 4).
+ * reset != 0 clears the counts afterwards.  dsv2hip_enc_surface_stats and dsv2hip_enc_rgb_stats keep counting the steps' unscaled
+ * surfaces only. */
+int  dsv2hip_enc_batch_surface_scaled(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf,
+                                      const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs);
+int  dsv2hip_enc_surface_frame_scaled(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs);
+int  dsv2hip_enc_scaled_dims(int src_w, int src_h, int subsamp, int layout, int *enc_w, int *enc_h,
+                             size_t row_bytes[3], int rows[3]);
+void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset);
 /* the same step with the pictures in HOST memory, as dsv_enc (dsv_encoder.c:1430) receives them: host_planar[k] is
  * stream k's packed planar picture of this step.  host_next (NULL, or NULL entries, allowed) names the picture each
  * stream will bring to the NEXT call: it is uploaded on a copy stream under this step's kernels, and the next call
@@ -576,7 +637,7 @@ int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size
  * all three calls; half-size BGRA is available with every other preset (0x1110, 0x1210, 0x1310), half-size BT.601 limited-range
  * pixels as RGBA (0x1011), and quarter and eighth size (0x2010, 0x3010) are not affected.  The scale goes through dsv2hip_dec_batch_surface,
  * dsv2hip_dec_surface_frame and dsv2hip_dec_surface_dims; dsv_dec, dsv2hip_dec_batch, dsv2hip_dec_batch_device,
- * dsv2hip_dec_device_frame and dsv2hip_dec_picture_bytes know nothing of it, and the encoder's surface calls refuse such a layout.
+ * dsv2hip_dec_device_frame and dsv2hip_dec_picture_bytes know nothing of it, and the encoder's plain surface calls refuse such a layout (dsv2hip_enc_batch_surface_scaled takes it).
  * Everything said of out surfaces above holds, applied to the reduced sizes: any pointer alignment, any pitch from the row's bytes
  * up to INT_MAX, cap[c] >= (rows[c] - 1) * pitch[c] + row_bytes[c], only bytes inside the rows written, surf[k] copied, layouts and
  * scales mixed freely within one step and one round (full-size NV12 beside quarter-size BGRA beside half-size planar), a refused
@@ -606,7 +667,7 @@ int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size
  * multiples of 8 and a reduced width that is a multiple of 16 >> s, i.e. of 8, 4, 2) / in the general form so far; rounds without a
  * scaled picture count as neither.  reset != 0 clears the counts afterwards.  The two other counters keep their meaning: a scaled
  * semiplanar or RGB picture's interleave / conversion counts there as any other. */
-enum { DSV2HIP_SCALE_HALF = 0x1000, DSV2HIP_SCALE_QUARTER = 0x2000, DSV2HIP_SCALE_EIGHTH = 0x3000 }; /* or-ed into the layout of an OUT surface */
+enum { DSV2HIP_SCALE_HALF = 0x1000, DSV2HIP_SCALE_QUARTER = 0x2000, DSV2HIP_SCALE_EIGHTH = 0x3000 }; /* or-ed into the layout of an OUT surface, or of an in surface of the _scaled calls */
 typedef struct dsv2hip_out_surface {
     void *plane[3];  /* device memory. PLANAR: Y, U, V.  SEMIPLANAR: Y, interleaved UV (U first); plane[2] ignored.  BGRA / RGBA: the picture */
     size_t pitch[3]; /* bytes from one row to the next; pitch[2] ignored for SEMIPLANAR, pitch[1..2] for BGRA / RGBA */

@@ -1,0 +1,565 @@
+// ingest_scale_check.cpp -- the bodies of k_ingest_surface_scaled and k_ingest_rgb_scaled (csrc/ingest_scale.h) run as plain C++ on
+// the CPU, thread by thread and (RGB) wavefront by wavefront, over a sweep of shifts, forms, chroma formats, byte orders, presets,
+// source widths and heights, pitches and pointer offsets; meant to be built with AddressSanitizer and UndefinedBehaviorSanitizer,
+// which see every read outside a source's allocation (an exact-size heap block: the last row has nothing behind it), every write
+// outside a plane's and every misaligned word access.  The program itself compares the three planes with the contract of
+// include/dsv2_hip.h restated here sample by sample (nothing shared with the kernels' text), checks that no byte outside the
+// planes' W' x H' / cw' x ch' changed (the border and 64 guard bytes round every plane), and sweeps the device-free validity rule
+// (ingest_scale::plan_source, surface_fits) against a restatement.  tests/test_ingest_scale_cpu.py builds and runs it:
+//   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+//         -I digital-subband-video-2_amd/csrc tools/ingest_scale_check.cpp -o ingest_scale_check && ./ingest_scale_check [--dump DIR]
+// --dump DIR writes, for a few named cases, NAME.src (the source planes, rows of exactly their bytes, plane behind plane) and NAME.yuv
+// (the encoder's planes, packed), and DIR/validity.txt: one line "name result" per case of the refusal matrix.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "ingest_scale.h"
+
+using namespace dsv2;
+
+namespace {
+
+constexpr uint8_t kGuard = 0xA5;
+constexpr int kGuardBytes = 64;
+
+const int kMatrix[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},
+                           {47, 157, 16, -26, -86, 112, 112, -102, -10},
+                           {77, 150, 29, -43, -85, 128, 128, -107, -21},
+                           {54, 183, 19, -29, -99, 128, 128, -116, -12}};
+int preset_of(int csc) { return ((csc & 0x200) ? 2 : 0) + ((csc & 0x100) ? 1 : 0); }
+int ceil_shift(int v, int s) { return (v + (1 << s) - 1) >> s; }
+
+// ---- planes as dframe_alloc lays them out (32-pixel border, stride a multiple of 16, 16-byte aligned origin), 64 guard bytes round them
+struct Plane {
+    uint8_t *alloc, *first, *org;
+    size_t bytes;
+    int stride, w, h;
+    Plane(int w_, int h_) : w(w_), h(h_)
+    {
+        stride = (w + 2 * kBorder + 15) & ~15;
+        bytes = (size_t) stride * (size_t) (h + 2 * kBorder) + 2 * kGuardBytes;
+        alloc = (uint8_t *) aligned_alloc(16, (bytes + 15) & ~(size_t) 15);
+        memset(alloc, kGuard, bytes);
+        first = alloc + kGuardBytes;
+        org = first + (size_t) kBorder * stride + kBorder;
+    }
+    ~Plane() { free(alloc); }
+    Plane(const Plane &) = delete;
+    // every byte is the guard value except the w x h samples, which are want(x, y)
+    template <class F> bool equals(F want, long *bad_x, long *bad_y, int *got, int *expected) const
+    {
+        for (size_t i = 0; i < bytes; i++) {
+            const long at = (long) i - kGuardBytes;
+            long y = at >= 0 ? at / stride - kBorder : -1000, x = at >= 0 ? at % stride - kBorder : -1000;
+            const bool inside = at >= 0 && x >= 0 && x < w && y >= 0 && y < h;
+            const int e = inside ? want((int) x, (int) y) : kGuard;
+            if (alloc[i] != e) {
+                *bad_x = x, *bad_y = y, *got = alloc[i], *expected = e;
+                return false;
+            }
+        }
+        return true;
+    }
+};
+
+// an exact-size source block: `offset` bytes, then rows of rb bytes `pitch` apart, nothing behind the last row; all noise
+struct SourceBlock {
+    uint8_t *alloc, *src;
+    size_t bytes, pitch;
+    std::vector<uint8_t> was;
+    SourceBlock(size_t rb, int rows, int pitch_kind, int offset, unsigned &seed)
+    {
+        pitch = pitch_kind == 0 ? rb : pitch_kind == 1 ? rb + 1 : ((rb + 15) & ~(size_t) 15) + 16;
+        bytes = (size_t) offset + (size_t) (rows - 1) * pitch + rb;
+        if (posix_memalign((void **) &alloc, 16, bytes) != 0) {
+            abort();
+        }
+        src = alloc + offset;
+        for (size_t i = 0; i < bytes; i++) {
+            seed = seed * 1664525u + 1013904223u;
+            alloc[i] = (uint8_t) (seed >> 24);
+        }
+    }
+    void freeze() { was.assign(alloc, alloc + bytes); }
+    bool untouched() const { return memcmp(was.data(), alloc, bytes) == 0; }
+    ~SourceBlock() { free(alloc); }
+    SourceBlock(const SourceBlock &) = delete;
+};
+
+const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+const int kSubsamp[5] = {DSV_SUBSAMP_444, DSV_SUBSAMP_422, DSV_SUBSAMP_420, DSV_SUBSAMP_411, DSV_SUBSAMP_410};
+const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
+long g_cases[2] = {0, 0}, g_wide[2] = {0, 0};
+const char *g_dump = nullptr;
+
+void dump_rows(FILE *f, const uint8_t *p, size_t pitch, size_t rb, int rows)
+{
+    for (int y = 0; y < rows; y++) {
+        fwrite(p + (size_t) y * pitch, 1, rb, f);
+    }
+}
+FILE *dump_open(const char *name, const char *ext)
+{
+    FILE *f = fopen((std::string(g_dump) + "/" + name + ext).c_str(), "wb");
+    if (!f) {
+        fprintf(stderr, "cannot write into %s\n", g_dump);
+        exit(1);
+    }
+    return f;
+}
+
+// ---- YUV ---------------------------------------------------------------------------------------------------------------------
+// the reduction, restated: one sample at a time, coordinates clamped.  at(x, y): sample of the source plane
+template <class F> int expect_reduced(F at, int pw, int ph, int s, int x, int y)
+{
+    const int n = 1 << s;
+    long sum = 0;
+    for (int j = 0; j < n; j++) {
+        for (int i = 0; i < n; i++) {
+            const int sx = x * n + i < pw - 1 ? x * n + i : pw - 1, sy = y * n + j < ph - 1 ? y * n + j : ph - 1;
+            sum += at(sx, sy);
+        }
+    }
+    return (int) ((sum + (1L << (2 * s - 1))) >> (2 * s));
+}
+
+template <bool WIDE> void run_yuv_grid(const ScaledSurfaceJob &j, int grid_x)
+{
+    const int oh = ceil_shift(j.ph, j.shift);
+    for (int by = 0; by < (oh + 3) / 4; by++) {
+        for (int ty = 0; ty < 4; ty++) {
+            const int oy = by * 4 + ty;
+            if (oy >= oh) {
+                continue;
+            }
+            for (int bx = 0; bx < grid_x; bx++) {
+                for (int tx = 0; tx < 64; tx++) {
+                    ingest_scaled_row<WIDE>(j, oy, bx * 64 + tx, grid_x * 64);
+                }
+            }
+        }
+    }
+}
+
+void check_yuv(int sw, int sh, int fmt, int s, bool semi, int pitch_kind, int offset, bool force_general, int grid_x, const char *dump_name = nullptr)
+{
+    const int hs = kHs[fmt], vs = kVs[fmt];
+    const int scw = ceil_shift(sw, hs), sch = ceil_shift(sh, vs);
+    const int W = ceil_shift(sw, s), H = ceil_shift(sh, s), cw = ceil_shift(W, hs), ch = ceil_shift(H, vs);
+    if (ceil_shift(scw, s) != cw || ceil_shift(sch, s) != ch) { // (nested round-ups commute: the header's claim)
+        fprintf(stderr, "round-ups do not commute at %dx%d\n", sw, sh);
+        exit(1);
+    }
+    unsigned seed = 977u * (unsigned) sw + 31u * (unsigned) sh + (unsigned) (fmt + 5 * pitch_kind + 20 * offset + 80 * s + (semi ? 320 : 0));
+    const int nsrc = semi ? 2 : 3;
+    const size_t rb[3] = {(size_t) sw, semi ? 2 * (size_t) scw : (size_t) scw, (size_t) scw};
+    const int rows[3] = {sh, sch, sch};
+    SourceBlock *blk[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < nsrc; c++) {
+        blk[c] = new SourceBlock(rb[c], rows[c], pitch_kind, offset, seed);
+        for (int y = 0; y < rows[c]; y += 3) { // some rows saturated, where the sums are extreme
+            memset(blk[c]->src + (size_t) y * blk[c]->pitch, (y % 2) ? 0 : 255, rb[c]);
+        }
+        blk[c]->freeze();
+    }
+    Plane Y(W, H), U(cw, ch), V(cw, ch);
+    Plane *dst[3] = {&Y, &U, &V};
+    ScaledSurfaceJob job[3];
+    bool wide = !force_general;
+    for (int c = 0; c < nsrc; c++) {
+        const bool uv = semi && c == 1;
+        job[c] = ScaledSurfaceJob{blk[c]->src, blk[c]->pitch, dst[c]->org, uv ? V.org : nullptr, dst[c]->stride, c ? scw : sw, c ? sch : sh, s};
+        wide = wide && scaled_surface_job_wide(job[c]);
+    }
+    for (int c = 0; c < nsrc; c++) {
+        wide ? run_yuv_grid<true>(job[c], grid_x) : run_yuv_grid<false>(job[c], grid_x);
+    }
+    g_cases[0]++;
+    g_wide[0] += wide;
+    for (int c = 0; c < 3; c++) {
+        const SourceBlock *b = blk[semi && c == 2 ? 1 : c];
+        const int step = semi && c ? 2 : 1, first = semi && c == 2 ? 1 : 0;
+        auto at = [&](int x, int y) { return (int) b->src[(size_t) y * b->pitch + (size_t) (x * step + first)]; };
+        long bx, by;
+        int got, want;
+        if (!dst[c]->equals([&](int x, int y) { return expect_reduced(at, c ? scw : sw, c ? sch : sh, s, x, y); }, &bx, &by, &got, &want)) {
+            fprintf(stderr, "MISMATCH yuv %dx%d %s s=%d semi=%d pitch_kind=%d offset=%d wide=%d: plane %d row %ld column %ld is %02x, expected %02x\n", sw,
+                    sh, kFmtName[fmt], s, (int) semi, pitch_kind, offset, (int) wide, c, by, bx, got, want);
+            exit(1);
+        }
+    }
+    for (int c = 0; c < nsrc; c++) {
+        if (!blk[c]->untouched()) {
+            fprintf(stderr, "a source plane was written: yuv %dx%d %s s=%d\n", sw, sh, kFmtName[fmt], s);
+            exit(1);
+        }
+    }
+    if (dump_name && g_dump) {
+        FILE *fs = dump_open(dump_name, ".src"), *fy = dump_open(dump_name, ".yuv");
+        for (int c = 0; c < nsrc; c++) {
+            dump_rows(fs, blk[c]->src, blk[c]->pitch, rb[c], rows[c]);
+        }
+        for (int c = 0; c < 3; c++) {
+            dump_rows(fy, dst[c]->org, (size_t) dst[c]->stride, (size_t) dst[c]->w, dst[c]->h);
+        }
+        fclose(fs);
+        fclose(fy);
+    }
+    for (int c = 0; c < nsrc; c++) {
+        delete blk[c];
+    }
+}
+
+// ---- RGB ---------------------------------------------------------------------------------------------------------------------
+struct Picture { // the surface's pixels as R, G, B triples, whatever its byte order and pitch
+    int w, h;
+    std::vector<int> rgb;
+    const int *at(int x, int y) const
+    {
+        x = x < w - 1 ? x : w - 1;
+        y = y < h - 1 ? y : h - 1;
+        return &rgb[3 * ((size_t) y * w + x)];
+    }
+};
+
+// row 0: Y' with a footprint of n x n; rows 1, 2: U', V' with (n << hs) x (n << vs)
+int expect_scaled(const Picture &p, int csc, int row, int fw_log2, int fh_log2, int x, int y)
+{
+    const int *m = kMatrix[preset_of(csc)] + 3 * row;
+    long sum = 0;
+    for (int dy = 0; dy < 1 << fh_log2; dy++) {
+        for (int dx = 0; dx < 1 << fw_log2; dx++) {
+            const int *c = p.at((x << fw_log2) + dx, (y << fh_log2) + dy);
+            sum += m[0] * c[0] + m[1] * c[1] + m[2] * c[2];
+        }
+    }
+    const int lg = fw_log2 + fh_log2;
+    if (row == 0) {
+        const long ybase = (csc & 0x200) ? 0 : 16;
+        return (int) ((sum + ((128 + 256 * ybase) << lg)) >> (8 + lg));
+    }
+    if (sum + (32896L << lg) < 0) {
+        fprintf(stderr, "a chroma sum is negative before its shift\n");
+        exit(1);
+    }
+    const long v = (sum + (32896L << lg)) >> (8 + lg);
+    return (int) (v < 255 ? v : 255);
+}
+
+void pack_coefs(ScaledRgbJob &j, int csc, bool bgra)
+{
+    const int *m = kMatrix[preset_of(csc)];
+    uint32_t q[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+    for (int row = 0; row < 3; row++) {
+        for (int c = 0; c < 3; c++) {
+            const int v = m[3 * row + c];
+            q[row][v < 0] |= (uint32_t) abs(v) << (8 * (bgra ? 2 - c : c));
+        }
+    }
+    j.ycoef = q[0][0], j.upos = q[1][0], j.uneg = q[1][1], j.vpos = q[2][0], j.vneg = q[2][1];
+    j.yoff = 128u + ((csc & 0x200) ? 0u : 4096u);
+}
+
+template <bool WIDE> void run_rgb_grid(const ScaledRgbJob &j, int grid_x)
+{
+    const int ch = ceil_shift(j.sh, j.shift + j.vs);
+    for (int cy = 0; cy < ch; cy++) { // one wavefront per chroma row and span
+        for (int bx = 0; bx < grid_x; bx++) {
+            ingest_rgb_scaled_band<WIDE>(j, cy, bx * kRgbScaledSpan, grid_x * kRgbScaledSpan);
+        }
+    }
+}
+
+void check_rgb(int sw, int sh, int fmt, int s, int csc, bool bgra, int pitch_kind, int offset, bool force_general, int grid_x,
+               const char *dump_name = nullptr)
+{
+    const int hs = kHs[fmt], vs = kVs[fmt];
+    const int W = ceil_shift(sw, s), H = ceil_shift(sh, s), cw = ceil_shift(W, hs), ch = ceil_shift(H, vs);
+    unsigned seed = 733u * (unsigned) sw + 37u * (unsigned) sh + (unsigned) (fmt + 5 * pitch_kind + 20 * offset + 80 * s);
+    SourceBlock blk(4 * (size_t) sw, sh, pitch_kind, offset, seed);
+    Picture pic{sw, sh, std::vector<int>(3 * (size_t) sw * sh)};
+    for (int y = 0; y < sh; y++) {
+        for (int x = 0; x < sw; x++) {
+            uint8_t *p = blk.src + (size_t) y * blk.pitch + 4 * (size_t) x;
+            seed = seed * 1664525u + 1013904223u;
+            if ((seed >> 29) == 0 || (y / 9) % 3 == 1) { // corners of the colour cube, and whole bands of them: where the sums are extreme
+                p[0] = (seed & 0x10000) ? 255 : 0, p[1] = (seed & 0x20000) ? 255 : 0, p[2] = (seed & 0x40000) ? 255 : 0;
+            }
+            int *c = &pic.rgb[3 * ((size_t) y * sw + x)];
+            c[0] = bgra ? p[2] : p[0], c[1] = p[1], c[2] = bgra ? p[0] : p[2];
+        }
+    }
+    blk.freeze();
+    Plane Y(W, H), U(cw, ch), V(cw, ch);
+    ScaledRgbJob j{blk.src, blk.pitch, {Y.org, U.org, V.org}, Y.stride, U.stride, sw, sh, hs, vs, s, 0, 0, 0, 0, 0, 0};
+    pack_coefs(j, csc, bgra);
+    const bool wide = scaled_rgb_job_wide(j) && !force_general;
+    wide ? run_rgb_grid<true>(j, grid_x) : run_rgb_grid<false>(j, grid_x);
+    g_cases[1]++;
+    g_wide[1] += wide;
+    const Plane *pl[3] = {&Y, &U, &V};
+    for (int c = 0; c < 3; c++) {
+        long bx, by;
+        int got, want;
+        if (!pl[c]->equals([&](int x, int y) { return expect_scaled(pic, csc, c, c ? hs + s : s, c ? vs + s : s, x, y); }, &bx, &by, &got, &want)) {
+            fprintf(stderr, "MISMATCH rgb %dx%d %s s=%d csc=0x%x %s pitch_kind=%d offset=%d wide=%d: plane %d row %ld column %ld is %02x, expected %02x\n",
+                    sw, sh, kFmtName[fmt], s, csc, bgra ? "bgra" : "rgba", pitch_kind, offset, (int) wide, c, by, bx, got, want);
+            exit(1);
+        }
+    }
+    if (!blk.untouched()) {
+        fprintf(stderr, "the surface was written: rgb %dx%d %s s=%d\n", sw, sh, kFmtName[fmt], s);
+        exit(1);
+    }
+    if (dump_name && g_dump) {
+        FILE *fs = dump_open(dump_name, ".src"), *fy = dump_open(dump_name, ".yuv");
+        dump_rows(fs, blk.src, blk.pitch, 4 * (size_t) sw, sh);
+        for (int c = 0; c < 3; c++) {
+            dump_rows(fy, pl[c]->org, (size_t) pl[c]->stride, (size_t) pl[c]->w, pl[c]->h);
+        }
+        fclose(fs);
+        fclose(fy);
+    }
+}
+
+// ---- the validity rule -----------------------------------------------------------------------------------------------------------
+// the grammar restated from the header: PLANAR, SEMIPLANAR, or BGRA / RGBA with any CSC bits, or-ed with at most one scale value; 0x1010 held back
+bool grammar(int layout)
+{
+    if (layout < 0 || (layout & ~0x33ff) != 0 || layout == 0x1010) {
+        return false;
+    }
+    const int low = layout & 0xff, csc = layout & 0x300;
+    return ((low == 0 || low == 1) && csc == 0) || low == 0x10 || low == 0x11;
+}
+
+void sweep_validity()
+{
+    long n = 0;
+    for (int layout = -2; layout < 0x8000; layout++) {
+        for (int fmt = 0; fmt < 6; fmt++) {
+            const int subsamp = fmt < 5 ? kSubsamp[fmt] : DSV_SUBSAMP_UYVY;
+            ingest_scale::Source s;
+            const bool rgb = (layout & 0xff) >= 0x10;
+            const bool want = grammar(layout) && !(rgb && fmt == 5);
+            if (ingest_scale::plan_source(67, 35, subsamp, layout, &s) != want) {
+                fprintf(stderr, "plan_source(layout 0x%x, subsamp 0x%x) is %d\n", layout, subsamp, (int) !want);
+                exit(1);
+            }
+            n++;
+        }
+    }
+    for (int fmt = 0; fmt < 5; fmt++) { // sizes, row bytes and rows against the header's table; sizes <= 0; the fit
+        for (int s = 0; s < 4; s++) {
+            for (int sw = -1; sw <= 70; sw++) {
+                for (int sh = -1; sh <= 40; sh += (sh < 4 ? 1 : 7)) {
+                    for (int kind = 0; kind < 3; kind++) {
+                        const int layout = (kind == 2 ? 0x111 : kind) | (s << 12);
+                        ingest_scale::Source src;
+                        const bool ok = ingest_scale::plan_source(sw, sh, kSubsamp[fmt], layout, &src);
+                        if (ok != (sw > 0 && sh > 0)) {
+                            fprintf(stderr, "plan_source(%d x %d) is %d\n", sw, sh, (int) ok);
+                            exit(1);
+                        }
+                        if (!ok) {
+                            continue;
+                        }
+                        const size_t scw = (size_t) ceil_shift(sw, kHs[fmt]);
+                        const int sch = ceil_shift(sh, kVs[fmt]);
+                        const size_t rb[3][3] = {{(size_t) sw, scw, scw}, {(size_t) sw, 2 * scw, 0}, {4 * (size_t) sw, 0, 0}};
+                        const int rows[3][3] = {{sh, sch, sch}, {sh, sch, 0}, {sh, 0, 0}};
+                        bool same = src.shift == s && src.enc_w == ceil_shift(sw, s) && src.enc_h == ceil_shift(sh, s) && src.nplanes == 3 - kind;
+                        for (int c = 0; c < 3; c++) {
+                            same = same && src.row_bytes[c] == rb[kind][c] && src.rows[c] == rows[kind][c];
+                        }
+                        if (!same) {
+                            fprintf(stderr, "plan_source(%d x %d, %s, layout 0x%x): wrong sizes\n", sw, sh, kFmtName[fmt], layout);
+                            exit(1);
+                        }
+                        // the fit: tight pitches pass, one byte less in any plane the layout has does not, nor does a NULL plane or another geometry
+                        dsv2hip_surface sf{};
+                        sf.layout = layout;
+                        for (int c = 0; c < src.nplanes; c++) {
+                            sf.plane[c] = (const void *) (uintptr_t) 0x1000;
+                            sf.pitch[c] = rb[kind][c];
+                        }
+                        bool fit = ingest_scale::surface_fits(src, sf, src.enc_w, src.enc_h) && !ingest_scale::surface_fits(src, sf, src.enc_w + 1, src.enc_h) &&
+                                   !ingest_scale::surface_fits(src, sf, src.enc_w, src.enc_h + 1);
+                        for (int c = 0; c < src.nplanes; c++) {
+                            dsv2hip_surface bad = sf;
+                            bad.pitch[c]--;
+                            fit = fit && !ingest_scale::surface_fits(src, bad, src.enc_w, src.enc_h);
+                            bad = sf;
+                            bad.plane[c] = nullptr;
+                            fit = fit && !ingest_scale::surface_fits(src, bad, src.enc_w, src.enc_h);
+                        }
+                        if (!fit) {
+                            fprintf(stderr, "surface_fits(%d x %d, %s, layout 0x%x) is wrong\n", sw, sh, kFmtName[fmt], layout);
+                            exit(1);
+                        }
+                        n++;
+                    }
+                }
+            }
+        }
+    }
+    printf("ingest_scale_check: %ld cases of the validity rule equal its restatement\n", n);
+}
+
+// the refusal matrix by name, for tests/test_ingest_scale_cpu.py: a 34x18 4:2:0 encoder (UYVY: 4:2:2 geometry), tight surfaces unless said
+void dump_validity()
+{
+    FILE *f = dump_open("validity", ".txt");
+    struct Case {
+        const char *name;
+        int layout, sw, sh, subsamp, spoil_pitch, null_plane; // spoil_pitch / null_plane: plane index or -1
+    };
+    const Case cases[] = {{"planar_half", 0x1000, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"nv12_quarter", 0x2001, 133, 69, DSV_SUBSAMP_420, -1, -1},
+                          {"bgra709_half", 0x1110, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"rgba_full_eighth", 0x3211, 269, 141, DSV_SUBSAMP_420, -1, -1},
+                          {"plain_planar", 0x0, 34, 18, DSV_SUBSAMP_420, -1, -1},
+                          {"layout_0x4000", 0x4000, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"layout_0x1010", 0x1010, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"layout_0x1012", 0x1012, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"planar_half_bt709", 0x1100, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"semiplanar_half_full", 0x1201, 67, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"source_69x35", 0x1000, 69, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"source_67x37", 0x1000, 67, 37, DSV_SUBSAMP_420, -1, -1},
+                          {"src_w_0", 0x1000, 0, 35, DSV_SUBSAMP_420, -1, -1},
+                          {"src_h_negative", 0x1000, 67, -35, DSV_SUBSAMP_420, -1, -1},
+                          {"pitch_short_planar_0", 0x1000, 67, 35, DSV_SUBSAMP_420, 0, -1},
+                          {"pitch_short_planar_1", 0x1000, 67, 35, DSV_SUBSAMP_420, 1, -1},
+                          {"pitch_short_planar_2", 0x1000, 67, 35, DSV_SUBSAMP_420, 2, -1},
+                          {"pitch_short_nv12_1", 0x1001, 67, 35, DSV_SUBSAMP_420, 1, -1},
+                          {"pitch_short_rgb_0", 0x1011, 67, 35, DSV_SUBSAMP_420, 0, -1},
+                          {"null_planar_2", 0x1000, 67, 35, DSV_SUBSAMP_420, -1, 2},
+                          {"null_nv12_1", 0x1001, 67, 35, DSV_SUBSAMP_420, -1, 1},
+                          {"null_nv12_2_is_ignored", 0x1001, 67, 35, DSV_SUBSAMP_420, -1, 2},
+                          {"null_rgb_0", 0x1011, 67, 35, DSV_SUBSAMP_420, -1, 0},
+                          {"rgb_on_uyvy_format", 0x1011, 67, 35, DSV_SUBSAMP_UYVY, -1, -1},
+                          {"nv16_on_uyvy_format", 0x1001, 67, 35, DSV_SUBSAMP_UYVY, -1, -1}};
+    for (const Case &c : cases) {
+        ingest_scale::Source src;
+        bool ok = ingest_scale::plan_source(c.sw, c.sh, c.subsamp, c.layout, &src);
+        if (ok) {
+            dsv2hip_surface sf{};
+            sf.layout = c.layout;
+            for (int p = 0; p < 3; p++) {
+                sf.plane[p] = (const void *) (uintptr_t) 0x1000;
+                sf.pitch[p] = src.row_bytes[p];
+            }
+            if (c.spoil_pitch >= 0) {
+                sf.pitch[c.spoil_pitch]--;
+            }
+            if (c.null_plane >= 0) {
+                sf.plane[c.null_plane] = nullptr;
+            }
+            ok = ingest_scale::surface_fits(src, sf, 34, 18);
+        }
+        fprintf(f, "%s %d\n", c.name, (int) ok);
+    }
+    fclose(f);
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc == 3 && strcmp(argv[1], "--dump") == 0) {
+        g_dump = argv[2];
+    } else if (argc != 1) {
+        fprintf(stderr, "usage: %s [--dump DIR]\n", argv[0]);
+        return 2;
+    }
+    sweep_validity();
+    static const int cscs[4] = {0x000, 0x100, 0x200, 0x300};
+    std::vector<int> ws, hs;
+    for (int w = 1; w <= 40; w++) {
+        ws.push_back(w);
+    }
+    for (int w : {63, 64, 65, 66, 130, 300}) {
+        ws.push_back(w);
+    }
+    for (int h = 1; h <= 18; h++) {
+        hs.push_back(h);
+    }
+    hs.push_back(33);
+    hs.push_back(65);
+    // every source size x shift x format x kind of surface (anything has a reduction of at least 1 x 1); byte order, preset, pitch and
+    // offset take turns; the wide form where the source allows it, and the general form on the same aligned source
+    long turn = 0;
+    for (int w : ws) {
+        for (int h : hs) {
+            for (int s = 1; s <= 3; s++) {
+                for (int fmt = 0; fmt < 5; fmt++, turn++) {
+                    const int csc = cscs[turn & 3];
+                    const bool bgra = ((turn >> 2) & 1) != 0;
+                    const int pk = (int) (turn % 3), off = (int) ((turn / 3) & 3);
+                    for (int semi = 0; semi < 2; semi++) {
+                        check_yuv(w, h, fmt, s, semi != 0, 2, 0, false, 1);   // aligned: wide where the row bytes allow
+                        check_yuv(w, h, fmt, s, semi != 0, pk, off, false, 1); // general (wide again where tight is aligned)
+                        check_yuv(w, h, fmt, s, semi != 0, 2, 0, true, 1);    // general on the aligned source
+                    }
+                    check_rgb(w, h, fmt, s, csc, bgra, 2, 0, false, 1);
+                    check_rgb(w, h, fmt, s, cscs[(turn + 1) & 3], !bgra, pk, off, false, 1);
+                    check_rgb(w, h, fmt, s, cscs[(turn + 2) & 3], bgra, 2, 0, true, 1);
+                }
+            }
+        }
+    }
+    // every pitch kind x offset x byte order x preset, both forms, at a few sizes round the footprints
+    for (int w : {16, 31, 32, 33, 61}) {
+        for (int h : {15, 16, 17, 33}) {
+            for (int s = 1; s <= 3; s++) {
+                for (int fmt = 0; fmt < 5; fmt++) {
+                    for (int pk = 0; pk < 3; pk++) {
+                        for (int off = 0; off < 4; off++) {
+                            check_yuv(w, h, fmt, s, false, pk, off, false, 1);
+                            check_yuv(w, h, fmt, s, true, pk, off, false, 1);
+                            for (int csc : cscs) {
+                                check_rgb(w, h, fmt, s, csc, (off & 1) != 0, pk, off, false, 1);
+                                check_rgb(w, h, fmt, s, csc, (off & 1) == 0, pk, off, false, 1);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    // rows of several workgroups, and rows wider than the grid covers (the loop that remains): 2080 bytes / 520 pixels over grids of 3 and 1
+    for (int s = 1; s <= 3; s++) {
+        for (int fmt : {0, 2, 4}) {
+            for (int grid_x : {3, 1}) {
+                check_yuv(2080, 9, fmt, s, false, 2, 0, false, grid_x);
+                check_yuv(2077, 9, fmt, s, true, 1, 1, false, grid_x);
+                check_rgb(520, 9, fmt, s, 0x100, true, 2, 0, false, grid_x);
+                check_rgb(519, 9, fmt, s, 0x200, false, 1, 3, false, grid_x);
+            }
+        }
+    }
+    check_yuv(67, 35, 2, 1, false, 1, 1, false, 1, "planar_420_s1_67x35");
+    check_yuv(133, 69, 2, 2, true, 0, 0, false, 1, "semi_420_s2_133x69");
+    check_yuv(64, 48, 0, 3, true, 2, 0, false, 1, "semi_444_s3_64x48");
+    check_yuv(297, 169, 4, 3, false, 2, 0, false, 1, "planar_410_s3_297x169");
+    check_yuv(75, 43, 3, 1, true, 1, 3, false, 1, "semi_411_s1_75x43");
+    check_yuv(37, 19, 1, 2, false, 0, 2, false, 1, "planar_422_s2_37x19");
+    check_rgb(67, 35, 2, 1, 0x100, true, 1, 1, false, 1, "bgra_100_420_s1_67x35");
+    check_rgb(133, 69, 2, 2, 0x200, false, 0, 0, false, 1, "rgba_200_420_s2_133x69");
+    check_rgb(64, 48, 0, 3, 0x000, false, 2, 0, false, 1, "rgba_000_444_s3_64x48");
+    check_rgb(297, 169, 4, 3, 0x300, true, 2, 0, false, 1, "bgra_300_410_s3_297x169");
+    check_rgb(75, 43, 3, 1, 0x000, true, 1, 3, false, 1, "bgra_000_411_s1_75x43");
+    check_rgb(36, 19, 1, 2, 0x300, false, 2, 0, false, 1, "rgba_300_422_s2_36x19");
+    check_rgb(33, 17, 0, 1, 0x100, false, 0, 2, false, 1, "rgba_100_444_s1_33x17");
+    if (g_dump) {
+        dump_validity();
+    }
+    printf("ingest_scale_check: %ld YUV cases (%ld in the wide form) and %ld RGB cases (%ld in the wide form) equal the sample-by-sample "
+           "contract; no byte outside the planes changed, the sources are as they were\n",
+           g_cases[0], g_wide[0], g_cases[1], g_wide[1]);
+    return 0;
+}
