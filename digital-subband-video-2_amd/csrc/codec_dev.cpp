@@ -351,10 +351,15 @@ void CodecDev::destroy()
         }
     }
     dev_release(d_ll);
+    // the symbol mirrors are made on demand (ensure_dev_syms / ensure_host_syms) and not by init(): an instance that is initialised
+    // again -- a decoder whose stream changes geometry -- must not find the capacities of the freed ones
     if (d_sym_pos) {
         dev_release(d_sym_pos);
         dev_release(d_sym_val);
+        d_sym_pos = nullptr;
+        d_sym_val = nullptr;
     }
+    sym_cap = 0;
     HIPCHK(hipHostFree(h_frame));
     HIPCHK(hipHostFree(h_mvs));
     HIPCHK(hipHostFree(h_intra));
@@ -364,7 +369,10 @@ void CodecDev::destroy()
     if (h_pos) {
         HIPCHK(hipHostFree(h_pos));
         HIPCHK(hipHostFree(h_val));
+        h_pos = nullptr;
+        h_val = nullptr;
     }
+    h_sym_cap = 0;
     arena.destroy(); // (last: the releases above skipped everything that lives inside it)
 }
 

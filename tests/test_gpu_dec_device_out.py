@@ -81,10 +81,26 @@ class DevOut:
         return a[self.offset:self.offset + self.nbytes]
 
 
-def device_decode(hip, streams, modes=None, out420p=None, sharp=None, offset=0):
+def lockstep(streams, schedule=None, delay=None):
+    """the steps of a run, each the ordered [(decoder, packet index)] it feeds: packet t (t - delay[k]) of every stream that has
+    one, or the caller's schedule -- in which a step holds whichever decoders and packets it names, each decoder's in order"""
+    if schedule is not None:
+        at = [0] * len(streams)
+        for step in schedule:
+            for k, p in step:
+                assert p == at[k] < len(streams[k]), "the schedule feeds decoder %d packet %d, its next one is %d" % (k, p, at[k])
+                at[k] += 1
+        return [list(step) for step in schedule if step]
+    delay = delay or [0] * len(streams)
+    return [[(k, t - delay[k]) for k in range(len(streams)) if 0 <= t - delay[k] < len(streams[k])]
+            for t in range(max(len(s) + d for s, d in zip(streams, delay)))]
+
+
+def device_decode(hip, streams, modes=None, out420p=None, sharp=None, offset=0, schedule=None, single=False):
     """Lockstep steps over one decoder per stream, pictures delivered to device memory.  Per stream: [(return code, frame number
     or None, [Y, U, V] or None)] per packet, as test_gpu_dec_drawinfo.decode gives for dsv_dec.  modes / out420p / sharp: per
-    stream; a mode or sharp entry may be a function of the packet's index (set before every step)."""
+    stream; a mode or sharp entry may be a function of the packet's index (set before every step).  schedule: lockstep()'s;
+    single: one dsv2hip_dec_device_frame per packet in place of the step's batch call."""
     bind(hip)
     n = len(streams)
     modes = modes or [0] * n
@@ -97,13 +113,15 @@ def device_decode(hip, streams, modes=None, out420p=None, sharp=None, offset=0):
     outs = [None] * n
     res = [[] for _ in range(n)]
     done = [False] * n
-    for t in range(max(len(s) for s in streams)):
-        live = [k for k in range(n) if t < len(streams[k]) and not done[k]]
+    for step in lockstep(streams, schedule):
+        at = {k: t for k, t in step if not done[k]}
+        live = list(at)
         m = len(live)
         decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
         bufs = (A.BUF * m)()
         ptrs, caps, had_meta = (C.c_void_p * m)(), (C.c_size_t * m)(), []
         for i, k in enumerate(live):
+            t = at[k]
             decs[k].draw_info = modes[k](t) if callable(modes[k]) else modes[k]
             assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k](t) if callable(sharp[k]) else sharp[k])) == 0
             mk_buf(hip, bufs[i], streams[k][t])
@@ -122,7 +140,13 @@ def device_decode(hip, streams, modes=None, out420p=None, sharp=None, offset=0):
         fns = (C.c_uint32 * m)()
         rets = (C.c_int * m)()
         torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        assert hip.dsv2hip_dec_batch_device(m, decp, bufs, ptrs, caps, fns, rets) == m
+        if single:
+            for i in range(m):
+                fn = C.c_uint32(0)
+                rets[i] = hip.dsv2hip_dec_device_frame(decp[i], C.byref(bufs[i]), ptrs[i], caps[i], C.byref(fn))
+                fns[i] = fn.value
+        else:
+            assert hip.dsv2hip_dec_batch_device(m, decp, bufs, ptrs, caps, fns, rets) == m
         for i, k in enumerate(live):
             planes = None
             if outs[k] is not None and had_meta[i]:

@@ -18,7 +18,7 @@ import dsvabi as A
 import yuv_rgb as Q
 from codec_run import configure_encoder, encode_stream
 from edge_cases import packet_bound_holds, stream_frames
-from test_gpu_dec_device_out import format_stream, mk_buf, npics, same_results
+from test_gpu_dec_device_out import format_stream, lockstep, mk_buf, npics, same_results
 from test_gpu_dec_drawinfo import stream
 from test_gpu_dec_rgb import OutSurf, aligned, is_rgb, planar_oracle, plus1, reset_forms, rgb_forms, tight
 from test_gpu_dec_rgb import bind as bind_rgb
@@ -82,25 +82,28 @@ def documented_wide(dims, layout, pitch, offset):
     return all(offset % 8 == 0 and pitch(rb) % 8 == 0 and rb % (16 >> s) == 0 for rb, _ in straight)
 
 
-def decode_steps(hip, streams, specs, modes=None, sharp=None, delay=None):
+def decode_steps(hip, streams, specs, modes=None, sharp=None, delay=None, schedule=None, single=False):
     """test_gpu_dec_rgb.decode_steps for layouts with a scale: lockstep steps over one decoder per stream, spec = dict(layout, pitch,
     offset) per stream; stream k hands in its first packet at step delay[k] (so a decoder without metadata can stand beside decoders
     that deliver pictures); modes / sharp entries may be functions of the stream's packet index.  Per stream: [(return code, frame
-    number or None, planes or None)] per packet.  The reported sizes and the guards are checked at every step."""
+    number or None, planes or None)] per packet.  The reported sizes and the guards are checked at every step.  schedule:
+    test_gpu_dec_device_out.lockstep()'s, in place of delay; single: one dsv2hip_dec_surface_frame per packet in place of the step's
+    batch call."""
     bind(hip)
     n = len(streams)
-    modes, sharp, delay = modes or [0] * n, sharp or [False] * n, delay or [0] * n
+    modes, sharp = modes or [0] * n, sharp or [False] * n
     decs = [A.DECODER() for _ in range(n)]
     surfs = [None] * n
     res = [[] for _ in range(n)]
     done = [False] * n
-    for t in range(max(len(s) + d for s, d in zip(streams, delay))):
-        live = [k for k in range(n) if 0 <= t - delay[k] < len(streams[k]) and not done[k]]
+    for step in lockstep(streams, schedule, delay):
+        pkt = {k: t for k, t in step if not done[k]}
+        live = list(pkt)
         m = len(live)
         decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
         bufs, arr, had_meta = (A.BUF * m)(), (OUTSURF * m)(), []
         for i, k in enumerate(live):
-            at = t - delay[k]
+            at = pkt[k]
             decs[k].draw_info = modes[k](at) if callable(modes[k]) else modes[k]
             assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k](at) if callable(sharp[k]) else sharp[k])) == 0
             mk_buf(hip, bufs[i], streams[k][at])
@@ -116,7 +119,13 @@ def decode_steps(hip, streams, specs, modes=None, sharp=None, delay=None):
             arr[i] = surfs[k].c
         fns, rets = (C.c_uint32 * m)(), (C.c_int * m)()
         torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        assert hip.dsv2hip_dec_batch_surface(m, decp, bufs, arr, fns, rets) == m
+        if single:
+            for i in range(m):
+                fn = C.c_uint32(0)
+                rets[i] = hip.dsv2hip_dec_surface_frame(decp[i], C.byref(bufs[i]), C.byref(arr[i]), C.byref(fn))
+                fns[i] = fn.value
+        else:
+            assert hip.dsv2hip_dec_batch_surface(m, decp, bufs, arr, fns, rets) == m
         for i, k in enumerate(live):
             planes = None
             if surfs[k] is not None and had_meta[i]:

@@ -12,7 +12,7 @@ import torch
 
 import dsvabi as A
 from codec_run import configure_encoder, encode_stream
-from test_gpu_dec_device_out import bind as bind_device, format_stream, mk_buf, npics, same_results
+from test_gpu_dec_device_out import bind as bind_device, format_stream, lockstep, mk_buf, npics, same_results
 from test_gpu_dec_drawinfo import decode, stream
 from test_gpu_dec_postsharp import expected as expected_sharp
 from test_gpu_enc_surface import SURFACE, bind as bind_enc
@@ -503,9 +503,10 @@ def test_transcode_through_surfaces_without_the_host():
 
 
 # ---- 9. every way out side by side -------------------------------------------------------------------------------------------
-def frame_decode(hip, streams, modes, sharp):
-    """dsv2hip_dec_batch over one decoder per stream into pinned frames, draw_info and postsharp per decoder: per stream
-    [(return code, frame number or None, [Y, U, V] or None)] per packet"""
+def frame_decode(hip, streams, modes, sharp, out420p=None, schedule=None, single=False):
+    """dsv2hip_dec_batch over one decoder per stream into pinned frames, draw_info, postsharp and out420p per decoder: per stream
+    [(return code, frame number or None, [Y, U, V] or None)] per packet.  schedule: test_gpu_dec_device_out.lockstep()'s; single:
+    one dsv_dec per packet in place of the step's batch call."""
     from test_gpu_dec_batch import bind as bind_batch, planes_of
     bind_batch(bind(hip))
     n = len(streams)
@@ -513,19 +514,28 @@ def frame_decode(hip, streams, modes, sharp):
     for d, mode, s in zip(decs, modes, sharp):
         d.draw_info = mode
         assert hip.dsv2hip_dec_set_postsharp(C.byref(d), int(s)) == 0
-    decp = (C.POINTER(A.DECODER) * n)(*[C.pointer(d) for d in decs])
+    for d, o in zip(decs, out420p or ()):
+        assert hip.dsv2hip_dec_set_out420p(C.byref(d), int(o)) == 0
     res = [[] for _ in range(n)]
-    for t in range(len(streams[0])):
-        bufs, outs, fns, rets = (A.BUF * n)(), (C.POINTER(A.FRAME) * n)(), (C.c_uint32 * n)(), (C.c_int * n)()
-        for k in range(n):
-            mk_buf(hip, bufs[k], streams[k][t])
-        assert hip.dsv2hip_dec_batch(n, decp, bufs, outs, fns, rets) == n
-        for k in range(n):
+    for step in lockstep(streams, schedule):
+        m = len(step)
+        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k, _ in step])
+        bufs, outs, fns, rets = (A.BUF * m)(), (C.POINTER(A.FRAME) * m)(), (C.c_uint32 * m)(), (C.c_int * m)()
+        for i, (k, t) in enumerate(step):
+            mk_buf(hip, bufs[i], streams[k][t])
+        if single:
+            for i in range(m):
+                fp, fn = C.POINTER(A.FRAME)(), C.c_uint32(0)
+                rets[i] = hip.dsv_dec(decp[i], C.byref(bufs[i]), C.byref(fp), C.byref(fn))
+                outs[i], fns[i] = fp, fn.value
+        else:
+            assert hip.dsv2hip_dec_batch(m, decp, bufs, outs, fns, rets) == m
+        for i, (k, _) in enumerate(step):
             planes = None
-            if rets[k] == A.DEC_OK and outs[k]:
-                planes = planes_of(outs[k])
-                hip.dsv_frame_ref_dec(outs[k])
-            res[k].append((rets[k], fns[k] if planes is not None else None, planes))
+            if rets[i] == A.DEC_OK and outs[i]:
+                planes = planes_of(outs[i])
+                hip.dsv_frame_ref_dec(outs[i])
+            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
     for d in decs:
         hip.dsv_dec_free(C.byref(d))
     return res
