@@ -68,5 +68,9 @@ void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool
 // decoder's staging picture.  wide: every job's destination and pitch are multiples of 8 and its row is writable up to a multiple of
 // 16 >> shift bytes (scale_job_wide).  max_oh: the most rows delivered.
 void egress_scale_batch(hipStream_t s, const ScaleOutJob *d_jobs, int n, int max_oh, bool wide);
+// ... at a size the caller names: n planes (device table) area-averaged on the way (egress_resize.h) into a caller's plane or the
+// decoder's staging picture.  wide: every job's destination and pitch are multiples of 4 and its row is writable up to a multiple of
+// 4 bytes (resize_job_wide).  max_ow, max_oh: the most samples a row and the most rows delivered.
+void egress_resize_batch(hipStream_t s, const ResizeOutJob *d_jobs, int n, int max_ow, int max_oh, bool wide);
 
 } // namespace dsv2

@@ -20,6 +20,7 @@
 #include "blockstat.h"
 #include "bmc.h"
 #include "egress_rgb.h"
+#include "egress_resize.h"
 #include "egress_scale.h"
 #include "egress_uv.h"
 #include "hme.h"
@@ -2437,6 +2438,39 @@ void egress_scale_batch(hipStream_t s, const ScaleOutJob *d_jobs, int n, int max
         DSV2_LAUNCH(k_egress_scale<true>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_egress_scale<false>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- decoder egress at a size the caller names: the exact area average of include/dsv2_hip.h ------------------------------------------
+// One job per plane (ResizeOutJob, dev.h), fetched by value and pinned to scalar registers.  A workgroup of 64 x 4 threads covers 256
+// samples of 4 OUTPUT rows, a thread four samples of one row, and the grid covers the largest plane of the launch: no loop over a row
+// or over rows.  The thread's work is egress_resize.h's egress_resize_quad (which tools/egress_resize_check.cpp runs on the CPU).
+constexpr int kResizeRows = 4, kResizeLanes = 64; // output rows per workgroup; threads along a row, four samples each
+template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_resize(const ResizeOutJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const ResizeOutJob jl = job_of(tab, blockIdx.y);
+    const ResizeOutJob j{uni_ptr(jl.src), uni_ptr(jl.dst), uni(jl.sstride), uni(jl.dpitch), uni(jl.pw), uni(jl.ph), uni(jl.ow), uni(jl.oh), uni(jl.a),
+                         uni(jl.b),       uni(jl.c),       uni(jl.d),       (uint32_t) uni((int) jl.D), (uint32_t) uni((int) jl.rD),
+                         (uint32_t) uni((int) jl.rb), (uint32_t) uni((int) jl.rd)};
+    const int y = (int) blockIdx.x * kResizeRows + (int) threadIdx.y;
+    const int x0 = 4 * ((int) blockIdx.z * kResizeLanes + (int) threadIdx.x);
+    if (y >= j.oh || x0 >= j.ow) {
+        return;
+    }
+    egress_resize_quad<WIDE>(j, y, x0);
+}
+
+void egress_resize_batch(hipStream_t s, const ResizeOutJob *d_jobs, int n, int max_ow, int max_oh, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_oh + kResizeRows - 1) / kResizeRows, n, (max_ow + 4 * kResizeLanes - 1) / (4 * kResizeLanes)), block(kResizeLanes, kResizeRows);
+    if (wide) {
+        DSV2_LAUNCH(k_egress_resize<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_egress_resize<false>, grid, block, 0, s, d_jobs);
     }
 }
 

@@ -1,7 +1,8 @@
 // dec_delivery.h -- which kernels a decoded picture leaves through, reading and writing what: planned per picture, free of any device
 // call and of any allocation.  decoder.cpp plans every picture of a round with it before it sizes and fills the round's job
 // tables; tools/dec_delivery_check.cpp compiles it for the host under AddressSanitizer + UndefinedBehaviorSanitizer and sweeps
-// target kind x scale x out420p x postsharp x draw_info x alignment over synthetic addresses (tests/test_dec_delivery_cpu.py).
+// target kind x scale x out420p x postsharp x draw_info x alignment over synthetic addresses (tests/test_dec_delivery_cpu.py);
+// tools/dec_delivery_sized_check.cpp does the same for sized targets (tests/test_dec_delivery_sized_cpu.py).
 #pragma once
 
 #include <stddef.h>
@@ -28,9 +29,13 @@ struct OutTarget {
     int fw[3] = {0, 0, 0}, fh[3] = {0, 0, 0}; // FRAME: the planes' sizes (a device target's follow from the picture's and the shift)
     void *frame_alloc = nullptr;
     int shift = 0;  // device targets: every plane at 1 / 2^shift of its size, box-averaged on the way out (egress_scale.h); 0 .. 3
+    int ow = 0, oh = 0; // device targets: the picture at this size, every plane area-averaged on the way out (egress_resize.h); 0 x 0: not
+                        // sized.  Never together with a shift
     int csc = 0;    // RGB: the layout's DSV2HIP_CSC_* bits
     bool bgra = false; // RGB: bytes in memory B G R A, else R G B A
     bool device() const { return kind != FRAME; }
+    bool sized() const { return ow != 0; }
+    bool reduced() const { return shift != 0 || sized(); } // leaves through the reduction or the resampling
 };
 
 inline OutTarget target_frame(const DSV_FRAME *f)
@@ -95,22 +100,25 @@ inline void rgb_out_coefs(RgbOutJob &j, int csc)
 
 // ---- what one picture contributes to a round --------------------------------------------------------------------------------------------
 // The jobs by launch class, in the order the round launches the classes: whole-frame copy, 4:2:0 conversion, egress, overlay, sharpening
-// in place, reduction, chroma interleave, RGB conversion.  A job of a later class may read what a job of an earlier one wrote -- the
+// in place, reduction, resampling, chroma interleave, RGB conversion.  A job of a later class may read what a job of an earlier one wrote -- the
 // decoder's two staging areas -- and nothing else is shared between them.
 struct DeliveryPlan {
     CopyJob copy[1];
     To420Job to420[3];
     EgressJob eg[3];
     ScaleOutJob scl[3];
+    ResizeOutJob rsz[3];
     UvEgressJob uv[1];
     RgbOutJob rgb[1];
     DPlane overlay[1]; // the luma plane the draw_info overlay goes onto: the delivered one, or the staged one
-    int n_copy = 0, n_to420 = 0, n_eg = 0, n_scl = 0, n_uv = 0, n_rgb = 0, n_overlay = 0;
+    int n_copy = 0, n_to420 = 0, n_eg = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb = 0, n_overlay = 0;
     bool sharpen_overlaid = false; // that plane is also sharpened in place, behind the overlay (a drawn-on picture under postsharp)
     // what the round needs to pick its kernels' forms
     bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
     bool scl_wide = true;                  // every reduction job allows the unconditional vector store (bmc.hip: k_egress_scale)
     int scl_rows = 0;                      // the most rows a reduction job delivers
+    bool rsz_wide = true;                  // every resampling job allows the unconditional dword store (bmc.hip: k_egress_resize)
+    int rsz_rows = 0, rsz_cols = 0;        // the most rows / samples a row a resampling job delivers
     bool uv_wide = true, uv_conv = false;  // the interleave job allows the 16-byte form / converts to 4:2:0 (bmc.hip: k_egress_uv)
     int uv_rows = 0;                       // the chroma rows it delivers ("4:1:0" to 4:2:0: more than the source has)
     bool rgb_wide = true;                  // the RGB job allows the 16-byte form (bmc.hip: k_egress_rgb)
@@ -120,10 +128,12 @@ struct DeliveryPlan {
 // sharpening to act on: its luma goes through the egress kernel into DecImpl's staged luma plane (w x h, 16-byte aligned origin and stride)
 inline bool needs_staged_luma(const OutTarget &t, bool sharp, int draw)
 {
-    return t.device() && (t.shift || t.kind == OutTarget::RGB) && (sharp || draw);
+    return t.device() && (t.reduced() || t.kind == OutTarget::RGB) && (sharp || draw);
 }
 // the reduced planes that k_egress_uv / k_egress_rgb then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
-inline bool needs_staged_scaled(const OutTarget &t) { return t.device() && t.shift && t.kind != OutTarget::PLANAR; }
+inline bool needs_staged_scaled(const OutTarget &t) { return t.device() && t.reduced() && t.kind != OutTarget::PLANAR; }
+// ... which a sized picture needs at up to the picture's own size, a shifted one at half size
+inline bool needs_staged_full(const OutTarget &t) { return needs_staged_scaled(t) && t.sized(); }
 
 // recon: the picture as decoded (read only; its format is the stream's); out_format: the delivered picture's, the stream's or 4:2:0 under
 // out420p; staged_luma / staged_scaled: the staging areas' planes, looked at only where the predicates above hold
@@ -154,7 +164,7 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
         p.eg_sharp = p.eg_sharp || sharpen;
         p.eg_wide = p.eg_wide && egress_job_wide(j, dst.w);
     };
-    if (t.device() && (t.shift || t.kind == OutTarget::RGB)) {
+    if (t.device() && (t.reduced() || t.kind == OutTarget::RGB)) {
         // Every plane is read in place by the reduction (egress_scale.h) and / or the RGB conversion.  A sharpened and / or drawn-on
         // picture: its full-size luma is staged first, stands in for the delivered luma plane below (overlay, sharpening behind the
         // overlay) and is what the reduction or the conversion then reads.  (No 4:2:0 conversion here: the surface call refuses the pair.)
@@ -174,6 +184,19 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
                 const ScaleOutJob &sj = p.scl[p.n_scl++] = ScaleOutJob{src[c].data, red.data, src[c].stride, src[c].w, src[c].h, red.stride, s};
                 p.scl_wide = p.scl_wide && scale_job_wide(sj, staged ? red.stride : red.w);
                 p.scl_rows = red.h > p.scl_rows ? red.h : p.scl_rows;
+                src[c] = red;
+            }
+        } else if (t.sized()) {
+            // the same routes at the size the caller names: luma ow x oh, chroma dsv_mk_frame's planes for that picture, each plane by
+            // its own ratio (egress_resize.h)
+            for (int c = 0; c < 3; c++) {
+                const bool staged = t.kind == OutTarget::RGB || (t.kind == OutTarget::SEMI && c);
+                DPlane red = staged ? staged_scaled[c] : DPlane{t.plane[c], t.pitch[c], 0, 0};
+                red.w = c ? (t.ow + (1 << hs) - 1) >> hs : t.ow, red.h = c ? (t.oh + (1 << vs) - 1) >> vs : t.oh;
+                const ResizeOutJob &rj = p.rsz[p.n_rsz++] = resize_job(src[c].data, src[c].stride, src[c].w, src[c].h, red.data, red.stride, red.w, red.h);
+                p.rsz_wide = p.rsz_wide && resize_job_wide(rj, staged ? red.stride : red.w);
+                p.rsz_rows = red.h > p.rsz_rows ? red.h : p.rsz_rows;
+                p.rsz_cols = red.w > p.rsz_cols ? red.w : p.rsz_cols;
                 src[c] = red;
             }
         }

@@ -51,18 +51,28 @@ struct DecImpl {
         }
         return rgb_luma;
     }
-    // Scaled delivery (DSV2HIP_SCALE_*) into a semiplanar or an RGB surface: the reduced planes that k_egress_uv / k_egress_rgb then
-    // read are staged here.  Sized for half size -- a quarter of a picture -- and laid out once with its strides; a quarter- or eighth-
-    // size picture uses the top left of the same planes.  16-byte aligned origins and strides, so rows are readable (and, by the wide
-    // form of the reduction, writable) up to the next multiple of 16 bytes; made on first use
+    // Scaled delivery (DSV2HIP_SCALE_*) and sized delivery into a semiplanar or an RGB surface: the reduced planes that k_egress_uv /
+    // k_egress_rgb then read are staged here.  Sized for half size -- a quarter of a picture -- and laid out once with its strides; a
+    // quarter- or eighth-size picture uses the top left of the same planes.  A sized picture can be as large as the picture itself:
+    // the first one (full) replaces the staging by one of the planes' own sizes, which serves every later delivery and is kept
+    // (four times the half-size layout's bytes) until destroy_dev.  The rounds of a
+    // decoder follow one another with the stream drained in between, so nothing reads the staging that is released.  16-byte aligned
+    // origins and strides, so rows are readable (and, by the wide forms of the reduction and the resampling, writable) up to the next
+    // multiple of 16 bytes; made on first use
     DPlane scaled[3] = {{nullptr, 0, 0, 0}, {nullptr, 0, 0, 0}, {nullptr, 0, 0, 0}};
-    const DPlane *staged_scaled()
+    bool scaled_full = false;
+    const DPlane *staged_scaled(bool full)
     {
+        if (scaled[0].data && full && !scaled_full) {
+            dev_release(scaled[0].data);
+            scaled[0].data = nullptr;
+        }
         if (!scaled[0].data) {
+            scaled_full = full;
             size_t off[3], total = 0;
             for (int c = 0; c < 3; c++) {
                 const DPlane &p = dev.pics[0].recon.p[c];
-                scaled[c].w = (p.w + 1) >> 1, scaled[c].h = (p.h + 1) >> 1;
+                scaled[c].w = full ? p.w : (p.w + 1) >> 1, scaled[c].h = full ? p.h : (p.h + 1) >> 1;
                 scaled[c].stride = (scaled[c].w + 15) & ~15;
                 off[c] = total;
                 total += (size_t) scaled[c].stride * (size_t) scaled[c].h;
@@ -217,6 +227,7 @@ thread_local DecClock t_dec_clock;
 std::atomic<unsigned long long> g_uv_rounds[2]; // device rounds whose chroma interleave ran in the wide / the general form (dsv2hip_dec_surface_stats)
 std::atomic<unsigned long long> g_rgb_rounds[2]; // ... whose RGB egress ran in the wide / the general form (dsv2hip_dec_rgb_stats)
 std::atomic<unsigned long long> g_scale_rounds[2]; // ... whose reduction ran in the wide / the general form (dsv2hip_dec_scale_stats)
+std::atomic<unsigned long long> g_resize_rounds[2]; // ... whose resampling ran in the wide / the general form (dsv2hip_dec_resize_stats)
 
 // Where a picture's plane sections are parsed: DSV2_DEC_DEVICE_PARSE = 0: on the host (one pool task per picture: ~2 ms of a
 // core per 1080p P picture -- the fastest decoder while there are ~16 host cores per GPU to burn); 1: P pictures on the device, one
@@ -336,24 +347,25 @@ struct Delivery {
     Tab<EgressJob> eg;
     Tab<OverlayJob> ov;
     Tab<ScaleOutJob> scl;
+    Tab<ResizeOutJob> rsz;
     Tab<UvEgressJob> uv;
     Tab<RgbOutJob> rgb;
-    size_t room[7] = {0, 0, 0, 0, 0, 0, 0}; // entries the round's plans need of each table, in the order above
-    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_uv = 0, n_rgb = 0;
-    bool eg_wide = true, eg_sharp = false, scl_wide = true, uv_wide = true, uv_conv = false, rgb_wide = true; // DeliveryPlan's, over the round
-    int scl_rows = 0, uv_rows = 0;
+    size_t room[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // entries the round's plans need of each table, in the order above
+    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb = 0;
+    bool eg_wide = true, eg_sharp = false, scl_wide = true, rsz_wide = true, uv_wide = true, uv_conv = false, rgb_wide = true; // DeliveryPlan's, over the round
+    int scl_rows = 0, rsz_rows = 0, rsz_cols = 0, uv_rows = 0;
     bool ov_vectors = false;         // some overlay job draws motion vectors
     std::vector<DPlane> sharp_drawn; // luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
     size_t count(const std::vector<DeliveryPlan> &plans) // the arena bytes the tables of these plans take
     {
         for (const DeliveryPlan &p : plans) {
-            const int n[7] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_uv, p.n_rgb};
-            for (int k = 0; k < 7; k++) {
+            const int n[8] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_rsz, p.n_uv, p.n_rgb};
+            for (int k = 0; k < 8; k++) {
                 room[k] += (size_t) n[k];
             }
         }
         return room[0] * sizeof(CopyJob) + room[1] * sizeof(To420Job) + room[2] * sizeof(EgressJob) + room[3] * sizeof(OverlayJob) +
-               room[4] * sizeof(ScaleOutJob) + room[5] * sizeof(UvEgressJob) + room[6] * sizeof(RgbOutJob) + 7 * 16;
+               room[4] * sizeof(ScaleOutJob) + room[5] * sizeof(ResizeOutJob) + room[6] * sizeof(UvEgressJob) + room[7] * sizeof(RgbOutJob) + 8 * 16;
     }
     void take(TableArena &tabs)
     {
@@ -362,8 +374,9 @@ struct Delivery {
         eg = Tab<EgressJob>(tabs, room[2]);
         ov = Tab<OverlayJob>(tabs, room[3]);
         scl = Tab<ScaleOutJob>(tabs, room[4]);
-        uv = Tab<UvEgressJob>(tabs, room[5]);
-        rgb = Tab<RgbOutJob>(tabs, room[6]);
+        rsz = Tab<ResizeOutJob>(tabs, room[5]);
+        uv = Tab<UvEgressJob>(tabs, room[6]);
+        rgb = Tab<RgbOutJob>(tabs, room[7]);
     }
     template <class T> static void append(Tab<T> &t, int &n, const T *jobs, int count)
     {
@@ -377,10 +390,12 @@ struct Delivery {
         append(to420, n_to420, p.to420, p.n_to420);
         append(eg, n_eg, p.eg, p.n_eg);
         append(scl, n_scl, p.scl, p.n_scl);
+        append(rsz, n_rsz, p.rsz, p.n_rsz);
         append(uv, n_uv, p.uv, p.n_uv);
         append(rgb, n_rgb, p.rgb, p.n_rgb);
         eg_wide = eg_wide && p.eg_wide, eg_sharp = eg_sharp || p.eg_sharp;
         scl_wide = scl_wide && p.scl_wide, scl_rows = std::max(scl_rows, p.scl_rows);
+        rsz_wide = rsz_wide && p.rsz_wide, rsz_rows = std::max(rsz_rows, p.rsz_rows), rsz_cols = std::max(rsz_cols, p.rsz_cols);
         uv_wide = uv_wide && p.uv_wide, uv_conv = uv_conv || p.uv_conv, uv_rows = std::max(uv_rows, p.uv_rows);
         rgb_wide = rgb_wide && p.rgb_wide;
         if (p.n_overlay) {
@@ -405,6 +420,10 @@ struct Delivery {
         if (n_scl) { // behind the overlay and the sharpening of the luma planes staged for it, in front of the two kernels that read what it stages
             egress_scale_batch(bs, scl.d, n_scl, scl_rows, scl_wide);
             g_scale_rounds[scl_wide ? 0 : 1]++;
+        }
+        if (n_rsz) { // (the same place in the order: a round may hold reduced and sized pictures side by side)
+            egress_resize_batch(bs, rsz.d, n_rsz, rsz_cols, rsz_rows, rsz_wide);
+            g_resize_rounds[rsz_wide ? 0 : 1]++;
         }
         if (n_uv) { // (chroma only: the overlay and the sharpening are none of its business, the reduction of a scaled picture's chroma is)
             egress_uv_batch(bs, uv.d, n_uv, uv_rows, uv_wide, uv_conv);
@@ -636,7 +655,7 @@ void round_plan(Round &r)
         DecImpl &im = *jb.im;
         static const DPlane none = {nullptr, 0, 0, 0};
         const DPlane &luma = needs_staged_luma(jb.target, jb.sharp, jb.draw) ? im.staged_luma() : none;
-        const DPlane *scaled = needs_staged_scaled(jb.target) ? im.staged_scaled() : nullptr;
+        const DPlane *scaled = needs_staged_scaled(jb.target) ? im.staged_scaled(needs_staged_full(jb.target)) : nullptr;
         r.plans.push_back(plan_delivery(im.dev.pics[im.cur].recon, jb.out_format, jb.target, jb.sharp, jb.draw, luma, scaled));
     }
 }
@@ -797,6 +816,38 @@ bool surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], int rows[3])
     row_bytes[0] = (size_t) width, rows[0] = height;
     row_bytes[1] = semi ? 2 * cw : cw, rows[1] = ch;
     row_bytes[2] = semi ? 0 : cw, rows[2] = semi ? 0 : ch;
+    return true;
+}
+
+// ... of the picture delivered at out_w x out_h (dsv2hip_dec_batch_surface_sized): dsv_mk_frame's plane sizes for that picture in the
+// stream's format.  False in addition for a layout with a scale value, a decoder that converts to 4:2:0, a size that is not positive or
+// outside w / 8 .. w by h / 8 .. h, and a plane whose resampling the kernel's 32-bit sums do not hold (resize_allowed).
+bool sized_dims(DSV_DECODER *d, int layout, int out_w, int out_h, size_t row_bytes[3], int rows[3])
+{
+    size_t full_rb[3];
+    int full_rows[3];
+    if (layout_shift(layout) || !surface_dims(d, layout, full_rb, full_rows)) {
+        return false;
+    }
+    const DSV_META &m = d->vidmeta;
+    if ((d->ref && ((DecImpl *) d->ref)->out420p) || !resize_allowed(m.width, m.height, out_w, out_h)) {
+        return false;
+    }
+    const int hs = DSV_FORMAT_H_SHIFT(m.subsamp), vs = DSV_FORMAT_V_SHIFT(m.subsamp);
+    const int cw = (m.width + (1 << hs) - 1) >> hs, ch = (m.height + (1 << vs) - 1) >> vs;
+    const int ocw = (out_w + (1 << hs) - 1) >> hs, och = (out_h + (1 << vs) - 1) >> vs;
+    if (!resize_allowed(cw, ch, ocw, och)) {
+        return false;
+    }
+    if (is_rgb_layout(layout)) {
+        row_bytes[0] = 4 * (size_t) out_w, rows[0] = out_h;
+        row_bytes[1] = row_bytes[2] = 0, rows[1] = rows[2] = 0;
+        return true;
+    }
+    const bool semi = layout == DSV2HIP_SURFACE_SEMIPLANAR;
+    row_bytes[0] = (size_t) out_w, rows[0] = out_h;
+    row_bytes[1] = semi ? 2 * (size_t) ocw : (size_t) ocw, rows[1] = och;
+    row_bytes[2] = semi ? 0 : (size_t) ocw, rows[2] = semi ? 0 : och;
     return true;
 }
 
@@ -983,8 +1034,10 @@ int dsv2hip_dec_surface_dims(DSV_DECODER *d, int layout, size_t row_bytes[3], in
 }
 
 // dsv2hip_dec_batch_device with a surface per decoder: nothing is consumed unless every decoder that could yield a picture (it
-// has metadata) brings a surface that holds one
-int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, DSV_FNUM *fn, int *ret)
+// has metadata) brings a surface that holds one.  out_w / out_h: the sizes of dsv2hip_dec_batch_surface_sized (0 x 0: not sized), or
+// none at all
+static int dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, const int *out_w, const int *out_h,
+                             DSV_FNUM *fn, int *ret)
 {
     if (n <= 0 || !decs || !bufs || !surf || !fn || !ret) {
         return -1;
@@ -998,16 +1051,56 @@ int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const ds
             continue;
         }
         const dsv2hip_out_surface &sf = surf[k];
+        const int ow = out_w ? out_w[k] : 0, oh = out_h ? out_h[k] : 0;
+        const bool sized = ow != 0 || oh != 0;
         size_t rb[3];
         int rows[3];
-        if (!surface_dims(decs[k], sf.layout, rb, rows)) {
+        if (!(sized ? sized_dims(decs[k], sf.layout, ow, oh, rb, rows) : surface_dims(decs[k], sf.layout, rb, rows))) {
             return -1;
         }
-        if (!target_surface(sf, rb, rows, &jobs[(size_t) k].target)) {
+        OutTarget &t = jobs[(size_t) k].target;
+        if (!target_surface(sf, rb, rows, &t)) {
             return -1;
+        }
+        if (sized && (ow != decs[k]->vidmeta.width || oh != decs[k]->vidmeta.height)) { // (at the picture's own size: the plain delivery)
+            t.ow = ow, t.oh = oh;
         }
     }
     return dec_batch_run(jobs, decs, bufs, nullptr, fn, ret);
+}
+
+int dsv2hip_dec_batch_surface(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, DSV_FNUM *fn, int *ret)
+{
+    return dec_batch_surface(n, decs, bufs, surf, nullptr, nullptr, fn, ret);
+}
+
+int dsv2hip_dec_sized_dims(DSV_DECODER *d, int layout, int out_w, int out_h, size_t row_bytes[3], int rows[3])
+{
+    if (!row_bytes || !rows) {
+        return -1;
+    }
+    if (out_w == 0 && out_h == 0) { // not sized
+        return surface_dims(d, layout, row_bytes, rows) ? 0 : -1;
+    }
+    return sized_dims(d, layout, out_w, out_h, row_bytes, rows) ? 0 : -1;
+}
+
+int dsv2hip_dec_batch_surface_sized(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, const int *out_w, const int *out_h,
+                                    DSV_FNUM *fn, int *ret)
+{
+    if (!out_w || !out_h) {
+        return -1;
+    }
+    return dec_batch_surface(n, decs, bufs, surf, out_w, out_h, fn, ret);
+}
+
+int dsv2hip_dec_surface_frame_sized(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_surface *surf, int out_w, int out_h, DSV_FNUM *fn)
+{
+    int ret = DSV_DEC_ERROR;
+    if (dsv2hip_dec_batch_surface_sized(1, &d, buf, surf, &out_w, &out_h, fn, &ret) != 1) {
+        return -1;
+    }
+    return ret;
 }
 
 int dsv2hip_dec_surface_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_surface *surf, DSV_FNUM *fn)
@@ -1021,6 +1114,7 @@ int dsv2hip_dec_surface_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_su
 
 void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds, out2, reset); }
 void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset) { read_rounds(g_scale_rounds, out2, reset); }
+void dsv2hip_dec_resize_stats(unsigned long long *out2, int reset) { read_rounds(g_resize_rounds, out2, reset); }
 void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset) { read_rounds(g_uv_rounds, out2, reset); }
 
 } // extern "C"

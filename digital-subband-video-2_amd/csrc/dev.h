@@ -255,6 +255,47 @@ inline bool scale_job_wide(const ScaleOutJob &j, int row_room)
 {
     return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 7) == 0 && row_room % (16 >> j.shift) == 0;
 }
+struct ResizeOutJob { // one plane of a decoded picture on its way out at a size the caller names (dsv2hip_dec_batch_surface_sized): the exact area
+                      // average of include/dsv2_hip.h (egress_resize.h, bmc.hip: k_egress_resize) into a plane of the caller's surface, or into
+                      // the decoder's staging picture that k_egress_uv / k_egress_rgb then read; 72 bytes, fetched by value through the scalar cache
+    const uint8_t *src; // pixel (0,0) of the source plane; nothing outside [0, pw) x [0, ph) is read
+    uint8_t *dst;       // device memory, any alignment: row y at dst + y * dpitch, ow bytes of it written, oh rows
+    int sstride, dpitch;
+    int pw, ph, ow, oh; // of the source plane; of the delivered one: ow <= pw <= 8 * ow, oh <= ph <= 8 * oh
+    int a, b, c, d;     // pw / ow = a / b and ph / oh = c / d in lowest terms
+    uint32_t D;         // a * c, at most 2^24
+    uint32_t rD, rb, rd; // resize_recip of D, b, d: a quotient by one of them is mulhi(n, r) or one more (egress_resize.h: resize_div)
+};
+inline uint32_t resize_recip(uint32_t den) { return den <= 1 ? 0xffffffffu : (uint32_t) ((1ull << 32) / den); } // min(floor(2^32 / den), 2^32 - 1)
+constexpr uint32_t kResizeMaxD = 1u << 24;
+constexpr int kResizeMaxSide = 32768;
+inline int resize_gcd(int x, int y)
+{
+    while (y) {
+        const int t = x % y;
+        x = y, y = t;
+    }
+    return x;
+}
+// a plane of pw x ph to ow x oh: inside the bounds of the contract (reduction only, down to an eighth, D and the sides within what
+// 32-bit sums and coordinates hold)
+inline bool resize_allowed(int pw, int ph, int ow, int oh)
+{
+    if (ow <= 0 || oh <= 0 || ow > pw || oh > ph || pw > kResizeMaxSide || ph > kResizeMaxSide || (int64_t) 8 * ow < pw || (int64_t) 8 * oh < ph) {
+        return false;
+    }
+    return (uint64_t) (pw / resize_gcd(pw, ow)) * (uint64_t) (ph / resize_gcd(ph, oh)) <= kResizeMaxD;
+}
+inline ResizeOutJob resize_job(const uint8_t *src, int sstride, int pw, int ph, uint8_t *dst, int dpitch, int ow, int oh)
+{
+    const int gx = resize_gcd(pw, ow), gy = resize_gcd(ph, oh);
+    ResizeOutJob j{src, dst, sstride, dpitch, pw, ph, ow, oh, pw / gx, ow / gx, ph / gy, oh / gy, 0, 0, 0, 0};
+    j.D = (uint32_t) j.a * (uint32_t) j.c;
+    j.rD = resize_recip(j.D), j.rb = resize_recip((uint32_t) j.b), j.rd = resize_recip((uint32_t) j.d);
+    return j;
+}
+// row_room: bytes of a destination row that may be written (a caller's surface: ow; the staging picture: its stride)
+inline bool resize_job_wide(const ResizeOutJob &j, int row_room) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 3) == 0 && row_room % 4 == 0; }
 void to420_batch(hipStream_t s, const To420Job *d_jobs, int n, int max_w, int max_h);
 void ingest_uyvy_batch(hipStream_t s, const IngestJob *d_jobs, int n, int w, int h); // src = interleaved UYVY rows
 void planes_to_host_batch(hipStream_t s, const PlaneOutJob *d_jobs, int n, int h);

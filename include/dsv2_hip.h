@@ -658,7 +658,7 @@ int dsv2hip_dec_device_frame(DSV_DECODER *dec, DSV_BUF *buf, void *dev_out, size
  * delivers through a full-size PLANAR surface: the overlay and the sharpening act on the full-size luma BEFORE the reduction (a
  * thumbnail of a drawn-on picture is the drawn-on picture reduced).  SEMIPLANAR: the interleave of the reduced U and V planes.  RGB:
  * THE CONVERSION above applied to the reduced planes -- pixel (x, y) of the reduced picture takes reduced chroma sample (x >> hs,
- * y >> vs).  The picture later P pictures predict from is never touched.  Arbitrary ratios and other filters are out of scope.
+ * y >> vs).  The picture later P pictures predict from is never touched.  Other ratios: DELIVERY AT ANY SMALLER SIZE below; other filters are out of scope.
  * Refused in addition -- as a whole, with -1, for a decoder that has metadata: a scaled layout on a decoder with
  * dsv2hip_dec_set_out420p on (reducing behind the 4:2:0 conversion is out of scope, as RGB behind it is);
  * dsv2hip_dec_surface_dims returns -1 for that pair too.
@@ -681,6 +681,64 @@ int dsv2hip_dec_surface_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_
 void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset);
 void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset);
 void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset);
+/* DELIVERY AT ANY SMALLER SIZE -- rendition ladders (1080p to 720p, 480p, 360p), model input (640 x 360, 224 x 224): the caller names
+ * the delivered picture's size out_w x out_h, and every plane is resampled to it on the way out, without a full-size write and read
+ * in between.  The size belongs to the CALL, per picture: dsv2hip_dec_batch_surface_sized is dsv2hip_dec_batch_surface with two more
+ * arrays, dsv2hip_dec_surface_frame_sized its one-decoder form.  Semantics, ownership, return values, "surf[k] copied", "only bytes
+ * inside the rows written", any pointer alignment, any pitch from the row's bytes up to INT_MAX, cap[c] >= (rows[c] - 1) * pitch[c] +
+ * row_bytes[c] (with the sized rows, which dsv2hip_dec_sized_dims reports) and "a refused call touches nothing" are those of the
+ * plain calls.  out_w[k] == 0 && out_h[k] == 0 means NOT SIZED: entry k behaves exactly as in the plain call, DSV2HIP_SCALE_* values in
+ * its layout allowed, so one step -- and one device round -- may hold a full-size NV12 picture, a quarter-size BGRA picture and a 720p
+ * planar picture side by side.  A sized entry's layout is a valid out-surface layout WITHOUT a scale value.
+ * SIZES.  out_w <= w, out_h <= h, 8 * out_w >= w, 8 * out_h >= h: reduction only, down to an eighth, each axis on its own (anamorphic
+ * sizes are allowed); the same bounds then hold for every chroma plane.  The delivered picture has exactly dsv_mk_frame's plane sizes
+ * for out_w x out_h in the stream's format: chroma ocw = ceil(out_w >> hs) by och = ceil(out_h >> vs).  Each plane is resampled on
+ * its own, pw x ph to ow x oh, by its own ratio; where the chroma ratio differs from the luma's (odd sizes) the chroma siting shifts
+ * by a fraction of a sample, which is accepted.  dsv2hip_dec_sized_dims reports PLANAR {out_w, ocw, ocw} by {out_h, och, och};
+ * SEMIPLANAR {out_w, 2 * ocw, 0} by {out_h, och, 0}; RGB {4 * out_w, 0, 0} by {out_h, 0, 0}; with out_w == out_h == 0 it is
+ * dsv2hip_dec_surface_dims.
+ * THE RESAMPLING (the contract) is an exact area average with one rounding, in integers.  Horizontally g = gcd(pw, ow), a = pw / g,
+ * b = ow / g: source pixel i covers the interval [i*b, (i+1)*b), output sample x covers [x*a, (x+1)*a), and
+ *   wx(x, i) = max(0, min((i+1)*b, (x+1)*a) - max(i*b, x*a))
+ * is the length of their overlap; for every x the weights sum to exactly a.  Vertically the same with ph, oh: c = ph / gcd(ph, oh),
+ * d = oh / gcd(ph, oh), wy(y, j) summing to c.  With D = a * c:
+ *
+ *   out(x, y) = ( SUM_j SUM_i  wy(y,j) * wx(x,i) * P(i, j)  +  floor(D / 2) )  /  D        (integer division, exact)
+ *
+ * - No coordinate outside the plane is ever read: the last sample's interval ends exactly at pw (pw * b = ow * a), so the formula
+ *   knows no clamp and no edge repetition.
+ * - Where pw = n * ow and ph = n * oh for n = 2, 4, 8 the result is exactly THE REDUCTION above (D = 4^s, rounding 1 << (2s - 1));
+ *   with ow = pw, oh = ph it is the identity.
+ * - Where the size is not divisible the two differ: DSV2HIP_SCALE_HALF on an odd width repeats the edge pixel in the last footprint,
+ *   a sized delivery to ceil(w / 2) spreads the ratio pw / ow over the whole row.
+ * - Constant planes stay constant.  A footprint spans at most 9 source pixels per axis (ratios up to 8).
+ * - The sum is at most 255 * D + D / 2.  The call requires D <= 2^24 and every plane side <= 32 768 for every plane, so unsigned 32-bit
+ *   sums suffice and x * a, i * b stay below 2^31; no plane of up to 4096 x 4096 comes near these limits (1919 x 1079 to 1279 x 719:
+ *   D = 2 070 601).  1920 x 1080 to 1280 x 720 is a = c = 3, b = d = 2, D = 9: two taps per axis.
+ * WHAT LEAVES, as with the scaled delivery: the picture is this function of the picture that the same decoder, under the same
+ * draw_info and postsharp settings, delivers through a full-size PLANAR surface -- the overlay and the sharpening act on the
+ * full-size luma first.  SEMIPLANAR: the interleave of the resampled U and V planes.  RGB: THE CONVERSION above applied to the
+ * resampled planes.  The picture later P pictures predict from is never touched.  A sized entry with out_w == w and out_h == h
+ * delivers exactly what the plain call delivers (it IS the plain delivery and counts in no resize statistic).
+ * Refused as a whole with -1 (dsv2hip_dec_sized_dims: -1 as well): a NULL out_w / out_h array; for a decoder that has metadata:
+ * exactly one of the two sizes zero, a negative size, a size outside the bounds above, D > 2^24 or a plane side > 32 768, a
+ * DSV2HIP_SCALE_* value together with a size, a sized entry on a decoder with dsv2hip_dec_set_out420p on, and everything the plain
+ * call refuses.  A decoder without metadata may pass anything, as before.
+ * MEMORY: a sized SEMIPLANAR or RGB picture is resampled into a staging picture of the decoder's own, laid out at the planes' full
+ * sizes on the first such picture (1.5 bytes a pixel for 4:2:0) and kept until the stream's geometry changes or the decoder is freed;
+ * sized PLANAR delivery stages nothing.
+ * Out of scope: enlargement; filters other than the area average; sized delivery behind out420p; the host DSV_FRAME path (dsv_dec,
+ * dsv2hip_dec_batch, dsv2hip_dec_batch_device know nothing of a size); a sized ingest on the encoder's side.
+ * dsv2hip_dec_resize_stats: out2[0] / out2[1] = device rounds of this process whose resampling ran in the wide form (every resampled
+ * plane that goes straight into a caller's surface -- PLANAR: all three, SEMIPLANAR: luma -- has a pointer and a pitch that are
+ * multiples of 4 and a width that is a multiple of 4: the kernel stores four samples as one dword) / in the general form so far;
+ * rounds without a sized picture count as neither.  reset != 0 clears the counts afterwards.  A round's sized pictures count here
+ * only, not in dsv2hip_dec_scale_stats; their interleave / conversion counts in the two other counters as any other picture's. */
+int dsv2hip_dec_sized_dims(DSV_DECODER *dec, int layout, int out_w, int out_h, size_t row_bytes[3], int rows[3]);
+int dsv2hip_dec_batch_surface_sized(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_surface *surf, const int *out_w, const int *out_h,
+                                    DSV_FNUM *fn, int *ret);
+int dsv2hip_dec_surface_frame_sized(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_surface *surf, int out_w, int out_h, DSV_FNUM *fn);
+void dsv2hip_dec_resize_stats(unsigned long long *out2, int reset);
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the

@@ -5,7 +5,8 @@ The packets are produced on the fly with the GPU encoder (bit-identical to the r
 picture is delivered to host memory as a DSV_FRAME exactly like dsv_dec does (that D2H copy is part of the
 timed region) -- or, with --device-out, through dsv2hip_dec_batch_device into one preallocated device buffer
 per decoder, or, with --surface-out planar / nv12 / bgra, through dsv2hip_dec_batch_surface into one preallocated pitched surface per
-decoder -- with --scale 2 / 4 / 8 at half, quarter or eighth size (DSV2HIP_SCALE_*) --, so that the deliveries can be compared."""
+decoder -- with --scale 2 / 4 / 8 at half, quarter or eighth size (DSV2HIP_SCALE_*), with --size WxH at that size
+(dsv2hip_dec_batch_surface_sized) --, so that the deliveries can be compared."""
 import argparse
 import ctypes as C
 import json
@@ -32,11 +33,16 @@ def main():
     ap.add_argument("--postsharp", action="store_true", help="dsv2hip_dec_set_postsharp on every decoder")
     ap.add_argument("--surface-out", choices=["planar", "nv12", "bgra"], help="deliver the pictures into pitched device surfaces (dsv2hip_dec_batch_surface)")
     ap.add_argument("--scale", type=int, choices=[1, 2, 4, 8], default=1, help="with --surface-out: deliver at 1 / scale of the size (DSV2HIP_SCALE_HALF / _QUARTER / _EIGHTH)")
+    ap.add_argument("--size", metavar="WxH", help="with --surface-out: deliver at this size, w / 8 .. w by h / 8 .. h (dsv2hip_dec_batch_surface_sized); not with --scale")
     ap.add_argument("--pitch-align", type=int, default=256, help="with --surface-out: every row pitch is the row's bytes rounded up to a multiple of this")
     args = ap.parse_args()
     assert not (args.device_out and args.surface_out), "--device-out and --surface-out are two deliveries"
     assert args.pitch_align >= 1
     assert args.scale == 1 or args.surface_out, "--scale belongs to a surface"
+    assert not args.size or args.surface_out, "--size belongs to a surface"
+    assert not args.size or args.scale == 1, "--size and --scale are two ways to a smaller picture"
+    size = tuple(int(v) for v in args.size.lower().split("x")) if args.size else None
+    assert size is None or (len(size) == 2 and size[0] > 0 and size[1] > 0), "--size WxH"
     import dsvabi as A
     from codec_run import decode_stream, encode_stream
     from conftest import load_pkg
@@ -60,6 +66,10 @@ def main():
         hip.dsv2hip_dec_batch_surface.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(OUTSURF),
                                                   C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         hip.dsv2hip_dec_batch_surface.restype = C.c_int
+        if size:
+            hip.dsv2hip_dec_batch_surface_sized.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(OUTSURF), C.POINTER(C.c_int),
+                                                            C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+            hip.dsv2hip_dec_batch_surface_sized.restype = C.c_int
     pkg = load_pkg()
     S, G, K, Wm = args.streams, max(1, min(args.groups, args.streams)), args.steps, args.warmup
     nfr = Wm + K
@@ -94,10 +104,15 @@ def main():
         C.memmove(pbuf.data, vids[0][0], len(vids[0][0]))
         assert hip.dsv_dec(C.byref(probe), C.byref(pbuf), C.byref(C.POINTER(A.FRAME)()), C.byref(pfn)) == A.DEC_GOT_META
         rb, nrows = (C.c_size_t * 3)(), (C.c_int * 3)()
-        assert hip.dsv2hip_dec_surface_dims(C.byref(probe), layout, rb, nrows) == 0
+        if size:
+            hip.dsv2hip_dec_sized_dims.argtypes = [C.POINTER(A.DECODER), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+            hip.dsv2hip_dec_sized_dims.restype = C.c_int
+            assert hip.dsv2hip_dec_sized_dims(C.byref(probe), layout, size[0], size[1], rb, nrows) == 0, "--size: not a size the decoder delivers"
+        else:
+            assert hip.dsv2hip_dec_surface_dims(C.byref(probe), layout, rb, nrows) == 0
         hip.dsv_dec_free(C.byref(probe))
         rows = [(rb[i], nrows[i]) for i in range(3) if nrows[i]]
-        assert sum(b * r for b, r in rows) == pic_bytes or args.scale > 1 or args.surface_out == "bgra"
+        assert sum(b * r for b, r in rows) == pic_bytes or args.scale > 1 or size or args.surface_out == "bgra"
         surf_out, keep = [], []
         for _ in range(S):
             c = OUTSURF()
@@ -139,11 +154,15 @@ def main():
             caps = (C.c_size_t * m)(*[pic_bytes] * m)
         if surf_out:
             surfs = (OUTSURF * m)(*[surf_out[s] for s in ids])
+            ows, ohs = (C.c_int * m)(*[size[0] if size else 0] * m), (C.c_int * m)(*[size[1] if size else 0] * m)
         bar.wait()
         for t in range(t0, t1):
             if surf_out:
                 had_meta = [decs[s].got_metadata for s in ids]
-                assert hip.dsv2hip_dec_batch_surface(m, decp, plan[g][t], surfs, fns, rets) == m
+                if size:
+                    assert hip.dsv2hip_dec_batch_surface_sized(m, decp, plan[g][t], surfs, ows, ohs, fns, rets) == m
+                else:
+                    assert hip.dsv2hip_dec_batch_surface(m, decp, plan[g][t], surfs, fns, rets) == m
                 decoded[g] += sum(1 for i in range(m) if rets[i] == A.DEC_OK and had_meta[i])
                 continue
             if dev_out:
@@ -185,8 +204,10 @@ def main():
     delivery = "device" if args.device_out else "host"
     where = delivery + " memory"
     if args.surface_out:
-        delivery = "surface-" + args.surface_out + ("" if args.scale == 1 else "-1/%d" % args.scale)
-        where = "%s device surfaces%s, pitch a multiple of %d" % (args.surface_out, "" if args.scale == 1 else " at 1/%d of the size" % args.scale, args.pitch_align)
+        smaller = "-%dx%d" % size if size else "" if args.scale == 1 else "-1/%d" % args.scale
+        delivery = "surface-" + args.surface_out + smaller
+        where = "%s device surfaces%s, pitch a multiple of %d" % (args.surface_out, " at %dx%d" % size if size else "" if args.scale == 1 else " at 1/%d of the size" % args.scale,
+                                                                   args.pitch_align)
     result = {"metric": "decoded frames/s, 1080p 4:2:0 qp=60 gop=48 (pictures identical to the reference decoder's)", "value": round(fps, 2),
               "unit": "frames/s", "n_gpus": 1, "steps": npk - first, "ms_per_step": round(1e3 * elapsed / max(1, npk - first), 3),
               "higher_is_better": True, "dtype": "u8/int32", "data": "synthetic",
