@@ -347,6 +347,41 @@ inline bool scaled_surface_job_wide(const ScaledSurfaceJob &j)
 // n RGB surfaces, the widest max_sw pixels, the most chroma rows of the reduced picture max_crows; wide: rgb_job_wide's predicate on the SOURCE
 void ingest_rgb_scaled_batch(hipStream_t s, const ScaledRgbJob *d_jobs, int n, int max_sw, int max_crows, bool wide);
 inline bool scaled_rgb_job_wide(const ScaledRgbJob &j) { return ((((uintptr_t) j.src) | j.pitch) & 15) == 0 && (j.sw & 3) == 0; }
+// Ingest at any larger size (dsv2hip_enc_batch_surface_sized): the records of k_ingest_sized and k_ingest_rgb_sized
+// (frame.hip, ingest_resize.h), in tables of their own behind the scaled ones.
+struct SizedRatio { // pw x ph -> ow x oh, the exact area average of include/dsv2_hip.h (ResizeOutJob's arithmetic); 24 bytes
+    uint16_t a, b, c, d; // pw / ow = a / b and ph / oh = c / d in lowest terms (a, c <= 32768)
+    uint32_t D;          // a * c
+    uint32_t rD, rb, rd; // resize_recip of the final divisor (YUV: D, RGB: 256 * D), of b, of d
+};
+struct SizedSurfaceJob { // one source plane -- or the U or the V half of an interleaved one -- resampled into a bordered source plane of the
+                         // encoder; 64 bytes, fetched by value through the scalar cache
+    const uint8_t *src; // device memory, any alignment: row y at src + y * pitch, sample i at byte off + step * i of it
+    size_t pitch;
+    uint8_t *dst; // plane from dframe_alloc
+    int dstride;
+    int ow, oh; // of dst
+    SizedRatio q;
+    uint16_t step, off; // 1, 0: a planar plane; 2, 0 / 2, 1: U / V of an interleaved plane
+};
+struct SizedRgbJob { // one packed four-byte RGB surface, resampled as RGB and converted with one rounding per sample into the three bordered
+                     // source planes of the encoder; 136 bytes, fetched by value through the scalar cache
+    const uint8_t *src; // device memory, any alignment: row y at src + y * pitch, pixels of 4 bytes
+    size_t pitch;
+    uint8_t *dst[3];      // Y, U, V planes from dframe_alloc
+    int ystride, cstride; // of dst[0]; of dst[1] and dst[2]
+    int ow, oh, cw, ch;   // of dst[0]; of dst[1] and dst[2]
+    SizedRatio ql, qc;    // the surface's picture -> ow x oh; -> cw x ch
+    uint32_t ycoef, upos, uneg, vpos, vneg; // RgbJob's quads
+    uint32_t yoff;                          // 128 + 256 * ybase
+};
+// n jobs, the widest destination row max_ow samples, the most destination rows max_oh; wide: sized_job_wide of every job
+void ingest_sized_batch(hipStream_t s, const SizedSurfaceJob *d_jobs, int n, int max_ow, int max_oh, bool wide);
+// row_bytes: of the SOURCE plane's rows (an interleaved plane: of both halves together)
+inline bool sized_job_wide(const SizedSurfaceJob &j, size_t row_bytes) { return ((((uintptr_t) j.src) | j.pitch | row_bytes) & 3) == 0; }
+// n RGB surfaces, the widest luma row max_ow, the most luma plus chroma rows max_rows; wide: sized_rgb_job_wide of every job
+void ingest_rgb_sized_batch(hipStream_t s, const SizedRgbJob *d_jobs, int n, int max_ow, int max_rows, bool wide);
+inline bool sized_rgb_job_wide(const SizedRgbJob &j) { return ((((uintptr_t) j.src) | j.pitch) & 3) == 0; }
 
 void ensure_device();
 void set_default_device(int ordinal);

@@ -26,6 +26,7 @@
 #include "batch.h"
 #include "codec.h"
 #include "ingest_scale.h"
+#include "ingest_resize.h"
 #include "sideinfo.h"
 
 using namespace dsv2;
@@ -841,6 +842,8 @@ struct Job {
     bool has_surf;
     int src_w, src_h, src_shift; // has_surf through the scaled calls with a scale: the picture IN THE SURFACE is src_w x src_h and is reduced by
                                  // 1 << src_shift on ingest (ingest_scale.h); surf.layout is then the layout without its scale value.  0: unscaled
+    bool sized;                  // has_surf through the sized calls, src_shift 0: the picture IN THE SURFACE is src_w x src_h, larger than the
+                                 // encoder's, and is resampled to it on ingest (ingest_resize.h)
     const uint8_t *host_planar; // ... or packed planar picture in host memory, uploaded by the batch engine (pinned: asynchronously)
     const uint8_t *host_next;   // the picture this stream will bring to the NEXT step: uploaded under this step's kernels
     bool from_frame;            // host_planar is a DSV_FRAME packed by dsv_enc: planar whatever the encoder's packed-input format
@@ -969,6 +972,8 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
         // picture, so the records of a scaled source lie in the same room: the arena is the size it always was)
         static_assert(3 * sizeof(ScaledSurfaceJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob) && sizeof(ScaledRgbJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob),
                       "a scaled source's records fit the room reserved for a stream's surface records");
+        static_assert(3 * sizeof(SizedSurfaceJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob) && sizeof(SizedRgbJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob),
+                      "a sized source's records fit the same room");
         tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob) + sizeof(RgbJob)) + 65536);
         if (n <= cap) {
             return;
@@ -1526,6 +1531,7 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 static std::atomic<int> g_fail_next_step{0};
 static std::atomic<unsigned long long> g_surface_steps[2]; // steps whose surface ingest ran in the wide / the general form (dsv2hip_enc_surface_stats)
 static std::atomic<unsigned long long> g_rgb_steps[2];     // the same for the RGB ingest (dsv2hip_enc_rgb_stats)
+static std::atomic<unsigned long long> g_resize_steps[4];  // sized YUV ingest wide / general, sized RGB ingest wide / general (dsv2hip_enc_resize_stats)
 static std::atomic<unsigned long long> g_scale_steps[4];   // scaled YUV ingest wide / general, scaled RGB ingest wide / general (dsv2hip_enc_scale_stats)
 
 static bool surface_is_rgb(int layout) { return (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_RGBA; }
@@ -1755,12 +1761,16 @@ static void g1_enqueue(Step &st)
     st.bsj = Tab<BlockStatsJob>(sc.tabs, (size_t) n);
     int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0, n_rgb = 0, n_rj = 0;
     int n_ssurf = 0, n_ssj = 0, n_srgb = 0, n_srj = 0; // the scaled ones (Job::src_shift): tables, forms and launches of their own
+    int n_zsurf = 0, n_zsj = 0, n_zrgb = 0, n_zrj = 0; // the sized ones (Job::sized): likewise, behind the scaled ones
     for (int k = 0; k < n; k++) {
         const bool rgb = st.jobs[k].has_surf && surface_is_rgb(st.jobs[k].surf.layout), scaled = st.jobs[k].has_surf && st.jobs[k].src_shift;
-        n_rgb += rgb && !scaled;
-        n_surf += st.jobs[k].has_surf && !rgb && !scaled;
+        const bool sized = st.jobs[k].has_surf && st.jobs[k].sized;
+        n_rgb += rgb && !scaled && !sized;
+        n_surf += st.jobs[k].has_surf && !rgb && !scaled && !sized;
         n_srgb += rgb && scaled;
         n_ssurf += !rgb && scaled;
+        n_zrgb += rgb && sized;
+        n_zsurf += !rgb && sized;
     }
     Tab<SurfaceJob> sj; // only a step with surface jobs has this table (behind all the others: theirs lie where they always did)
     if (n_surf) {
@@ -1778,7 +1788,15 @@ static void g1_enqueue(Step &st)
     if (n_srgb) {
         srj = Tab<ScaledRgbJob>(sc.tabs, (size_t) n_srgb);
     }
-    bool surf_wide = true, rgb_wide = true, ssurf_wide = true, srgb_wide = true;
+    Tab<SizedSurfaceJob> zsj; // the sized sources' tables: behind the scaled ones
+    if (n_zsurf) {
+        zsj = Tab<SizedSurfaceJob>(sc.tabs, 3 * (size_t) n_zsurf);
+    }
+    Tab<SizedRgbJob> zrj;
+    if (n_zrgb) {
+        zrj = Tab<SizedRgbJob>(sc.tabs, (size_t) n_zrgb);
+    }
+    bool surf_wide = true, rgb_wide = true, ssurf_wide = true, srgb_wide = true, zsurf_wide = true, zrgb_wide = true;
     int ssurf_row_bytes = 0, srgb_sw = 0;
     for (int k = 0; k < n; k++) {
         Job &jb = st.jobs[k];
@@ -1789,6 +1807,28 @@ static void g1_enqueue(Step &st)
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
+        } else if (jb.has_surf && jb.sized && surface_is_rgb(jb.surf.layout)) {
+            const dsv2hip_surface &sf = jb.surf;
+            const DPlane *dp = cur.src.p;
+            SizedRgbJob &j = zrj.h[n_zrj++];
+            j = SizedRgbJob{(const uint8_t *) sf.plane[0], sf.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h,
+                            dp[1].w, dp[1].h, ingest_resize::sized_ratio(jb.src_w, jb.src_h, dp[0].w, dp[0].h, true),
+                            ingest_resize::sized_ratio(jb.src_w, jb.src_h, dp[1].w, dp[1].h, true), 0, 0, 0, 0, 0, 0};
+            rgb_job_coefs(j, sf.layout);
+            zrgb_wide = zrgb_wide && sized_rgb_job_wide(j);
+        } else if (jb.has_surf && jb.sized) {
+            const dsv2hip_surface &sf = jb.surf;
+            const bool semi = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR;
+            const int hs = DSV_FORMAT_H_SHIFT(cur.src.format), vs = DSV_FORMAT_V_SHIFT(cur.src.format);
+            const int scw = (jb.src_w + (1 << hs) - 1) >> hs, sch = (jb.src_h + (1 << vs) - 1) >> vs; // dsv_mk_frame's, of the SOURCE
+            for (int c = 0; c < 3; c++) { // (an interleaved plane: two records, its U and its V half)
+                const DPlane &dp = cur.src.p[c];
+                const int sp = semi && c == 2 ? 1 : c, pw = c ? scw : jb.src_w, ph = c ? sch : jb.src_h;
+                SizedSurfaceJob &j = zsj.h[n_zsj++];
+                j = SizedSurfaceJob{(const uint8_t *) sf.plane[sp], sf.pitch[sp], dp.data, dp.stride, dp.w, dp.h,
+                                    ingest_resize::sized_ratio(pw, ph, dp.w, dp.h, false), (uint16_t) (semi && c ? 2 : 1), (uint16_t) (semi && c == 2 ? 1 : 0)};
+                zsurf_wide = zsurf_wide && sized_job_wide(j, (size_t) (semi && c ? 2 * pw : pw));
+            }
         } else if (jb.has_surf && jb.src_shift && surface_is_rgb(jb.surf.layout)) {
             const dsv2hip_surface &sf = jb.surf;
             const DPlane *dp = cur.src.p;
@@ -1906,6 +1946,14 @@ static void g1_enqueue(Step &st)
     if (n_srj) {
         ingest_rgb_scaled_batch(bs, srj.d, n_srj, srgb_sw, f0.p[1].h, srgb_wide);
         g_scale_steps[srgb_wide ? 2 : 3]++;
+    }
+    if (n_zsj) {
+        ingest_sized_batch(bs, zsj.d, n_zsj, f0.p[0].w, f0.p[0].h, zsurf_wide);
+        g_resize_steps[zsurf_wide ? 0 : 1]++;
+    }
+    if (n_zrj) {
+        ingest_rgb_sized_batch(bs, zrj.d, n_zrj, f0.p[0].w, f0.p[0].h + f0.p[1].h, zrgb_wide);
+        g_resize_steps[zrgb_wide ? 2 : 3]++;
     }
     extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
     extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
@@ -2889,6 +2937,87 @@ void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset)
         }
         if (reset) {
             g_scale_steps[i].store(0);
+        }
+    }
+}
+
+/* ---- ingest at any larger size: a surface of src_w x src_h for an encoder of W x H, W <= src_w <= 8 W, H <= src_h <= 8 H ----
+ * The rule is ingest_resize.h's device-free one (plan_sized_source, sized_surface_fits).  An entry whose layout carries a scale value
+ * is the scaled call's entry; one at the encoder's own size must pass surface_ok and is the plain call's job. */
+static bool sized_surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf, int src_w, int src_h, ingest_resize::Sized *z)
+{
+    if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
+        return false;
+    }
+    if (!ingest_resize::plan_sized_source(src_w, src_h, enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, sf->layout, z) ||
+        !ingest_resize::sized_surface_fits(*z, *sf)) {
+        return false;
+    }
+    return z->src.shift != 0 || z->sized || surface_ok(enc, sf);
+}
+
+static void sized_job(Job &jb, DSV_ENCODER *enc, const dsv2hip_surface &sf, const ingest_resize::Sized &z, int src_w, int src_h, DSV_BUF *bufs)
+{
+    scaled_job(jb, enc, sf, z.src, src_w, src_h, bufs);
+    if (z.sized) {
+        jb.src_w = src_w, jb.src_h = src_h, jb.sized = true;
+    }
+}
+
+int dsv2hip_enc_batch_surface_sized(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs)
+{
+    if (n <= 0 || !encs || !surf || !src_w || !src_h || !bufs || !nbufs) {
+        return -1;
+    }
+    std::vector<ingest_resize::Sized> src((size_t) n);
+    for (int k = 0; k < n; k++) {
+        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !sized_surface_ok(encs[k], &surf[k], src_w[k], src_h[k], &src[(size_t) k])) {
+            return -1;
+        }
+    }
+    std::vector<Job> jobs((size_t) n);
+    for (int k = 0; k < n; k++) {
+        sized_job(jobs[(size_t) k], encs[k], surf[k], src[(size_t) k], src_w[k], src_h[k], bufs + 4 * k);
+    }
+    const bool ok = enc_batch_ok(jobs.data(), n);
+    for (int k = 0; k < n; k++) {
+        nbufs[k] = jobs[(size_t) k].nbuf;
+    }
+    return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
+}
+
+int dsv2hip_enc_surface_frame_sized(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
+{
+    ingest_resize::Sized z;
+    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !sized_surface_ok(enc, surf, src_w, src_h, &z)) {
+        return 0;
+    }
+    Job jb;
+    sized_job(jb, enc, *surf, z, src_w, src_h, bufs);
+    enc_batch(&jb, 1);
+    return jb.nbuf;
+}
+
+int dsv2hip_enc_sized_dims(int src_w, int src_h, int enc_w, int enc_h, int subsamp, int layout, size_t row_bytes[3], int rows[3])
+{
+    ingest_resize::Sized z;
+    if (!row_bytes || !rows || !ingest_resize::plan_sized_source(src_w, src_h, enc_w, enc_h, subsamp, layout, &z)) {
+        return -1;
+    }
+    for (int c = 0; c < 3; c++) {
+        row_bytes[c] = z.src.row_bytes[c], rows[c] = z.src.rows[c];
+    }
+    return 0;
+}
+
+void dsv2hip_enc_resize_stats(unsigned long long *out4, int reset)
+{
+    for (int i = 0; i < 4; i++) {
+        if (out4) {
+            out4[i] = g_resize_steps[i].load();
+        }
+        if (reset) {
+            g_resize_steps[i].store(0);
         }
     }
 }

@@ -11,6 +11,7 @@
 #include "dev.h"
 #include "ingest_rgb.h"
 #include "ingest_scale.h"
+#include "ingest_resize.h"
 #include "prio.h"
 
 namespace dsv2 {
@@ -537,6 +538,86 @@ void ingest_rgb_scaled_batch(hipStream_t s, const ScaledRgbJob *d_jobs, int n, i
         DSV2_LAUNCH(k_ingest_rgb_scaled<true>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_ingest_rgb_scaled<false>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- ingest at any larger size (dsv2hip_enc_batch_surface_sized) ----------------------------------------------------------------
+// The threads' work is ingest_resize.h's (which tools/ingest_resize_check.cpp runs on the CPU); the records are fetched by value and
+// pinned to scalar registers as above.  A thread: four samples of one destination row; a wavefront: 256 samples of one row; the grid:
+// 256-sample groups, groups of four rows, jobs -- no loop over a row or over rows.
+__device__ __forceinline__ SizedRatio uni_ratio(const SizedRatio &q)
+{
+    return SizedRatio{(uint16_t) uni((int) q.a), (uint16_t) uni((int) q.b), (uint16_t) uni((int) q.c), (uint16_t) uni((int) q.d),
+                      (uint32_t) uni((int) q.D), (uint32_t) uni((int) q.rD), (uint32_t) uni((int) q.rb), (uint32_t) uni((int) q.rd)};
+}
+
+template <bool WIDE> __global__ __launch_bounds__(256) void k_ingest_sized(const SizedSurfaceJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const SizedSurfaceJob jl = job_of(tab, blockIdx.z);
+    const SizedSurfaceJob j{uni_ptr(jl.src), ((size_t) (unsigned) uni((int) (jl.pitch >> 32)) << 32) | (unsigned) uni((int) jl.pitch), uni_ptr(jl.dst),
+                            uni(jl.dstride), uni(jl.ow), uni(jl.oh), uni_ratio(jl.q), (uint16_t) uni((int) jl.step), (uint16_t) uni((int) jl.off)};
+    const int y = (int) blockIdx.y * 4 + uni((int) threadIdx.y); // one destination row per wavefront
+    const int x0 = ((int) blockIdx.x * 64 + (int) threadIdx.x) * 4;
+    if (y >= j.oh || x0 >= j.ow) {
+        return;
+    }
+    ingest_sized_quad<WIDE>(j, y, x0);
+}
+
+void ingest_sized_batch(hipStream_t s, const SizedSurfaceJob *d_jobs, int n, int max_ow, int max_oh, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_ow + 255) / 256, (max_oh + 3) / 4, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_sized<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_sized<false>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// grid rows 0 .. oh - 1: luma rows; oh .. oh + ch - 1: chroma rows (U and V)
+template <bool WIDE> __global__ __launch_bounds__(256) void k_ingest_rgb_sized(const SizedRgbJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const SizedRgbJob jl = job_of(tab, blockIdx.z);
+    const SizedRgbJob j{uni_ptr(jl.src),
+                        ((size_t) (unsigned) uni((int) (jl.pitch >> 32)) << 32) | (unsigned) uni((int) jl.pitch),
+                        {uni_ptr(jl.dst[0]), uni_ptr(jl.dst[1]), uni_ptr(jl.dst[2])},
+                        uni(jl.ystride),
+                        uni(jl.cstride),
+                        uni(jl.ow),
+                        uni(jl.oh),
+                        uni(jl.cw),
+                        uni(jl.ch),
+                        uni_ratio(jl.ql),
+                        uni_ratio(jl.qc),
+                        (uint32_t) uni((int) jl.ycoef),
+                        (uint32_t) uni((int) jl.upos),
+                        (uint32_t) uni((int) jl.uneg),
+                        (uint32_t) uni((int) jl.vpos),
+                        (uint32_t) uni((int) jl.vneg),
+                        (uint32_t) uni((int) jl.yoff)};
+    const int gy = (int) blockIdx.y * 4 + uni((int) threadIdx.y);
+    const int x0 = ((int) blockIdx.x * 64 + (int) threadIdx.x) * 4;
+    if (gy >= j.oh + j.ch || x0 >= (gy < j.oh ? j.ow : j.cw)) {
+        return;
+    }
+    ingest_sized_rgb_quad<WIDE>(j, gy, x0);
+}
+
+void ingest_rgb_sized_batch(hipStream_t s, const SizedRgbJob *d_jobs, int n, int max_ow, int max_rows, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((max_ow + 255) / 256, (max_rows + 3) / 4, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_rgb_sized<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_rgb_sized<false>, grid, block, 0, s, d_jobs);
     }
 }
 

@@ -517,6 +517,68 @@ int  dsv2hip_enc_surface_frame_scaled(DSV_ENCODER *enc, const dsv2hip_surface *s
 int  dsv2hip_enc_scaled_dims(int src_w, int src_h, int subsamp, int layout, int *enc_w, int *enc_h,
                              size_t row_bytes[3], int rows[3]);
 void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset);
+/* INGEST AT ANY LARGER SIZE -- a rendition ladder (720p, 480p, 360p, 224 x 224) from ONE 1080p surface: the mirror image of the
+ * decoder's sized delivery below.  An encoder of W x H reads a surface that holds src_w[k] x src_h[k], and the picture is resampled to
+ * W x H in the ingest pass by THE RESAMPLING defined at dsv2hip_dec_batch_surface_sized: the exact area average, one rounding.
+ * An entry's meaning follows from its layout:
+ *   - a layout with a DSV2HIP_SCALE_* value: the entry is exactly dsv2hip_enc_batch_surface_scaled's entry -- the same rule
+ *     (W = ceil(src_w / n), H = ceil(src_h / n)), the same edge-repeating reduction, the same kernels, the same counters;
+ *   - a layout without one: the entry is SIZED.  Any source with W <= src_w <= 8 W and H <= src_h <= 8 H is allowed, each axis on its
+ *     own, anamorphic sizes included;
+ *   - a sized entry with src_w = W and src_h = H is the plain ingest: it takes the plain path, must pass what the plain call asks,
+ *     and counts in dsv2hip_enc_surface_stats / dsv2hip_enc_rgb_stats and in no resize statistic.
+ * One step may hold plain, scaled and sized entries of any layouts side by side.  The source planes are dsv_mk_frame's for
+ * src_w x src_h in the encoder's chroma format (scw x sch the chroma size of THAT picture), as for the scaled call:
+ *   PLANAR      {src_w, scw, scw} bytes by {src_h, sch, sch} rows
+ *   SEMIPLANAR  {src_w, 2 * scw}  bytes by {src_h, sch}      rows
+ *   BGRA / RGBA {4 * src_w}       bytes by {src_h}           rows
+ * and every pitch must be at least its SOURCE row's bytes.  dsv2hip_enc_sized_dims reports these planes for an encoder of
+ * enc_w x enc_h: 0, or -1 for exactly what the batch call would refuse about sizes, layout or format (and for a NULL pointer).
+ *
+ * THE CONTRACT (the packets are exactly dsv_enc's on the planar W x H picture defined here).
+ * YUV surfaces: each SOURCE plane P, pw x ph, is resampled on its own to the encoder's plane ow x oh (luma W x H, chroma cw x ch):
+ * with pw / ow = a / b and ph / oh = c / d in lowest terms, D = a * c and wx, wy the overlap lengths of the resampling,
+ *
+ *   out(x, y) = ( SUM j SUM i  wy(y,j) * wx(x,i) * P(i, j)  +  floor(D / 2) ) / D
+ *
+ * SEMIPLANAR: the de-interleaved U and V planes are resampled.  The bounds are the resampling's, per plane: D <= 2^24, sides
+ * <= 32 768.  No coordinate outside the plane exists in the formula, and none is read.  So a picture decoded at full size into a surface
+ * and encoded through the sized call gives the packets of the same picture decoded at that size (dsv2hip_dec_batch_surface_sized,
+ * PLANAR) and encoded through the plain call; and where src = n * enc for n = 2, 4, 8 the result equals the scaled call's.
+ * RGB surfaces: ONE rounding per sample -- the packed picture is resampled as RGB and the matrix is applied to the weighted sums.
+ * Let w(x,y; i,j) = wy * wx for src_w x src_h -> ow x oh, where ow x oh = W x H for luma (D) and = cw x ch, the encoder's chroma
+ * plane, for chroma (Dc; a ratio of up to 32 per axis).  With S_R = SUM w * R, S_G, S_B and the rows and ybase of the table above:
+ *
+ *   Y'(x,y)   = ( yr*S_R + yg*S_G + yb*S_B + (128 + 256*ybase) * D ) / (256 * D)
+ *   U'(cx,cy) = min(255, ( ur*S_R + ug*S_G + ub*S_B + 32896 * Dc ) / (256 * Dc) )
+ *   V' likewise with vr, vg, vb
+ *
+ * Where src = n * enc and W, H are multiples of the chroma subsampling this is exactly the scaled call's formula.  A footprint of
+ * equal pixels gives what one pixel gives (the weights of a sample add up to D).  Every numerator is non-negative: the weights are,
+ * and a chroma row's negative coefficients times 255 stay below 32 896.  For every plane of an RGB source the call requires
+ * D <= 65 535 (Dc likewise) in addition: the weights of a sample add up to D, so a channel sum is at most 255 * D, a matrix row's
+ * positive part at most 128 * 255 * D (luma: 256 * 255 * D less what the bias takes: the largest luma numerator of the four presets is
+ * 65 408 * D), and with the bias every numerator is at most 65 536 * D, which fits 32 bits exactly when D <= 65 535; the divisor
+ * 256 * D is then below 2^24 (tests/test_ingest_resize_cpu.py checks both over the extreme colours of all four presets).
+ * 1920 x 1080 -> 1280 x 720 (D = 9, Dc = 9), 854 x 480 (D = 8 640, Dc = 17 280 at 4:2:0) and 224 x 224 (D = 8 100, Dc = 16 200) all pass
+ * this bound (224 x 224 is taken from a source of up to 1792 wide: 1920 > 8 * 224 is outside the ratio, for YUV and RGB alike).
+ * 1920 x 1080 -> 1918 x 1078 (D = 960 * 540 = 518 400) is refused for an RGB source and passes for a YUV one.
+ * REFUSALS.  The batch call returns -1 before any encoder, counter, buffer or nbufs entry is touched, and the one-frame call returns
+ * 0, for: everything the scaled call refuses; a sized entry outside the bounds above, per plane; src_w or src_h <= 0.
+ * dsv2hip_enc_batch_surface, dsv2hip_enc_surface_frame and the scaled calls are unchanged: the scaled call with s = 0 and a source
+ * size that is not the encoder's stays refused.
+ * dsv2hip_enc_resize_stats: out4[0] / out4[1] = lockstep steps of this process whose sized YUV ingest ran in the wide form (every
+ * sized YUV source plane of the step: pointer, pitch and SOURCE row bytes multiples of 4) / in the general form; out4[2] / out4[3] =
+ * the same for the sized RGB ingest (every sized RGB surface of the step: pointer and pitch multiples of 4).  Sized entries count
+ * here only; scaled entries count in dsv2hip_enc_scale_stats, own-size entries in the plain surfaces' counters.  reset != 0 clears
+ * the counts afterwards.
+ * Out of scope: enlargement; filters other than the area average; three-byte RGB and 10-bit; host surfaces. */
+int  dsv2hip_enc_batch_surface_sized(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf,
+                                     const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs);
+int  dsv2hip_enc_surface_frame_sized(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs);
+int  dsv2hip_enc_sized_dims(int src_w, int src_h, int enc_w, int enc_h, int subsamp, int layout,
+                            size_t row_bytes[3], int rows[3]);
+void dsv2hip_enc_resize_stats(unsigned long long *out4, int reset);
 /* the same step with the pictures in HOST memory, as dsv_enc (dsv_encoder.c:1430) receives them: host_planar[k] is
  * stream k's packed planar picture of this step.  host_next (NULL, or NULL entries, allowed) names the picture each
  * stream will bring to the NEXT call: it is uploaded on a copy stream under this step's kernels, and the next call
@@ -728,7 +790,7 @@ void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset);
  * sizes on the first such picture (1.5 bytes a pixel for 4:2:0) and kept until the stream's geometry changes or the decoder is freed;
  * sized PLANAR delivery stages nothing.
  * Out of scope: enlargement; filters other than the area average; sized delivery behind out420p; the host DSV_FRAME path (dsv_dec,
- * dsv2hip_dec_batch, dsv2hip_dec_batch_device know nothing of a size); a sized ingest on the encoder's side.
+ * dsv2hip_dec_batch, dsv2hip_dec_batch_device know nothing of a size).  (The encoder's side: dsv2hip_enc_batch_surface_sized, above.)
  * dsv2hip_dec_resize_stats: out2[0] / out2[1] = device rounds of this process whose resampling ran in the wide form (every resampled
  * plane that goes straight into a caller's surface -- PLANAR: all three, SEMIPLANAR: luma -- has a pointer and a pitch that are
  * multiples of 4 and a width that is a multiple of 4: the kernel stores four samples as one dword) / in the general form so far;

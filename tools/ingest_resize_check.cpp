@@ -1,0 +1,661 @@
+// ingest_resize_check.cpp -- the bodies of k_ingest_sized and k_ingest_rgb_sized (csrc/ingest_resize.h) run as plain C++ on the CPU,
+// thread by thread in the kernels' grid, over a sweep of ratios, forms, layouts, chroma formats, byte orders, presets, pitches and
+// pointer offsets; meant to be built with AddressSanitizer and UndefinedBehaviorSanitizer, which see every read outside a source's
+// allocation (an exact-size heap block: the last row has nothing behind it), every write outside a plane's and every misaligned word
+// access.  The program itself compares every plane with the contract of include/dsv2_hip.h restated here sample by sample in 64-bit
+// integers (nothing shared with the kernels' text), checks that no byte outside the planes' ow x oh changed (the border and 64 guard
+// bytes round every plane) and that no source byte changed, and sweeps the device-free validity rule
+// (ingest_resize::plan_sized_source, sized_surface_fits) against a restatement.  tests/test_ingest_resize_cpu.py builds and runs it:
+//   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+//         -I digital-subband-video-2_amd/csrc tools/ingest_resize_check.cpp -o ingest_resize_check && ./ingest_resize_check [--dump DIR]
+// --dump DIR writes, for a few named cases, NAME.src (the source planes, rows of exactly their bytes, plane behind plane) and NAME.yuv
+// (the encoder's planes, packed), DIR/validity.txt: one line "name result" per case of the refusal matrix, and DIR/cases.txt: one
+// line per picture-level case that ran ("yuv|rgb form layout format sw sh w h content pitch offset").
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "ingest_resize.h"
+
+using namespace dsv2;
+
+namespace {
+
+constexpr uint8_t kGuard = 0xA5;
+constexpr int kGuardBytes = 64;
+
+const int kMatrix[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},
+                           {47, 157, 16, -26, -86, 112, 112, -102, -10},
+                           {77, 150, 29, -43, -85, 128, 128, -107, -21},
+                           {54, 183, 19, -29, -99, 128, 128, -116, -12}};
+int preset_of(int csc) { return ((csc & 0x200) ? 2 : 0) + ((csc & 0x100) ? 1 : 0); }
+int ceil_shift(int v, int s) { return (v + (1 << s) - 1) >> s; }
+long gcd_of(long x, long y) { return y ? gcd_of(y, x % y) : x; }
+
+// ---- planes as dframe_alloc lays them out (32-pixel border, stride a multiple of 16, 16-byte aligned origin), 64 guard bytes round them
+struct Plane {
+    uint8_t *alloc, *first, *org;
+    size_t bytes;
+    int stride, w, h;
+    Plane(int w_, int h_) : w(w_), h(h_)
+    {
+        stride = (w + 2 * kBorder + 15) & ~15;
+        bytes = (size_t) stride * (size_t) (h + 2 * kBorder) + 2 * kGuardBytes;
+        alloc = (uint8_t *) aligned_alloc(16, (bytes + 15) & ~(size_t) 15);
+        memset(alloc, kGuard, bytes);
+        first = alloc + kGuardBytes;
+        org = first + (size_t) kBorder * stride + kBorder;
+    }
+    ~Plane() { free(alloc); }
+    Plane(const Plane &) = delete;
+    // every byte is the guard value except the w x h samples, which are want(x, y)
+    template <class F> bool equals(F want, long *bad_x, long *bad_y, int *got, int *expected) const
+    {
+        for (size_t i = 0; i < bytes; i++) {
+            const long at = (long) i - kGuardBytes;
+            long y = at >= 0 ? at / stride - kBorder : -1000, x = at >= 0 ? at % stride - kBorder : -1000;
+            const bool inside = at >= 0 && x >= 0 && x < w && y >= 0 && y < h;
+            const int e = inside ? want((int) x, (int) y) : kGuard;
+            if (alloc[i] != e) {
+                *bad_x = x, *bad_y = y, *got = alloc[i], *expected = e;
+                return false;
+            }
+        }
+        return true;
+    }
+};
+
+// an exact-size source block: `offset` bytes, then rows of rb bytes `pitch` apart, nothing behind the last row
+// content: -1 noise with some saturated rows, else the constant
+struct SourceBlock {
+    uint8_t *alloc, *src;
+    size_t bytes, pitch;
+    std::vector<uint8_t> was;
+    SourceBlock(size_t rb, int rows, int pitch_kind, int offset, int content, unsigned &seed)
+    {
+        pitch = pitch_kind == 0 ? rb : pitch_kind == 1 ? rb + 1 : ((rb + 15) & ~(size_t) 15) + 16;
+        bytes = (size_t) offset + (size_t) (rows - 1) * pitch + rb;
+        if (posix_memalign((void **) &alloc, 16, bytes) != 0) {
+            abort();
+        }
+        src = alloc + offset;
+        for (size_t i = 0; i < bytes; i++) {
+            seed = seed * 1664525u + 1013904223u;
+            alloc[i] = content < 0 ? (uint8_t) (seed >> 24) : (uint8_t) content;
+        }
+        if (content < 0) {
+            for (int y = 0; y < rows; y += 3) { // some rows saturated, where the sums are extreme
+                memset(src + (size_t) y * pitch, (y % 2) ? 0 : 255, rb);
+            }
+        }
+        was.assign(alloc, alloc + bytes);
+    }
+    bool untouched() const { return memcmp(was.data(), alloc, bytes) == 0; }
+    ~SourceBlock() { free(alloc); }
+    SourceBlock(const SourceBlock &) = delete;
+};
+
+const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+const int kSubsamp[5] = {DSV_SUBSAMP_444, DSV_SUBSAMP_422, DSV_SUBSAMP_420, DSV_SUBSAMP_411, DSV_SUBSAMP_410};
+const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
+long g_cases[2] = {0, 0}, g_wide[2] = {0, 0}, g_planes = 0;
+const char *g_dump = nullptr;
+FILE *g_case_list = nullptr;
+
+void dump_rows(FILE *f, const uint8_t *p, size_t pitch, size_t rb, int rows)
+{
+    for (int y = 0; y < rows; y++) {
+        fwrite(p + (size_t) y * pitch, 1, rb, f);
+    }
+}
+FILE *dump_open(const char *name, const char *ext)
+{
+    FILE *f = fopen((std::string(g_dump) + "/" + name + ext).c_str(), "wb");
+    if (!f) {
+        fprintf(stderr, "cannot write into %s\n", g_dump);
+        exit(1);
+    }
+    return f;
+}
+
+// ---- the resampling, restated: the overlap of [lo0, hi0) and [lo1, hi1) --------------------------------------------------------
+long overlap(long lo0, long hi0, long lo1, long hi1)
+{
+    const long lo = lo0 > lo1 ? lo0 : lo1, hi = hi0 < hi1 ? hi0 : hi1;
+    return hi > lo ? hi - lo : 0;
+}
+// SUM SUM wy * wx * at(i, j) over the pixels round the sample's footprint (each is asked for its weight; they must add up to D), and D
+template <class F> long weighted_sum(F at, int pw, int ph, int ow, int oh, int x, int y, long *D)
+{
+    const long gx = gcd_of(pw, ow), gy = gcd_of(ph, oh), a = pw / gx, b = ow / gx, c = ph / gy, d = oh / gy;
+    long sum = 0, wsum = 0;
+    const int j_lo = (int) ((long) y * c / d), i_lo = (int) ((long) x * a / b); // (pixels before these weigh 0; behind the window too)
+    for (int j = j_lo > 0 ? j_lo - 1 : 0; j < ph && j <= j_lo + (int) (c / d) + 2; j++) {
+        const long wy = overlap((long) j * d, (long) (j + 1) * d, (long) y * c, (long) (y + 1) * c);
+        for (int i = i_lo > 0 ? i_lo - 1 : 0; i < pw && i <= i_lo + (int) (a / b) + 2; i++) {
+            const long wx = overlap((long) i * b, (long) (i + 1) * b, (long) x * a, (long) (x + 1) * a);
+            if (wx * wy) {
+                sum += wy * wx * at(i, j);
+            }
+            wsum += wx * wy;
+        }
+    }
+    *D = a * c;
+    if (wsum != a * c) {
+        fprintf(stderr, "restatement: the weights of sample (%d, %d) of %dx%d -> %dx%d add up to %ld, not D = %ld\n", x, y, pw, ph, ow, oh, wsum, a * c);
+        exit(1);
+    }
+    return sum;
+}
+
+template <bool WIDE> void run_yuv_grid(const SizedSurfaceJob &j)
+{
+    for (int by = 0; by < (j.oh + 3) / 4; by++) {
+        for (int bx = 0; bx < (j.ow + 255) / 256; bx++) {
+            for (int ty = 0; ty < 4; ty++) {
+                for (int tx = 0; tx < 64; tx++) {
+                    const int y = by * 4 + ty, x0 = (bx * 64 + tx) * 4;
+                    if (y < j.oh && x0 < j.ow) { // (the kernel's guard)
+                        ingest_sized_quad<WIDE>(j, y, x0);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- one plane: pw x ph -> ow x oh, step / off as the kernel's job has them ------------------------------------------------------
+void check_plane(int pw, int ph, int ow, int oh, int step, int off, int pitch_kind, int offset, int want_wide, int content = -1)
+{
+    if (!resize_allowed(pw, ph, ow, oh)) {
+        fprintf(stderr, "check_plane: %dx%d -> %dx%d is outside the bounds\n", pw, ph, ow, oh);
+        exit(1);
+    }
+    unsigned seed = 131u * (unsigned) pw + 7u * (unsigned) ph + 1009u * (unsigned) ow + 17u * (unsigned) oh + (unsigned) (step + pitch_kind + offset);
+    const size_t rb = (size_t) step * (size_t) pw;
+    SourceBlock blk(rb, ph, pitch_kind, offset, content, seed);
+    Plane P(ow, oh);
+    const SizedSurfaceJob j{blk.src, blk.pitch, P.org, P.stride, ow, oh, ingest_resize::sized_ratio(pw, ph, ow, oh, false), (uint16_t) step, (uint16_t) off};
+    const bool can_wide = sized_job_wide(j, rb), wide = want_wide && can_wide;
+    wide ? run_yuv_grid<true>(j) : run_yuv_grid<false>(j);
+    g_planes++;
+    auto at = [&](int x, int y) { return (long) blk.src[(size_t) y * blk.pitch + (size_t) (x * step + off)]; };
+    long bx, by;
+    int got, want;
+    if (!P.equals(
+            [&](int x, int y) {
+                long D;
+                const long s = weighted_sum(at, pw, ph, ow, oh, x, y, &D);
+                return (int) ((s + D / 2) / D);
+            },
+            &bx, &by, &got, &want)) {
+        fprintf(stderr, "MISMATCH plane %dx%d -> %dx%d step=%d off=%d pitch_kind=%d offset=%d wide=%d: row %ld column %ld is %02x, expected %02x\n", pw, ph, ow,
+                oh, step, off, pitch_kind, offset, (int) wide, by, bx, got, want);
+        exit(1);
+    }
+    if (!blk.untouched()) {
+        fprintf(stderr, "a source plane was written: %dx%d -> %dx%d\n", pw, ph, ow, oh);
+        exit(1);
+    }
+}
+
+// ---- one YUV picture: sw x sh -> W x H in a chroma format, planar or semiplanar ----------------------------------------------------
+void check_yuv(int sw, int sh, int W, int H, int fmt, bool semi, int pitch_kind, int offset, bool force_general, int content = -1,
+               const char *dump_name = nullptr)
+{
+    const int hs = kHs[fmt], vs = kVs[fmt];
+    const int scw = ceil_shift(sw, hs), sch = ceil_shift(sh, vs), cw = ceil_shift(W, hs), ch = ceil_shift(H, vs);
+    unsigned seed = 977u * (unsigned) sw + 31u * (unsigned) sh + 7u * (unsigned) W + (unsigned) (fmt + 5 * pitch_kind + 20 * offset + (semi ? 320 : 0));
+    const int nsrc = semi ? 2 : 3;
+    const size_t rb[3] = {(size_t) sw, semi ? 2 * (size_t) scw : (size_t) scw, (size_t) scw};
+    const int rows[3] = {sh, sch, sch};
+    SourceBlock *blk[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < nsrc; c++) {
+        blk[c] = new SourceBlock(rb[c], rows[c], pitch_kind, offset, content, seed);
+    }
+    Plane Y(W, H), U(cw, ch), V(cw, ch);
+    Plane *dst[3] = {&Y, &U, &V};
+    SizedSurfaceJob job[3];
+    bool wide = !force_general;
+    for (int c = 0; c < 3; c++) {
+        const int sp = semi && c == 2 ? 1 : c, pw = c ? scw : sw, ph = c ? sch : sh;
+        if (!resize_allowed(pw, ph, dst[c]->w, dst[c]->h)) {
+            fprintf(stderr, "check_yuv: plane %d of %dx%d -> %dx%d is outside the bounds\n", c, sw, sh, W, H);
+            exit(1);
+        }
+        job[c] = SizedSurfaceJob{blk[sp]->src, blk[sp]->pitch, dst[c]->org, dst[c]->stride, dst[c]->w, dst[c]->h,
+                                 ingest_resize::sized_ratio(pw, ph, dst[c]->w, dst[c]->h, false), (uint16_t) (semi && c ? 2 : 1),
+                                 (uint16_t) (semi && c == 2 ? 1 : 0)};
+        wide = wide && sized_job_wide(job[c], rb[sp]);
+    }
+    for (int c = 0; c < 3; c++) {
+        wide ? run_yuv_grid<true>(job[c]) : run_yuv_grid<false>(job[c]);
+    }
+    g_cases[0]++;
+    g_wide[0] += wide;
+    if (g_case_list) {
+        fprintf(g_case_list, "yuv %s %s %s %d %d %d %d %d %d %d\n", wide ? "wide" : "general", semi ? "semi" : "planar", kFmtName[fmt], sw, sh, W, H, content,
+                pitch_kind, offset);
+    }
+    for (int c = 0; c < 3; c++) {
+        const SourceBlock *b = blk[semi && c == 2 ? 1 : c];
+        const int step = semi && c ? 2 : 1, first = semi && c == 2 ? 1 : 0;
+        auto at = [&](int x, int y) { return (long) b->src[(size_t) y * b->pitch + (size_t) (x * step + first)]; };
+        long bx, by;
+        int got, want;
+        if (!dst[c]->equals(
+                [&](int x, int y) {
+                    long D;
+                    const long s = weighted_sum(at, c ? scw : sw, c ? sch : sh, dst[c]->w, dst[c]->h, x, y, &D);
+                    return (int) ((s + D / 2) / D);
+                },
+                &bx, &by, &got, &want)) {
+            fprintf(stderr, "MISMATCH yuv %dx%d -> %dx%d %s semi=%d pitch_kind=%d offset=%d wide=%d: plane %d row %ld column %ld is %02x, expected %02x\n", sw,
+                    sh, W, H, kFmtName[fmt], (int) semi, pitch_kind, offset, (int) wide, c, by, bx, got, want);
+            exit(1);
+        }
+    }
+    for (int c = 0; c < nsrc; c++) {
+        if (!blk[c]->untouched()) {
+            fprintf(stderr, "a source plane was written: yuv %dx%d -> %dx%d\n", sw, sh, W, H);
+            exit(1);
+        }
+    }
+    if (dump_name && g_dump) {
+        FILE *fs = dump_open(dump_name, ".src"), *fy = dump_open(dump_name, ".yuv");
+        for (int c = 0; c < nsrc; c++) {
+            dump_rows(fs, blk[c]->src, blk[c]->pitch, rb[c], rows[c]);
+        }
+        for (int c = 0; c < 3; c++) {
+            dump_rows(fy, dst[c]->org, (size_t) dst[c]->stride, (size_t) dst[c]->w, dst[c]->h);
+        }
+        fclose(fs);
+        fclose(fy);
+    }
+    for (int c = 0; c < nsrc; c++) {
+        delete blk[c];
+    }
+}
+
+// ---- RGB ---------------------------------------------------------------------------------------------------------------------
+// the job's quads, restated from the header's table: bytes in the surface's channel order
+void fill_coefs(SizedRgbJob &j, bool bgra, int csc)
+{
+    const int *m = kMatrix[preset_of(csc)];
+    uint32_t q[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+    for (int row = 0; row < 3; row++) {
+        for (int c = 0; c < 3; c++) {
+            const int v = m[3 * row + c], at = 8 * (bgra ? 2 - c : c);
+            q[row][v < 0] |= (uint32_t) (v < 0 ? -v : v) << at;
+        }
+    }
+    j.ycoef = q[0][0], j.upos = q[1][0], j.uneg = q[1][1], j.vpos = q[2][0], j.vneg = q[2][1];
+    j.yoff = 128u + ((csc & 0x200) ? 0u : 256u * 16u);
+}
+
+template <bool WIDE> void run_rgb_grid(const SizedRgbJob &j)
+{
+    for (int by = 0; by < (j.oh + j.ch + 3) / 4; by++) {
+        for (int bx = 0; bx < (j.ow + 255) / 256; bx++) {
+            for (int ty = 0; ty < 4; ty++) {
+                for (int tx = 0; tx < 64; tx++) {
+                    const int gy = by * 4 + ty, x0 = (bx * 64 + tx) * 4;
+                    if (!(gy >= j.oh + j.ch || x0 >= (gy < j.oh ? j.ow : j.cw))) { // (the kernel's guard)
+                        ingest_sized_rgb_quad<WIDE>(j, gy, x0);
+                    }
+                }
+            }
+        }
+    }
+}
+
+void check_rgb(int sw, int sh, int W, int H, int fmt, bool bgra, int csc, int pitch_kind, int offset, bool force_general, int content = -1,
+               const char *dump_name = nullptr)
+{
+    const int hs = kHs[fmt], vs = kVs[fmt], cw = ceil_shift(W, hs), ch = ceil_shift(H, vs);
+    ingest_resize::Sized z;
+    if (!ingest_resize::plan_sized_source(sw, sh, W, H, kSubsamp[fmt], (bgra ? DSV2HIP_SURFACE_BGRA : DSV2HIP_SURFACE_RGBA) | csc, &z)) {
+        fprintf(stderr, "check_rgb: %dx%d -> %dx%d %s is refused\n", sw, sh, W, H, kFmtName[fmt]);
+        exit(1);
+    }
+    unsigned seed = 613u * (unsigned) sw + 29u * (unsigned) sh + 3u * (unsigned) W + (unsigned) (fmt + 5 * pitch_kind + 20 * offset + csc);
+    SourceBlock blk(4 * (size_t) sw, sh, pitch_kind, offset, content, seed);
+    Plane Y(W, H), U(cw, ch), V(cw, ch);
+    Plane *dst[3] = {&Y, &U, &V};
+    SizedRgbJob j{blk.src, blk.pitch, {Y.org, U.org, V.org}, Y.stride, U.stride, W, H, cw, ch, ingest_resize::sized_ratio(sw, sh, W, H, true),
+                  ingest_resize::sized_ratio(sw, sh, cw, ch, true), 0, 0, 0, 0, 0, 0};
+    fill_coefs(j, bgra, csc);
+    const bool wide = !force_general && sized_rgb_job_wide(j);
+    wide ? run_rgb_grid<true>(j) : run_rgb_grid<false>(j);
+    g_cases[1]++;
+    g_wide[1] += wide;
+    if (g_case_list) {
+        fprintf(g_case_list, "rgb %s %s%03x %s %d %d %d %d %d %d %d\n", wide ? "wide" : "general", bgra ? "bgra" : "rgba", csc, kFmtName[fmt], sw, sh, W, H,
+                content, pitch_kind, offset);
+    }
+    const int *m = kMatrix[preset_of(csc)];
+    for (int c = 0; c < 3; c++) {
+        long bx, by;
+        int got, want;
+        if (!dst[c]->equals(
+                [&](int x, int y) {
+                    long D, S[3];
+                    for (int k = 0; k < 3; k++) { // R, G, B
+                        const int byte = bgra ? 2 - k : k;
+                        S[k] = weighted_sum([&](int i, int jj) { return (long) blk.src[(size_t) jj * blk.pitch + 4 * (size_t) i + (size_t) byte]; }, sw, sh,
+                                            dst[c]->w, dst[c]->h, x, y, &D);
+                    }
+                    const long lin = m[3 * c] * S[0] + m[3 * c + 1] * S[1] + m[3 * c + 2] * S[2];
+                    const long num = lin + (c ? 32896L : 128 + 256 * ((csc & 0x200) ? 0L : 16L)) * D;
+                    if (num < 0 || num >= (1L << 32) || 256 * D >= (1L << 24)) {
+                        fprintf(stderr, "a numerator or divisor leaves its range: %ld / (256 * %ld)\n", num, D);
+                        exit(1);
+                    }
+                    const long v = num / (256 * D);
+                    return (int) (c && v > 255 ? 255 : v);
+                },
+                &bx, &by, &got, &want)) {
+            fprintf(stderr, "MISMATCH rgb %dx%d -> %dx%d %s bgra=%d csc=%03x pitch_kind=%d offset=%d wide=%d: plane %d row %ld column %ld is %02x, expected %02x\n",
+                    sw, sh, W, H, kFmtName[fmt], (int) bgra, csc, pitch_kind, offset, (int) wide, c, by, bx, got, want);
+            exit(1);
+        }
+    }
+    if (!blk.untouched()) {
+        fprintf(stderr, "the source was written: rgb %dx%d -> %dx%d\n", sw, sh, W, H);
+        exit(1);
+    }
+    if (dump_name && g_dump) {
+        FILE *fs = dump_open(dump_name, ".src"), *fy = dump_open(dump_name, ".yuv");
+        dump_rows(fs, blk.src, blk.pitch, 4 * (size_t) sw, sh);
+        for (int c = 0; c < 3; c++) {
+            dump_rows(fy, dst[c]->org, (size_t) dst[c]->stride, (size_t) dst[c]->w, dst[c]->h);
+        }
+        fclose(fs);
+        fclose(fy);
+    }
+}
+
+// ---- the validity rule against a restatement --------------------------------------------------------------------------------------
+bool plane_ok(long pw, long ph, long ow, long oh, long max_d, long max_ratio_x, long max_ratio_y)
+{
+    if (ow <= 0 || oh <= 0 || ow > pw || oh > ph || pw > 32768 || ph > 32768 || max_ratio_x * ow < pw || max_ratio_y * oh < ph) {
+        return false;
+    }
+    return (pw / gcd_of(pw, ow)) * (ph / gcd_of(ph, oh)) <= max_d;
+}
+// what a SIZED entry (a layout without a scale value) of src -> enc in format fmt is allowed to be; kind 0 planar, 1 semi, 2 rgb
+bool restated_sized(long sw, long sh, long W, long H, int fmt, int kind)
+{
+    if (sw <= 0 || sh <= 0 || W <= 0 || H <= 0) {
+        return false;
+    }
+    const int hs = kHs[fmt], vs = kVs[fmt];
+    const long cw = (W + (1 << hs) - 1) >> hs, ch = (H + (1 << vs) - 1) >> vs, scw = (sw + (1 << hs) - 1) >> hs, sch = (sh + (1 << vs) - 1) >> vs;
+    if (kind == 2) {
+        return plane_ok(sw, sh, W, H, 65535, 8, 8) && plane_ok(sw, sh, cw, ch, 65535, 8L << hs, 8L << vs);
+    }
+    return plane_ok(sw, sh, W, H, 1L << 24, 8, 8) && plane_ok(scw, sch, cw, ch, 1L << 24, 8, 8);
+}
+
+long g_rule[2] = {0, 0};
+void rule_case(int sw, int sh, int W, int H, int fmt, int kind)
+{
+    const int layout = kind == 2 ? (DSV2HIP_SURFACE_RGBA | DSV2HIP_CSC_BT709) : kind == 1 ? DSV2HIP_SURFACE_SEMIPLANAR : DSV2HIP_SURFACE_PLANAR;
+    ingest_resize::Sized z;
+    const bool got = ingest_resize::plan_sized_source(sw, sh, W, H, kSubsamp[fmt], layout, &z), want = restated_sized(sw, sh, W, H, fmt, kind);
+    if (got != want || (got && z.sized != (sw != W || sh != H))) {
+        fprintf(stderr, "validity rule: %dx%d -> %dx%d %s kind %d is %d, the restatement says %d\n", sw, sh, W, H, kFmtName[fmt], kind, (int) got, (int) want);
+        exit(1);
+    }
+    g_rule[want]++;
+}
+
+void sweep_rule()
+{
+    for (int fmt = 0; fmt < 5; fmt++) {
+        for (int kind = 0; kind < 3; kind++) {
+            // at and around the ratio bounds 1 and 8 per axis, non-positive sizes
+            for (int W : {1, 2, 16, 17, 34}) {
+                for (int H : {1, 9, 18}) {
+                    for (int sw : {-1, 0, W - 1, W, W + 1, 8 * W - 1, 8 * W, 8 * W + 1}) {
+                        for (int sh : {-3, 0, H - 1, H, H + 1, 8 * H - 1, 8 * H, 8 * H + 1}) {
+                            rule_case(sw, sh, W, H, fmt, kind);
+                        }
+                    }
+                }
+            }
+            rule_case(16, 16, 0, 16, fmt, kind);
+            rule_case(16, 16, 16, -1, fmt, kind);
+            // D: RGB at and round 65 535 (255 x 257 = 65 535, 256 x 256 = 65 536), YUV at and round 2^24 (4096 x 4096), sides of 32 768
+            for (int sw : {255, 256, 257, 4093, 4096, 4097, 4099}) {
+                for (int sh : {255, 256, 257, 4093, 4096, 4097, 4099}) {
+                    rule_case(sw, sh, sw - 1, sh - 1, fmt, kind);
+                    rule_case(sw, sh, sw - 2, sh - 1, fmt, kind);
+                }
+            }
+            for (int sw : {32767, 32768, 32769}) {
+                rule_case(sw, 64, 16384, 32, fmt, kind);
+                rule_case(64, sw, 32, 16384, fmt, kind);
+            }
+            // the header's examples
+            rule_case(1920, 1080, 1280, 720, fmt, kind);
+            rule_case(1920, 1080, 854, 480, fmt, kind);
+            rule_case(1920, 1080, 224, 224, fmt, kind);
+            rule_case(1920, 1080, 1918, 1078, fmt, kind);
+            rule_case(1920, 1080, 640, 360, fmt, kind);
+        }
+    }
+    ingest_resize::Sized z;
+    const bool ladder = ingest_resize::plan_sized_source(1920, 1080, 1280, 720, DSV_SUBSAMP_420, DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709, &z) &&
+                        ingest_resize::plan_sized_source(1920, 1080, 854, 480, DSV_SUBSAMP_420, DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709, &z) &&
+                        // (224 x 224: inside the RGB bound on D -- 8 100 and 16 200 -- and refused for its ratio, 1920 > 8 * 224, as a YUV source is)
+                        ingest_resize::sized_ratio(1920, 1080, 224, 224, true).D == 8100 && ingest_resize::sized_ratio(1920, 1080, 112, 112, true).D == 16200 &&
+                        !ingest_resize::plan_sized_source(1920, 1080, 224, 224, DSV_SUBSAMP_420, DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709, &z) &&
+                        ingest_resize::plan_sized_source(1792, 1080, 224, 224, DSV_SUBSAMP_420, DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709, &z) &&
+                        !ingest_resize::plan_sized_source(1920, 1080, 1918, 1078, DSV_SUBSAMP_420, DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709, &z) &&
+                        ingest_resize::plan_sized_source(1920, 1080, 1918, 1078, DSV_SUBSAMP_420, DSV2HIP_SURFACE_SEMIPLANAR, &z);
+    if (!ladder || !g_rule[0] || !g_rule[1]) {
+        fprintf(stderr, "validity rule: the header's examples do not hold\n");
+        exit(1);
+    }
+}
+
+// the refusal matrix of a 34x18 4:2:0 encoder, through plan_sized_source + sized_surface_fits as the calls use them
+void write_validity()
+{
+    if (!g_dump) {
+        return;
+    }
+    FILE *f = dump_open("validity", ".txt");
+    static uint8_t mem[16];
+    auto entry = [&](const char *name, int sw, int sh, int subsamp, int layout, const size_t (&pitch)[3], int null_plane) {
+        dsv2hip_surface sf;
+        memset(&sf, 0, sizeof(sf));
+        sf.layout = layout;
+        for (int c = 0; c < 3; c++) {
+            sf.plane[c] = c == null_plane ? nullptr : mem;
+            sf.pitch[c] = pitch[c];
+        }
+        ingest_resize::Sized z;
+        const bool ok = ingest_resize::plan_sized_source(sw, sh, 34, 18, subsamp, layout, &z) && ingest_resize::sized_surface_fits(z, sf);
+        fprintf(f, "%s %d\n", name, (int) ok);
+    };
+    const int P = DSV2HIP_SURFACE_PLANAR, S = DSV2HIP_SURFACE_SEMIPLANAR, B7 = DSV2HIP_SURFACE_BGRA | DSV2HIP_CSC_BT709,
+              RF = DSV2HIP_SURFACE_RGBA | DSV2HIP_CSC_FULL_RANGE, F = DSV_SUBSAMP_420;
+    const size_t big[3] = {4096, 4096, 4096};
+    entry("planar_51x27", 51, 27, F, P, big, -1);
+    entry("nv12_35x19", 35, 19, F, S, big, -1);
+    entry("bgra709_51x27", 51, 27, F, B7, big, -1);
+    entry("rgba_full_272x144", 272, 144, F, RF, big, -1);
+    entry("own_size_planar", 34, 18, F, P, big, -1);
+    entry("anamorphic_272x18", 272, 18, F, P, big, -1);
+    entry("nv12_half_67x35", 67, 35, F, S | DSV2HIP_SCALE_HALF, big, -1);
+    entry("nv12_half_51x27", 51, 27, F, S | DSV2HIP_SCALE_HALF, big, -1);
+    entry("source_273x18", 273, 18, F, P, big, -1);
+    entry("source_33x18", 33, 18, F, P, big, -1);
+    entry("source_34x145", 34, 145, F, S, big, -1);
+    entry("src_w_0", 0, 27, F, P, big, -1);
+    entry("src_h_0", 51, 0, F, B7, big, -1);
+    entry("src_w_negative", -51, 27, F, S, big, -1);
+    entry("layout_0x4000", 51, 27, F, 0x4000, big, -1);
+    entry("layout_0x1010", 67, 35, F, 0x1010, big, -1);
+    entry("layout_0x2", 51, 27, F, 0x2, big, -1);
+    entry("planar_bt709", 51, 27, F, P | DSV2HIP_CSC_BT709, big, -1);
+    {
+        const size_t p0[3] = {50, 26, 26}, p1[3] = {51, 25, 26}, p2[3] = {51, 26, 25}, ok3[3] = {51, 26, 26};
+        entry("pitch_tight_planar", 51, 27, F, P, ok3, -1);
+        entry("pitch_short_planar_0", 51, 27, F, P, p0, -1);
+        entry("pitch_short_planar_1", 51, 27, F, P, p1, -1);
+        entry("pitch_short_planar_2", 51, 27, F, P, p2, -1);
+        const size_t s1[3] = {51, 51, 0}, sok[3] = {51, 52, 0}, r0[3] = {203, 0, 0}, rok[3] = {204, 0, 0};
+        entry("pitch_tight_nv12", 51, 27, F, S, sok, 2);
+        entry("pitch_short_nv12_1", 51, 27, F, S, s1, -1);
+        entry("pitch_tight_rgb", 51, 27, F, B7, rok, 1);
+        entry("pitch_short_rgb_0", 51, 27, F, B7, r0, -1);
+    }
+    entry("null_planar_2", 51, 27, F, P, big, 2);
+    entry("null_nv12_1", 51, 27, F, S, big, 1);
+    entry("null_rgb_0", 51, 27, F, RF, big, 0);
+    entry("rgb_on_uyvy_format", 51, 27, DSV_SUBSAMP_UYVY, B7, big, -1);
+    entry("nv16_on_uyvy_format", 51, 27, DSV_SUBSAMP_UYVY, S, big, -1);
+    entry("format_0x1", 51, 27, 0x1, P, big, -1);
+    fclose(f);
+}
+
+const int kShapes[12][4] = {{48, 32, 32, 24}, {50, 38, 33, 21}, {25, 19, 17, 11}, {64, 48, 9, 7},   {64, 48, 64, 6},  {64, 48, 8, 48},
+                            {16, 16, 16, 16}, {16, 16, 2, 2},   {64, 48, 32, 24}, {64, 48, 16, 12}, {97, 61, 13, 8},  {131, 67, 130, 66}};
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc == 3 && !strcmp(argv[1], "--dump")) {
+        g_dump = argv[2];
+        g_case_list = dump_open("cases", ".txt");
+    }
+    sweep_rule();
+    write_validity();
+
+    // 1. planes: every source size a destination plane of up to 20 x 9 admits.  The horizontal and the vertical walk share nothing, so
+    //    every (ow, pw) runs against a few (oh, ph) and every (oh, ph) against a few (ow, pw) -- in the general form at pitch + 1 and
+    //    offset 1 as a planar plane and as the U and the V half of an interleaved one, and in the wide form (aligned pitch, width
+    //    padded by the pitch alone: only where the row bytes are a multiple of 4) -- and the cross product as a planar plane in
+    //    the general form with tight rows, thinned to one in three.
+    const int few_h[4][2] = {{1, 1}, {3, 4}, {9, 31}, {5, 40}}, few_w[5][2] = {{1, 1}, {4, 6}, {17, 25}, {20, 160}, {7, 20}};
+    for (int ow = 1; ow <= 20; ow++) {
+        for (int pw = ow; pw <= 8 * ow; pw++) {
+            for (int oh = 1; oh <= 9; oh++) {
+                for (int ph = oh; ph <= 8 * oh; ph++) {
+                    if ((pw + ph + ow) % 3 == 0) {
+                        check_plane(pw, ph, ow, oh, 1, 0, 0, (pw + ph) & 3, 0);
+                    }
+                }
+            }
+            for (const auto &v : few_h) {
+                for (int kind = 0; kind < 3; kind++) {
+                    check_plane(pw, v[1], ow, v[0], kind ? 2 : 1, kind == 2, 1, 1, 0);
+                    check_plane(pw, v[1], ow, v[0], kind ? 2 : 1, kind == 2, 2, 0, 1);
+                }
+            }
+        }
+    }
+    for (int oh = 1; oh <= 9; oh++) {
+        for (int ph = oh; ph <= 8 * oh; ph++) {
+            for (const auto &h : few_w) {
+                for (int kind = 0; kind < 3; kind++) {
+                    check_plane(h[1], ph, h[0], oh, kind ? 2 : 1, kind == 2, 2, 0, 1);
+                    check_plane(h[1], ph, h[0], oh, kind ? 2 : 1, kind == 2, 0, 3, 0);
+                }
+            }
+        }
+    }
+    // the largest a and b a plane can have (32768 / 32767), and the largest D (4096 x 4096 = 2^24): the 24-bit products' operands
+    for (int kind = 0; kind < 3; kind++) {
+        check_plane(32768, 2, 32767, 2, kind ? 2 : 1, kind == 2, 2, 0, 1);
+        check_plane(32768, 3, 32767, 2, kind ? 2 : 1, kind == 2, 1, 1, 0);
+    }
+    check_plane(4096, 4096, 4095, 4095, 1, 0, 0, 0, 1, 255);
+    // 2. pictures: the twelve shapes x {planar, semi} x both forms x offsets 0 .. 3 x pitches tight / + 1 / aligned, noise; constants
+    for (int k = 0; k < 12; k++) {
+        const int *s = kShapes[k];
+        for (int semi = 0; semi < 2; semi++) {
+            for (int offset = 0; offset < 4; offset++) {
+                for (int pitch_kind = 0; pitch_kind < 3; pitch_kind++) {
+                    check_yuv(s[0], s[1], s[2], s[3], 2, semi != 0, pitch_kind, offset, false);
+                    if (offset == 0) {
+                        check_yuv(s[0], s[1], s[2], s[3], 2, semi != 0, pitch_kind, offset, true);
+                    }
+                }
+            }
+            for (int value : {0, 1, 254, 255}) {
+                check_yuv(s[0], s[1], s[2], s[3], 2, semi != 0, 2, 0, false, value);
+                check_yuv(s[0], s[1], s[2], s[3], 2, semi != 0, 1, 1, false, value);
+            }
+        }
+    }
+    // 3. every chroma format, a row of more than one workgroup (2 x 256 + 3 samples), dumps for the numpy oracle
+    for (int fmt = 0; fmt < 5; fmt++) {
+        for (int semi = 0; semi < 2; semi++) {
+            check_yuv(51, 27, 34, 18, fmt, semi != 0, 2, 0, false);
+            check_yuv(35, 19, 34, 18, fmt, semi != 0, 1, 1, false);
+            check_yuv(127, 121, 16, 16, fmt, semi != 0, 0, 2, false);
+        }
+    }
+    check_yuv(1036, 13, 515, 6, 2, false, 2, 0, false);
+    check_yuv(1036, 13, 515, 6, 2, true, 2, 0, false);
+    check_yuv(777, 9, 515, 6, 2, true, 1, 3, false);
+    check_yuv(51, 27, 34, 18, 2, false, 2, 0, false, -1, "planar_420_51x27_34x18");
+    check_yuv(51, 27, 34, 18, 2, true, 1, 1, false, -1, "semi_420_51x27_34x18");
+    check_yuv(127, 121, 16, 16, 0, true, 0, 0, false, -1, "semi_444_127x121_16x16");
+    check_yuv(48, 32, 48, 16, 1, false, 0, 0, false, -1, "planar_422_48x32_48x16");
+    check_yuv(97, 61, 38, 22, 3, true, 2, 0, false, -1, "semi_411_97x61_38x22");
+    check_yuv(97, 61, 38, 22, 4, false, 2, 0, true, -1, "planar_410_97x61_38x22");
+    check_yuv(128, 128, 16, 16, 2, true, 2, 0, false, -1, "semi_420_128x128_16x16");
+    // 4. RGB: both byte orders x four presets x five formats; footprints of 2 taps (35 -> 34), 9 (127 -> 16) and 33 (4:1:0 chroma of
+    //    254 x 250 -> 32 x 32: 254 -> 8); the pitches and offsets of the YUV sweep
+    for (int fmt = 0; fmt < 5; fmt++) {
+        for (int csc = 0; csc < 4; csc++) {
+            for (int bgra = 0; bgra < 2; bgra++) {
+                const int k = fmt + csc + bgra;
+                check_rgb(35, 19, 34, 18, fmt, bgra != 0, csc << 8, k % 3, k % 4, false);
+                check_rgb(51, 27, 34, 18, fmt, bgra != 0, csc << 8, (k + 1) % 3, 0, (k & 1) != 0);
+                check_rgb(127, 121, 16, 16, fmt, bgra != 0, csc << 8, 2, 0, false);
+            }
+        }
+        check_rgb(254, 250, 32, 32, fmt, true, 0x100, 1, 1, false);
+        check_rgb(254, 250, 32, 32, fmt, false, 0x200, 2, 0, false);
+        for (int value : {0, 1, 254, 255}) {
+            check_rgb(51, 27, 34, 18, fmt, (value & 1) != 0, 0x300, 0, 0, false, value);
+            check_rgb(127, 121, 16, 16, fmt, (value & 1) == 0, 0x000, 0, 2, false, value);
+        }
+    }
+    for (int offset = 0; offset < 4; offset++) {
+        for (int pitch_kind = 0; pitch_kind < 3; pitch_kind++) {
+            check_rgb(50, 38, 33, 21, 2, (offset & 1) != 0, 0x100, pitch_kind, offset, false);
+            check_rgb(48, 32, 48, 16, 2, (offset & 1) == 0, 0x200, pitch_kind, offset, false);
+        }
+    }
+    check_rgb(777, 9, 515, 6, 2, true, 0x100, 2, 0, false);
+    check_rgb(51, 27, 34, 18, 2, true, 0x100, 2, 0, false, -1, "bgra_100_420_51x27_34x18");
+    check_rgb(51, 27, 34, 18, 2, false, 0x200, 1, 1, false, -1, "rgba_200_420_51x27_34x18");
+    check_rgb(127, 121, 16, 16, 0, false, 0x000, 0, 0, false, -1, "rgba_000_444_127x121_16x16");
+    check_rgb(254, 250, 32, 32, 4, true, 0x300, 2, 0, false, -1, "bgra_300_410_254x250_32x32");
+    check_rgb(97, 61, 38, 22, 3, false, 0x100, 2, 0, true, -1, "rgba_100_411_97x61_38x22");
+    check_rgb(97, 61, 38, 22, 1, true, 0x200, 0, 3, false, -1, "bgra_200_422_97x61_38x22");
+    check_rgb(128, 128, 16, 16, 2, true, 0x100, 2, 0, false, -1, "bgra_100_420_128x128_16x16");
+
+    if (g_case_list) {
+        fclose(g_case_list);
+    }
+    printf("%ld planes; %ld YUV pictures, %ld in the wide form; %ld RGB pictures, %ld in the wide form\n", g_planes, g_cases[0], g_wide[0], g_cases[1],
+           g_wide[1]);
+    printf("%ld + %ld cases of the validity rule equal its restatement\n", g_rule[1], g_rule[0]);
+    if (g_wide[0] == 0 || g_wide[0] == g_cases[0] || g_wide[1] == 0 || g_wide[1] == g_cases[1]) {
+        fprintf(stderr, "both forms must occur\n");
+        return 1;
+    }
+    return 0;
+}
