@@ -199,6 +199,21 @@ struct RgbJob { // one packed four-byte RGB surface (dsv2hip_surface, BGRA / RGB
     uint32_t ycoef, upos, uneg, vpos, vneg;
     uint32_t yoff; // 128 + 256 * ybase
 };
+constexpr int kRgb3Packed = 0, kRgb3Planar = 1; // Rgb3Job::kind
+struct Rgb3Job { // one RGB surface without a fourth byte (dsv2hip_surface: BGR / RGB, three bytes a pixel; RGBP, a plane per colour) on its way
+                 // into the three bordered source planes, converted on the way (ingest_rgb3.h, frame.hip: k_ingest_rgb3); 128 bytes, fetched
+                 // by value through the scalar cache like RgbJob
+    const uint8_t *src[3]; // device memory, any alignment.  Packed: row y at src[0] + y * pitch[0], w pixels of 3 bytes, src[1..2] and
+    size_t pitch[3];       // pitch[1..2] unused.  Planar: row y of R, G, B at src[c] + y * pitch[c], w bytes
+    uint8_t *dst[3];       // Y, U, V planes from dframe_alloc
+    int ystride, cstride;  // RgbJob's, as all that follows but `kind`
+    int w, h;
+    int hs, vs;
+    int kind;              // kRgb3Packed, kRgb3Planar; one launch takes jobs of one kind
+    // the quads in the order the colour bytes take in a pixel dword: memory order (packed), R G B (planar)
+    uint32_t ycoef, upos, uneg, vpos, vneg;
+    uint32_t yoff;
+};
 struct PlaneOutJob {
     DPlane src;
     uint8_t *dst; // pinned host memory, w * h bytes
@@ -315,6 +330,17 @@ inline bool surface_job_wide(const SurfaceJob &j)
 // n RGB surfaces of h rows; wide: every job's source pointer and pitch are multiples of 16 and w of 4 (rgb_job_wide)
 void ingest_rgb_batch(hipStream_t s, const RgbJob *d_jobs, int n, int h, bool wide);
 inline bool rgb_job_wide(const RgbJob &j) { return ((((uintptr_t) j.src) | j.pitch) & 15) == 0 && (j.w & 3) == 0; }
+// n three-byte or planar RGB surfaces of h rows, all of one kind (planar: Rgb3Job::kind of every job is kRgb3Planar); wide: every
+// job's source pointers and pitches -- those its kind uses -- and w are multiples of 4 (rgb3_job_wide)
+void ingest_rgb3_batch(hipStream_t s, const Rgb3Job *d_jobs, int n, int h, bool planar, bool wide);
+inline bool rgb3_job_wide(const Rgb3Job &j)
+{
+    uintptr_t m = (uintptr_t) j.src[0] | j.pitch[0] | (uintptr_t) j.w;
+    if (j.kind == kRgb3Planar) {
+        m |= (uintptr_t) j.src[1] | j.pitch[1] | (uintptr_t) j.src[2] | j.pitch[2];
+    }
+    return (m & 3) == 0;
+}
 // Half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled): the records of k_ingest_surface_scaled and
 // k_ingest_rgb_scaled (frame.hip, ingest_scale.h), in tables of their own behind the two above.
 struct ScaledSurfaceJob { // one SOURCE plane of a caller's surface, box-averaged (the decoder's REDUCTION, include/dsv2_hip.h) on its way into a

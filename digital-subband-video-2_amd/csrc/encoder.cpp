@@ -974,6 +974,7 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
                       "a scaled source's records fit the room reserved for a stream's surface records");
         static_assert(3 * sizeof(SizedSurfaceJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob) && sizeof(SizedRgbJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob),
                       "a sized source's records fit the same room");
+        static_assert(sizeof(Rgb3Job) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob), "a three-byte or planar RGB surface's record fits the same room");
         tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob) + sizeof(RgbJob)) + 65536);
         if (n <= cap) {
             return;
@@ -1531,10 +1532,17 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 static std::atomic<int> g_fail_next_step{0};
 static std::atomic<unsigned long long> g_surface_steps[2]; // steps whose surface ingest ran in the wide / the general form (dsv2hip_enc_surface_stats)
 static std::atomic<unsigned long long> g_rgb_steps[2];     // the same for the RGB ingest (dsv2hip_enc_rgb_stats)
+static std::atomic<unsigned long long> g_rgb3_steps[4];    // three-byte RGB ingest wide / general, planar RGB ingest wide / general (dsv2hip_enc_rgb3_stats)
 static std::atomic<unsigned long long> g_resize_steps[4];  // sized YUV ingest wide / general, sized RGB ingest wide / general (dsv2hip_enc_resize_stats)
 static std::atomic<unsigned long long> g_scale_steps[4];   // scaled YUV ingest wide / general, scaled RGB ingest wide / general (dsv2hip_enc_scale_stats)
 
 static bool surface_is_rgb(int layout) { return (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_RGBA; }
+// BGR, RGB (three bytes a pixel) or RGBP (a plane per colour), or-ed with any DSV2HIP_CSC_* bits: the plain ingest's alone
+static bool surface_is_rgb3(int layout)
+{
+    const int order = layout & ~0x300;
+    return order == DSV2HIP_SURFACE_BGR || order == DSV2HIP_SURFACE_RGB || order == DSV2HIP_SURFACE_RGBP;
+}
 
 // The conversion of include/dsv2_hip.h for an RGB surface of `layout` as k_ingest_rgb takes it: each row of the preset's matrix as
 // byte quads in the surface's channel order (alpha weighs 0), chroma rows split into positive parts and magnitudes of negative ones
@@ -1546,7 +1554,7 @@ template <class RgbJobT> static void rgb_job_coefs(RgbJobT &j, int layout)
                                       {54, 183, 19, -29, -99, 128, 128, -116, -12}}; // BT709 | FULL
     const bool full = (layout & DSV2HIP_CSC_FULL_RANGE) != 0;
     const int *m = presets[(full ? 2 : 0) + ((layout & DSV2HIP_CSC_BT709) ? 1 : 0)];
-    const bool bgra = (layout & ~0x300) == DSV2HIP_SURFACE_BGRA;
+    const bool bgra = (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_BGR; // blue is byte 0 of a pixel
     uint32_t q[3][2];
     for (int row = 0; row < 3; row++) {
         q[row][0] = q[row][1] = 0;
@@ -1762,11 +1770,14 @@ static void g1_enqueue(Step &st)
     int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0, n_rgb = 0, n_rj = 0;
     int n_ssurf = 0, n_ssj = 0, n_srgb = 0, n_srj = 0; // the scaled ones (Job::src_shift): tables, forms and launches of their own
     int n_zsurf = 0, n_zsj = 0, n_zrgb = 0, n_zrj = 0; // the sized ones (Job::sized): likewise, behind the scaled ones
+    int n_rgb3[2] = {0, 0}, n_r3j[2] = {0, 0};         // three-byte / planar RGB (never scaled or sized): a table each, behind all of them
     for (int k = 0; k < n; k++) {
         const bool rgb = st.jobs[k].has_surf && surface_is_rgb(st.jobs[k].surf.layout), scaled = st.jobs[k].has_surf && st.jobs[k].src_shift;
         const bool sized = st.jobs[k].has_surf && st.jobs[k].sized;
+        const bool rgb3 = st.jobs[k].has_surf && surface_is_rgb3(st.jobs[k].surf.layout);
         n_rgb += rgb && !scaled && !sized;
-        n_surf += st.jobs[k].has_surf && !rgb && !scaled && !sized;
+        n_surf += st.jobs[k].has_surf && !rgb && !rgb3 && !scaled && !sized;
+        n_rgb3[(st.jobs[k].surf.layout & ~0x300) == DSV2HIP_SURFACE_RGBP] += rgb3;
         n_srgb += rgb && scaled;
         n_ssurf += !rgb && scaled;
         n_zrgb += rgb && sized;
@@ -1796,6 +1807,13 @@ static void g1_enqueue(Step &st)
     if (n_zrgb) {
         zrj = Tab<SizedRgbJob>(sc.tabs, (size_t) n_zrgb);
     }
+    Tab<Rgb3Job> r3j[2]; // only a step with such surfaces has them
+    for (int kind = 0; kind < 2; kind++) {
+        if (n_rgb3[kind]) {
+            r3j[kind] = Tab<Rgb3Job>(sc.tabs, (size_t) n_rgb3[kind]);
+        }
+    }
+    bool rgb3_wide[2] = {true, true};
     bool surf_wide = true, rgb_wide = true, ssurf_wide = true, srgb_wide = true, zsurf_wide = true, zrgb_wide = true;
     int ssurf_row_bytes = 0, srgb_sw = 0;
     for (int k = 0; k < n; k++) {
@@ -1807,6 +1825,18 @@ static void g1_enqueue(Step &st)
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
+        } else if (jb.has_surf && surface_is_rgb3(jb.surf.layout)) {
+            const dsv2hip_surface &sf = jb.surf;
+            const DPlane *dp = cur.src.p;
+            const int kind = (sf.layout & ~0x300) == DSV2HIP_SURFACE_RGBP ? kRgb3Planar : kRgb3Packed;
+            Rgb3Job &j = r3j[kind].h[n_r3j[kind]++];
+            j = Rgb3Job{{(const uint8_t *) sf.plane[0], nullptr, nullptr}, {sf.pitch[0], 0, 0}, {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride,
+                        dp[0].w, dp[0].h, DSV_FORMAT_H_SHIFT(cur.src.format), DSV_FORMAT_V_SHIFT(cur.src.format), kind, 0, 0, 0, 0, 0, 0};
+            for (int c = 1; c < 3 && kind == kRgb3Planar; c++) {
+                j.src[c] = (const uint8_t *) sf.plane[c], j.pitch[c] = sf.pitch[c];
+            }
+            rgb_job_coefs(j, kind == kRgb3Planar ? DSV2HIP_SURFACE_RGBA | (sf.layout & 0x300) : sf.layout); // (planar: R is byte 0 of a pixel dword)
+            rgb3_wide[kind] = rgb3_wide[kind] && rgb3_job_wide(j);
         } else if (jb.has_surf && jb.sized && surface_is_rgb(jb.surf.layout)) {
             const dsv2hip_surface &sf = jb.surf;
             const DPlane *dp = cur.src.p;
@@ -1954,6 +1984,12 @@ static void g1_enqueue(Step &st)
     if (n_zrj) {
         ingest_rgb_sized_batch(bs, zrj.d, n_zrj, f0.p[0].w, f0.p[0].h + f0.p[1].h, zrgb_wide);
         g_resize_steps[zrgb_wide ? 2 : 3]++;
+    }
+    for (int kind = 0; kind < 2; kind++) {
+        if (n_r3j[kind]) {
+            ingest_rgb3_batch(bs, r3j[kind].d, n_r3j[kind], f0.p[0].h, kind == kRgb3Planar, rgb3_wide[kind]);
+            g_rgb3_steps[2 * kind + (rgb3_wide[kind] ? 0 : 1)]++;
+        }
     }
     extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
     extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
@@ -2764,7 +2800,7 @@ int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, 
 }
 
 /* a surface the ingest can read, for an encoder that takes one: layout, planes, every pitch at least its row's bytes (an RGB surface:
- * plane[0] and pitch[0] alone, four bytes a pixel) */
+ * plane[0] and pitch[0] alone, four bytes a pixel -- BGR / RGB: three; RGBP: three planes of w bytes a row) */
 static bool surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf)
 {
     if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
@@ -2776,6 +2812,15 @@ static bool surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf)
         const int f = enc->vidmeta.subsamp;
         const bool known = f == DSV_SUBSAMP_444 || f == DSV_SUBSAMP_422 || f == DSV_SUBSAMP_420 || f == DSV_SUBSAMP_411 || f == DSV_SUBSAMP_410;
         return known && sf->plane[0] && sf->pitch[0] >= 4 * w;
+    }
+    if (surface_is_rgb3(sf->layout)) { // (likewise; three bytes a pixel in plane[0], or a plane of w bytes a row per colour)
+        if (!ingest_scale::rgb_format(enc->vidmeta.subsamp)) {
+            return false;
+        }
+        if ((sf->layout & ~0x300) == DSV2HIP_SURFACE_RGBP) {
+            return sf->plane[0] && sf->plane[1] && sf->plane[2] && sf->pitch[0] >= w && sf->pitch[1] >= w && sf->pitch[2] >= w;
+        }
+        return sf->plane[0] && sf->pitch[0] >= 3 * w;
     }
     if (sf->layout != DSV2HIP_SURFACE_PLANAR && sf->layout != DSV2HIP_SURFACE_SEMIPLANAR) {
         return false;
@@ -2850,6 +2895,18 @@ void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset)
         }
         if (reset) {
             g_rgb_steps[i].store(0);
+        }
+    }
+}
+
+void dsv2hip_enc_rgb3_stats(unsigned long long *out4, int reset)
+{
+    for (int i = 0; i < 4; i++) {
+        if (out4) {
+            out4[i] = g_rgb3_steps[i].load();
+        }
+        if (reset) {
+            g_rgb3_steps[i].store(0);
         }
     }
 }

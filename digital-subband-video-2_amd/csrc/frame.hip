@@ -10,6 +10,7 @@
 // adjacent strip ends (frame.c:377-380).
 #include "dev.h"
 #include "ingest_rgb.h"
+#include "ingest_rgb3.h"
 #include "ingest_scale.h"
 #include "ingest_resize.h"
 #include "prio.h"
@@ -463,6 +464,56 @@ void ingest_rgb_batch(hipStream_t s, const RgbJob *d_jobs, int n, int h, bool wi
         DSV2_LAUNCH(k_ingest_rgb<16>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_ingest_rgb<4>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- RGB surfaces without a fourth byte (dsv2hip_surface, BGR / RGB / RGBP), converted on the way in ----------------------------
+// One Rgb3Job per surface, fetched by value and pinned to scalar registers as above; the thread's work is ingest_rgb3.h's
+// ingest_rgb3_rows (which tools/ingest_rgb3_check.cpp runs on the CPU), k_ingest_rgb's decomposition with another fetch.  A launch
+// takes jobs of ONE kind: the packed kernels never look at src[1..2] and pitch[1..2].
+template <int KIND, bool WIDE> __global__ __launch_bounds__(256) void k_ingest_rgb3(const Rgb3Job *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const Rgb3Job jl = job_of(tab, blockIdx.y);
+    constexpr bool PLANAR = KIND == kRgb3Planar;
+    const auto uni_pitch = [](size_t p) { return ((size_t) (unsigned) uni((int) (p >> 32)) << 32) | (unsigned) uni((int) p); };
+    const Rgb3Job j{{uni_ptr(jl.src[0]), PLANAR ? uni_ptr(jl.src[1]) : nullptr, PLANAR ? uni_ptr(jl.src[2]) : nullptr},
+                    {uni_pitch(jl.pitch[0]), PLANAR ? uni_pitch(jl.pitch[1]) : 0, PLANAR ? uni_pitch(jl.pitch[2]) : 0},
+                    {uni_ptr(jl.dst[0]), uni_ptr(jl.dst[1]), uni_ptr(jl.dst[2])},
+                    uni(jl.ystride),
+                    uni(jl.cstride),
+                    uni(jl.w),
+                    uni(jl.h),
+                    uni(jl.hs),
+                    uni(jl.vs),
+                    KIND,
+                    (uint32_t) uni((int) jl.ycoef),
+                    (uint32_t) uni((int) jl.upos),
+                    (uint32_t) uni((int) jl.uneg),
+                    (uint32_t) uni((int) jl.vpos),
+                    (uint32_t) uni((int) jl.vneg),
+                    (uint32_t) uni((int) jl.yoff)};
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    ingest_rgb3_rows<KIND, WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void ingest_rgb3_batch(hipStream_t s, const Rgb3Job *d_jobs, int n, int h, bool planar, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kSurfaceRows - 1) / kSurfaceRows, n), block(64, 4);
+    if (planar && wide) {
+        DSV2_LAUNCH((k_ingest_rgb3<kRgb3Planar, true>), grid, block, 0, s, d_jobs);
+    } else if (planar) {
+        DSV2_LAUNCH((k_ingest_rgb3<kRgb3Planar, false>), grid, block, 0, s, d_jobs);
+    } else if (wide) {
+        DSV2_LAUNCH((k_ingest_rgb3<kRgb3Packed, true>), grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH((k_ingest_rgb3<kRgb3Packed, false>), grid, block, 0, s, d_jobs);
     }
 }
 

@@ -120,6 +120,33 @@ __host__ __device__ __forceinline__ void rgb_chroma(const RgbJob &j, const uint3
     }
 }
 
+// luma, U and V of the thread's 4 x 4 pixels px[row][pixel] (top-left pixel (x, y0), x and y0 multiples of 4), stored: all that follows
+// the fetch, shared with ingest_rgb3.h.  WIDE: w is a multiple of 4.
+template <int HS, int VS, bool WIDE> __host__ __device__ __forceinline__ void rgb_emit(const RgbJob &j, const uint32_t (&px)[4][4], int x, int y0)
+{
+    const int w = j.w, h = j.h;
+    // Y(x, y) = (yr * R + yg * G + yb * B + 128 + 256 * ybase) >> 8: byte 1 of the sum, which is below 65 536
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        if (y0 + r >= h) {
+            break;
+        }
+        const uint32_t y01 = perm_b32(dot4_u8(px[r][1], j.ycoef, j.yoff), dot4_u8(px[r][0], j.ycoef, j.yoff), 0x00000501u);
+        const uint32_t y23 = perm_b32(dot4_u8(px[r][3], j.ycoef, j.yoff), dot4_u8(px[r][2], j.ycoef, j.yoff), 0x00000501u);
+        const uint32_t o = perm_b32(y23, y01, 0x05040100u);
+        uint8_t *yrow = j.dst[0] + (size_t) (y0 + r) * (size_t) j.ystride;
+        if (WIDE || x + 4 <= w) {
+            st_global<uint32_t>(yrow, x, o); // (x is a multiple of 4, the plane's origin and stride of 16)
+        } else {
+            for (int i = 0; x + i < w; i++) {
+                st_global<uint8_t>(yrow, x + i, (uint8_t) (o >> (8 * i)));
+            }
+        }
+    }
+    rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[1], j.upos, j.uneg);
+    rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[2], j.vpos, j.vneg);
+}
+
 // rows y0 .. y0 + 3 (y0 a multiple of 4, below h) of job j, pixels x_first .. x_first + 3 (a multiple of 4) and on in steps of x_step,
 // for a stream with chroma shifts HS, VS
 template <int VEC, int HS, int VS> __host__ __device__ __forceinline__ void ingest_rgb_rows_fmt(const RgbJob &j, int y0, int x_first, int x_step)
@@ -150,26 +177,7 @@ template <int VEC, int HS, int VS> __host__ __device__ __forceinline__ void inge
                 }
             }
         }
-        // Y(x, y) = (yr * R + yg * G + yb * B + 128 + 256 * ybase) >> 8: byte 1 of the sum, which is below 65 536
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            if (y0 + r >= h) {
-                break;
-            }
-            const uint32_t y01 = perm_b32(dot4_u8(px[r][1], j.ycoef, j.yoff), dot4_u8(px[r][0], j.ycoef, j.yoff), 0x00000501u);
-            const uint32_t y23 = perm_b32(dot4_u8(px[r][3], j.ycoef, j.yoff), dot4_u8(px[r][2], j.ycoef, j.yoff), 0x00000501u);
-            const uint32_t o = perm_b32(y23, y01, 0x05040100u);
-            uint8_t *yrow = j.dst[0] + (size_t) (y0 + r) * (size_t) j.ystride;
-            if (WIDE || x + 4 <= w) {
-                st_global<uint32_t>(yrow, x, o); // (x is a multiple of 4, the plane's origin and stride of 16)
-            } else {
-                for (int i = 0; x + i < w; i++) {
-                    st_global<uint8_t>(yrow, x + i, (uint8_t) (o >> (8 * i)));
-                }
-            }
-        }
-        rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[1], j.upos, j.uneg);
-        rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[2], j.vpos, j.vneg);
+        rgb_emit<HS, VS, WIDE>(j, px, x, y0);
     }
 }
 

@@ -456,6 +456,35 @@ int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *
 int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs);
 void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset);
 void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset);
+/* THREE-BYTE AND PLANAR RGB SURFACES, converted on ingest -- the image-side layouts that have no fourth byte: an OpenCV Mat (BGR24), a
+ * PIL / numpy / torch uint8[h, w, 3] picture, and torch's own image convention uint8[3, h, w].  They are read in place: no kernel
+ * on the caller's side that pads every pixel to four bytes or transposes the planes.
+ *   BGR / RGB: plane[0] = the picture, row y at plane[0] + y * pitch[0], w pixels of 3 bytes in the named byte order;
+ *              pitch[0] >= 3 * w; plane[1..2] and pitch[1..2] are ignored.
+ *   RGBP:      plane[0] = R, plane[1] = G, plane[2] = B, each w bytes by h rows, one byte a sample, pitch[c] >= w for each, all three
+ *              pointers non-NULL.  The planes are named by pointer: a tensor ordered B, G, R passes them in the other order (one
+ *              layout value, not two).  A contiguous torch uint8[3, h, w] tensor is plane[c] = data_ptr + c * h * w, pitch[c] = w.
+ * A valid layout is one of the three values or-ed with any subset of DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE, as BGRA / RGBA are;
+ * any other bit, a DSV2HIP_SCALE_* value included, is refused.  The layouts go through dsv2hip_enc_batch_surface and
+ * dsv2hip_enc_surface_frame, and everything said of in-surfaces above holds: only read, and only inside the rows (no byte of
+ * padding, no byte behind the last row, no word that holds no byte of a row), surf[k] copied, any pointer alignment and any pitch,
+ * layouts mixed freely within one step -- packed, NV12, BGRA, RGB, RGBP ... -- the stream in any of the five chroma formats, and a
+ * refused call touches nothing.  Pointers and pitches that are multiples of 4 with w a multiple of 4, throughout the step's surfaces
+ * of the kind (three-byte; planar), take the fast form of its ingest.
+ * The conversion is THE CONVERSION above, character for character: a three-byte or planar picture gives exactly the packets that
+ * the same pixels give as an RGBA surface with any alpha.
+ * Refused: everything dsv2hip_enc_batch_surface refuses, a NULL plane the layout needs, pitch[0] < 3 * w (RGBP: any pitch[c] < w), an
+ * encoder with dsv2hip_enc_set_uyvy_input on, a stream format outside the five.
+ * Out of scope: the _scaled and _sized calls below refuse the three layouts altogether, also at the encoder's own size, and
+ * dsv2hip_enc_scaled_dims / dsv2hip_enc_sized_dims return -1 for them; every decoder out-surface call, dsv2hip_dec_surface_dims and
+ * dsv2hip_dec_sized_dims refuse them (delivery into these layouts is not done).
+ * dsv2hip_enc_rgb3_stats: out4[0] / out4[1] = lockstep steps of this process whose three-byte ingest ran in the fast / in the general
+ * form so far, out4[2] / out4[3] the same for planar RGB; reset != 0 clears the counts afterwards.  dsv2hip_enc_rgb_stats keeps
+ * counting the steps' four-byte surfaces only, dsv2hip_enc_surface_stats their YUV surfaces only. */
+enum { DSV2HIP_SURFACE_BGR = 0x20,    /* packed, bytes in memory: B G R, three bytes a pixel */
+       DSV2HIP_SURFACE_RGB = 0x21,    /* packed, bytes in memory: R G B */
+       DSV2HIP_SURFACE_RGBP = 0x22 }; /* planar: plane[0] = R, plane[1] = G, plane[2] = B, one byte a sample */
+void dsv2hip_enc_rgb3_stats(unsigned long long *out4, int reset);
 /* HALF, QUARTER AND EIGHTH-SIZE INGEST -- a proxy ladder (1080p + 540p + 270p) from ONE full-size surface of a renderer, a screen
  * capture, a hardware decoder or a torch image tensor: an encoder of W' x H' reads a surface that holds src_w x src_h with
  * W' = ceil(src_w / n), H' = ceil(src_h / n), and the picture is reduced in the ingest pass -- one read of the source, no full-size
@@ -572,7 +601,8 @@ void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset);
  * the same for the sized RGB ingest (every sized RGB surface of the step: pointer and pitch multiples of 4).  Sized entries count
  * here only; scaled entries count in dsv2hip_enc_scale_stats, own-size entries in the plain surfaces' counters.  reset != 0 clears
  * the counts afterwards.
- * Out of scope: enlargement; filters other than the area average; three-byte RGB and 10-bit; host surfaces. */
+ * Out of scope: enlargement; filters other than the area average; three-byte and planar RGB at another size than the encoder's
+ * (DSV2HIP_SURFACE_BGR / _RGB / _RGBP are the plain call's alone); 10-bit; host surfaces. */
 int  dsv2hip_enc_batch_surface_sized(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf,
                                      const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs);
 int  dsv2hip_enc_surface_frame_sized(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs);
@@ -789,7 +819,8 @@ void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset);
  * MEMORY: a sized SEMIPLANAR or RGB picture is resampled into a staging picture of the decoder's own, laid out at the planes' full
  * sizes on the first such picture (1.5 bytes a pixel for 4:2:0) and kept until the stream's geometry changes or the decoder is freed;
  * sized PLANAR delivery stages nothing.
- * Out of scope: enlargement; filters other than the area average; sized delivery behind out420p; the host DSV_FRAME path (dsv_dec,
+ * Out of scope: enlargement; filters other than the area average; sized delivery behind out420p; three-byte and planar RGB out surfaces
+ * (DSV2HIP_SURFACE_BGR / _RGB / _RGBP are refused by every out-surface call); the host DSV_FRAME path (dsv_dec,
  * dsv2hip_dec_batch, dsv2hip_dec_batch_device know nothing of a size).  (The encoder's side: dsv2hip_enc_batch_surface_sized, above.)
  * dsv2hip_dec_resize_stats: out2[0] / out2[1] = device rounds of this process whose resampling ran in the wide form (every resampled
  * plane that goes straight into a caller's surface -- PLANAR: all three, SEMIPLANAR: luma -- has a pointer and a pitch that are

@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Frames/s of the batch encoder fed from device-resident pictures three ways (experiments):
-tools/probe/ingest_rgb.py [packed] [nv12] [bgra]   (default: all three)
+tools/probe/ingest_rgb.py [packed] [nv12] [bgra] [rgb24] [rgbp]   (default: the first three)
 1080p 4:2:0, 192 streams in one lockstep group, 12 timed steps behind 2 warm-up steps:
   packed  dsv2hip_enc_batch on packed planar pictures (k_ingest16)
   nv12    dsv2hip_enc_batch_surface, NV12, pitch 2048 (k_ingest_surface<16>: 1.5 P bytes in, 1.5 P out)
   bgra    dsv2hip_enc_batch_surface, BGRA (BT.601, limited range), pitch 8192 (k_ingest_rgb<16>: 4 P bytes in, 1.5 P out)
+  rgb24   dsv2hip_enc_batch_surface, BGR, three bytes a pixel, pitch 6144 (k_ingest_rgb3<packed, wide>: 3 P bytes in, 1.5 P out)
+  rgbp    dsv2hip_enc_batch_surface, RGBP, three planes of pitch 2048 (k_ingest_rgb3<planar, wide>: 3 P bytes in, 1.5 P out)
 Every stream reads memory of its own (copies of 4 videos: about 24 GB of BGRA surfaces, 9 GB of NV12), so no stream's reads are
 served from the cache by another's.  The three legs encode the same pictures: the BGRA surfaces are made so that their conversion
 is close to the packed pictures (not equal: the legs' packet bytes differ), which keeps the encoder's work behind the ingest alike.
 Prints frames/s and the kernel launches of the ingest stage per step (dsv2hip_prof_read) for each.  The ingest kernels' time per
 launch: rocprofv3 --kernel-trace --stats -- python tools/probe/ingest_rgb.py.  DSV2HIP_LIB=<other build> with `packed` alone runs
-a build without the RGB layouts."""
+a build without the RGB layouts.  bgra, rgb24 and rgbp encode the same colours, so their packet bytes are equal."""
 import ctypes as C
 import os
 import sys
@@ -21,8 +23,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 W, H, S, WARM, STEPS, NVID = 1920, 1080, 192, 2, 12, 4
-PITCH, PITCH_RGB = 2048, 8192
-BGRA = 0x10
+PITCH, PITCH_RGB, PITCH_RGB24 = 2048, 8192, 6144
+BGRA, BGR, RGBP = 0x10, 0x20, 0x22
 
 
 class SURFACE(C.Structure):
@@ -62,12 +64,24 @@ def main():
             uf = (u.float() - 128.0).repeat_interleave(2, 0).repeat_interleave(2, 1) * (255.0 / 224.0)
             vf = (v.float() - 128.0).repeat_interleave(2, 0).repeat_interleave(2, 1) * (255.0 / 224.0)
             r, g, b = yf + 1.402 * vf, yf - 0.344136 * uf - 0.714136 * vf, yf + 1.772 * uf
-            t = torch.zeros((H, PITCH_RGB), dtype=torch.uint8, device="cuda")
-            px = t[:, :4 * W].view(H, W, 4)
-            for i, c in enumerate((b, g, r)):
-                px[..., i] = c.round().clamp(0, 255).to(torch.uint8)
-            px[..., 3] = 255
-            keep, layout = [t], BGRA
+            b, g, r = (c.round().clamp(0, 255).to(torch.uint8) for c in (b, g, r))
+            if mode == "rgbp":  # the same colours as three planes
+                keep, layout = [], RGBP
+                for c in (r, g, b):
+                    t = torch.zeros((H, PITCH), dtype=torch.uint8, device="cuda")
+                    t[:, :W] = c
+                    keep.append(t)
+            elif mode == "rgb24":  # ... and as three bytes a pixel
+                t = torch.zeros((H, PITCH_RGB24), dtype=torch.uint8, device="cuda")
+                px = t[:, :3 * W].view(H, W, 3)
+                px[..., 0], px[..., 1], px[..., 2] = b, g, r
+                keep, layout = [t], BGR
+            else:
+                t = torch.zeros((H, PITCH_RGB), dtype=torch.uint8, device="cuda")
+                px = t[:, :4 * W].view(H, W, 4)
+                px[..., 0], px[..., 1], px[..., 2] = b, g, r
+                px[..., 3] = 255
+                keep, layout = [t], BGRA
         return keep, layout
 
     def own(keep, layout):
