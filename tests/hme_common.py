@@ -50,9 +50,10 @@ def build_pyramid(lib, base, levels):
 class Scene:
     """src = frame t, ogr = frame t-1 (original), ref = degraded frame t-1 (stands for the reconstruction).
     `planes` = ((Y, U, V) of the current picture, of the previous one, of the degraded previous one) replaces the synthetic
-    video's pictures by given ones, already on the format's chroma grid."""
+    video's pictures by given ones, already on the format's chroma grid.  `blk` = (blk_w, blk_h, nblocks_h, nblocks_v) replaces the
+    block geometry that the encoder's rule gives the size (the encoder's block_size_override)."""
 
-    def __init__(self, ref_lib, w, h, subsamp, seed, t=3, with_prev_mvs=True, planes=None):
+    def __init__(self, ref_lib, w, h, subsamp, seed, t=3, with_prev_mvs=True, planes=None, blk=None):
         self.w, self.h, self.subsamp = w, h, subsamp
         if planes is None:
             pkg = load_pkg()
@@ -75,7 +76,7 @@ class Scene:
         for f in (self.src0, self.ogr0, self.ref0):
             ref_lib.dsv_extend_frame(f.ptr())
         self.meta = A.mk_meta(w, h, subsamp)
-        self.params = A.mk_params(self.meta, w, h, 1, 0, temporal_mc=t & 1)
+        self.params = A.mk_params(self.meta, w, h, 1, 0, temporal_mc=t & 1, blk=blk)
         self.nb = self.params.nblocks_h * self.params.nblocks_v
         self.levels = pyramid_levels(w, h, self.params.nblocks_h, self.params.nblocks_v)
         self.src = build_pyramid(ref_lib, self.src0, self.levels)
