@@ -25,8 +25,7 @@
 
 #include "batch.h"
 #include "codec.h"
-#include "ingest_scale.h"
-#include "ingest_resize.h"
+#include "enc_ingest.h"
 #include "sideinfo.h"
 
 using namespace dsv2;
@@ -838,12 +837,7 @@ struct Job {
     EncImpl *im;
     DSV_FRAME *frame;          // host picture (dsv_enc) ...
     const uint8_t *dev_planar; // ... or packed planar picture already in HBM
-    dsv2hip_surface surf;      // ... or (has_surf) a pitched planar / semi-planar surface in HBM, by value: the caller's array may go
-    bool has_surf;
-    int src_w, src_h, src_shift; // has_surf through the scaled calls with a scale: the picture IN THE SURFACE is src_w x src_h and is reduced by
-                                 // 1 << src_shift on ingest (ingest_scale.h); surf.layout is then the layout without its scale value.  0: unscaled
-    bool sized;                  // has_surf through the sized calls, src_shift 0: the picture IN THE SURFACE is src_w x src_h, larger than the
-                                 // encoder's, and is resampled to it on ingest (ingest_resize.h)
+    enc_ingest::Source source; // ... or a pitched surface in HBM of any accepted kind, by whichever route (enc_ingest.h)
     const uint8_t *host_planar; // ... or packed planar picture in host memory, uploaded by the batch engine (pinned: asynchronously)
     const uint8_t *host_next;   // the picture this stream will bring to the NEXT step: uploaded under this step's kernels
     bool from_frame;            // host_planar is a DSV_FRAME packed by dsv_enc: planar whatever the encoder's packed-input format
@@ -967,15 +961,9 @@ struct BatchScratch { // pinned + device memory for the job tables, the step's H
     int cap = 0;
     void ensure(int n)
     {
-        // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture; behind them the three source planes of a
-        // stream that brings a surface, or the one record of a stream that brings an RGB surface.  A stream brings ONE kind of
-        // picture, so the records of a scaled source lie in the same room: the arena is the size it always was)
-        static_assert(3 * sizeof(ScaledSurfaceJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob) && sizeof(ScaledRgbJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob),
-                      "a scaled source's records fit the room reserved for a stream's surface records");
-        static_assert(3 * sizeof(SizedSurfaceJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob) && sizeof(SizedRgbJob) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob),
-                      "a sized source's records fit the same room");
-        static_assert(sizeof(Rgb3Job) <= 3 * sizeof(SurfaceJob) + sizeof(RgbJob), "a three-byte or planar RGB surface's record fits the same room");
-        tabs.reserve((size_t) n * (12288 + 3 * sizeof(SurfaceJob) + sizeof(RgbJob)) + 65536);
+        // (the last 4 KB a stream: the tables of a redone picture, redo_overflowed_picture; behind them the records a stream's surface
+        // brings, which are some of its plan's arrays)
+        tabs.reserve((size_t) n * (12288 + enc_ingest::kPlanRecordBytes) + 65536);
         if (n <= cap) {
             return;
         }
@@ -1530,44 +1518,9 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 // counters (thrown behind H1a, the search drained), 2 = as a search token that never came (thrown with the step's ingest,
 // pyramids and source pre-pass still enqueued on the stream)
 static std::atomic<int> g_fail_next_step{0};
-static std::atomic<unsigned long long> g_surface_steps[2]; // steps whose surface ingest ran in the wide / the general form (dsv2hip_enc_surface_stats)
-static std::atomic<unsigned long long> g_rgb_steps[2];     // the same for the RGB ingest (dsv2hip_enc_rgb_stats)
-static std::atomic<unsigned long long> g_rgb3_steps[4];    // three-byte RGB ingest wide / general, planar RGB ingest wide / general (dsv2hip_enc_rgb3_stats)
-static std::atomic<unsigned long long> g_resize_steps[4];  // sized YUV ingest wide / general, sized RGB ingest wide / general (dsv2hip_enc_resize_stats)
-static std::atomic<unsigned long long> g_scale_steps[4];   // scaled YUV ingest wide / general, scaled RGB ingest wide / general (dsv2hip_enc_scale_stats)
-
-static bool surface_is_rgb(int layout) { return (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_RGBA; }
-// BGR, RGB (three bytes a pixel) or RGBP (a plane per colour), or-ed with any DSV2HIP_CSC_* bits: the plain ingest's alone
-static bool surface_is_rgb3(int layout)
-{
-    const int order = layout & ~0x300;
-    return order == DSV2HIP_SURFACE_BGR || order == DSV2HIP_SURFACE_RGB || order == DSV2HIP_SURFACE_RGBP;
-}
-
-// The conversion of include/dsv2_hip.h for an RGB surface of `layout` as k_ingest_rgb takes it: each row of the preset's matrix as
-// byte quads in the surface's channel order (alpha weighs 0), chroma rows split into positive parts and magnitudes of negative ones
-template <class RgbJobT> static void rgb_job_coefs(RgbJobT &j, int layout)
-{
-    static const int presets[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},   // BT601 (limited)
-                                      {47, 157, 16, -26, -86, 112, 112, -102, -10},  // BT709 (limited)
-                                      {77, 150, 29, -43, -85, 128, 128, -107, -21},  // BT601 | FULL
-                                      {54, 183, 19, -29, -99, 128, 128, -116, -12}}; // BT709 | FULL
-    const bool full = (layout & DSV2HIP_CSC_FULL_RANGE) != 0;
-    const int *m = presets[(full ? 2 : 0) + ((layout & DSV2HIP_CSC_BT709) ? 1 : 0)];
-    const bool bgra = (layout & ~0x300) == DSV2HIP_SURFACE_BGRA || (layout & ~0x300) == DSV2HIP_SURFACE_BGR; // blue is byte 0 of a pixel
-    uint32_t q[3][2];
-    for (int row = 0; row < 3; row++) {
-        q[row][0] = q[row][1] = 0;
-        for (int c = 0; c < 3; c++) { // R, G, B
-            const int v = m[3 * row + c], at = 8 * (bgra ? 2 - c : c);
-            q[row][v < 0] |= (uint32_t) (v < 0 ? -v : v) << at;
-        }
-    }
-    j.ycoef = q[0][0];
-    j.upos = q[1][0], j.uneg = q[1][1];
-    j.vpos = q[2][0], j.vneg = q[2][1];
-    j.yoff = 128u + (full ? 0u : 256u * 16u);
-}
+// steps whose ingest of a launch class ran in the wide / the general form: [2 * class + (wide ? 0 : 1)] (dsv2hip_enc_surface_stats,
+// _rgb_stats, _scale_stats, _resize_stats, _rgb3_stats, each over its one or two classes)
+static std::atomic<unsigned long long> g_ingest_steps[2 * enc_ingest::kClasses];
 
 // workgroups per (picture, plane) of the entropy coder's chunk kernels; each walks its share of the plane's 1 024-symbol chunks
 static const int kEntSlots = (int) env_int("DSV2_ENT_SLOTS", 32); // (192 until round 6: four in five of those workgroups found no chunk)
@@ -1748,6 +1701,99 @@ static void upload_next(Step &st)
     }
 }
 
+// The way in of a step's surfaces: the records of their plans (enc_ingest.h), one table per launch class -- a class that no picture of
+// the step uses has no table and no launch -- and what picks each launch's form.  The tables lie behind the step's fixed ones, in the
+// order of the classes.
+struct Ingest {
+    Tab<SurfaceJob> surf;
+    Tab<RgbJob> rgb;
+    Tab<ScaledSurfaceJob> scaled_surf;
+    Tab<ScaledRgbJob> scaled_rgb;
+    Tab<SizedSurfaceJob> sized_surf;
+    Tab<SizedRgbJob> sized_rgb;
+    Tab<Rgb3Job> rgb3[2];
+    size_t room[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0}; // entries the step's plans need of each table
+    int n[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool wide[enc_ingest::kClasses] = {true, true, true, true, true, true, true, true}; // IngestPlan's, over the step
+    int scaled_row_bytes = 0, scaled_rgb_sw = 0;
+    void count(const std::vector<enc_ingest::IngestPlan> &plans)
+    {
+        for (const enc_ingest::IngestPlan &p : plans) {
+            for (int c = 0; c < enc_ingest::kClasses; c++) {
+                room[c] += (size_t) p.n[c];
+            }
+        }
+    }
+    void take(TableArena &tabs) // (beyond what BatchScratch::ensure reserved: fatal, TableArena::take)
+    {
+        using namespace enc_ingest;
+        surf = Tab<SurfaceJob>(tabs, room[SURF]);
+        rgb = Tab<RgbJob>(tabs, room[RGB]);
+        scaled_surf = Tab<ScaledSurfaceJob>(tabs, room[SCALED_SURF]);
+        scaled_rgb = Tab<ScaledRgbJob>(tabs, room[SCALED_RGB]);
+        sized_surf = Tab<SizedSurfaceJob>(tabs, room[SIZED_SURF]);
+        sized_rgb = Tab<SizedRgbJob>(tabs, room[SIZED_RGB]);
+        rgb3[0] = Tab<Rgb3Job>(tabs, room[RGB3_PACKED]);
+        rgb3[1] = Tab<Rgb3Job>(tabs, room[RGB3_PLANAR]);
+    }
+    template <class T> void append(Tab<T> &t, int cl, const T *jobs, const enc_ingest::IngestPlan &p)
+    {
+        std::copy_n(jobs, p.n[cl], t.h + n[cl]);
+        n[cl] += p.n[cl];
+        wide[cl] = wide[cl] && p.wide[cl];
+    }
+    void add(const enc_ingest::IngestPlan &p)
+    {
+        using namespace enc_ingest;
+        append(surf, SURF, p.surf, p);
+        append(rgb, RGB, p.rgb, p);
+        append(scaled_surf, SCALED_SURF, p.scaled_surf, p);
+        append(scaled_rgb, SCALED_RGB, p.scaled_rgb, p);
+        append(sized_surf, SIZED_SURF, p.sized_surf, p);
+        append(sized_rgb, SIZED_RGB, p.sized_rgb, p);
+        append(rgb3[0], RGB3_PACKED, p.rgb3, p);
+        append(rgb3[1], RGB3_PLANAR, p.rgb3, p);
+        scaled_row_bytes = std::max(scaled_row_bytes, p.scaled_row_bytes);
+        scaled_rgb_sw = std::max(scaled_rgb_sw, p.scaled_rgb_sw);
+    }
+    bool ran(int cl) const // the class has records: its launch follows, in the form that is counted here
+    {
+        if (n[cl]) {
+            g_ingest_steps[2 * cl + (wide[cl] ? 0 : 1)]++;
+        }
+        return n[cl] != 0;
+    }
+    // f0: the source planes of the step's geometry
+    void enqueue(hipStream_t bs, const DFrame &f0) const
+    {
+        using namespace enc_ingest;
+        const int w = f0.p[0].w, h = f0.p[0].h, ch = f0.p[1].h;
+        if (ran(SURF)) {
+            ingest_surface_batch(bs, surf.d, n[SURF], h, wide[SURF]);
+        }
+        if (ran(RGB)) {
+            ingest_rgb_batch(bs, rgb.d, n[RGB], h, wide[RGB]);
+        }
+        if (ran(SCALED_SURF)) {
+            ingest_surface_scaled_batch(bs, scaled_surf.d, n[SCALED_SURF], scaled_row_bytes, h, wide[SCALED_SURF]);
+        }
+        if (ran(SCALED_RGB)) {
+            ingest_rgb_scaled_batch(bs, scaled_rgb.d, n[SCALED_RGB], scaled_rgb_sw, ch, wide[SCALED_RGB]);
+        }
+        if (ran(SIZED_SURF)) {
+            ingest_sized_batch(bs, sized_surf.d, n[SIZED_SURF], w, h, wide[SIZED_SURF]);
+        }
+        if (ran(SIZED_RGB)) {
+            ingest_rgb_sized_batch(bs, sized_rgb.d, n[SIZED_RGB], w, h + ch, wide[SIZED_RGB]);
+        }
+        for (int kind = 0; kind < 2; kind++) {
+            if (ran(RGB3_PACKED + kind)) {
+                ingest_rgb3_batch(bs, rgb3[kind].d, n[RGB3_PACKED + kind], h, kind == kRgb3Planar, wide[RGB3_PACKED + kind]);
+            }
+        }
+    }
+};
+
 // ingest, border extension, pyramids, the coarsest level's read-back, the intra pictures' block analysis: every per-picture
 // helper runs ONCE for the whole batch over a device table of jobs
 static void g1_enqueue(Step &st)
@@ -1767,55 +1813,14 @@ static void g1_enqueue(Step &st)
     Tab<IntraJob> intra(sc.tabs, (size_t) n);
     Tab<PlaneOutJob> small(sc.tabs, (size_t) n);
     st.bsj = Tab<BlockStatsJob>(sc.tabs, (size_t) n);
-    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0, n_surf = 0, n_sj = 0, n_rgb = 0, n_rj = 0;
-    int n_ssurf = 0, n_ssj = 0, n_srgb = 0, n_srj = 0; // the scaled ones (Job::src_shift): tables, forms and launches of their own
-    int n_zsurf = 0, n_zsj = 0, n_zrgb = 0, n_zrj = 0; // the sized ones (Job::sized): likewise, behind the scaled ones
-    int n_rgb3[2] = {0, 0}, n_r3j[2] = {0, 0};         // three-byte / planar RGB (never scaled or sized): a table each, behind all of them
+    int n_ing = 0, n_ingu = 0, n_pyr = 0, n_intra = 0;
+    std::vector<enc_ingest::IngestPlan> plans((size_t) n); // (a picture that is no surface: an empty plan)
     for (int k = 0; k < n; k++) {
-        const bool rgb = st.jobs[k].has_surf && surface_is_rgb(st.jobs[k].surf.layout), scaled = st.jobs[k].has_surf && st.jobs[k].src_shift;
-        const bool sized = st.jobs[k].has_surf && st.jobs[k].sized;
-        const bool rgb3 = st.jobs[k].has_surf && surface_is_rgb3(st.jobs[k].surf.layout);
-        n_rgb += rgb && !scaled && !sized;
-        n_surf += st.jobs[k].has_surf && !rgb && !rgb3 && !scaled && !sized;
-        n_rgb3[(st.jobs[k].surf.layout & ~0x300) == DSV2HIP_SURFACE_RGBP] += rgb3;
-        n_srgb += rgb && scaled;
-        n_ssurf += !rgb && scaled;
-        n_zrgb += rgb && sized;
-        n_zsurf += !rgb && sized;
+        plans[(size_t) k] = enc_ingest::plan_ingest(st.jobs[k].im->dev.pics[st.jobs[k].im->cur].src, st.jobs[k].source);
     }
-    Tab<SurfaceJob> sj; // only a step with surface jobs has this table (behind all the others: theirs lie where they always did)
-    if (n_surf) {
-        sj = Tab<SurfaceJob>(sc.tabs, 3 * (size_t) n_surf);
-    }
-    Tab<RgbJob> rj; // only a step with RGB surfaces has this one, behind the SurfaceJob table
-    if (n_rgb) {
-        rj = Tab<RgbJob>(sc.tabs, (size_t) n_rgb);
-    }
-    Tab<ScaledSurfaceJob> ssj; // the scaled sources' tables: behind the existing ones, which lie where they always did
-    if (n_ssurf) {
-        ssj = Tab<ScaledSurfaceJob>(sc.tabs, 3 * (size_t) n_ssurf);
-    }
-    Tab<ScaledRgbJob> srj;
-    if (n_srgb) {
-        srj = Tab<ScaledRgbJob>(sc.tabs, (size_t) n_srgb);
-    }
-    Tab<SizedSurfaceJob> zsj; // the sized sources' tables: behind the scaled ones
-    if (n_zsurf) {
-        zsj = Tab<SizedSurfaceJob>(sc.tabs, 3 * (size_t) n_zsurf);
-    }
-    Tab<SizedRgbJob> zrj;
-    if (n_zrgb) {
-        zrj = Tab<SizedRgbJob>(sc.tabs, (size_t) n_zrgb);
-    }
-    Tab<Rgb3Job> r3j[2]; // only a step with such surfaces has them
-    for (int kind = 0; kind < 2; kind++) {
-        if (n_rgb3[kind]) {
-            r3j[kind] = Tab<Rgb3Job>(sc.tabs, (size_t) n_rgb3[kind]);
-        }
-    }
-    bool rgb3_wide[2] = {true, true};
-    bool surf_wide = true, rgb_wide = true, ssurf_wide = true, srgb_wide = true, zsurf_wide = true, zrgb_wide = true;
-    int ssurf_row_bytes = 0, srgb_sw = 0;
+    Ingest in;
+    in.count(plans);
+    in.take(sc.tabs);
     for (int k = 0; k < n; k++) {
         Job &jb = st.jobs[k];
         CodecDev &dv = jb.im->dev;
@@ -1825,81 +1830,8 @@ static void g1_enqueue(Step &st)
         }
         if (jb.frame) {
             dframe_upload(&cur.src, jb.frame, bs);
-        } else if (jb.has_surf && surface_is_rgb3(jb.surf.layout)) {
-            const dsv2hip_surface &sf = jb.surf;
-            const DPlane *dp = cur.src.p;
-            const int kind = (sf.layout & ~0x300) == DSV2HIP_SURFACE_RGBP ? kRgb3Planar : kRgb3Packed;
-            Rgb3Job &j = r3j[kind].h[n_r3j[kind]++];
-            j = Rgb3Job{{(const uint8_t *) sf.plane[0], nullptr, nullptr}, {sf.pitch[0], 0, 0}, {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride,
-                        dp[0].w, dp[0].h, DSV_FORMAT_H_SHIFT(cur.src.format), DSV_FORMAT_V_SHIFT(cur.src.format), kind, 0, 0, 0, 0, 0, 0};
-            for (int c = 1; c < 3 && kind == kRgb3Planar; c++) {
-                j.src[c] = (const uint8_t *) sf.plane[c], j.pitch[c] = sf.pitch[c];
-            }
-            rgb_job_coefs(j, kind == kRgb3Planar ? DSV2HIP_SURFACE_RGBA | (sf.layout & 0x300) : sf.layout); // (planar: R is byte 0 of a pixel dword)
-            rgb3_wide[kind] = rgb3_wide[kind] && rgb3_job_wide(j);
-        } else if (jb.has_surf && jb.sized && surface_is_rgb(jb.surf.layout)) {
-            const dsv2hip_surface &sf = jb.surf;
-            const DPlane *dp = cur.src.p;
-            SizedRgbJob &j = zrj.h[n_zrj++];
-            j = SizedRgbJob{(const uint8_t *) sf.plane[0], sf.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h,
-                            dp[1].w, dp[1].h, ingest_resize::sized_ratio(jb.src_w, jb.src_h, dp[0].w, dp[0].h, true),
-                            ingest_resize::sized_ratio(jb.src_w, jb.src_h, dp[1].w, dp[1].h, true), 0, 0, 0, 0, 0, 0};
-            rgb_job_coefs(j, sf.layout);
-            zrgb_wide = zrgb_wide && sized_rgb_job_wide(j);
-        } else if (jb.has_surf && jb.sized) {
-            const dsv2hip_surface &sf = jb.surf;
-            const bool semi = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR;
-            const int hs = DSV_FORMAT_H_SHIFT(cur.src.format), vs = DSV_FORMAT_V_SHIFT(cur.src.format);
-            const int scw = (jb.src_w + (1 << hs) - 1) >> hs, sch = (jb.src_h + (1 << vs) - 1) >> vs; // dsv_mk_frame's, of the SOURCE
-            for (int c = 0; c < 3; c++) { // (an interleaved plane: two records, its U and its V half)
-                const DPlane &dp = cur.src.p[c];
-                const int sp = semi && c == 2 ? 1 : c, pw = c ? scw : jb.src_w, ph = c ? sch : jb.src_h;
-                SizedSurfaceJob &j = zsj.h[n_zsj++];
-                j = SizedSurfaceJob{(const uint8_t *) sf.plane[sp], sf.pitch[sp], dp.data, dp.stride, dp.w, dp.h,
-                                    ingest_resize::sized_ratio(pw, ph, dp.w, dp.h, false), (uint16_t) (semi && c ? 2 : 1), (uint16_t) (semi && c == 2 ? 1 : 0)};
-                zsurf_wide = zsurf_wide && sized_job_wide(j, (size_t) (semi && c ? 2 * pw : pw));
-            }
-        } else if (jb.has_surf && jb.src_shift && surface_is_rgb(jb.surf.layout)) {
-            const dsv2hip_surface &sf = jb.surf;
-            const DPlane *dp = cur.src.p;
-            ScaledRgbJob &j = srj.h[n_srj++];
-            j = ScaledRgbJob{(const uint8_t *) sf.plane[0], sf.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, jb.src_w, jb.src_h,
-                             DSV_FORMAT_H_SHIFT(cur.src.format), DSV_FORMAT_V_SHIFT(cur.src.format), jb.src_shift, 0, 0, 0, 0, 0, 0};
-            rgb_job_coefs(j, sf.layout);
-            srgb_wide = srgb_wide && scaled_rgb_job_wide(j);
-            srgb_sw = std::max(srgb_sw, jb.src_w);
-        } else if (jb.has_surf && jb.src_shift) {
-            const dsv2hip_surface &sf = jb.surf;
-            const int nsrc = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR ? 2 : 3;
-            const int hs = DSV_FORMAT_H_SHIFT(cur.src.format), vs = DSV_FORMAT_V_SHIFT(cur.src.format);
-            const int scw = (jb.src_w + (1 << hs) - 1) >> hs, sch = (jb.src_h + (1 << vs) - 1) >> vs; // dsv_mk_frame's, of the SOURCE
-            for (int c = 0; c < nsrc; c++) {
-                const DPlane &dp = cur.src.p[c];
-                const bool uv = nsrc == 2 && c == 1;
-                ScaledSurfaceJob &j = ssj.h[n_ssj++];
-                j = ScaledSurfaceJob{(const uint8_t *) sf.plane[c], sf.pitch[c], dp.data, uv ? cur.src.p[2].data : nullptr, dp.stride,
-                                     c ? scw : jb.src_w, c ? sch : jb.src_h, jb.src_shift};
-                ssurf_wide = ssurf_wide && scaled_surface_job_wide(j);
-                ssurf_row_bytes = std::max(ssurf_row_bytes, uv ? 2 * j.pw : j.pw);
-            }
-        } else if (jb.has_surf && surface_is_rgb(jb.surf.layout)) {
-            const dsv2hip_surface &sf = jb.surf;
-            const DPlane *dp = cur.src.p;
-            RgbJob &j = rj.h[n_rj++];
-            j = RgbJob{(const uint8_t *) sf.plane[0], sf.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h,
-                       DSV_FORMAT_H_SHIFT(cur.src.format), DSV_FORMAT_V_SHIFT(cur.src.format), 0, 0, 0, 0, 0, 0};
-            rgb_job_coefs(j, sf.layout);
-            rgb_wide = rgb_wide && rgb_job_wide(j);
-        } else if (jb.has_surf) {
-            const dsv2hip_surface &sf = jb.surf;
-            const int nsrc = sf.layout == DSV2HIP_SURFACE_SEMIPLANAR ? 2 : 3;
-            for (int c = 0; c < nsrc; c++) {
-                const DPlane &dp = cur.src.p[c];
-                const bool uv = nsrc == 2 && c == 1;
-                SurfaceJob &j = sj.h[n_sj++];
-                j = SurfaceJob{(const uint8_t *) sf.plane[c], sf.pitch[c], dp.data, uv ? cur.src.p[2].data : nullptr, dp.stride, dp.w, dp.h};
-                surf_wide = surf_wide && surface_job_wide(j);
-            }
+        } else if (jb.source.surface()) {
+            in.add(plans[(size_t) k]);
         } else {
             IngestJob &ij = jb.im->input_uyvy && !jb.from_frame ? ingu.h[n_ingu++] : ing.h[n_ing++];
             ij.src = jb.dev_planar;
@@ -1961,36 +1893,7 @@ static void g1_enqueue(Step &st)
         ingest_batch(bs, ing.d, n_ing, f0.p[0].w, f0.p[0].h + f0.p[1].h + f0.p[2].h);
     }
     ingest_uyvy_batch(bs, ingu.d, n_ingu, f0.p[0].w, f0.p[0].h);
-    if (n_sj) {
-        ingest_surface_batch(bs, sj.d, n_sj, f0.p[0].h, surf_wide);
-        g_surface_steps[surf_wide ? 0 : 1]++;
-    }
-    if (n_rj) {
-        ingest_rgb_batch(bs, rj.d, n_rj, f0.p[0].h, rgb_wide);
-        g_rgb_steps[rgb_wide ? 0 : 1]++;
-    }
-    if (n_ssj) {
-        ingest_surface_scaled_batch(bs, ssj.d, n_ssj, ssurf_row_bytes, f0.p[0].h, ssurf_wide);
-        g_scale_steps[ssurf_wide ? 0 : 1]++;
-    }
-    if (n_srj) {
-        ingest_rgb_scaled_batch(bs, srj.d, n_srj, srgb_sw, f0.p[1].h, srgb_wide);
-        g_scale_steps[srgb_wide ? 2 : 3]++;
-    }
-    if (n_zsj) {
-        ingest_sized_batch(bs, zsj.d, n_zsj, f0.p[0].w, f0.p[0].h, zsurf_wide);
-        g_resize_steps[zsurf_wide ? 0 : 1]++;
-    }
-    if (n_zrj) {
-        ingest_rgb_sized_batch(bs, zrj.d, n_zrj, f0.p[0].w, f0.p[0].h + f0.p[1].h, zrgb_wide);
-        g_resize_steps[zrgb_wide ? 2 : 3]++;
-    }
-    for (int kind = 0; kind < 2; kind++) {
-        if (n_r3j[kind]) {
-            ingest_rgb3_batch(bs, r3j[kind].d, n_r3j[kind], f0.p[0].h, kind == kRgb3Planar, rgb3_wide[kind]);
-            g_rgb3_steps[2 * kind + (rgb3_wide[kind] ? 0 : 1)]++;
-        }
-    }
+    in.enqueue(bs, f0);
     extend_planes(bs, ext_y.d, n, f0.p[0].w, f0.p[0].h);
     extend_planes(bs, ext_c.d, 2 * n, f0.p[1].w, f0.p[1].h);
     for (int l = 0; l < L; l++) {
@@ -2799,57 +2702,35 @@ int dsv2hip_enc_batch(int n, DSV_ENCODER **encs, const void *const *dev_planar, 
     return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
 }
 
-/* a surface the ingest can read, for an encoder that takes one: layout, planes, every pitch at least its row's bytes (an RGB surface:
- * plane[0] and pitch[0] alone, four bytes a pixel -- BGR / RGB: three; RGBP: three planes of w bytes a row) */
-static bool surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf)
+/* ---- pictures that are pitched surfaces in device memory, through the three surface calls (enc_ingest.h: Call) ----
+ * plain:  planar, or luma + one interleaved UV plane (NV12 with 4:2:0), or RGB of four or three bytes a pixel or a plane per colour, at
+ *         the encoder's size;
+ * scaled: a surface of src_w x src_h for an encoder of ceil(src_w / n) x ceil(src_h / n), n = 2, 4, 8 by the layout's scale value;
+ * sized:  a surface of src_w x src_h for an encoder of W x H, W <= src_w <= 8 W, H <= src_h <= 8 H.
+ * What an encoder takes through which call is enc_ingest::accept's one rule. */
+static bool accept_surface(enc_ingest::Call call, const DSV_ENCODER *enc, const dsv2hip_surface &sf, int src_w, int src_h, enc_ingest::Source *out)
 {
-    if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
-        return false;
-    }
-    const int hs = DSV_FORMAT_H_SHIFT(enc->vidmeta.subsamp);
-    const size_t w = (size_t) enc->vidmeta.width, cw = (w + ((size_t) 1 << hs) - 1) >> hs;
-    if (surface_is_rgb(sf->layout)) { // (a stream format outside the five the conversion knows is refused: k_ingest_rgb has no code for it)
-        const int f = enc->vidmeta.subsamp;
-        const bool known = f == DSV_SUBSAMP_444 || f == DSV_SUBSAMP_422 || f == DSV_SUBSAMP_420 || f == DSV_SUBSAMP_411 || f == DSV_SUBSAMP_410;
-        return known && sf->plane[0] && sf->pitch[0] >= 4 * w;
-    }
-    if (surface_is_rgb3(sf->layout)) { // (likewise; three bytes a pixel in plane[0], or a plane of w bytes a row per colour)
-        if (!ingest_scale::rgb_format(enc->vidmeta.subsamp)) {
-            return false;
-        }
-        if ((sf->layout & ~0x300) == DSV2HIP_SURFACE_RGBP) {
-            return sf->plane[0] && sf->plane[1] && sf->plane[2] && sf->pitch[0] >= w && sf->pitch[1] >= w && sf->pitch[2] >= w;
-        }
-        return sf->plane[0] && sf->pitch[0] >= 3 * w;
-    }
-    if (sf->layout != DSV2HIP_SURFACE_PLANAR && sf->layout != DSV2HIP_SURFACE_SEMIPLANAR) {
-        return false;
-    }
-    if (sf->layout == DSV2HIP_SURFACE_SEMIPLANAR) {
-        return sf->plane[0] && sf->plane[1] && sf->pitch[0] >= w && sf->pitch[1] >= 2 * cw;
-    }
-    return sf->plane[0] && sf->plane[1] && sf->plane[2] && sf->pitch[0] >= w && sf->pitch[1] >= cw && sf->pitch[2] >= cw;
+    const bool uyvy_input = enc->ref && ((const EncImpl *) enc->ref)->input_uyvy;
+    return enc_ingest::accept(call, enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, uyvy_input, sf, src_w, src_h, out);
 }
 
-/* dsv2hip_enc_batch for pictures that are pitched surfaces in device memory: planar, or luma + one interleaved UV plane (NV12 with
- * 4:2:0).  surf[k] is read during the call only.  Refused as a whole with -1, nothing touched, for what dsv2hip_enc_batch refuses,
- * a surface surface_ok does not pass, or an encoder with UYVY input on. */
-int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs)
+/* dsv2hip_enc_batch for surfaces; surf[k] is read during the call only.  Refused as a whole with -1, nothing touched, for what
+ * dsv2hip_enc_batch refuses or a surface accept() does not pass.  src_w, src_h: of the scaled and the sized call */
+static int surface_batch(enc_ingest::Call call, int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs,
+                         int *nbufs)
 {
-    if (n <= 0 || !encs || !surf || !bufs || !nbufs) {
+    const bool plain = call == enc_ingest::CALL_PLAIN;
+    if (n <= 0 || !encs || !surf || (!plain && (!src_w || !src_h)) || !bufs || !nbufs) {
         return -1;
-    }
-    for (int k = 0; k < n; k++) {
-        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !surface_ok(encs[k], &surf[k])) {
-            return -1;
-        }
     }
     std::vector<Job> jobs((size_t) n);
     for (int k = 0; k < n; k++) {
         memset(&jobs[(size_t) k], 0, sizeof(Job));
+        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) ||
+            !accept_surface(call, encs[k], surf[k], plain ? 0 : src_w[k], plain ? 0 : src_h[k], &jobs[(size_t) k].source)) {
+            return -1;
+        }
         jobs[(size_t) k].enc = encs[k];
-        jobs[(size_t) k].surf = surf[k];
-        jobs[(size_t) k].has_surf = true;
         jobs[(size_t) k].bufs = bufs + 4 * k;
     }
     const bool ok = enc_batch_ok(jobs.data(), n);
@@ -2860,117 +2741,42 @@ int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *
 }
 
 /* dsv2hip_enc_device_frame for one surface: a step of its own; 0 packets where the batch call would return -1 */
-int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs)
+static int surface_frame(enc_ingest::Call call, DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
 {
-    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !surface_ok(enc, surf)) {
-        return 0;
-    }
     Job jb;
     memset(&jb, 0, sizeof(jb));
-    jb.enc = enc;
-    jb.surf = *surf;
-    jb.has_surf = true;
-    jb.bufs = bufs;
-    enc_batch(&jb, 1);
-    return jb.nbuf;
-}
-
-void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset)
-{
-    for (int i = 0; i < 2; i++) {
-        if (out2) {
-            out2[i] = g_surface_steps[i].load();
-        }
-        if (reset) {
-            g_surface_steps[i].store(0);
-        }
-    }
-}
-
-void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset)
-{
-    for (int i = 0; i < 2; i++) {
-        if (out2) {
-            out2[i] = g_rgb_steps[i].load();
-        }
-        if (reset) {
-            g_rgb_steps[i].store(0);
-        }
-    }
-}
-
-void dsv2hip_enc_rgb3_stats(unsigned long long *out4, int reset)
-{
-    for (int i = 0; i < 4; i++) {
-        if (out4) {
-            out4[i] = g_rgb3_steps[i].load();
-        }
-        if (reset) {
-            g_rgb3_steps[i].store(0);
-        }
-    }
-}
-
-/* ---- half, quarter and eighth-size ingest: a surface of src_w x src_h for an encoder of ceil(src_w / n) x ceil(src_h / n) ----
- * The rule is ingest_scale.h's device-free one (plan_source, surface_fits); with no scale value in the layout the surface must pass
- * surface_ok as well, and the step is then the plain call's, job for job. */
-static bool scaled_surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf, int src_w, int src_h, ingest_scale::Source *src)
-{
-    if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
-        return false;
-    }
-    if (!ingest_scale::plan_source(src_w, src_h, enc->vidmeta.subsamp, sf->layout, src) ||
-        !ingest_scale::surface_fits(*src, *sf, enc->vidmeta.width, enc->vidmeta.height)) {
-        return false;
-    }
-    return src->shift != 0 || surface_ok(enc, sf);
-}
-
-static void scaled_job(Job &jb, DSV_ENCODER *enc, const dsv2hip_surface &sf, const ingest_scale::Source &src, int src_w, int src_h, DSV_BUF *bufs)
-{
-    memset(&jb, 0, sizeof(Job));
-    jb.enc = enc;
-    jb.surf = sf;
-    jb.surf.layout = src.plain_layout;
-    jb.has_surf = true;
-    if (src.shift) {
-        jb.src_w = src_w, jb.src_h = src_h, jb.src_shift = src.shift;
-    }
-    jb.bufs = bufs;
-}
-
-int dsv2hip_enc_batch_surface_scaled(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs)
-{
-    if (n <= 0 || !encs || !surf || !src_w || !src_h || !bufs || !nbufs) {
-        return -1;
-    }
-    std::vector<ingest_scale::Source> src((size_t) n);
-    for (int k = 0; k < n; k++) {
-        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !scaled_surface_ok(encs[k], &surf[k], src_w[k], src_h[k], &src[(size_t) k])) {
-            return -1;
-        }
-    }
-    std::vector<Job> jobs((size_t) n);
-    for (int k = 0; k < n; k++) {
-        scaled_job(jobs[(size_t) k], encs[k], surf[k], src[(size_t) k], src_w[k], src_h[k], bufs + 4 * k);
-    }
-    const bool ok = enc_batch_ok(jobs.data(), n);
-    for (int k = 0; k < n; k++) {
-        nbufs[k] = jobs[(size_t) k].nbuf;
-    }
-    return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
-}
-
-int dsv2hip_enc_surface_frame_scaled(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
-{
-    ingest_scale::Source src;
-    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !scaled_surface_ok(enc, surf, src_w, src_h, &src)) {
+    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !accept_surface(call, enc, *surf, src_w, src_h, &jb.source)) {
         return 0;
     }
-    Job jb;
-    scaled_job(jb, enc, *surf, src, src_w, src_h, bufs);
+    jb.enc = enc;
+    jb.bufs = bufs;
     enc_batch(&jb, 1);
     return jb.nbuf;
+}
+
+int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs)
+{
+    return surface_batch(enc_ingest::CALL_PLAIN, n, encs, surf, nullptr, nullptr, bufs, nbufs);
+}
+int dsv2hip_enc_surface_frame(DSV_ENCODER *enc, const dsv2hip_surface *surf, DSV_BUF *bufs)
+{
+    return surface_frame(enc_ingest::CALL_PLAIN, enc, surf, 0, 0, bufs);
+}
+int dsv2hip_enc_batch_surface_scaled(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs)
+{
+    return surface_batch(enc_ingest::CALL_SCALED, n, encs, surf, src_w, src_h, bufs, nbufs);
+}
+int dsv2hip_enc_surface_frame_scaled(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
+{
+    return surface_frame(enc_ingest::CALL_SCALED, enc, surf, src_w, src_h, bufs);
+}
+int dsv2hip_enc_batch_surface_sized(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs)
+{
+    return surface_batch(enc_ingest::CALL_SIZED, n, encs, surf, src_w, src_h, bufs, nbufs);
+}
+int dsv2hip_enc_surface_frame_sized(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
+{
+    return surface_frame(enc_ingest::CALL_SIZED, enc, surf, src_w, src_h, bufs);
 }
 
 int dsv2hip_enc_scaled_dims(int src_w, int src_h, int subsamp, int layout, int *enc_w, int *enc_h, size_t row_bytes[3], int rows[3])
@@ -2986,75 +2792,6 @@ int dsv2hip_enc_scaled_dims(int src_w, int src_h, int subsamp, int layout, int *
     return 0;
 }
 
-void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset)
-{
-    for (int i = 0; i < 4; i++) {
-        if (out4) {
-            out4[i] = g_scale_steps[i].load();
-        }
-        if (reset) {
-            g_scale_steps[i].store(0);
-        }
-    }
-}
-
-/* ---- ingest at any larger size: a surface of src_w x src_h for an encoder of W x H, W <= src_w <= 8 W, H <= src_h <= 8 H ----
- * The rule is ingest_resize.h's device-free one (plan_sized_source, sized_surface_fits).  An entry whose layout carries a scale value
- * is the scaled call's entry; one at the encoder's own size must pass surface_ok and is the plain call's job. */
-static bool sized_surface_ok(const DSV_ENCODER *enc, const dsv2hip_surface *sf, int src_w, int src_h, ingest_resize::Sized *z)
-{
-    if (enc->ref && ((const EncImpl *) enc->ref)->input_uyvy) {
-        return false;
-    }
-    if (!ingest_resize::plan_sized_source(src_w, src_h, enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, sf->layout, z) ||
-        !ingest_resize::sized_surface_fits(*z, *sf)) {
-        return false;
-    }
-    return z->src.shift != 0 || z->sized || surface_ok(enc, sf);
-}
-
-static void sized_job(Job &jb, DSV_ENCODER *enc, const dsv2hip_surface &sf, const ingest_resize::Sized &z, int src_w, int src_h, DSV_BUF *bufs)
-{
-    scaled_job(jb, enc, sf, z.src, src_w, src_h, bufs);
-    if (z.sized) {
-        jb.src_w = src_w, jb.src_h = src_h, jb.sized = true;
-    }
-}
-
-int dsv2hip_enc_batch_surface_sized(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs, int *nbufs)
-{
-    if (n <= 0 || !encs || !surf || !src_w || !src_h || !bufs || !nbufs) {
-        return -1;
-    }
-    std::vector<ingest_resize::Sized> src((size_t) n);
-    for (int k = 0; k < n; k++) {
-        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !sized_surface_ok(encs[k], &surf[k], src_w[k], src_h[k], &src[(size_t) k])) {
-            return -1;
-        }
-    }
-    std::vector<Job> jobs((size_t) n);
-    for (int k = 0; k < n; k++) {
-        sized_job(jobs[(size_t) k], encs[k], surf[k], src[(size_t) k], src_w[k], src_h[k], bufs + 4 * k);
-    }
-    const bool ok = enc_batch_ok(jobs.data(), n);
-    for (int k = 0; k < n; k++) {
-        nbufs[k] = jobs[(size_t) k].nbuf;
-    }
-    return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
-}
-
-int dsv2hip_enc_surface_frame_sized(DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
-{
-    ingest_resize::Sized z;
-    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !sized_surface_ok(enc, surf, src_w, src_h, &z)) {
-        return 0;
-    }
-    Job jb;
-    sized_job(jb, enc, *surf, z, src_w, src_h, bufs);
-    enc_batch(&jb, 1);
-    return jb.nbuf;
-}
-
 int dsv2hip_enc_sized_dims(int src_w, int src_h, int enc_w, int enc_h, int subsamp, int layout, size_t row_bytes[3], int rows[3])
 {
     ingest_resize::Sized z;
@@ -3067,17 +2804,24 @@ int dsv2hip_enc_sized_dims(int src_w, int src_h, int enc_w, int enc_h, int subsa
     return 0;
 }
 
-void dsv2hip_enc_resize_stats(unsigned long long *out4, int reset)
+/* steps whose ingest of launch classes first .. first + classes - 1 ran in the wide / the general form: two counts a class; reset != 0
+ * clears them afterwards */
+static void ingest_stats(int first, int classes, unsigned long long *out, int reset)
 {
-    for (int i = 0; i < 4; i++) {
-        if (out4) {
-            out4[i] = g_resize_steps[i].load();
+    for (int i = 0; i < 2 * classes; i++) {
+        if (out) {
+            out[i] = g_ingest_steps[2 * first + i].load();
         }
         if (reset) {
-            g_resize_steps[i].store(0);
+            g_ingest_steps[2 * first + i].store(0);
         }
     }
 }
+void dsv2hip_enc_surface_stats(unsigned long long *out2, int reset) { ingest_stats(enc_ingest::SURF, 1, out2, reset); }
+void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset) { ingest_stats(enc_ingest::RGB, 1, out2, reset); }
+void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::SCALED_SURF, 2, out4, reset); }
+void dsv2hip_enc_resize_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::SIZED_SURF, 2, out4, reset); }
+void dsv2hip_enc_rgb3_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::RGB3_PACKED, 2, out4, reset); }
 
 /* the same with the pictures in HOST memory (packed planar Y, U, V).  host_planar[k]: stream k's picture of this
  * step; host_next (may be NULL, entries may be NULL): the picture stream k will bring to the NEXT call -- it is

@@ -378,3 +378,101 @@ def test_refused_with_an_encoder_of_another_geometry():
         got = encode_steps(hip, [encs[k]], lambda s, t: Surface(content(w, h, "420", 3, 5)[t], w, h, "420", **spec[k]), 3)
         hip.dsv_enc_free(C.byref(encs[k]))
         same_packets(reference(w, h, "420", 3, 5), got[0], "%dx%d" % (w, h))
+
+
+# ---- 7. every way in, side by side ---------------------------------------------------------------------------------------------
+BGRA, RGBA, BGR, RGBP, BT709, HALF = 0x10, 0x11, 0x20, 0x22, 0x100, 0x1000
+# (call, layout, the picture in the surface, its planes as (row bytes, rows)) for nine 34x18 4:2:0 encoders
+WAYS_IN = [("plain", PLANAR, (34, 18), [(34, 18), (17, 9), (17, 9)]),
+           ("plain", SEMI, (34, 18), [(34, 18), (34, 9)]),
+           ("plain", BGRA, (34, 18), [(136, 18)]),
+           ("plain", BGR, (34, 18), [(102, 18)]),
+           ("plain", RGBP, (34, 18), [(34, 18)] * 3),
+           ("scaled", SEMI | HALF, (67, 35), [(67, 35), (68, 18)]),
+           ("scaled", RGBA | HALF, (67, 35), [(268, 35)]),
+           ("sized", PLANAR, (35, 19), [(35, 19), (18, 10), (18, 10)]),
+           ("sized", BGRA | BT709, (51, 27), [(204, 27)])]
+
+
+def bind_all_calls(hip):
+    P = C.POINTER
+    bind(hip)
+    for call in ("scaled", "sized"):
+        f = getattr(hip, "dsv2hip_enc_batch_surface_" + call)
+        f.argtypes, f.restype = [C.c_int, P(P(A.ENCODER)), P(SURFACE), P(C.c_int), P(C.c_int), P(A.BUF), P(C.c_int)], C.c_int
+        f = getattr(hip, "dsv2hip_enc_surface_frame_" + call)
+        f.argtypes, f.restype = [P(A.ENCODER), P(SURFACE), C.c_int, C.c_int, P(A.BUF)], C.c_int
+    for name in ("surface", "rgb", "scale", "resize", "rgb3"):
+        f = getattr(hip, "dsv2hip_enc_%s_stats" % name)
+        f.argtypes, f.restype = [P(C.c_ulonglong), C.c_int], None
+    return hip
+
+
+def all_forms(hip, reset=False):
+    got = {}
+    for name, n in (("surface", 2), ("rgb", 2), ("scale", 4), ("resize", 4), ("rgb3", 4)):
+        out = (C.c_ulonglong * n)()
+        getattr(hip, "dsv2hip_enc_%s_stats" % name)(out, int(reset))
+        got[name] = tuple(out)
+    return got
+
+
+def test_every_ingest_in_one_session():
+    """Nine 34x18 4:2:0 encoders, three frames (I P P); per frame the plain call with planar, NV12, BGRA, BGR and RGBP, the scaled call
+    with NV12 and RGBA at half size from 67x35 and the sized call with planar from 35x19 and BGRA-709 from 51x27.  Every stream's packets
+    are those of a fresh encoder fed the same surfaces alone through the matching one-frame call, and each of the five form counters
+    counts its own kind and no other: tight pitches and 16-byte aligned planes, so only the sized RGB ingest (pitch 204) is wide."""
+    hip = bind_all_calls(A.load_hip())
+    w, h, nfr = 34, 18, 3
+    rng = np.random.RandomState(34)
+    surfs = []  # [stream][frame]: (SURFACE, its tensors)
+    for s, (_, layout, _, planes) in enumerate(WAYS_IN):
+        per_frame = []
+        for t in range(nfr):
+            c, keep = SURFACE(), []
+            c.layout = layout
+            for i, (rb, rows) in enumerate(planes):
+                y, x = np.mgrid[0:rows, 0:rb]
+                pl = ((3 * x + 5 * y + 11 * s + 2 * t) % 200 + rng.randint(0, 9, size=(rows, rb))).astype(np.uint8)
+                keep.append(torch.from_numpy(pl).cuda())
+                assert keep[-1].data_ptr() % 16 == 0
+                c.plane[i], c.pitch[i] = keep[-1].data_ptr(), rb
+            per_frame.append((c, keep))
+        surfs.append(per_frame)
+    torch.cuda.synchronize()
+    groups = {call: [s for s, way in enumerate(WAYS_IN) if way[0] == call] for call in ("plain", "scaled", "sized")}
+    encs = new_encoders(hip, w, h, "420", len(WAYS_IN))
+    got = [[] for _ in WAYS_IN]
+    all_forms(hip, reset=True)
+    for t in range(nfr):
+        for call, ids in groups.items():
+            n = len(ids)
+            encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(encs[s]) for s in ids])
+            arr = (SURFACE * n)(*[surfs[s][t][0] for s in ids])
+            sw, sh = (C.c_int * n)(*[WAYS_IN[s][2][0] for s in ids]), (C.c_int * n)(*[WAYS_IN[s][2][1] for s in ids])
+            bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)()
+            if call == "plain":
+                assert hip.dsv2hip_enc_batch_surface(n, encp, arr, bufs, nbufs) == 0
+            else:
+                assert getattr(hip, "dsv2hip_enc_batch_surface_" + call)(n, encp, arr, sw, sh, bufs, nbufs) == 0
+            part = [[] for _ in ids]
+            take_packets(hip, bufs, nbufs, part)
+            for k, s in enumerate(ids):
+                got[s] += part[k]
+    counted = all_forms(hip)
+    assert counted == dict(surface=(0, 3), rgb=(0, 3), scale=(0, 3, 0, 3), resize=(0, 3, 3, 0), rgb3=(0, 3, 0, 3)), counted
+    for e in encs:
+        hip.dsv_enc_free(C.byref(e))
+    for s, (call, _, (sw, sh), _) in enumerate(WAYS_IN):
+        enc = new_encoders(hip, w, h, "420", 1)[0]
+        alone, bufs = [[]], (A.BUF * 4)()
+        for t in range(nfr):
+            c = surfs[s][t][0]
+            if call == "plain":
+                nb = hip.dsv2hip_enc_surface_frame(C.byref(enc), C.byref(c), bufs)
+            else:
+                nb = getattr(hip, "dsv2hip_enc_surface_frame_" + call)(C.byref(enc), C.byref(c), sw, sh, bufs)
+            assert nb > 0, "stream %d, frame %d: no packets" % (s, t)
+            take_packets(hip, bufs, (C.c_int * 1)(nb), alone)
+        hip.dsv_enc_free(C.byref(enc))
+        same_packets(alone[0], got[s], "stream %d (%s call, layout %#x)" % (s, call, WAYS_IN[s][1]))

@@ -5,7 +5,9 @@
 // access.  The program itself compares every plane with the contract of include/dsv2_hip.h restated here sample by sample in 64-bit
 // integers (nothing shared with the kernels' text), checks that no byte outside the planes' ow x oh changed (the border and 64 guard
 // bytes round every plane) and that no source byte changed, and sweeps the device-free validity rule
-// (ingest_resize::plan_sized_source, sized_surface_fits) against a restatement.  tests/test_ingest_resize_cpu.py builds and runs it:
+// (ingest_resize::plan_sized_source, sized_surface_fits) against a restatement.
+// The job records the bodies run on are the library's own: csrc/enc_ingest.h accepts each surface and plans them (tools/ingest_plan.h).
+// tests/test_ingest_resize_cpu.py builds and runs it:
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I digital-subband-video-2_amd/csrc tools/ingest_resize_check.cpp -o ingest_resize_check && ./ingest_resize_check [--dump DIR]
 // --dump DIR writes, for a few named cases, NAME.src (the source planes, rows of exactly their bytes, plane behind plane) and NAME.yuv
@@ -18,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "ingest_plan.h"
 #include "ingest_resize.h"
 
 using namespace dsv2;
@@ -168,6 +171,8 @@ template <bool WIDE> void run_yuv_grid(const SizedSurfaceJob &j)
 }
 
 // ---- one plane: pw x ph -> ow x oh, step / off as the kernel's job has them ------------------------------------------------------
+// (the one record this program writes itself: a plane on its own, at ratios and sizes no picture brings -- 1 : 1, one sample, the
+// largest a, b and D -- where the planner has nothing to say; the pictures below take theirs from it)
 void check_plane(int pw, int ph, int ow, int oh, int step, int off, int pitch_kind, int offset, int want_wide, int content = -1)
 {
     if (!resize_allowed(pw, ph, ow, oh)) {
@@ -202,6 +207,22 @@ void check_plane(int pw, int ph, int ow, int oh, int step, int off, int pitch_ki
     }
 }
 
+// The plan of a picture of sw x sh through the sized call (outside the bounds: refused, the end).  One of the encoder's own size is the
+// plain ingest's business and no caller reaches the sized kernels with it: the program still runs their bodies at 1 : 1, planned from
+// a source record written here.
+enc_ingest::IngestPlan plan_sized(int subsamp, const Plane &Y, const Plane &U, const Plane &V, const dsv2hip_surface &sf, enc_ingest::Source::Kind kind, int sw,
+                                  int sh)
+{
+    if (sw != Y.w || sh != Y.h) {
+        return planned(enc_ingest::CALL_SIZED, subsamp, Y, U, V, sf, sw, sh);
+    }
+    enc_ingest::Source own{kind, enc_ingest::Source::SIZED, {}, {}, sw, sh, 0, sf.layout};
+    for (int c = 0; c < 3; c++) {
+        own.plane[c] = (const uint8_t *) sf.plane[c], own.pitch[c] = sf.pitch[c];
+    }
+    return planned_from(subsamp, Y, U, V, own);
+}
+
 // ---- one YUV picture: sw x sh -> W x H in a chroma format, planar or semiplanar ----------------------------------------------------
 void check_yuv(int sw, int sh, int W, int H, int fmt, bool semi, int pitch_kind, int offset, bool force_general, int content = -1,
                const char *dump_name = nullptr)
@@ -218,21 +239,16 @@ void check_yuv(int sw, int sh, int W, int H, int fmt, bool semi, int pitch_kind,
     }
     Plane Y(W, H), U(cw, ch), V(cw, ch);
     Plane *dst[3] = {&Y, &U, &V};
-    SizedSurfaceJob job[3];
-    bool wide = !force_general;
-    for (int c = 0; c < 3; c++) {
-        const int sp = semi && c == 2 ? 1 : c, pw = c ? scw : sw, ph = c ? sch : sh;
-        if (!resize_allowed(pw, ph, dst[c]->w, dst[c]->h)) {
-            fprintf(stderr, "check_yuv: plane %d of %dx%d -> %dx%d is outside the bounds\n", c, sw, sh, W, H);
-            exit(1);
-        }
-        job[c] = SizedSurfaceJob{blk[sp]->src, blk[sp]->pitch, dst[c]->org, dst[c]->stride, dst[c]->w, dst[c]->h,
-                                 ingest_resize::sized_ratio(pw, ph, dst[c]->w, dst[c]->h, false), (uint16_t) (semi && c ? 2 : 1),
-                                 (uint16_t) (semi && c == 2 ? 1 : 0)};
-        wide = wide && sized_job_wide(job[c], rb[sp]);
+    dsv2hip_surface sf{};
+    sf.layout = semi ? DSV2HIP_SURFACE_SEMIPLANAR : DSV2HIP_SURFACE_PLANAR;
+    for (int c = 0; c < nsrc; c++) {
+        sf.plane[c] = blk[c]->src, sf.pitch[c] = blk[c]->pitch;
     }
+    const enc_ingest::IngestPlan plan = plan_sized(kSubsamp[fmt], Y, U, V, sf, semi ? enc_ingest::Source::SEMI : enc_ingest::Source::PLANAR, sw, sh);
+    expect_records(plan, enc_ingest::SIZED_SURF, 3);
+    const bool wide = !force_general && plan.wide[enc_ingest::SIZED_SURF];
     for (int c = 0; c < 3; c++) {
-        wide ? run_yuv_grid<true>(job[c]) : run_yuv_grid<false>(job[c]);
+        wide ? run_yuv_grid<true>(plan.sized_surf[c]) : run_yuv_grid<false>(plan.sized_surf[c]);
     }
     g_cases[0]++;
     g_wide[0] += wide;
@@ -281,21 +297,6 @@ void check_yuv(int sw, int sh, int W, int H, int fmt, bool semi, int pitch_kind,
 }
 
 // ---- RGB ---------------------------------------------------------------------------------------------------------------------
-// the job's quads, restated from the header's table: bytes in the surface's channel order
-void fill_coefs(SizedRgbJob &j, bool bgra, int csc)
-{
-    const int *m = kMatrix[preset_of(csc)];
-    uint32_t q[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-    for (int row = 0; row < 3; row++) {
-        for (int c = 0; c < 3; c++) {
-            const int v = m[3 * row + c], at = 8 * (bgra ? 2 - c : c);
-            q[row][v < 0] |= (uint32_t) (v < 0 ? -v : v) << at;
-        }
-    }
-    j.ycoef = q[0][0], j.upos = q[1][0], j.uneg = q[1][1], j.vpos = q[2][0], j.vneg = q[2][1];
-    j.yoff = 128u + ((csc & 0x200) ? 0u : 256u * 16u);
-}
-
 template <bool WIDE> void run_rgb_grid(const SizedRgbJob &j)
 {
     for (int by = 0; by < (j.oh + j.ch + 3) / 4; by++) {
@@ -316,19 +317,15 @@ void check_rgb(int sw, int sh, int W, int H, int fmt, bool bgra, int csc, int pi
                const char *dump_name = nullptr)
 {
     const int hs = kHs[fmt], vs = kVs[fmt], cw = ceil_shift(W, hs), ch = ceil_shift(H, vs);
-    ingest_resize::Sized z;
-    if (!ingest_resize::plan_sized_source(sw, sh, W, H, kSubsamp[fmt], (bgra ? DSV2HIP_SURFACE_BGRA : DSV2HIP_SURFACE_RGBA) | csc, &z)) {
-        fprintf(stderr, "check_rgb: %dx%d -> %dx%d %s is refused\n", sw, sh, W, H, kFmtName[fmt]);
-        exit(1);
-    }
     unsigned seed = 613u * (unsigned) sw + 29u * (unsigned) sh + 3u * (unsigned) W + (unsigned) (fmt + 5 * pitch_kind + 20 * offset + csc);
     SourceBlock blk(4 * (size_t) sw, sh, pitch_kind, offset, content, seed);
     Plane Y(W, H), U(cw, ch), V(cw, ch);
     Plane *dst[3] = {&Y, &U, &V};
-    SizedRgbJob j{blk.src, blk.pitch, {Y.org, U.org, V.org}, Y.stride, U.stride, W, H, cw, ch, ingest_resize::sized_ratio(sw, sh, W, H, true),
-                  ingest_resize::sized_ratio(sw, sh, cw, ch, true), 0, 0, 0, 0, 0, 0};
-    fill_coefs(j, bgra, csc);
-    const bool wide = !force_general && sized_rgb_job_wide(j);
+    const dsv2hip_surface sf{{blk.src, nullptr, nullptr}, {blk.pitch, 0, 0}, (bgra ? DSV2HIP_SURFACE_BGRA : DSV2HIP_SURFACE_RGBA) | csc};
+    const enc_ingest::IngestPlan plan = plan_sized(kSubsamp[fmt], Y, U, V, sf, enc_ingest::Source::RGB4, sw, sh);
+    expect_records(plan, enc_ingest::SIZED_RGB, 1);
+    const SizedRgbJob &j = plan.sized_rgb[0];
+    const bool wide = !force_general && plan.wide[enc_ingest::SIZED_RGB];
     wide ? run_rgb_grid<true>(j) : run_rgb_grid<false>(j);
     g_cases[1]++;
     g_wide[1] += wide;

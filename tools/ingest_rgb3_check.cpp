@@ -6,6 +6,7 @@
 //   - with the conversion of include/dsv2_hip.h restated here sample by sample (nothing shared with the kernel's text), and
 //   - with what the body of k_ingest_rgb (csrc/ingest_rgb.h) makes of the same pixels as an RGBA surface with noise for alpha,
 // and checks that no byte outside the planes' w x h / cw x ch changed and that the surface is as it was.
+// The job records the bodies run on are the library's own: csrc/enc_ingest.h accepts each surface and plans them (tools/ingest_plan.h).
 // tests/test_ingest_rgb3_cpu.py builds and runs it:
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I digital-subband-video-2_amd/csrc tools/ingest_rgb3_check.cpp -o ingest_rgb3_check && ./ingest_rgb3_check [--dump DIR]
@@ -18,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "ingest_plan.h"
 #include "ingest_rgb3.h"
 
 using namespace dsv2;
@@ -105,22 +107,6 @@ struct Source {
     ~Source() { free(alloc); }
 };
 
-// a job's coefficient quads, built here from the matrix (the library's encoder.cpp has its own copy of this packing); b_first: byte 0
-// of a pixel dword is blue
-template <class JobT> void pack_coefs(JobT &j, int csc, bool b_first)
-{
-    const int *m = kMatrix[preset_of(csc)];
-    uint32_t q[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-    for (int row = 0; row < 3; row++) {
-        for (int c = 0; c < 3; c++) {
-            const int v = m[3 * row + c];
-            q[row][v < 0] |= (uint32_t) abs(v) << (8 * (b_first ? 2 - c : c));
-        }
-    }
-    j.ycoef = q[0][0], j.upos = q[1][0], j.uneg = q[1][1], j.vpos = q[2][0], j.vneg = q[2][1];
-    j.yoff = 128u + ((csc & 0x200) ? 0u : 4096u);
-}
-
 template <class F> void run_grid(int h, F thread)
 {
     const int blocks = (h + 15) / 16;
@@ -138,6 +124,7 @@ template <class F> void run_grid(int h, F thread)
 }
 
 const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+const int kSubsamp[5] = {DSV_SUBSAMP_444, DSV_SUBSAMP_422, DSV_SUBSAMP_420, DSV_SUBSAMP_411, DSV_SUBSAMP_410};
 const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
 long g_cases = 0, g_wide[2] = {0, 0};
 const char *g_dump = nullptr;
@@ -179,11 +166,16 @@ void check(int w, int h, int fmt, int csc, Order order, int pitch_kind, int offs
         s->keep();
     }
     Plane Y(w, h), U(cw, ch), V(cw, ch);
-    Rgb3Job j{{src[0]->org, planar ? src[1]->org : nullptr, planar ? src[2]->org : nullptr},
-              {src[0]->pitch, planar ? src[1]->pitch : 0, planar ? src[2]->pitch : 0},
-              {Y.org, U.org, V.org}, Y.stride, U.stride, w, h, hs, vs, planar ? kRgb3Planar : kRgb3Packed, 0, 0, 0, 0, 0, 0};
-    pack_coefs(j, csc, order == BGR);
-    const bool wide = rgb3_job_wide(j) && !force_general;
+    dsv2hip_surface sf{};
+    sf.layout = (DSV2HIP_SURFACE_BGR + (int) order) | csc;
+    for (int c = 0; c < nsrc; c++) {
+        sf.plane[c] = src[(size_t) c]->org, sf.pitch[c] = src[(size_t) c]->pitch;
+    }
+    const int cl = planar ? enc_ingest::RGB3_PLANAR : enc_ingest::RGB3_PACKED;
+    const enc_ingest::IngestPlan plan = planned(enc_ingest::CALL_PLAIN, kSubsamp[fmt], Y, U, V, sf, w, h);
+    expect_records(plan, cl, 1);
+    const Rgb3Job &j = plan.rgb3[0];
+    const bool wide = plan.wide[cl] && !force_general;
     if (planar) {
         wide ? run_grid(h, [&](int y0, int x, int step) { ingest_rgb3_rows<kRgb3Planar, true>(j, y0, x, step); })
              : run_grid(h, [&](int y0, int x, int step) { ingest_rgb3_rows<kRgb3Planar, false>(j, y0, x, step); });
@@ -229,8 +221,10 @@ void check(int w, int h, int fmt, int csc, Order order, int pitch_kind, int offs
             rgba[4 * i + 3] = (uint8_t) (seed >> 24);
         }
         Plane Y4(w, h), U4(cw, ch), V4(cw, ch);
-        RgbJob j4{rgba.data(), 4 * (size_t) w, {Y4.org, U4.org, V4.org}, Y4.stride, U4.stride, w, h, hs, vs, 0, 0, 0, 0, 0, 0};
-        pack_coefs(j4, csc, false);
+        const dsv2hip_surface sf4{{rgba.data(), nullptr, nullptr}, {4 * (size_t) w, 0, 0}, DSV2HIP_SURFACE_RGBA | csc};
+        const enc_ingest::IngestPlan plan4 = planned(enc_ingest::CALL_PLAIN, kSubsamp[fmt], Y4, U4, V4, sf4, w, h);
+        expect_records(plan4, enc_ingest::RGB, 1);
+        const RgbJob &j4 = plan4.rgb[0];
         run_grid(h, [&](int y0, int x, int step) { ingest_rgb_rows<4>(j4, y0, x, step); });
         const Plane *p4[3] = {&Y4, &U4, &V4};
         for (int c = 0; c < 3; c++) {

@@ -3,7 +3,9 @@
 // AddressSanitizer and UndefinedBehaviorSanitizer, which see every read outside the surface's allocation (an exact-size heap block:
 // the last row has nothing behind it), every write outside a plane's and every misaligned word access.  The program itself compares
 // the three planes with the conversion of include/dsv2_hip.h restated here sample by sample (nothing shared with the kernel's
-// text), and checks that no byte outside the planes' w x h / cw x ch changed.  tests/test_ingest_rgb_cpu.py builds and runs it:
+// text), and checks that no byte outside the planes' w x h / cw x ch changed.
+// The job records the bodies run on are the library's own: csrc/enc_ingest.h accepts each surface and plans them (tools/ingest_plan.h).
+// tests/test_ingest_rgb_cpu.py builds and runs it:
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I digital-subband-video-2_amd/csrc tools/ingest_rgb_check.cpp -o ingest_rgb_check && ./ingest_rgb_check [--dump DIR]
 // --dump DIR writes, for a few named cases, NAME.src (the pixels, h rows of 4 * w bytes) and NAME.yuv (the converted planes, packed).
@@ -14,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "ingest_plan.h"
 #include "ingest_rgb.h"
 
 using namespace dsv2;
@@ -77,21 +80,6 @@ struct Plane {
     ~Plane() { free(alloc); }
 };
 
-// the job's coefficient quads, built here from the matrix (the library's encoder.cpp has its own copy of this packing)
-void pack_coefs(RgbJob &j, int csc, bool bgra)
-{
-    const int *m = kMatrix[preset_of(csc)];
-    uint32_t q[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-    for (int row = 0; row < 3; row++) {
-        for (int c = 0; c < 3; c++) {
-            const int v = m[3 * row + c];
-            q[row][v < 0] |= (uint32_t) abs(v) << (8 * (bgra ? 2 - c : c));
-        }
-    }
-    j.ycoef = q[0][0], j.upos = q[1][0], j.uneg = q[1][1], j.vpos = q[2][0], j.vneg = q[2][1];
-    j.yoff = 128u + ((csc & 0x200) ? 0u : 4096u);
-}
-
 template <int VEC> void run_grid(const RgbJob &j)
 {
     const int blocks = (j.h + 15) / 16;
@@ -109,6 +97,7 @@ template <int VEC> void run_grid(const RgbJob &j)
 }
 
 const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+const int kSubsamp[5] = {DSV_SUBSAMP_444, DSV_SUBSAMP_422, DSV_SUBSAMP_420, DSV_SUBSAMP_411, DSV_SUBSAMP_410};
 const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
 long g_cases = 0, g_wide = 0;
 const char *g_dump = nullptr;
@@ -145,9 +134,11 @@ void check(int w, int h, int fmt, int csc, bool bgra, int pitch_kind, int offset
     }
     std::vector<uint8_t> was(alloc, alloc + bytes);
     Plane Y(w, h), U(cw, ch), V(cw, ch);
-    RgbJob j{src, pitch, {Y.org, U.org, V.org}, Y.stride, U.stride, w, h, hs, vs, 0, 0, 0, 0, 0, 0};
-    pack_coefs(j, csc, bgra);
-    const bool wide = rgb_job_wide(j) && !force_general;
+    const dsv2hip_surface sf{{src, nullptr, nullptr}, {pitch, 0, 0}, (bgra ? DSV2HIP_SURFACE_BGRA : DSV2HIP_SURFACE_RGBA) | csc};
+    const enc_ingest::IngestPlan plan = planned(enc_ingest::CALL_PLAIN, kSubsamp[fmt], Y, U, V, sf, w, h);
+    expect_records(plan, enc_ingest::RGB, 1);
+    const RgbJob &j = plan.rgb[0];
+    const bool wide = plan.wide[enc_ingest::RGB] && !force_general;
     wide ? run_grid<16>(j) : run_grid<4>(j);
     g_cases++;
     g_wide += wide;

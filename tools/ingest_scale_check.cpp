@@ -5,7 +5,9 @@
 // outside a plane's and every misaligned word access.  The program itself compares the three planes with the contract of
 // include/dsv2_hip.h restated here sample by sample (nothing shared with the kernels' text), checks that no byte outside the
 // planes' W' x H' / cw' x ch' changed (the border and 64 guard bytes round every plane), and sweeps the device-free validity rule
-// (ingest_scale::plan_source, surface_fits) against a restatement.  tests/test_ingest_scale_cpu.py builds and runs it:
+// (ingest_scale::plan_source, surface_fits) against a restatement.
+// The job records the bodies run on are the library's own: csrc/enc_ingest.h accepts each surface and plans them (tools/ingest_plan.h).
+// tests/test_ingest_scale_cpu.py builds and runs it:
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I digital-subband-video-2_amd/csrc tools/ingest_scale_check.cpp -o ingest_scale_check && ./ingest_scale_check [--dump DIR]
 // --dump DIR writes, for a few named cases, NAME.src (the source planes, rows of exactly their bytes, plane behind plane) and NAME.yuv
@@ -17,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "ingest_plan.h"
 #include "ingest_scale.h"
 
 using namespace dsv2;
@@ -168,15 +171,16 @@ void check_yuv(int sw, int sh, int fmt, int s, bool semi, int pitch_kind, int of
     }
     Plane Y(W, H), U(cw, ch), V(cw, ch);
     Plane *dst[3] = {&Y, &U, &V};
-    ScaledSurfaceJob job[3];
-    bool wide = !force_general;
+    dsv2hip_surface sf{};
+    sf.layout = (semi ? DSV2HIP_SURFACE_SEMIPLANAR : DSV2HIP_SURFACE_PLANAR) | (s << 12);
     for (int c = 0; c < nsrc; c++) {
-        const bool uv = semi && c == 1;
-        job[c] = ScaledSurfaceJob{blk[c]->src, blk[c]->pitch, dst[c]->org, uv ? V.org : nullptr, dst[c]->stride, c ? scw : sw, c ? sch : sh, s};
-        wide = wide && scaled_surface_job_wide(job[c]);
+        sf.plane[c] = blk[c]->src, sf.pitch[c] = blk[c]->pitch;
     }
+    const enc_ingest::IngestPlan plan = planned(enc_ingest::CALL_SCALED, kSubsamp[fmt], Y, U, V, sf, sw, sh);
+    expect_records(plan, enc_ingest::SCALED_SURF, nsrc);
+    const bool wide = !force_general && plan.wide[enc_ingest::SCALED_SURF];
     for (int c = 0; c < nsrc; c++) {
-        wide ? run_yuv_grid<true>(job[c], grid_x) : run_yuv_grid<false>(job[c], grid_x);
+        wide ? run_yuv_grid<true>(plan.scaled_surf[c], grid_x) : run_yuv_grid<false>(plan.scaled_surf[c], grid_x);
     }
     g_cases[0]++;
     g_wide[0] += wide;
@@ -250,20 +254,6 @@ int expect_scaled(const Picture &p, int csc, int row, int fw_log2, int fh_log2, 
     return (int) (v < 255 ? v : 255);
 }
 
-void pack_coefs(ScaledRgbJob &j, int csc, bool bgra)
-{
-    const int *m = kMatrix[preset_of(csc)];
-    uint32_t q[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-    for (int row = 0; row < 3; row++) {
-        for (int c = 0; c < 3; c++) {
-            const int v = m[3 * row + c];
-            q[row][v < 0] |= (uint32_t) abs(v) << (8 * (bgra ? 2 - c : c));
-        }
-    }
-    j.ycoef = q[0][0], j.upos = q[1][0], j.uneg = q[1][1], j.vpos = q[2][0], j.vneg = q[2][1];
-    j.yoff = 128u + ((csc & 0x200) ? 0u : 4096u);
-}
-
 template <bool WIDE> void run_rgb_grid(const ScaledRgbJob &j, int grid_x)
 {
     const int ch = ceil_shift(j.sh, j.shift + j.vs);
@@ -295,9 +285,16 @@ void check_rgb(int sw, int sh, int fmt, int s, int csc, bool bgra, int pitch_kin
     }
     blk.freeze();
     Plane Y(W, H), U(cw, ch), V(cw, ch);
-    ScaledRgbJob j{blk.src, blk.pitch, {Y.org, U.org, V.org}, Y.stride, U.stride, sw, sh, hs, vs, s, 0, 0, 0, 0, 0, 0};
-    pack_coefs(j, csc, bgra);
-    const bool wide = scaled_rgb_job_wide(j) && !force_general;
+    const dsv2hip_surface sf{{blk.src, nullptr, nullptr}, {blk.pitch, 0, 0}, (bgra ? DSV2HIP_SURFACE_BGRA : DSV2HIP_SURFACE_RGBA) | csc | (s << 12)};
+    // (0x1010, BGRA | BT601 | limited | HALF, is the value the grammar holds back: no caller can bring it, so its record is planned from
+    // a source record written here, and the kernel's body still sees the combination)
+    const enc_ingest::Source held_back{enc_ingest::Source::RGB4, enc_ingest::Source::REDUCED, {blk.src, nullptr, nullptr}, {blk.pitch, 0, 0}, sw, sh, s,
+                                       DSV2HIP_SURFACE_BGRA};
+    const enc_ingest::IngestPlan plan = sf.layout == 0x1010 ? planned_from(kSubsamp[fmt], Y, U, V, held_back)
+                                                            : planned(enc_ingest::CALL_SCALED, kSubsamp[fmt], Y, U, V, sf, sw, sh);
+    expect_records(plan, enc_ingest::SCALED_RGB, 1);
+    const ScaledRgbJob &j = plan.scaled_rgb[0];
+    const bool wide = plan.wide[enc_ingest::SCALED_RGB] && !force_general;
     wide ? run_rgb_grid<true>(j, grid_x) : run_rgb_grid<false>(j, grid_x);
     g_cases[1]++;
     g_wide[1] += wide;
