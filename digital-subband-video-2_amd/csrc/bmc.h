@@ -64,6 +64,9 @@ void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch
 // ... into packed four-byte RGB surfaces: n pictures of h rows (device table), converted on the way (egress_rgb.h).  wide: every
 // job's destination and pitch are multiples of 16 and its w of 4 (rgb_out_job_wide).
 void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide);
+// ... into the three planes R, G, B of callers' tensors: n pictures of at most h rows (device table), converted on the way
+// (egress_tensor.h).  wide: every job's plane pointers and pitches are multiples of four elements and its w of 4 (tensor_job_wide).
+void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h, bool wide);
 // ... at half, quarter or eighth size: n planes (device table) box-averaged on the way (egress_scale.h) into a caller's plane or the
 // decoder's staging picture.  wide: every job's destination and pitch are multiples of 8 and its row is writable up to a multiple of
 // 16 >> shift bytes (scale_job_wide).  max_oh: the most rows delivered.

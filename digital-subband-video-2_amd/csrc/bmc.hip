@@ -20,6 +20,7 @@
 #include "blockstat.h"
 #include "bmc.h"
 #include "egress_rgb.h"
+#include "egress_tensor.h"
 #include "egress_resize.h"
 #include "egress_scale.h"
 #include "egress_uv.h"
@@ -2407,6 +2408,55 @@ void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool
         DSV2_LAUNCH(k_egress_rgb<true>, grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH(k_egress_rgb<false>, grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- decoder egress into the three planes R, G, B of a caller's tensor: uint8, binary16, bfloat16 or binary32 elements -----------------
+// One job per picture (TensorOutJob, dev.h), fetched by value and pinned to scalar registers; k_egress_rgb's shape: 64 x 4 threads
+// cover 16 rows and walk the row in passes of 256 pixels.  The thread's work is egress_tensor.h's egress_tensor_rows (which
+// tools/egress_tensor_check.cpp runs on the CPU); the job's element type is uniform over the workgroup.
+__device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float, uni(__builtin_bit_cast(int, v))); }
+template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_tensor(const TensorOutJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const TensorOutJob jl = job_of(tab, blockIdx.y);
+    const TensorOutJob j{uni_ptr(jl.sy),
+                         uni_ptr(jl.su),
+                         uni_ptr(jl.sv),
+                         {uni_ptr(jl.dst[0]), uni_ptr(jl.dst[1]), uni_ptr(jl.dst[2])},
+                         uni(jl.ystride),
+                         uni(jl.cstride),
+                         {uni(jl.dpitch[0]), uni(jl.dpitch[1]), uni(jl.dpitch[2])},
+                         uni(jl.w),
+                         uni(jl.h),
+                         uni(jl.hs),
+                         uni(jl.vs),
+                         uni(jl.ky),
+                         uni(jl.ybase),
+                         uni(jl.rv),
+                         uni(jl.gu),
+                         uni(jl.gv),
+                         uni(jl.bu),
+                         uni(jl.dtype),
+                         {uni(jl.scale[0]), uni(jl.scale[1]), uni(jl.scale[2])},
+                         {uni(jl.bias[0]), uni(jl.bias[1]), uni(jl.bias[2])}};
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    egress_tensor_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_egress_tensor<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_egress_tensor<false>, grid, block, 0, s, d_jobs);
     }
 }
 

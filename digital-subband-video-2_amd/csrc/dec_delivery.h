@@ -2,9 +2,11 @@
 // call and of any allocation.  decoder.cpp plans every picture of a round with it before it sizes and fills the round's job
 // tables; tools/dec_delivery_check.cpp compiles it for the host under AddressSanitizer + UndefinedBehaviorSanitizer and sweeps
 // target kind x scale x out420p x postsharp x draw_info x alignment over synthetic addresses (tests/test_dec_delivery_cpu.py);
-// tools/dec_delivery_sized_check.cpp does the same for sized targets (tests/test_dec_delivery_sized_cpu.py).
+// tools/dec_delivery_sized_check.cpp does the same for sized targets (tests/test_dec_delivery_sized_cpu.py),
+// tools/dec_tensor_plan_check.cpp for tensor targets (tests/test_dec_tensor_plan_cpu.py).
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 
 #include "dev.h"
@@ -22,7 +24,8 @@ struct OutTarget {
         FRAME,  // a bordered frame on pinned memory the device writes directly: plane[] / pitch[] are its planes, frame_alloc its block
         PLANAR, // the caller's device planes Y, U, V (a packed buffer: pitch {w, cw, cw})
         SEMI,   // ... Y and one plane of interleaved U V rows (plane[2] unused)
-        RGB     // ... one plane of four-byte pixels, plane[0], converted on the way out (plane[1..2] unused)
+        RGB,    // ... one plane of four-byte pixels, plane[0], converted on the way out (plane[1..2] unused)
+        TENSOR  // ... the planes R, G, B of a tensor (dsv2hip_out_tensor), converted on the way out; pitches in bytes
     } kind = FRAME;
     uint8_t *plane[3] = {nullptr, nullptr, nullptr};
     int pitch[3] = {0, 0, 0};
@@ -31,9 +34,12 @@ struct OutTarget {
     int shift = 0;  // device targets: every plane at 1 / 2^shift of its size, box-averaged on the way out (egress_scale.h); 0 .. 3
     int ow = 0, oh = 0; // device targets: the picture at this size, every plane area-averaged on the way out (egress_resize.h); 0 x 0: not
                         // sized.  Never together with a shift
-    int csc = 0;    // RGB: the layout's DSV2HIP_CSC_* bits
+    int csc = 0;    // RGB, TENSOR: the DSV2HIP_CSC_* bits
     bool bgra = false; // RGB: bytes in memory B G R A, else R G B A
+    int dtype = 0;  // TENSOR: DSV2HIP_TENSOR_*
+    float scale[3] = {0, 0, 0}, bias[3] = {0, 0, 0}; // TENSOR, float element types: the per-plane constants
     bool device() const { return kind != FRAME; }
+    bool converted() const { return kind == RGB || kind == TENSOR; } // leaves through a YUV -> RGB conversion, which reads every plane in place
     bool sized() const { return ow != 0; }
     bool reduced() const { return shift != 0 || sized(); } // leaves through the reduction or the resampling
 };
@@ -73,6 +79,33 @@ inline bool target_surface(const dsv2hip_out_surface &sf, const size_t row_bytes
     return true;
 }
 
+// A caller's tensor whose element type, CSC bits and size dsv2hip_dec_tensor_dims accepted with these rows (the three planes are
+// alike): false for a plane that is missing or not aligned to its element, a pitch that is no multiple of the element, below the
+// row's bytes or beyond an int, a capacity that does not hold the rows, or (float element types) a constant that is not finite.
+inline bool target_tensor(const dsv2hip_out_tensor &tn, size_t row_bytes, int rows, OutTarget *out)
+{
+    OutTarget t;
+    t.kind = OutTarget::TENSOR;
+    t.dtype = tn.dtype, t.csc = tn.csc;
+    const size_t elem = (size_t) tensor_elem(tn.dtype);
+    for (int c = 0; c < 3; c++) {
+        if (!tn.plane[c] || ((uintptr_t) tn.plane[c]) % elem || tn.pitch[c] % elem || tn.pitch[c] < row_bytes || tn.pitch[c] > (size_t) INT32_MAX ||
+            tn.cap[c] < (size_t) (rows - 1) * tn.pitch[c] + row_bytes) {
+            return false;
+        }
+        if (tn.dtype != DSV2HIP_TENSOR_U8) {
+            if (!isfinite(tn.scale[c]) || !isfinite(tn.bias[c])) {
+                return false;
+            }
+            t.scale[c] = tn.scale[c], t.bias[c] = tn.bias[c];
+        }
+        t.plane[c] = (uint8_t *) tn.plane[c];
+        t.pitch[c] = (int) tn.pitch[c];
+    }
+    *out = t;
+    return true;
+}
+
 // the packed buffer of dsv2hip_dec_batch_device: the planar surface with pitch {w, cw, cw}, plane behind plane
 inline OutTarget target_packed(void *buf, const size_t row_bytes[3], const int rows[3])
 {
@@ -100,7 +133,7 @@ inline void rgb_out_coefs(RgbOutJob &j, int csc)
 
 // ---- what one picture contributes to a round --------------------------------------------------------------------------------------------
 // The jobs by launch class, in the order the round launches the classes: whole-frame copy, 4:2:0 conversion, egress, overlay, sharpening
-// in place, reduction, resampling, chroma interleave, RGB conversion.  A job of a later class may read what a job of an earlier one wrote -- the
+// in place, reduction, resampling, chroma interleave, RGB conversion, tensor conversion.  A job of a later class may read what a job of an earlier one wrote -- the
 // decoder's two staging areas -- and nothing else is shared between them.
 struct DeliveryPlan {
     CopyJob copy[1];
@@ -122,15 +155,19 @@ struct DeliveryPlan {
     bool uv_wide = true, uv_conv = false;  // the interleave job allows the 16-byte form / converts to 4:2:0 (bmc.hip: k_egress_uv)
     int uv_rows = 0;                       // the chroma rows it delivers ("4:1:0" to 4:2:0: more than the source has)
     bool rgb_wide = true;                  // the RGB job allows the 16-byte form (bmc.hip: k_egress_rgb)
+    // (behind everything the plans of the other targets hold: theirs are what they were)
+    TensorOutJob ten[1];
+    int n_ten = 0;
+    bool ten_wide = true;                  // the tensor job allows the unconditional vector stores (bmc.hip: k_egress_tensor)
 };
 
-// A sharpened and / or drawn-on picture that leaves reduced or as RGB has no delivered full-size luma plane for the overlay and the
+// A sharpened and / or drawn-on picture that leaves reduced, as RGB or as a tensor has no delivered full-size luma plane for the overlay and the
 // sharpening to act on: its luma goes through the egress kernel into DecImpl's staged luma plane (w x h, 16-byte aligned origin and stride)
 inline bool needs_staged_luma(const OutTarget &t, bool sharp, int draw)
 {
-    return t.device() && (t.reduced() || t.kind == OutTarget::RGB) && (sharp || draw);
+    return t.device() && (t.reduced() || t.converted()) && (sharp || draw);
 }
-// the reduced planes that k_egress_uv / k_egress_rgb then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
+// the reduced planes that k_egress_uv / k_egress_rgb / k_egress_tensor then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
 inline bool needs_staged_scaled(const OutTarget &t) { return t.device() && t.reduced() && t.kind != OutTarget::PLANAR; }
 // ... which a sized picture needs at up to the picture's own size, a shifted one at half size
 inline bool needs_staged_full(const OutTarget &t) { return needs_staged_scaled(t) && t.sized(); }
@@ -164,7 +201,7 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
         p.eg_sharp = p.eg_sharp || sharpen;
         p.eg_wide = p.eg_wide && egress_job_wide(j, dst.w);
     };
-    if (t.device() && (t.reduced() || t.kind == OutTarget::RGB)) {
+    if (t.device() && (t.reduced() || t.converted())) {
         // Every plane is read in place by the reduction (egress_scale.h) and / or the RGB conversion.  A sharpened and / or drawn-on
         // picture: its full-size luma is staged first, stands in for the delivered luma plane below (overlay, sharpening behind the
         // overlay) and is what the reduction or the conversion then reads.  (No 4:2:0 conversion here: the surface call refuses the pair.)
@@ -178,7 +215,7 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
             // into the staged scaled picture, from which the unchanged k_egress_uv (mode 0) / k_egress_rgb run on the reduced geometry
             const int s = t.shift, up = (1 << s) - 1;
             for (int c = 0; c < 3; c++) {
-                const bool staged = t.kind == OutTarget::RGB || (t.kind == OutTarget::SEMI && c);
+                const bool staged = t.converted() || (t.kind == OutTarget::SEMI && c);
                 DPlane red = staged ? staged_scaled[c] : DPlane{t.plane[c], t.pitch[c], 0, 0};
                 red.w = (src[c].w + up) >> s, red.h = (src[c].h + up) >> s;
                 const ScaleOutJob &sj = p.scl[p.n_scl++] = ScaleOutJob{src[c].data, red.data, src[c].stride, src[c].w, src[c].h, red.stride, s};
@@ -190,7 +227,7 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
             // the same routes at the size the caller names: luma ow x oh, chroma dsv_mk_frame's planes for that picture, each plane by
             // its own ratio (egress_resize.h)
             for (int c = 0; c < 3; c++) {
-                const bool staged = t.kind == OutTarget::RGB || (t.kind == OutTarget::SEMI && c);
+                const bool staged = t.converted() || (t.kind == OutTarget::SEMI && c);
                 DPlane red = staged ? staged_scaled[c] : DPlane{t.plane[c], t.pitch[c], 0, 0};
                 red.w = c ? (t.ow + (1 << hs) - 1) >> hs : t.ow, red.h = c ? (t.oh + (1 << vs) - 1) >> vs : t.oh;
                 const ResizeOutJob &rj = p.rsz[p.n_rsz++] = resize_job(src[c].data, src[c].stride, src[c].w, src[c].h, red.data, red.stride, red.w, red.h);
@@ -210,6 +247,31 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
                                                          src[0].w, src[0].h, hs, vs, 0, 0, 0, 0, 0, 0, t.bgra};
             rgb_out_coefs(rj, t.csc);
             p.rgb_wide = rgb_out_job_wide(rj);
+        } else if (t.kind == OutTarget::TENSOR) {
+            TensorOutJob &tj = p.ten[p.n_ten++] = TensorOutJob{src[0].data,
+                                                               src[1].data,
+                                                               src[2].data,
+                                                               {t.plane[0], t.plane[1], t.plane[2]},
+                                                               src[0].stride,
+                                                               src[1].stride,
+                                                               {t.pitch[0], t.pitch[1], t.pitch[2]},
+                                                               src[0].w,
+                                                               src[0].h,
+                                                               hs,
+                                                               vs,
+                                                               0,
+                                                               0,
+                                                               0,
+                                                               0,
+                                                               0,
+                                                               0,
+                                                               t.dtype,
+                                                               {t.scale[0], t.scale[1], t.scale[2]},
+                                                               {t.bias[0], t.bias[1], t.bias[2]}};
+            RgbOutJob coefs{};
+            rgb_out_coefs(coefs, t.csc);
+            tj.ky = coefs.ky, tj.ybase = coefs.ybase, tj.rv = coefs.rv, tj.gu = coefs.gu, tj.gv = coefs.gv, tj.bu = coefs.bu;
+            p.ten_wide = tensor_job_wide(tj);
         }
     } else if (!conv && !t.device() && !sharp_out) {
         p.copy[p.n_copy++] = CopyJob{recon.alloc, t.frame_alloc, recon.bytes};

@@ -254,6 +254,30 @@ struct RgbOutJob { // one decoded picture on its way into a packed four-byte RGB
     int bgra;                    // the surface's byte order: non-zero B G R A, zero R G B A
 };
 inline bool rgb_out_job_wide(const RgbOutJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && (j.w & 3) == 0; }
+constexpr int kTensorU8 = 0, kTensorF16 = 1, kTensorBF16 = 2, kTensorF32 = 3; // TensorOutJob::dtype (DSV2HIP_TENSOR_*)
+inline int tensor_elem(int dtype) { return dtype == kTensorU8 ? 1 : dtype == kTensorF32 ? 4 : 2; } // bytes of an element
+struct TensorOutJob { // one decoded picture on its way into three planes R, G, B of a caller's tensor (dsv2hip_out_tensor: uint8, binary16, bfloat16
+                      // or binary32 elements), converted on the way (egress_tensor.h, bmc.hip: k_egress_tensor); 136 bytes, fetched by value
+                      // through the scalar cache like RgbOutJob, whose source side it shares
+    const uint8_t *sy, *su, *sv; // RgbOutJob's
+    uint8_t *dst[3];             // device memory, element aligned: row y of R, G, B at dst[c] + y * dpitch[c], w elements of it written
+    int ystride, cstride;
+    int dpitch[3];               // bytes, multiples of the element size
+    int w, h;                    // of the picture
+    int hs, vs;                  // the stream's chroma shifts
+    int ky, ybase, rv, gu, gv, bu; // the conversion of include/dsv2_hip.h
+    int dtype;                   // kTensor*
+    float scale[3], bias[3];     // float dtypes: plane c holds fl32(fl32(byte * scale[c]) + bias[c]), rounded to the element type
+};
+// every plane's pointer and pitch multiples of four elements and w of 4: a thread's four samples of a row leave as one vector store
+inline bool tensor_job_wide(const TensorOutJob &j)
+{
+    uintptr_t bits = 0;
+    for (int c = 0; c < 3; c++) {
+        bits |= ((uintptr_t) j.dst[c]) | (uintptr_t) j.dpitch[c];
+    }
+    return (bits & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
+}
 struct ScaleOutJob { // one plane of a decoded picture on its way out at half, quarter or eighth size (dsv2hip_out_surface, DSV2HIP_SCALE_*): the box
                      // average of include/dsv2_hip.h (egress_scale.h, bmc.hip: k_egress_scale) into a plane of the caller's surface, or into the
                      // decoder's staging picture that k_egress_uv / k_egress_rgb then read; 40 bytes, fetched by value through the scalar cache

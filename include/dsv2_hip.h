@@ -820,7 +820,7 @@ void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset);
  * sizes on the first such picture (1.5 bytes a pixel for 4:2:0) and kept until the stream's geometry changes or the decoder is freed;
  * sized PLANAR delivery stages nothing.
  * Out of scope: enlargement; filters other than the area average; sized delivery behind out420p; three-byte and planar RGB out surfaces
- * (DSV2HIP_SURFACE_BGR / _RGB / _RGBP are refused by every out-surface call); the host DSV_FRAME path (dsv_dec,
+ * (DSV2HIP_SURFACE_BGR / _RGB / _RGBP are refused by every out-surface call; planar RGB leaves through the tensor calls below); the host DSV_FRAME path (dsv_dec,
  * dsv2hip_dec_batch, dsv2hip_dec_batch_device know nothing of a size).  (The encoder's side: dsv2hip_enc_batch_surface_sized, above.)
  * dsv2hip_dec_resize_stats: out2[0] / out2[1] = device rounds of this process whose resampling ran in the wide form (every resampled
  * plane that goes straight into a caller's surface -- PLANAR: all three, SEMIPLANAR: luma -- has a pointer and a pitch that are
@@ -832,6 +832,64 @@ int dsv2hip_dec_batch_surface_sized(int n, DSV_DECODER **decs, DSV_BUF *bufs, co
                                     DSV_FNUM *fn, int *ret);
 int dsv2hip_dec_surface_frame_sized(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_surface *surf, int out_w, int out_h, DSV_FNUM *fn);
 void dsv2hip_dec_resize_stats(unsigned long long *out2, int reset);
+/* PLANAR RGB TENSORS, u8 / f16 / bf16 / f32 -- what a vision model reads: [3, h, w], one plane per channel, usually floating point,
+ * usually normalised per channel.  The picture leaves the decoder in that form, full size or at any smaller size, without a four-byte
+ * surface and a second kernel of the caller's (drop alpha, transpose, convert, normalise) in between.  The out-surface calls keep
+ * refusing the layouts 0x20 .. 0x22: a tensor has an element type and per-channel constants, which dsv2hip_out_surface has no room
+ * for, so it has a descriptor and entry points of its own, and these serve the uint8 planar case too (what the encoder reads in place
+ * as DSV2HIP_SURFACE_RGBP).
+ * A contiguous torch [3, h, w] tensor is plane[c] = data_ptr + c * h * w * elem, pitch[c] = w * elem; a batch [n, 3, h, w] is n
+ * descriptors.  The planes are named by POINTER: plane[0] receives R, plane[1] G, plane[2] B, and a model trained on B, G, R passes
+ * them in the other order (scale[c] / bias[c] belong to plane[c]).  Planes may lie anywhere, also in different allocations.
+ * Semantics are those of dsv2hip_dec_batch_surface and dsv2hip_dec_batch_surface_sized: ret[k], fn[k], packet consumption and decoder
+ * state are dsv_dec's; t[k] is copied; only the row_bytes of each of the rows of each plane are written -- padding, the bytes behind
+ * the last row and anything else never are; a decoder without metadata may pass anything (its entry is not looked at); draw_info and
+ * postsharp act on the full-size luma before everything else; one step may mix element types, sizes, presets, constants and stream
+ * geometries; a refused call touches nothing: no packet, decoder, fn, ret or tensor.
+ * SIZE.  out_w == 0 && out_h == 0: the picture's own size.  Else the rules of DELIVERY AT ANY SMALLER SIZE above (reduction only,
+ * down to an eighth per axis, every plane within THE RESAMPLING's bounds); out_w == w && out_h == h is the plain delivery and counts
+ * in no resize statistic.  dsv2hip_dec_tensor_dims reports row_bytes = out_w * elem and rows = out_h (one pair: the three planes are
+ * alike; elem = 1, 2, 2, 4), or the picture's own size for 0 x 0, and -1 wherever the batch call would refuse for dtype, size or
+ * decoder.
+ * THE CONTRACT.  The bytes R, G, B of pixel (x, y) are THE CONVERSION of the decoder's RGB surfaces (above; csc: any subset of
+ * DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE) applied to the planar picture the same decoder delivers under the same settings --
+ * for a sized tensor, to the planes resampled by THE RESAMPLING.  A U8 tensor therefore holds exactly bytes 0, 1, 2 of the RGBA
+ * surface of the same call; scale and bias are ignored for it and may hold anything.  For a float dtype plane c holds, for its byte v,
+ *
+ *   f = fl32( fl32( (float) v * scale[c] ) + bias[c] )
+ *
+ * two IEEE binary32 operations, each rounded to nearest even, NOT fused into one multiply-add.  F32 stores f; F16 stores f converted
+ * to binary16, round to nearest even, subnormals kept, overflow to infinity; BF16 stores f converted to bfloat16, round to nearest
+ * even: (bits + 0x7fff + ((bits >> 16) & 1)) >> 16.  numpy reproduces all of it bit for bit: v.astype(np.float32) * np.float32(s) +
+ * np.float32(b), then .astype(np.float16).  torchvision's ToTensor + Normalize(mean, std) is scale = 1 / (255 * std), bias = -mean /
+ * std, folded by the caller; THIS form is the contract, and torch's own two steps (divide by 255, subtract, divide) may differ from it
+ * in the last bit.
+ * Refused as a whole with -1, for a decoder that has metadata: an unknown dtype; a csc bit outside the two; a NULL plane; a plane
+ * pointer or a pitch that is not a multiple of the element size; a pitch below the row's bytes or beyond INT_MAX; cap[c] <
+ * (rows - 1) * pitch[c] + row_bytes; scale[c] or bias[c] not finite (float dtypes only); dsv2hip_dec_set_out420p on; exactly one of
+ * out_w / out_h zero; a size dsv2hip_dec_sized_dims refuses for an RGB layout.
+ * MEMORY: as an RGB surface's -- a drawn-on or sharpened picture stages its luma, a sized one its resampled planes.
+ * Out of scope: interleaved [h, w, 3] out tensors; the DSV2HIP_SCALE_* presets (a size covers them where it divides; THE RESAMPLING
+ * says where the two differ); tensors and surfaces in one step; enlargement; any change to what the surface calls accept.
+ * dsv2hip_dec_tensor_stats: out2[0] / out2[1] = device rounds of this process whose tensor conversion ran in the wide form (every
+ * plane pointer and pitch of every tensor of the round a multiple of four elements and the delivered width a multiple of 4 -- any
+ * contiguous torch tensor with w % 4 == 0: a thread's four samples of a row leave as one 4 / 8 / 16-byte store) / in the general form
+ * so far; reset != 0 clears the counts afterwards.  Sized tensors also count in dsv2hip_dec_resize_stats, as any sized picture;
+ * nothing counts in dsv2hip_dec_rgb_stats. */
+enum { DSV2HIP_TENSOR_U8 = 0, DSV2HIP_TENSOR_F16 = 1, DSV2HIP_TENSOR_BF16 = 2, DSV2HIP_TENSOR_F32 = 3 };
+typedef struct dsv2hip_out_tensor {
+    void  *plane[3];   /* device memory: the R, G and B planes, named by pointer */
+    size_t pitch[3];   /* bytes from one row to the next */
+    size_t cap[3];     /* bytes the caller owns from plane[c] on */
+    int    dtype;      /* DSV2HIP_TENSOR_* */
+    int    csc;        /* any subset of DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE */
+    int    out_w, out_h; /* 0, 0: the picture's own size; else the rules of DELIVERY AT ANY SMALLER SIZE */
+    float  scale[3], bias[3]; /* for plane[c]; ignored (may hold anything) for U8 */
+} dsv2hip_out_tensor;
+int  dsv2hip_dec_tensor_dims(DSV_DECODER *dec, int dtype, int out_w, int out_h, size_t *row_bytes, int *rows);
+int  dsv2hip_dec_batch_tensor(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_tensor *t, DSV_FNUM *fn, int *ret);
+int  dsv2hip_dec_tensor_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_tensor *t, DSV_FNUM *fn);
+void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset);
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the

@@ -1,0 +1,343 @@
+// egress_tensor_check.cpp -- the body of k_egress_tensor (csrc/egress_tensor.h) run as plain C++ on the CPU, thread by thread, over a
+// sweep of forms, element types, presets, chroma formats, widths, heights, pitches, pointer offsets and constants; meant to be built
+// with AddressSanitizer and UndefinedBehaviorSanitizer, which see every read outside the source planes' allocations (exact-size heap
+// blocks: planes as dframe_alloc lays them out, and the luma also as the decoder stages it), every write outside a plane's and every
+// misaligned word access.  The program itself compares the three planes with the conversion and the float contract of
+// include/dsv2_hip.h restated here element by element (nothing shared with the kernel's text: the binary16 rounding is done in
+// integers), and checks that no byte outside the h rows of w elements changed -- guard bytes in front, padding between the rows,
+// guard bytes behind -- and that the source planes are as they were.
+// tests/test_egress_tensor_cpu.py builds and runs it:
+//   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+//         -I digital-subband-video-2_amd/csrc tools/egress_tensor_check.cpp -o egress_tensor_check && ./egress_tensor_check [--dump DIR]
+// --dump DIR writes, for a few named cases, NAME.yuv (the source planes, packed), NAME.const (scale[3], bias[3] as binary32) and
+// NAME.ten (the planes R, G, B, h rows of w elements each).  NAME = dtype_csc_format_WxH[_ramp].
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "egress_tensor.h"
+
+using namespace dsv2;
+
+namespace {
+
+constexpr uint8_t kGuard = 0xA5;
+constexpr int kLead = 64; // guard bytes in front of and behind every plane
+
+// ---- the contract, restated: one element at a time, in the header's own terms ---------------------------------------------------
+const long kPreset[4][6] = {{298, 16, 409, -100, -208, 516}, {298, 16, 459, -55, -136, 541}, {256, 0, 359, -88, -183, 454}, {256, 0, 403, -48, -120, 475}};
+int preset_of(int csc) { return ((csc & 0x200) ? 2 : 0) + ((csc & 0x100) ? 1 : 0); }
+
+long floor_shift8(long v) { return v >= 0 ? v / 256 : -((-v + 255) / 256); }
+uint8_t clamp255(long v) { return (uint8_t) (v < 0 ? 0 : v > 255 ? 255 : v); }
+
+void expect_pixel(int csc, int Y, int U, int V, uint8_t out[3])
+{
+    const long *p = kPreset[preset_of(csc)];
+    const long C = p[0] * (Y - p[1]), D = U - 128, E = V - 128;
+    out[0] = clamp255(floor_shift8(C + p[2] * E + 128));
+    out[1] = clamp255(floor_shift8(C + p[3] * D + p[4] * E + 128));
+    out[2] = clamp255(floor_shift8(C + p[5] * D + 128));
+}
+
+uint32_t bits_of(float f)
+{
+    uint32_t b;
+    memcpy(&b, &f, 4);
+    return b;
+}
+
+// binary32 bits to binary16 bits, round to nearest even, subnormals kept, overflow to infinity (finite or infinite input)
+uint32_t half_of(uint32_t b)
+{
+    const uint32_t sign = (b >> 16) & 0x8000u, mag = b & 0x7fffffffu;
+    if (mag >= 0x7f800000u) {
+        return sign | 0x7c00u;
+    }
+    const int e = (int) (mag >> 23) - 127; // unbiased exponent (zero and binary32 subnormals: -127, far below binary16's range)
+    if (e < -25) {
+        return sign; // below half of the smallest subnormal
+    }
+    uint64_t m = (mag & 0x7fffffu) | 0x800000u; // 1.23
+    int drop;                                   // bits of m that go
+    uint32_t base;
+    if (e < -14) {
+        drop = 13 + (-14 - e), base = 0; // subnormal: the value is m * 2^(e - 23), in units of 2^-24
+    } else {
+        drop = 13, base = (uint32_t) (e + 15 - 1) << 10; // the hidden bit adds the last exponent step
+    }
+    const uint64_t q = m >> drop, rest = m & ((1ull << drop) - 1), half = 1ull << (drop - 1);
+    uint32_t r = base + (uint32_t) q;
+    if (rest > half || (rest == half && (q & 1))) {
+        r++;
+    }
+    return sign | (r > 0x7c00u ? 0x7c00u : r);
+}
+
+uint32_t expect_elem(int dtype, uint8_t v, float scale, float bias)
+{
+    volatile float p = (float) v * scale; // (two operations, each rounded on its own)
+    volatile float f = p + bias;
+    const uint32_t b = bits_of(f);
+    return dtype == kTensorF32 ? b : dtype == kTensorF16 ? half_of(b) : (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+}
+
+// ---- source planes: an exact-size heap block each ---------------------------------------------------------------------------------
+struct Plane {
+    uint8_t *alloc, *org;
+    size_t bytes;
+    int stride, w, h;
+    std::vector<uint8_t> was;
+    // bordered: as dframe_alloc lays a plane out (32-pixel border, stride a multiple of 16, 16-byte aligned origin); else as the
+    // decoder stages a luma plane: no border, stride = w rounded up to 16, h rows
+    Plane(int w_, int h_, bool bordered, unsigned seed) : w(w_), h(h_)
+    {
+        const int b = bordered ? kBorder : 0;
+        stride = (w + 2 * b + 15) & ~15;
+        bytes = (size_t) stride * (size_t) (h + 2 * b);
+        alloc = (uint8_t *) aligned_alloc(16, bytes);
+        for (size_t i = 0; i < bytes; i++) { // (border and padding hold noise too)
+            seed = seed * 1664525u + 1013904223u;
+            alloc[i] = (seed >> 29) == 0 ? ((seed & 0x10000) ? 255 : 0) : (seed >> 28) == 2 ? ((seed & 0x10000) ? 235 : 16) : (uint8_t) (seed >> 20);
+        }
+        org = alloc + (size_t) b * stride + b;
+        was.assign(alloc, alloc + bytes);
+    }
+    ~Plane() { free(alloc); }
+    Plane(const Plane &) = delete;
+    int at(int x, int y) const { return org[(size_t) y * stride + x]; }
+    bool unchanged() const { return memcmp(was.data(), alloc, bytes) == 0; }
+    void fill(int (*f)(int, int)) // the visible samples, for a case with chosen content
+    {
+        for (int y = 0; y < h; y++) {
+            for (int x = 0; x < w; x++) {
+                org[(size_t) y * stride + x] = (uint8_t) f(x, y);
+            }
+        }
+        was.assign(alloc, alloc + bytes);
+    }
+};
+
+template <bool WIDE> void run_grid(const TensorOutJob &j)
+{
+    const int blocks = (j.h + 15) / 16;
+    for (int bx = 0; bx < blocks; bx++) {
+        for (int ty = 0; ty < 4; ty++) {
+            const int y0 = (bx * 4 + ty) * 4;
+            if (y0 >= j.h) {
+                continue;
+            }
+            for (int tx = 0; tx < 64; tx++) {
+                egress_tensor_rows<WIDE>(j, y0, tx * 4, 64 * 4);
+            }
+        }
+    }
+}
+
+const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
+const char *const kTypeName[4] = {"u8", "f16", "bf16", "f32"};
+long g_cases = 0, g_wide = 0;
+const char *g_dump = nullptr;
+
+// scale[3], bias[3]: 1 / 255; ImageNet's Normalize folded (scale = 1 / (255 * std), bias = -mean / std); binary16 subnormals and zeros;
+// binary16 overflow to infinity; the three mixed
+const float kConst[5][6] = {
+    {(float) (1.0 / 255.0), (float) (1.0 / 255.0), (float) (1.0 / 255.0), 0.0f, 0.0f, 0.0f},
+    {(float) (1.0 / (255.0 * 0.229)), (float) (1.0 / (255.0 * 0.224)), (float) (1.0 / (255.0 * 0.225)), (float) (-0.485 / 0.229), (float) (-0.456 / 0.224),
+     (float) (-0.406 / 0.225)},
+    {1e-7f, 1e-7f, 1e-7f, 0.0f, 0.0f, 0.0f},
+    {300.0f, 300.0f, 300.0f, -5.0f, -5.0f, -5.0f},
+    {1e-7f, (float) (1.0 / (255.0 * 0.224)), 300.0f, 0.0f, (float) (-0.456 / 0.224), -5.0f}};
+
+size_t pitch_of(int w, int elem, int pitch_kind)
+{
+    const size_t rb = (size_t) w * (size_t) elem, up = (rb + 15) & ~(size_t) 15;
+    return pitch_kind == 0 ? rb : pitch_kind == 1 ? rb + (size_t) elem : up + 16;
+}
+
+// offset: elements behind a 16-byte boundary; force_general: run the general form even where the wide one would be picked (a round
+// takes it when ANY of its tensors needs it)
+void check(const Plane &Y, const Plane &U, const Plane &V, int fmt, int csc, int dtype, int pitch_kind, int offset, int konst, bool force_general,
+           const char *dump_name = nullptr)
+{
+    const int w = Y.w, h = Y.h, hs = kHs[fmt], vs = kVs[fmt], elem = tensor_elem(dtype);
+    const size_t rb = (size_t) w * (size_t) elem, pitch = pitch_of(w, elem, pitch_kind);
+    const size_t start = (size_t) kLead + (size_t) offset * (size_t) elem;
+    const size_t bytes = start + (size_t) (h - 1) * pitch + rb + kLead;
+    uint8_t *alloc[3];
+    const long *p = kPreset[preset_of(csc)];
+    const float *k = kConst[konst];
+    TensorOutJob j{};
+    j.sy = Y.org, j.su = U.org, j.sv = V.org, j.ystride = Y.stride, j.cstride = U.stride, j.w = w, j.h = h, j.hs = hs, j.vs = vs;
+    j.ky = (int) p[0], j.ybase = (int) p[1], j.rv = (int) p[2], j.gu = (int) p[3], j.gv = (int) p[4], j.bu = (int) p[5], j.dtype = dtype;
+    for (int c = 0; c < 3; c++) {
+        if (posix_memalign((void **) &alloc[c], 16, bytes) != 0) {
+            abort();
+        }
+        memset(alloc[c], kGuard, bytes);
+        j.dst[c] = alloc[c] + start, j.dpitch[c] = (int) pitch;
+        j.scale[c] = k[c], j.bias[c] = k[3 + c];
+    }
+    const bool wide = tensor_job_wide(j) && !force_general;
+    wide ? run_grid<true>(j) : run_grid<false>(j);
+    g_cases++;
+    g_wide += wide;
+    std::vector<uint8_t> want[3];
+    for (int c = 0; c < 3; c++) {
+        want[c].assign(bytes, kGuard);
+    }
+    for (int y = 0; y < h; y++) {
+        for (int x = 0; x < w; x++) {
+            uint8_t px[3];
+            expect_pixel(csc, Y.at(x, y), U.at(x >> hs, y >> vs), V.at(x >> hs, y >> vs), px);
+            for (int c = 0; c < 3; c++) {
+                uint8_t *at = &want[c][start + (size_t) y * pitch + (size_t) x * (size_t) elem];
+                if (dtype == kTensorU8) {
+                    at[0] = px[c];
+                } else {
+                    const uint32_t e = expect_elem(dtype, px[c], k[c], k[3 + c]);
+                    memcpy(at, &e, (size_t) elem); // (little endian)
+                }
+            }
+        }
+    }
+    for (int c = 0; c < 3; c++) {
+        if (memcmp(want[c].data(), alloc[c], bytes) != 0) {
+            size_t i = 0;
+            while (want[c][i] == alloc[c][i]) {
+                i++;
+            }
+            const long rel = (long) i - (long) start;
+            fprintf(stderr, "MISMATCH %dx%d %s %s csc=0x%x pitch=%zu offset=%d consts=%d wide=%d: byte %ld of plane %d (row %ld, byte %ld of it) is %02x, expected %02x\n",
+                    w, h, kTypeName[dtype], kFmtName[fmt], csc, pitch, offset, konst, (int) wide, rel, c, rel >= 0 ? rel / (long) pitch : -1L,
+                    rel >= 0 ? rel % (long) pitch : rel, alloc[c][i], want[c][i]);
+            exit(1);
+        }
+    }
+    if (!Y.unchanged() || !U.unchanged() || !V.unchanged()) {
+        fprintf(stderr, "a source plane was written: %dx%d %s %s pitch=%zu offset=%d\n", w, h, kTypeName[dtype], kFmtName[fmt], pitch, offset);
+        exit(1);
+    }
+    if (dump_name && g_dump) {
+        FILE *fy = fopen((std::string(g_dump) + "/" + dump_name + ".yuv").c_str(), "wb");
+        FILE *fc = fopen((std::string(g_dump) + "/" + dump_name + ".const").c_str(), "wb");
+        FILE *ft = fopen((std::string(g_dump) + "/" + dump_name + ".ten").c_str(), "wb");
+        if (!fy || !fc || !ft) {
+            fprintf(stderr, "cannot write into %s\n", g_dump);
+            exit(1);
+        }
+        const Plane *pl[3] = {&Y, &U, &V};
+        for (int c = 0; c < 3; c++) {
+            for (int y = 0; y < pl[c]->h; y++) {
+                fwrite(pl[c]->org + (size_t) y * pl[c]->stride, 1, (size_t) pl[c]->w, fy);
+            }
+        }
+        fwrite(k, sizeof(float), 6, fc);
+        for (int c = 0; c < 3; c++) {
+            for (int y = 0; y < h; y++) {
+                fwrite(j.dst[c] + (size_t) y * pitch, 1, rb, ft);
+            }
+        }
+        fclose(fy);
+        fclose(fc);
+        fclose(ft);
+    }
+    for (int c = 0; c < 3; c++) {
+        free(alloc[c]);
+    }
+}
+
+struct Source { // the three planes of a w x h picture of format fmt; staged: the luma as the decoder stages it
+    Plane Y, U, V;
+    Source(int w, int h, int fmt, bool staged)
+        : Y(w, h, !staged, 977u * (unsigned) w + 31u * (unsigned) h + (unsigned) fmt),
+          U((w + (1 << kHs[fmt]) - 1) >> kHs[fmt], (h + (1 << kVs[fmt]) - 1) >> kVs[fmt], true, 7919u * (unsigned) w + 13u * (unsigned) h + (unsigned) fmt),
+          V((w + (1 << kHs[fmt]) - 1) >> kHs[fmt], (h + (1 << kVs[fmt]) - 1) >> kVs[fmt], true, 104729u * (unsigned) w + 7u * (unsigned) h + (unsigned) fmt)
+    {
+    }
+};
+
+void named(int w, int h, int fmt, int csc, int dtype, int pitch_kind, int offset, int konst)
+{
+    Source s(w, h, fmt, false);
+    char name[96];
+    snprintf(name, sizeof name, "%s_%03x_%s_%dx%d", kTypeName[dtype], csc, kFmtName[fmt], w, h);
+    check(s.Y, s.U, s.V, fmt, csc, dtype, pitch_kind, offset, konst, false, name);
+}
+
+// full range, U = V = 128, Y a ramp over 32 x 8 pixels: R = G = B = Y, so all 256 byte values occur in every channel
+void grey_ramp(int dtype, int konst)
+{
+    Source s(32, 8, 2, false);
+    s.Y.fill([](int x, int y) { return (32 * y + x) & 255; });
+    s.U.fill([](int, int) { return 128; });
+    s.V.fill([](int, int) { return 128; });
+    char name[96];
+    snprintf(name, sizeof name, "%s_200_420_32x8_ramp", kTypeName[dtype]);
+    check(s.Y, s.U, s.V, 2, 0x200, dtype, 0, 0, konst, false, name);
+    check(s.Y, s.U, s.V, 2, 0x200, dtype, 1, 1, konst, false);
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc == 3 && strcmp(argv[1], "--dump") == 0) {
+        g_dump = argv[2];
+    } else if (argc != 1) {
+        fprintf(stderr, "usage: %s [--dump DIR]\n", argv[0]);
+        return 2;
+    }
+    static const int cscs[4] = {0x000, 0x100, 0x200, 0x300};
+    static const int ws[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 16, 17, 255, 256, 257, 260}, hts[] = {1, 2, 3, 4, 5, 16, 17};
+    long turn = 0;
+    for (int w : ws) {
+        for (int h : hts) {
+            for (int fmt = 0; fmt < 5; fmt++) {
+                const Source s(w, h, fmt, false), staged(w, h, fmt, true);
+                for (int csc : cscs) {
+                    for (int dtype = 0; dtype < 4; dtype++) {
+                        for (int pitch_kind = 0; pitch_kind < 3; pitch_kind++) {
+                            for (int offset = 0; offset < 4; offset++, turn++) {
+                                const Source &src = (turn & 1) ? staged : s;
+                                const int konst = (int) (turn % 5);
+                                check(src.Y, src.U, src.V, fmt, csc, dtype, pitch_kind, offset, konst, false); // wide where everything allows
+                                if (offset == 0 && w % 4 == 0 && pitch_of(w, tensor_elem(dtype), pitch_kind) % (size_t) (4 * tensor_elem(dtype)) == 0) {
+                                    check(src.Y, src.U, src.V, fmt, csc, dtype, pitch_kind, offset, konst, true); // general on an aligned tensor
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (g_wide == 0 || g_wide == g_cases) {
+        fprintf(stderr, "FAILED: the sweep holds only one form\n");
+        return 1;
+    }
+    for (int dtype = 0; dtype < 4; dtype++) {
+        for (int konst = 0; konst < 5; konst++) {
+            grey_ramp(dtype, konst); // (dumped once per element type: the last constants stay in the file)
+        }
+    }
+    named(22, 18, 2, 0x000, kTensorU8, 1, 1, 0);
+    named(18, 18, 4, 0x300, kTensorU8, 1, 3, 0);
+    named(18, 18, 3, 0x100, kTensorF16, 0, 2, 1);
+    named(17, 16, 0, 0x200, kTensorBF16, 0, 0, 1);
+    named(68, 38, 1, 0x000, kTensorF32, 2, 0, 1);
+    named(260, 16, 2, 0x300, kTensorF16, 2, 0, 2);  // binary16 subnormals and zeros
+    named(36, 20, 2, 0x100, kTensorF16, 2, 0, 3);   // binary16 overflow to infinity
+    named(34, 18, 1, 0x200, kTensorBF16, 1, 1, 4);
+    named(34, 18, 0, 0x300, kTensorF32, 1, 1, 4);
+    named(516, 16, 2, 0x000, kTensorU8, 2, 0, 0);   // a row of more than one pass
+    named(20, 17, 0, 0x100, kTensorF32, 0, 0, 0);
+    printf("egress_tensor_check: %ld cases (%ld in the wide form) equal the element-by-element contract; no byte outside the rows changed, the "
+           "source planes are as they were\n",
+           g_cases, g_wide);
+    return 0;
+}
