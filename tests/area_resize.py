@@ -16,6 +16,9 @@ import numpy as np
 
 MAX_D = 1 << 24
 MAX_SIDE = 32768
+# the plane sizes (pw, ph, ow, oh) that the sweeps of tools/egress_resize_check.cpp and tools/ingest_resize_check.cpp must hold
+SWEEP_SHAPES = [(48, 32, 32, 24), (50, 38, 33, 21), (25, 19, 17, 11), (64, 48, 9, 7), (64, 48, 64, 6), (64, 48, 8, 48), (16, 16, 16, 16),
+                (16, 16, 2, 2), (64, 48, 32, 24), (64, 48, 16, 12), (97, 61, 13, 8), (131, 67, 130, 66)]
 
 
 def ratio(src, dst):

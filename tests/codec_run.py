@@ -5,6 +5,39 @@ import numpy as np
 
 import dsvabi as A
 
+# chroma format name -> (DSV_SUBSAMP_* code, horizontal shift, vertical shift); "410" is the reference's quarter by quarter (dsv.h:87-95)
+FMT = {"444": (0x0, 0, 0), "422": (0x4, 1, 0), "420": (0x5, 1, 1), "411": (0x8, 2, 0), "410": (0xA, 2, 2)}
+
+
+def frames(w, h, hs, vs, n, seed):
+    """n packed planar pictures: moving waves with a little noise in luma, moving ramps in chroma"""
+    rng = np.random.default_rng(seed)
+    cw, ch = (w + (1 << hs) - 1) >> hs, (h + (1 << vs) - 1) >> vs
+    yy, xx = np.mgrid[0:h, 0:w]
+    cy, cx = np.mgrid[0:ch, 0:cw]
+    out = []
+    for t in range(n):
+        y = ((np.sin((xx + 3 * t) / 17.0) + np.cos((yy + 2 * t) / 11.0)) * 50 + 128 + rng.integers(-3, 4, (h, w))).clip(0, 255).astype(np.uint8)
+        u = ((cx * 2 + t * 3) % 200 + 20).astype(np.uint8)
+        v = ((cy * 3 + t * 5) % 180 + 30).astype(np.uint8)
+        out.append(y.tobytes() + u.tobytes() + v.tobytes())
+    return out
+
+
+def ueg(v):
+    """bit string of the interleaved exp-Golomb code (bs.c:132)"""
+    v += 1
+    nb = v.bit_length() - 1
+    return "".join("0" + str((v >> i) & 1) for i in range(nb - 1, -1, -1)) + "1"
+
+
+def meta_packet(fields):
+    """a metadata packet that carries the given fields"""
+    bits = "".join(ueg(f) for f in fields) + "0"
+    bits += "0" * (-len(bits) % 8)
+    body = bytes(int(bits[i:i + 8], 2) for i in range(0, len(bits), 8))
+    return b"DSV2" + bytes([8, 0x00]) + bytes(8) + body
+
 
 def configure_encoder(lib, enc, meta, qp=60, gop=48, effort=10, rc_mode=0, **over):
     """Field set-up as the reference CLI does it (dsv_main.c:548-723) for the given flags."""

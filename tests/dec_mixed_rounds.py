@@ -129,12 +129,12 @@ def geometry(fd):
 @functools.lru_cache(maxsize=None)
 def reference(fd, draw=0, sharp=False):
     """the reference decoder's [(return code, frame number or None, [Y, U, V] or None)] per packet of the feed, with the reference's
-    own overlay and -- tests/test_gpu_dec_postsharp.py: expected -- its own dsv_post_process on the luma (shared, never modified)"""
-    from test_gpu_dec_drawinfo import decode
+    own overlay and -- tests/dec_out.py: expected_sharp -- its own dsv_post_process on the luma (shared, never modified)"""
+    from dec_out import decode
     A.load_ref().dsv_set_log_level(0)  # (the reference reports every damaged plane)
     if sharp:
-        from test_gpu_dec_postsharp import expected
-        res = expected(A.load_ref(), packets(fd), mode=draw, sharp=True)
+        from dec_out import expected_sharp
+        res = expected_sharp(A.load_ref(), packets(fd), mode=draw, sharp=True)
     else:
         res = decode(A.load_ref(), packets(fd), draw)
     for _, _, pl in res:
@@ -155,7 +155,7 @@ def child_report(fd):
     reference(fd) as JSON"""
     import json
     import os
-    from test_gpu_dec_drawinfo import decode
+    from dec_out import decode
     ref, libc = A.load_ref(), C.CDLL(None)
     ref.dsv_set_log_level(1)
     dec = A.DECODER()
@@ -193,7 +193,7 @@ def wanted(fd, opt):
     if opt.out420p:
         assert all(sp.fmt == "420" for sp in fd.parts)
     if opt.way[0] == "surface":
-        from test_gpu_dec_scale import in_layout
+        from dec_out import in_layout
         assert len(set(sp.fmt for sp in fd.parts)) == 1
         return in_layout(want, opt.way[1], geometry(fd)[2])
     return want
@@ -366,7 +366,7 @@ def slices(row):
 
 # ---- the driver ------------------------------------------------------------------------------------------------------------------
 def pitch_of(name):
-    import test_gpu_dec_rgb as G
+    import dec_out as G
     return {"tight": G.tight, "plus1": G.plus1, "aligned": G.aligned}[name]
 
 
@@ -376,10 +376,7 @@ def run(hip, cs, single=False):
     dsv2hip_dec_batch_surface for the surfaces -- or, single, one dsv_dec / dsv2hip_dec_device_frame / dsv2hip_dec_surface_frame per
     packet.  The decoders of one kind run their whole schedule before the next kind's, as in test_every_delivery_in_one_round.
     Returns {decoder: [(return code, frame number or None, planes or None)] per packet}."""
-    from test_gpu_dec_device_out import device_decode
-    from test_gpu_dec_scale import bind, decode_steps
-    from test_gpu_dec_surface import frame_decode
-    bind(hip)
+    from dec_out import Surfaces, decode_steps, device_decode, frame_decode
     got = {}
     for what in ("frame", "packed", "surface"):
         ids = [k for k, o in enumerate(cs.opts) if o.way[0] == what]
@@ -395,7 +392,7 @@ def run(hip, cs, single=False):
             res = device_decode(hip, streams, out420p=[o.out420p for o in opts], **kw)
         else:
             assert not any(o.out420p for o in opts)
-            res = decode_steps(hip, streams, [dict(layout=o.way[1], pitch=pitch_of(o.way[2]), offset=o.way[3]) for o in opts], **kw)
+            res = decode_steps(hip, streams, Surfaces([dict(layout=o.way[1], pitch=pitch_of(o.way[2]), offset=o.way[3]) for o in opts]), **kw)
         got.update({k: res[local[k]] for k in ids})
     return got
 
@@ -404,7 +401,7 @@ def run_threads(hip, cs):
     """one thread per decoder, each looping plain dsv_dec over its own packets: the submit queue (csrc/decoder.cpp: g_dec_queue) forms
     the steps"""
     import threading
-    from test_gpu_dec_surface import frame_decode
+    from dec_out import frame_decode
     got, errors, start = {}, [], threading.Barrier(len(cs.feeds))
 
     def work(k):

@@ -9,16 +9,14 @@ import numpy as np
 import dsvabi as A
 import ingest_resize as IR
 import rgb_csc as R
-from codec_run import encode_stream
-from edge_cases import content_planes, packet_bound_holds
-from test_gpu_enc_rgb import rgb_content
-from test_gpu_enc_surface import PLANAR, SEMI, content
-from test_gpu_formats import FMT
+from codec_run import FMT
+from edge_cases import content_planes
+from enc_in import LADDER_CFG, LADDER_LOSSLESS, LADDER_NFR, LADDER_SEED, content, ref_packets, rgb_content
+from hipabi import PLANAR, SEMI
 
-CFG = dict(qp=60, gop=4)
-LOSSLESS = dict(qp=100, gop=4)
+CFG, LOSSLESS = LADDER_CFG, LADDER_LOSSLESS
 CHECKER_CFG = dict(qp=30, gop=4)
-NFR, SEED = 4, 5
+NFR, SEED = LADDER_NFR, LADDER_SEED
 BGRA709, RGBAFULL = R.BGRA | R.BT709, R.RGBA | R.FULL
 LAYOUTS = [PLANAR, SEMI, BGRA709, RGBAFULL]
 LAYOUT_IDS = {PLANAR: "planar", SEMI: "semiplanar", BGRA709: "bgra709", RGBAFULL: "rgbafull"}
@@ -36,15 +34,6 @@ CONSTANT_SOURCES = [(24, 24), (127, 121)]  # -> 16x16
 CHECKER = (99, 51, 66, 34)
 
 
-def is_rgb(layout):
-    return (layout & 0xff) in (R.BGRA, R.RGBA)
-
-
-def kind_of(layout):
-    """which oracle a layout's pictures come from: the YUV content for both YUV layouts, the RGB content through the layout's conversion"""
-    return layout if is_rgb(layout) else "yuv"
-
-
 @functools.lru_cache(maxsize=None)
 def oracle_pictures(sw, sh, w, h, name, kind):
     """the encoder's pictures (packed planar bytes) for the content made at the SOURCE size with seed 5"""
@@ -52,19 +41,6 @@ def oracle_pictures(sw, sh, w, h, name, kind):
     if kind == "yuv":
         return tuple(IR.packed(IR.resize_yuv(IR.split_planar(f, sw, sh, hs, vs), w, h, hs, vs)) for f in content(sw, sh, name, NFR, SEED))
     return tuple(IR.packed(IR.convert_sized(px, kind, w, h, hs, vs)) for px in rgb_content(sw, sh, NFR, SEED))
-
-
-def conditions(packets, w, h, name):
-    """both conditions of a case.  (4:1:1 and "4:1:0": the reference gives their packets the buffer of 4:2:0, dsv_encoder.c:1062-1066.)"""
-    packet_bound_holds(packets, w, h, FMT[name][0] if name in ("444", "422", "420") else A.SUBSAMP_420)
-    kinds = {pk[5] & 1 for pk in packets if pk[5] & 0x04}  # (dsv.h: packet type at byte 5, picture = 0x04, bit 0 = predicted)
-    assert kinds == {0, 1}, "broken test case: I and P pictures do not both occur"
-
-
-def ref_packets(pictures, w, h, name, cfg):
-    packets = tuple(encode_stream(A.load_ref(), list(pictures), w, h, FMT[name][0], eos=False, **cfg)[0])
-    conditions(packets, w, h, name)
-    return packets
 
 
 @functools.lru_cache(maxsize=None)

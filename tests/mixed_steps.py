@@ -17,6 +17,7 @@ import dsvabi as A
 import rgb_csc as R
 from codec_run import configure_encoder, encode_stream
 from conftest import load_pkg
+from hipabi import PLANAR, SEMI, SURFACE, bind
 
 FMT = {"444": (A.SUBSAMP_444, 0, 0), "422": (A.SUBSAMP_422, 1, 0), "420": (A.SUBSAMP_420, 1, 1)}
 W, H = 176, 144  # the smallest size at which noise and scene cuts stay inside the reference's packet bound
@@ -282,29 +283,6 @@ class env:
                 os.environ[k] = v
 
 
-class SURFACE(C.Structure):
-    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("layout", C.c_int)]
-
-
-def bind(hip):
-    P = C.POINTER
-    encs, bufs, counts = P(P(A.ENCODER)), P(A.BUF), P(C.c_int)
-    hip.dsv2hip_enc_batch.argtypes = [C.c_int, encs, P(C.c_void_p), bufs, counts]
-    hip.dsv2hip_enc_batch_host.argtypes = [C.c_int, encs, P(C.c_void_p), P(C.c_void_p), bufs, counts]
-    hip.dsv2hip_enc_batch_surface.argtypes = [C.c_int, encs, P(SURFACE), bufs, counts]
-    hip.dsv2hip_enc_device_frame.argtypes = [P(A.ENCODER), C.c_void_p, bufs]
-    for name in ("dsv2hip_enc_batch", "dsv2hip_enc_batch_host", "dsv2hip_enc_batch_surface", "dsv2hip_enc_device_frame"):
-        getattr(hip, name).restype = C.c_int
-    hip.dsv2hip_host_alloc.argtypes = [C.c_size_t]
-    hip.dsv2hip_host_alloc.restype = C.c_void_p
-    hip.dsv2hip_host_free.argtypes = [C.c_void_p]
-    hip.dsv2hip_enc_list_growths.restype = C.c_long
-    for name in ("dsv2hip_enc_surface_stats", "dsv2hip_enc_rgb_stats"):
-        getattr(hip, name).argtypes = [P(C.c_ulonglong), C.c_int]
-        getattr(hip, name).restype = None
-    return hip
-
-
 SURFACE_KINDS = ("packed", "planar", "semiplanar", "bgra601", "rgba709full")
 RGB_LAYOUTS = {3: R.BGRA | R.BT601, 4: R.RGBA | R.BT709 | R.FULL}  # stream index % 5 -> the layout that defines its pictures
 
@@ -320,8 +298,7 @@ def up16(x):
 
 def make_surface(st, s, t, general):
     """stream index s's picture t as the device surface of kind s % 5; general: off the 16-byte grid (the ingests' general forms)"""
-    from test_gpu_enc_rgb import RgbSurface
-    from test_gpu_enc_surface import PLANAR, SEMI, Surface
+    from enc_in import RgbSurface, Surface
     sp, kind = st["spec"], s % 5
     w, h = sp.w, sp.h
     cw, _ = chroma_dims(w, h, sp.fmt)
@@ -398,7 +375,7 @@ class Runner:
             self.surface_steps += 1
             surfs = [make_surface(self.streams[s], s, self.pos[s], general) for s in ids]
             torch.cuda.synchronize()
-            assert hip.dsv2hip_enc_batch_surface(n, encp, (SURFACE * n)(*[SURFACE.from_buffer_copy(sf.c) for sf in surfs]), bufs, nbufs) == 0
+            assert hip.dsv2hip_enc_batch_surface(n, encp, (SURFACE * n)(*[sf.c for sf in surfs]), bufs, nbufs) == 0
             for sf in surfs:
                 sf.check_untouched()
         elif kind == "frame":

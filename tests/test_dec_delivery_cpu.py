@@ -3,15 +3,12 @@ writing what -- compiled for the host and swept under AddressSanitizer + Undefin
 stand-alone program: nothing sanitized is loaded into Python) over chroma format x size x target kind x scale x out420p x postsharp x
 draw_info x pointer offset x pitch, on synthetic addresses.  The program checks coverage, launch order, kernel forms, job counts and
 sources of every case by its own interval arithmetic and states how many cases hit each row of the planner's table."""
-import os
 import re
-import subprocess
 
 import pytest
 
-import dsvabi as A
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 # 5 formats x 6 sizes x (a pinned frame: 2 out420p; planar / semiplanar: (2 out420p + 3 shifts) x 9 placements; RGB: 4 shifts x 9) x 4 sharp / draw
 CASES = 5 * 6 * (2 + 2 * 5 * 9 + 4 * 9) * 4
 TABLE_ROWS = 12
@@ -20,16 +17,7 @@ TABLE_ROWS = 12
 @pytest.fixture(scope="module")
 def sweep(tmp_path_factory):
     """builds tools/dec_delivery_check.cpp with the sanitizers, runs its whole sweep and returns what it printed"""
-    exe = str(tmp_path_factory.mktemp("dec_delivery") / "dec_delivery_check")
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "dec_delivery_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    return r.stdout
+    return build_and_run("tools/dec_delivery_check.cpp", tmp_path_factory.mktemp("dec_delivery"))[0]
 
 
 def test_every_case_of_the_sweep_holds(sweep):

@@ -4,15 +4,12 @@ into Python) over chroma format x size x delivered size x target kind x postshar
 addresses.  The program checks that every job's destination lies inside the target or the staging it was given, that staging is asked
 for exactly when the predicates say so, and that a target which is not sized gets no resampling job, no full-size staging and the
 predicates' answers of before (what its plan does hold is the business of tests/test_dec_delivery_cpu.py, which is unchanged)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-import dsvabi as A
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 # 5 formats x 7 sizes x 8 delivered sizes x 3 kinds x 4 sharp / draw x 9 placements; the plain comparison: one delivered size, 4 shifts
 CASES = 5 * 7 * 8 * 3 * 4 * 9
 PLAIN = 5 * 7 * 3 * 4 * 9 * 4
@@ -21,16 +18,7 @@ PLAIN = 5 * 7 * 3 * 4 * 9 * 4
 @pytest.fixture(scope="module")
 def sweep(tmp_path_factory):
     """builds tools/dec_delivery_sized_check.cpp with the sanitizers, runs its whole sweep and returns what it printed"""
-    exe = str(tmp_path_factory.mktemp("dec_delivery_sized") / "dec_delivery_sized_check")
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "dec_delivery_sized_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    return r.stdout
+    return build_and_run("tools/dec_delivery_sized_check.cpp", tmp_path_factory.mktemp("dec_delivery_sized"))[0]
 
 
 def test_every_sized_case_of_the_sweep_holds(sweep):

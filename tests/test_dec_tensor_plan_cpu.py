@@ -10,13 +10,12 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 
 import pytest
 
 import dsvabi as A
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 HEADER = "digital-subband-video-2_amd/csrc/dec_delivery.h"
 ELEM = {0: 1, 1: 2, 2: 2, 3: 4}
 # 5 formats x 5 sizes x 4 element types x 4 delivered sizes x 4 sharp / draw x 4 offsets x 3 pitches
@@ -28,18 +27,7 @@ PARENT = 5 * 5 * (2 + (2 + 3 + 3) + (2 + 3 + 3) + (1 + 3 + 3)) * 4 * 9
 @pytest.fixture(scope="module")
 def sweep(tmp_path_factory):
     """builds tools/dec_tensor_plan_check.cpp with the sanitizers, runs its whole sweep and returns what it printed"""
-    work = tmp_path_factory.mktemp("dec_tensor_plan")
-    exe = str(work / "dec_tensor_plan_check")
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"),
-           os.path.join(A.ROOT, "tools", "dec_tensor_plan_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    return r.stdout
+    return build_and_run("tools/dec_tensor_plan_check.cpp", tmp_path_factory.mktemp("dec_tensor_plan"))[0]
 
 
 def test_every_tensor_case_of_the_sweep_holds(sweep):

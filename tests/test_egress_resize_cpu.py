@@ -17,30 +17,18 @@ import pytest
 import area_resize as R
 import box_reduce as B
 import dsvabi as A
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 FORMATS = [0x0, 0x4, 0x5, 0x8, 0xA]  # DSV_SUBSAMP_444, _422, _420, _411, _410
-# the sizes the sweep must hold: (pw, ph, ow, oh)
-SHAPES = [(48, 32, 32, 24), (50, 38, 33, 21), (25, 19, 17, 11), (64, 48, 9, 7), (64, 48, 64, 6), (64, 48, 8, 48), (16, 16, 16, 16),
-          (16, 16, 2, 2), (64, 48, 32, 24), (64, 48, 16, 12), (97, 61, 13, 8), (131, 67, 130, 66)]
+SHAPES = R.SWEEP_SHAPES
 
 
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     """builds tools/egress_resize_check.cpp with the sanitizers, runs its whole sweep and returns the directory of its dumped cases"""
-    work = tmp_path_factory.mktemp("egress_resize")
-    exe, out = str(work / "egress_resize_check"), work / "dump"
-    out.mkdir()
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "egress_resize_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--dump", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert "in the wide form" in r.stdout and "quotients of the division helper" in r.stdout
-    return str(out)
+    out, dump = build_and_run("tools/egress_resize_check.cpp", tmp_path_factory.mktemp("egress_resize"), ["--dump", "{dump}"])
+    assert "in the wide form" in out and "quotients of the division helper" in out
+    return dump
 
 
 def test_kernel_body_sweep_is_clean_and_equals_the_numpy_oracle(dump_dir):
@@ -166,7 +154,7 @@ def test_sized_plane_sizes_are_mk_frames(fmt):
 
 # ---- why tests/test_gpu_dec_resize.py takes its 4:1:1 and "4:1:0" streams from 54x38 ---------------------------------------------------
 def reference_stream(fmt, w, h):
-    """the return code of a child process that has the reference encoder make tests/test_gpu_dec_device_out.format_stream(fmt, w, h, 3)
+    """the return code of a child process that has the reference encoder make tests/dec_out.format_stream(fmt, w, h, 3)
     (a child: where the encoder is not defined it ends the process that calls it)"""
     code = "from test_gpu_dec_device_out import format_stream; assert len(format_stream(%r, %d, %d, 3)) >= 4" % (fmt, w, h)
     env = dict(os.environ, PYTHONPATH=os.path.join(A.ROOT, "tests"))

@@ -5,16 +5,14 @@ restatement and the oracle of tests/test_gpu_dec_rgb.py to one another -- and th
 conversion, over all 2^24 (Y, U, V) and, for the round trip behind the encoder's conversion, all 2^24 (R, G, B).
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import dsvabi as A
 import rgb_csc as R
 import yuv_rgb as Q
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 FMT = {"444": (0, 0), "422": (1, 0), "420": (1, 1), "411": (2, 0), "410": (2, 2)}
 CSC_IDS = ["bt601", "bt709", "bt601_full", "bt709_full"]
 
@@ -22,19 +20,9 @@ CSC_IDS = ["bt601", "bt709", "bt601_full", "bt709_full"]
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     """builds tools/egress_rgb_check.cpp with the sanitizers, runs its whole sweep and returns the directory of its dumped cases"""
-    work = tmp_path_factory.mktemp("egress_rgb")
-    exe, out = str(work / "egress_rgb_check"), work / "dump"
-    out.mkdir()
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "egress_rgb_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--dump", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert "in the wide form" in r.stdout
-    return str(out)
+    out, dump = build_and_run("tools/egress_rgb_check.cpp", tmp_path_factory.mktemp("egress_rgb"), ["--dump", "{dump}"])
+    assert "in the wide form" in out
+    return dump
 
 
 def test_kernel_body_sweep_is_clean_and_equals_the_numpy_oracle(dump_dir):

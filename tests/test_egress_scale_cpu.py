@@ -6,34 +6,23 @@ reduction: half size is the reference's dsv_ds2x_frame_luma, constants stay, and
 """
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import box_reduce as B
 import dsvabi as A
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 FORMATS = [0x0, 0x4, 0x5, 0x8, 0xA]  # DSV_SUBSAMP_444, _422, _420, _411, _410
 
 
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     """builds tools/egress_scale_check.cpp with the sanitizers, runs its whole sweep and returns the directory of its dumped cases"""
-    work = tmp_path_factory.mktemp("egress_scale")
-    exe, out = str(work / "egress_scale_check"), work / "dump"
-    out.mkdir()
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "egress_scale_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--dump", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert "in the wide form" in r.stdout
-    return str(out)
+    out, dump = build_and_run("tools/egress_scale_check.cpp", tmp_path_factory.mktemp("egress_scale"), ["--dump", "{dump}"])
+    assert "in the wide form" in out
+    return dump
 
 
 def test_kernel_body_sweep_is_clean_and_equals_the_numpy_oracle(dump_dir):

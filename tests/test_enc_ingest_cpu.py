@@ -3,15 +3,12 @@ picture enters through, reading and writing what -- compiled for the host and sw
 by tools/enc_ingest_check.cpp (a stand-alone program: nothing sanitized is loaded into Python) over chroma format x encoder size x source
 kind x (call, route) x pointer offset x pitch, on synthetic addresses.  The program checks acceptance, record counts, coverage, reads and
 kernel forms of every case by its own interval arithmetic and states how many cases hit each row of its two tables."""
-import os
 import re
-import subprocess
 
 import pytest
 
-import dsvabi as A
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 # 12 ways in: the plain call; the scaled call without a scale and at a half, a quarter, an eighth; the sized call at the encoder's own size, from
 # one column more, 3 : 2 and 8 : 1, and with the three scale values
 WAYS = 1 + 4 + 7
@@ -25,16 +22,7 @@ TABLE_ROWS = COUNT_ROWS + WAYS * KINDS
 @pytest.fixture(scope="module")
 def sweep(tmp_path_factory):
     """builds tools/enc_ingest_check.cpp with the sanitizers, runs its whole sweep and returns what it printed"""
-    exe = str(tmp_path_factory.mktemp("enc_ingest") / "enc_ingest_check")
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "enc_ingest_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    return r.stdout
+    return build_and_run("tools/enc_ingest_check.cpp", tmp_path_factory.mktemp("enc_ingest"))[0]
 
 
 def test_every_case_of_the_sweep_holds(sweep):

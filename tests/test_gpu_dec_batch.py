@@ -7,72 +7,12 @@ import numpy as np
 import pytest
 
 import dsvabi as A
-from codec_run import decode_stream, encode_stream
+from codec_run import decode_stream, encode_stream, frames
 from conftest import load_pkg
+from dec_out import Surfaces, batch_decode, check, decode_steps, expected_sharp, in_layout, pictures, same_results
+from hipabi import PLANAR, SEMI, bind
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
-
-
-def bind(hip):
-    hip.dsv2hip_dec_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(A.DECODER)), C.POINTER(A.BUF), C.POINTER(C.POINTER(A.FRAME)),
-                                      C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
-    hip.dsv2hip_dec_batch.restype = C.c_int
-    for name in ("dsv2hip_dec_set_out420p", "dsv2hip_dec_set_postsharp"):
-        getattr(hip, name).argtypes = [C.POINTER(A.DECODER), C.c_int]
-        getattr(hip, name).restype = C.c_int
-
-
-def planes_of(fp):
-    f = fp.contents
-    out = []
-    for c in range(3):
-        p = f.planes[c]
-        a = np.ctypeslib.as_array(p.data, shape=(p.h * p.stride,))
-        out.append(a.reshape(-1, p.stride)[:p.h, :p.w].copy())
-    return out
-
-
-def batch_decode(hip, streams, modes=None, sharp=None, out420p=None):
-    """streams: list of packet lists.  Step t feeds packet t of every stream that still has one.
-    modes / sharp / out420p: per stream, the decoder's draw_info word, postsharp and out420p switches."""
-    n = len(streams)
-    decs = [A.DECODER() for _ in range(n)]
-    for k, d in enumerate(decs):
-        d.draw_info = modes[k] if modes else 0
-        if sharp and sharp[k]:
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(d), 1) == 0
-        if out420p and out420p[k]:
-            assert hip.dsv2hip_dec_set_out420p(C.byref(d), 1) == 0
-    got = [[] for _ in range(n)]
-    for t in range(max(len(s) for s in streams)):
-        live = [k for k in range(n) if t < len(streams[k])]
-        m = len(live)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
-        bufs = (A.BUF * m)()
-        for i, k in enumerate(live):
-            pk = streams[k][t]
-            hip.dsv_mk_buf(C.byref(bufs[i]), len(pk) + 64)
-            C.memmove(bufs[i].data, pk, len(pk))
-        outs = (C.POINTER(A.FRAME) * m)()
-        fns = (C.c_uint32 * m)()
-        rets = (C.c_int * m)()
-        assert hip.dsv2hip_dec_batch(m, decp, bufs, outs, fns, rets) == m
-        for i, k in enumerate(live):
-            assert rets[i] != A.DEC_ERROR
-            if rets[i] == A.DEC_OK and outs[i]:
-                got[k].append((fns[i], *planes_of(outs[i])))
-                hip.dsv_frame_ref_dec(outs[i])
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return got
-
-
-def check(want, got):
-    assert len(want) == len(got)
-    for (fa, *pa), (fb, *pb) in zip(want, got):
-        assert fa == fb
-        for c in range(3):
-            assert np.array_equal(pa[c], pb[c]), "frame %d plane %d differs" % (fa, c)
 
 
 def test_dec_batch_mixed_streams():
@@ -118,8 +58,6 @@ def test_lossless_round_trip_1080p_through_both_batch_engines():
     from codec_run import configure_encoder
     hip = A.load_hip()
     bind(hip)
-    hip.dsv2hip_enc_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(A.ENCODER)), C.POINTER(C.c_void_p), C.POINTER(A.BUF), C.POINTER(C.c_int)]
-    hip.dsv2hip_enc_batch.restype = C.c_int
     pkg = load_pkg()
     w, h, ns, nf = 1920, 1080, 2, 3
     vids = [pkg.synth.SynthVideo(w, h, "420", seed=40 + s) for s in range(ns)]
@@ -173,7 +111,6 @@ SURF_OPTS = [(0, k == 2, k == 3) for k in range(10)]
 
 @functools.lru_cache(maxsize=None)
 def kind_stream(k):
-    from test_gpu_formats import frames
     w, h, gop, qp, offset = KINDS[k]
     fr = frames(w, h, 1, 0, 3, 30 + k)
     enc = lambda f, eos: encode_stream(A.load_ref(), f, w, h, SUBSAMP_422, eos=eos, qp=qp, gop=gop)[0]
@@ -183,9 +120,8 @@ def kind_stream(k):
 @functools.lru_cache(maxsize=None)
 def kind_want(k, mode, sharp, to420):
     """the reference decode of stream k with the post-steps applied by the reference / the oracle (shared, never modified)"""
-    from test_gpu_dec_postsharp import expected
     w, h = KINDS[k][:2]
-    want = expected(A.load_ref(), kind_stream(k), mode=mode, sharp=sharp, to420=(SUBSAMP_422, w, h) if to420 else None)
+    want = expected_sharp(A.load_ref(), kind_stream(k), mode=mode, sharp=sharp, to420=(SUBSAMP_422, w, h) if to420 else None)
     assert sum(1 for r in want if r[2] is not None) == 3
     return tuple(want)
 
@@ -198,25 +134,20 @@ def test_one_round_of_every_kind(parse_mode):
     and through dsv2hip_dec_batch_surface into planar and semiplanar surfaces (leg B).  Every delivered picture equals the
     reference decode of its stream with the same post-steps.  (No stream carries a damaged plane section: the damaged packets
     of test_gpu_robustness.py are drawn at random inside its test, so the zfail table stays empty here.)"""
-    import test_gpu_dec_surface as S
-    from test_gpu_dec_device_out import same_results
-    from test_gpu_dec_drawinfo import pictures
-    hip = S.bind(A.load_hip())
-    bind(hip)
+    hip = bind(A.load_hip())
     assert A.block_geometry(80, 48)[2:] == (5, 3) and 80 % A.block_geometry(80, 48)[0] == 0 and 48 % A.block_geometry(80, 48)[1] == 0
     streams = [kind_stream(k) for k in range(len(KINDS))]
     kinds = [[r[0] for r in kind_want(k, 0, False, False)] for k in range(len(KINDS))]
     assert all(k[3] == A.DEC_OK for k in kinds) and len(streams[4]) == len(streams[0]) + 1  # (step 3; an offset stream is one packet longer)
-    S.PITCH.setdefault("align64", lambda rb: (rb + 63) // 64 * 64)
-    specs = [dict(layout=S.SEMI if k % 2 else S.PLANAR, pitch="plus3" if k == 5 else "align64", offset=0) for k in range(len(KINDS))]
+    specs = [dict(layout=SEMI if k % 2 else PLANAR, pitch=(lambda rb: rb + 3) if k == 5 else (lambda rb: (rb + 63) // 64 * 64), offset=0) for k in range(len(KINDS))]
     try:
         assert hip.dsv2hip_dec_set_parse_mode(parse_mode) == parse_mode
         got = batch_decode(hip, streams, *zip(*HOST_OPTS))
         for k, opts in enumerate(HOST_OPTS):
             check(pictures(kind_want(k, *opts)), got[k])
         modes, sharp, out420p = zip(*SURF_OPTS)
-        got = S.surface_decode(hip, streams, specs, modes=modes, sharp=sharp, out420p=out420p)
+        got = decode_steps(hip, streams, Surfaces(specs), modes=modes, sharp=sharp, out420p=out420p)
         for k, opts in enumerate(SURF_OPTS):
-            S.same(kind_want(k, *opts), got[k], specs[k]["layout"])
+            same_results(in_layout(kind_want(k, *opts), specs[k]["layout"]), got[k])
     finally:
         hip.dsv2hip_dec_set_parse_mode(-1)

@@ -4,7 +4,6 @@ any width and alignment), every chroma format, draw_info and -out420p, both pars
 [dev_out, dev_out + picture_bytes) is written, a refused call consumes nothing, and the device buffers feed dsv2hip_enc_batch
 without a host copy."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -12,177 +11,10 @@ import torch
 
 import dsvabi as A
 from codec_run import configure_encoder, encode_stream
-from test_gpu_dec_drawinfo import decode, stream
-from test_gpu_formats import FMT as FMT5, frames as plain_frames
-from test_oracle_fmt import chroma_dims, orc_to420
+from dec_out import DevOut, decode, device_decode, format_stream, npics, orc_to420, out_dims, same_results, split_planes, stream
+from hipabi import GUARD, bind, mk_buf
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
-
-GUARD = 0xA5
-NO_FN = 0xFFFFFFFF
-
-
-def bind(hip):
-    P = C.POINTER
-    hip.dsv2hip_dec_picture_bytes.argtypes = [P(A.DECODER)]
-    hip.dsv2hip_dec_picture_bytes.restype = C.c_size_t
-    hip.dsv2hip_dec_batch_device.argtypes = [C.c_int, P(P(A.DECODER)), P(A.BUF), P(C.c_void_p), P(C.c_size_t), P(C.c_uint32), P(C.c_int)]
-    hip.dsv2hip_dec_batch_device.restype = C.c_int
-    hip.dsv2hip_dec_device_frame.argtypes = [P(A.DECODER), P(A.BUF), C.c_void_p, C.c_size_t, P(C.c_uint32)]
-    hip.dsv2hip_dec_device_frame.restype = C.c_int
-    hip.dsv2hip_dec_set_out420p.argtypes = [P(A.DECODER), C.c_int]
-    hip.dsv2hip_dec_set_postsharp.argtypes = [P(A.DECODER), C.c_int]
-    hip.dsv2hip_dec_set_postsharp.restype = C.c_int
-    hip.dsv2hip_dec_set_parse_mode.argtypes = [C.c_int]
-    hip.dsv2hip_dec_set_parse_mode.restype = C.c_int
-    return hip
-
-
-def mk_buf(hip, buf, pk):
-    hip.dsv_mk_buf(C.byref(buf), len(pk) + 64)
-    C.memmove(buf.data, pk, len(pk))
-
-
-def out_dims(dec, out420p):
-    """[(w, h)] of the three planes of the picture as delivered (dsv_mk_frame's plane sizes)"""
-    m = dec.vidmeta
-    cw, ch = chroma_dims(A.SUBSAMP_420 if out420p else m.subsamp, m.width, m.height)
-    return [(m.width, m.height), (cw, ch), (cw, ch)]
-
-
-def split_planes(flat, dims):
-    out, at = [], 0
-    for w, h in dims:
-        out.append(flat[at:at + w * h].reshape(h, w).copy())
-        at += w * h
-    assert at == flat.size
-    return out
-
-
-class DevOut:
-    """One decoder's device buffer: picture_bytes + 64 bytes of 0xA5, handed over at base + offset."""
-
-    def __init__(self, nbytes, offset):
-        self.nbytes, self.offset = nbytes, offset
-        self.t = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda")
-        assert self.t.data_ptr() % 16 == 0
-
-    def arm(self):
-        self.t.fill_(GUARD)
-
-    def ptr(self):
-        return self.t.data_ptr() + self.offset
-
-    def picture(self):
-        """the delivered bytes; asserts that every byte around them still holds the guard value"""
-        a = self.t.cpu().numpy()
-        assert np.all(a[:self.offset] == GUARD), "bytes before the picture were written"
-        assert np.all(a[self.offset + self.nbytes:] == GUARD), "bytes behind the picture were written"
-        return a[self.offset:self.offset + self.nbytes]
-
-
-def lockstep(streams, schedule=None, delay=None):
-    """the steps of a run, each the ordered [(decoder, packet index)] it feeds: packet t (t - delay[k]) of every stream that has
-    one, or the caller's schedule -- in which a step holds whichever decoders and packets it names, each decoder's in order"""
-    if schedule is not None:
-        at = [0] * len(streams)
-        for step in schedule:
-            for k, p in step:
-                assert p == at[k] < len(streams[k]), "the schedule feeds decoder %d packet %d, its next one is %d" % (k, p, at[k])
-                at[k] += 1
-        return [list(step) for step in schedule if step]
-    delay = delay or [0] * len(streams)
-    return [[(k, t - delay[k]) for k in range(len(streams)) if 0 <= t - delay[k] < len(streams[k])]
-            for t in range(max(len(s) + d for s, d in zip(streams, delay)))]
-
-
-def device_decode(hip, streams, modes=None, out420p=None, sharp=None, offset=0, schedule=None, single=False):
-    """Lockstep steps over one decoder per stream, pictures delivered to device memory.  Per stream: [(return code, frame number
-    or None, [Y, U, V] or None)] per packet, as test_gpu_dec_drawinfo.decode gives for dsv_dec.  modes / out420p / sharp: per
-    stream; a mode or sharp entry may be a function of the packet's index (set before every step).  schedule: lockstep()'s;
-    single: one dsv2hip_dec_device_frame per packet in place of the step's batch call."""
-    bind(hip)
-    n = len(streams)
-    modes = modes or [0] * n
-    out420p = out420p or [False] * n
-    sharp = sharp or [False] * n
-    decs = [A.DECODER() for _ in range(n)]
-    for d, o in zip(decs, out420p):
-        if o:
-            assert hip.dsv2hip_dec_set_out420p(C.byref(d), 1) == 0
-    outs = [None] * n
-    res = [[] for _ in range(n)]
-    done = [False] * n
-    for step in lockstep(streams, schedule):
-        at = {k: t for k, t in step if not done[k]}
-        live = list(at)
-        m = len(live)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
-        bufs = (A.BUF * m)()
-        ptrs, caps, had_meta = (C.c_void_p * m)(), (C.c_size_t * m)(), []
-        for i, k in enumerate(live):
-            t = at[k]
-            decs[k].draw_info = modes[k](t) if callable(modes[k]) else modes[k]
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k](t) if callable(sharp[k]) else sharp[k])) == 0
-            mk_buf(hip, bufs[i], streams[k][t])
-            pb = hip.dsv2hip_dec_picture_bytes(C.byref(decs[k]))
-            had_meta.append(pb > 0)
-            if pb:
-                dims = out_dims(decs[k], out420p[k])
-                assert pb == sum(w * h for w, h in dims)
-                if outs[k] is None or outs[k].nbytes != pb:
-                    outs[k] = DevOut(pb, offset)
-                outs[k].arm()
-                ptrs[i], caps[i] = outs[k].ptr(), pb
-            else:
-                assert decs[k].got_metadata == 0
-                ptrs[i], caps[i] = None, 0
-        fns = (C.c_uint32 * m)()
-        rets = (C.c_int * m)()
-        torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        if single:
-            for i in range(m):
-                fn = C.c_uint32(0)
-                rets[i] = hip.dsv2hip_dec_device_frame(decp[i], C.byref(bufs[i]), ptrs[i], caps[i], C.byref(fn))
-                fns[i] = fn.value
-        else:
-            assert hip.dsv2hip_dec_batch_device(m, decp, bufs, ptrs, caps, fns, rets) == m
-        for i, k in enumerate(live):
-            planes = None
-            if outs[k] is not None and had_meta[i]:
-                flat = outs[k].picture()  # (guards checked after every step, picture or not)
-                if rets[i] == A.DEC_OK:
-                    planes = split_planes(flat, out_dims(decs[k], out420p[k]))
-                else:
-                    assert np.all(flat == GUARD)
-            if planes is None and rets[i] == A.DEC_OK:
-                assert fns[i] == NO_FN
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-            done[k] = rets[i] == A.DEC_EOS
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res
-
-
-def same_results(want, got, planes=(0, 1, 2)):
-    assert [r[0] for r in want] == [r[0] for r in got]
-    assert [r[1] for r in want] == [r[1] for r in got]
-    for (_, fn, pw), (_, _, pg) in zip(want, got):
-        assert (pw is None) == (pg is None)
-        if pw is not None:
-            for c in planes:
-                assert pw[c].shape == pg[c].shape
-                assert np.array_equal(pw[c], pg[c]), "frame %d plane %d differs in %d samples" % (fn, c, int(np.sum(pw[c] != pg[c])))
-
-
-@functools.lru_cache(maxsize=None)
-def format_stream(name, w, h, nfr):
-    code, hs, vs = FMT5[name]
-    return tuple(encode_stream(A.load_ref(), plain_frames(w, h, hs, vs, nfr, 5), w, h, code, eos=True, qp=60, gop=12)[0])
-
-
-def npics(results):
-    return sum(1 for r in results if r[2] is not None)
 
 
 def test_picture_bytes_of_a_null_and_a_fresh_decoder():
@@ -294,8 +126,6 @@ def test_transcode_without_the_host():
     """Two CIF streams decoded into device buffers whose pointers go straight to dsv2hip_enc_batch: the packets are the
     reference encoder's on the reference decoder's pictures.  dsv2hip_dec_device_frame gives the batch call's pictures."""
     ref, hip = A.load_ref(), bind(A.load_hip())
-    hip.dsv2hip_enc_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(A.ENCODER)), C.POINTER(C.c_void_p), C.POINTER(A.BUF), C.POINTER(C.c_int)]
-    hip.dsv2hip_enc_batch.restype = C.c_int
     w, h, ns = 352, 288, 2
     streams = [stream(w, h, "420", 5, 4, seed=70 + s) for s in range(ns)]
     refpics = [[r for r in decode(ref, pk, 0) if r[2] is not None] for pk in streams]

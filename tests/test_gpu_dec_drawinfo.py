@@ -6,64 +6,14 @@ damaged input -- and must never reach the picture the next P picture predicts fr
 The one documented difference: the reference stores the intra marks without a bounds check, which in a clipped last block row /
 column lands outside the luma plane; the product drops such a mark.  Mode bit 4 is therefore compared with the reference on
 block-aligned geometries only and checked on the product alone on clipped ones."""
-import ctypes as C
-import functools
-
 import numpy as np
 import pytest
 
 import dsvabi as A
-from codec_run import encode_stream
-from conftest import load_pkg
-from test_gpu_dec_batch import bind, check, planes_of
+from dec_out import batch_decode, check, decode, pictures, stream
+from hipabi import bind
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
-
-FMT = {"420": A.SUBSAMP_420, "444": A.SUBSAMP_444}
-
-
-@functools.lru_cache(maxsize=None)
-def stream(w, h, fmt, nfr, gop, seed=70, qp=60):
-    """Packets (metadata, pictures, end of stream) of a synthetic video encoded by the reference."""
-    v = load_pkg().synth.SynthVideo(w, h, fmt, seed=seed)
-    frames = [v.frame_bytes(t) for t in range(nfr)]
-    return tuple(encode_stream(A.load_ref(), frames, w, h, FMT[fmt], eos=True, qp=qp, gop=gop)[0])
-
-
-def decode(lib, packets, mode, out420p=False, room=None):
-    """[(return code, frame number, [Y, U, V] or None)] per packet; `mode`: the draw_info word, or a function of the packet's
-    index that gives it (set before every call).  Goes on after DSV_DEC_ERROR.  room[k]: bytes of zeroed memory that packet k's
-    buffer owns behind its stated length (len + 64 as ever) -- for a packet cut short, whose section lengths still name the bytes
-    that are gone."""
-    dec = A.DECODER()
-    if out420p:
-        lib.dsv2hip_dec_set_out420p.argtypes = [C.POINTER(A.DECODER), C.c_int]
-        assert lib.dsv2hip_dec_set_out420p(C.byref(dec), 1) == 0
-    out = []
-    for k, pk in enumerate(packets):
-        dec.draw_info = mode(k) if callable(mode) else mode
-        buf = A.BUF()
-        lib.dsv_mk_buf(C.byref(buf), len(pk) + 64 + (room[k] if room else 0))
-        buf.len = len(pk) + 64
-        C.memmove(buf.data, pk, len(pk))
-        fp = C.POINTER(A.FRAME)()
-        fn = C.c_uint32(0)
-        code = lib.dsv_dec(C.byref(dec), C.byref(buf), C.byref(fp), C.byref(fn))
-        planes = None
-        if code == A.DEC_OK and fp:
-            planes = planes_of(fp)
-            lib.dsv_frame_ref_dec(fp)
-        out.append((code, fn.value if planes is not None else None, planes))
-        if code == A.DEC_EOS:
-            break
-    lib.dsv_dec_free(C.byref(dec))
-    return out
-
-
-def pictures(results):
-    for code, _, _ in results:
-        assert code != A.DEC_ERROR
-    return [(fn, *pl) for _, fn, pl in results if pl is not None]
 
 
 def same(want, got, planes=(0, 1, 2)):
@@ -157,36 +107,6 @@ def test_clipped_geometry(w, h, fmt, nfr):
         assert np.array_equal(p7[2], p0[2]) and np.array_equal(p7[3], p0[3])
 
 
-def batch_decode(hip, streams, modes):
-    """test_gpu_dec_batch.batch_decode with draw_info set per decoder"""
-    n = len(streams)
-    decs = [A.DECODER() for _ in range(n)]
-    for d, m in zip(decs, modes):
-        d.draw_info = m
-    got = [[] for _ in range(n)]
-    for t in range(max(len(s) for s in streams)):
-        live = [k for k in range(n) if t < len(streams[k])]
-        m = len(live)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
-        bufs = (A.BUF * m)()
-        for i, k in enumerate(live):
-            pk = streams[k][t]
-            hip.dsv_mk_buf(C.byref(bufs[i]), len(pk) + 64)
-            C.memmove(bufs[i].data, pk, len(pk))
-        outs = (C.POINTER(A.FRAME) * m)()
-        fns = (C.c_uint32 * m)()
-        rets = (C.c_int * m)()
-        assert hip.dsv2hip_dec_batch(m, decp, bufs, outs, fns, rets) == m
-        for i, k in enumerate(live):
-            assert rets[i] != A.DEC_ERROR
-            if rets[i] == A.DEC_OK and outs[i]:
-                got[k].append((fns[i], *planes_of(outs[i])))
-                hip.dsv_frame_ref_dec(outs[i])
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return got
-
-
 def test_batch_mixes_drawn_and_undrawn_decoders():
     """One lockstep step sequence over four decoders: CIF mode 7, CIF undrawn, CIF mode 2 and (a second geometry) 720p mode 5."""
     ref, hip = A.load_ref(), A.load_hip()
@@ -201,9 +121,7 @@ def test_batch_mixes_drawn_and_undrawn_decoders():
 
 
 def test_every_mode_with_the_device_parser():
-    ref, hip = A.load_ref(), A.load_hip()
-    hip.dsv2hip_dec_set_parse_mode.argtypes = [C.c_int]
-    hip.dsv2hip_dec_set_parse_mode.restype = C.c_int
+    ref, hip = A.load_ref(), bind(A.load_hip())
     try:
         assert hip.dsv2hip_dec_set_parse_mode(2) == 2
         every_mode_equals_reference(ref, hip, 352, 288, stream(352, 288, "420", 9, 4), 9)

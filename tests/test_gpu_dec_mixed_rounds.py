@@ -12,29 +12,10 @@ import torch
 
 import dec_mixed_rounds as D
 import dsvabi as A
-from test_gpu_dec_device_out import DevOut, mk_buf, out_dims, split_planes
-from test_gpu_dec_rgb import OutSurf
-from test_gpu_dec_scale import bind
-from test_gpu_dec_surface import OUTSURF, surface_dims
+from dec_out import DevOut, OutSurf, out_dims, split_planes
+from hipabi import OUTSURF, PARSE_IDS, bind, mk_buf, parse_mode, surface_dims
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
-
-PARSE_IDS = {0: "host-parse", 1: "P-on-device", 2: "device-parse"}
-
-
-class parse_mode:
-    """dsv2hip_dec_set_parse_mode for the pictures handed over inside the block"""
-
-    def __init__(self, mode):
-        self.hip, self.mode = bind(A.load_hip()), mode
-
-    def __enter__(self):
-        if self.mode is not None:
-            assert self.hip.dsv2hip_dec_set_parse_mode(self.mode) == self.mode
-        return self.hip
-
-    def __exit__(self, *a):
-        self.hip.dsv2hip_dec_set_parse_mode(-1)
 
 
 def run_and_check(cs, mode=None, single=False):
@@ -109,8 +90,6 @@ def test_parameters_change_under_a_decoder(entry):
 def test_threads_of_plain_dsv_dec_with_different_streams():
     """8 threads loop plain dsv_dec, each on another row: the submit queue forms the steps"""
     hip = bind(A.load_hip())
-    hip.dsv2hip_dec_queue_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_dec_queue_stats.restype = None
     cs = D.case("threads")
     D.run(hip, cs._replace(feeds=cs.feeds[:1], opts=cs.opts[:1], schedule=D.together(cs.feeds[:1])))  # (binds every prototype before the threads start)
     hip.dsv2hip_dec_queue_stats(None, 1)

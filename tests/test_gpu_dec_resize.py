@@ -18,63 +18,18 @@ import dsvabi as A
 import yuv_rgb as Q
 from codec_run import configure_encoder, encode_stream
 from edge_cases import packet_bound_holds
-from test_gpu_dec_device_out import format_stream, lockstep, mk_buf, npics, same_results
-from test_gpu_dec_drawinfo import stream
-from test_gpu_dec_rgb import OutSurf, aligned, is_rgb, planar_oracle, plus1, rgb_forms, tight
-from test_gpu_dec_scale import BGRA709, EIGHTH, HALF, LAYOUT_IDS, LAYOUTS, QUARTER, RGBAFULL, content_stream, reset_all, scale_forms
-from test_gpu_dec_scale import bind as bind_scale
-from test_gpu_dec_scale import decode_steps as plain_steps
-from test_gpu_dec_scale import in_layout as scaled_layout
-from test_gpu_dec_surface import NO_FN, OUTSURF, PLANAR, SEMI, surface_dims
-from test_gpu_dec_surface import forms as uv_forms
-from test_gpu_enc_surface import SURFACE
-from test_gpu_enc_surface import bind as bind_enc
-from test_gpu_formats import FMT
+from codec_run import FMT, meta_packet
+from dec_out import (OutSurf, Sized, Surfaces, aligned, content_stream, decode_steps, expected_dims, format_stream, in_layout, is_rgb, npics, planar_oracle,
+                     plus1, same_results, stream, tight)
+from hipabi import (EIGHTH, HALF, OUTSURF, PLANAR, QUARTER, SEMI, SURFACE, bind, dec_resize_forms as resize_forms, dec_rgb_forms as rgb_forms,
+                    dec_scale_forms as scale_forms, dec_uv_forms as uv_forms, mk_buf, reset_dec_forms as reset_every, sized_dims)
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
 DECP = C.POINTER(A.DECODER)
-
-
-def bind(hip):
-    bind_scale(hip)
-    hip.dsv2hip_dec_resize_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_dec_resize_stats.restype = None
-    hip.dsv2hip_dec_sized_dims.argtypes = [DECP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
-    hip.dsv2hip_dec_sized_dims.restype = C.c_int
-    hip.dsv2hip_dec_batch_surface_sized.argtypes = [C.c_int, C.POINTER(DECP), C.POINTER(A.BUF), C.POINTER(OUTSURF), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                    C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
-    hip.dsv2hip_dec_batch_surface_sized.restype = C.c_int
-    hip.dsv2hip_dec_surface_frame_sized.argtypes = [DECP, C.POINTER(A.BUF), C.POINTER(OUTSURF), C.c_int, C.c_int, C.POINTER(C.c_uint32)]
-    hip.dsv2hip_dec_surface_frame_sized.restype = C.c_int
-    return hip
-
-
-def resize_forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_dec_resize_stats(out, int(reset))
-    return out[0], out[1]
-
-
-def reset_every(hip):
-    reset_all(hip)
-    resize_forms(hip, reset=True)
-
-
-def sized_dims(hip, dec, layout, ow, oh):
-    rb, rows = (C.c_size_t * 3)(), (C.c_int * 3)()
-    if hip.dsv2hip_dec_sized_dims(C.byref(dec), layout, ow, oh, rb, rows) != 0:
-        return None
-    return [(rb[c], rows[c]) for c in range(3)]
-
-
-def expected_dims(md, layout, ow, oh):
-    """include/dsv2_hip.h: dsv_mk_frame's plane sizes for out_w x out_h in the stream's format, as the layout's rows"""
-    if is_rgb(layout):
-        return [(4 * ow, oh), (0, 0), (0, 0)]
-    hs, vs = A.format_shifts(md.subsamp)
-    (_, _), (cw, ch), _ = R.plane_sizes(ow, oh, hs, vs)
-    return [(ow, oh), (2 * cw, ch), (0, 0)] if layout == SEMI else [(ow, oh), (cw, ch), (cw, ch)]
+BGRA709, RGBAFULL = Q.BGRA | Q.BT709, Q.RGBA | Q.FULL
+LAYOUTS = [PLANAR, SEMI, BGRA709, RGBAFULL]
+LAYOUT_IDS = ["planar", "semiplanar", "bgra709", "rgba601full"]
 
 
 def documented_wide(dims, layout, pitch, offset):
@@ -84,99 +39,10 @@ def documented_wide(dims, layout, pitch, offset):
     return all(offset % 4 == 0 and pitch(rb) % 4 == 0 and rb % 4 == 0 for rb, _ in straight)
 
 
-def decode_steps(hip, streams, specs, modes=None, sharp=None, delay=None, single=False):
-    """test_gpu_dec_scale.decode_steps through the sized calls: spec = dict(layout, pitch, offset, size) per stream, size (out_w, out_h)
-    or None for an entry that is not sized (whose layout may carry a scale).  Per stream: [(return code, frame number or None, planes or
-    None)] per packet.  The reported sizes and the guards are checked at every step.  single: one dsv2hip_dec_surface_frame_sized per
-    packet in place of the step's batch call."""
-    bind(hip)
-    n = len(streams)
-    modes, sharp = modes or [0] * n, sharp or [False] * n
-    decs = [A.DECODER() for _ in range(n)]
-    surfs = [None] * n
-    res = [[] for _ in range(n)]
-    done = [False] * n
-    for step in lockstep(streams, None, delay):
-        pkt = {k: t for k, t in step if not done[k]}
-        live = list(pkt)
-        m = len(live)
-        decp = (DECP * m)(*[C.pointer(decs[k]) for k in live])
-        bufs, arr, had_meta = (A.BUF * m)(), (OUTSURF * m)(), []
-        ows, ohs = (C.c_int * m)(), (C.c_int * m)()
-        for i, k in enumerate(live):
-            at = pkt[k]
-            spec = dict(specs[k])
-            size = spec.pop("size")
-            ows[i], ohs[i] = size or (0, 0)
-            decs[k].draw_info = modes[k](at) if callable(modes[k]) else modes[k]
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k](at) if callable(sharp[k]) else sharp[k])) == 0
-            mk_buf(hip, bufs[i], streams[k][at])
-            dims = sized_dims(hip, decs[k], spec["layout"], ows[i], ohs[i])
-            had_meta.append(dims is not None)
-            if dims is None:
-                assert decs[k].got_metadata == 0  # (its entry stays all zeros)
-                continue
-            if size:
-                assert dims == expected_dims(decs[k].vidmeta, spec["layout"], *size)
-            else:
-                assert dims == surface_dims(hip, decs[k], spec["layout"])
-            if surfs[k] is None:
-                surfs[k] = OutSurf(dims, **spec)
-            surfs[k].arm()
-            arr[i] = surfs[k].c
-        fns, rets = (C.c_uint32 * m)(), (C.c_int * m)()
-        torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        if single:
-            for i in range(m):
-                fn = C.c_uint32(0)
-                rets[i] = hip.dsv2hip_dec_surface_frame_sized(decp[i], C.byref(bufs[i]), C.byref(arr[i]), ows[i], ohs[i], C.byref(fn))
-                fns[i] = fn.value
-        else:
-            assert hip.dsv2hip_dec_batch_surface_sized(m, decp, bufs, arr, ows, ohs, fns, rets) == m
-        for i, k in enumerate(live):
-            planes = None
-            if surfs[k] is not None and had_meta[i]:
-                if rets[i] == A.DEC_OK:
-                    planes = surfs[k].planes()  # (guards checked after every step)
-                else:
-                    assert surfs[k].untouched()
-            if planes is None and rets[i] == A.DEC_OK:
-                assert fns[i] == NO_FN
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-            done[k] = rets[i] == A.DEC_EOS
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res
-
-
-def in_layout(results, layout, fmt, size):
-    """full-size planar results ([Y, U, V] per picture) as the planes of `layout` at `size`: resampled, then interleaved or converted"""
-    if size is None:
-        return scaled_layout(results, layout, fmt)
-    _, hs, vs = FMT[fmt]
-    out = []
-    for code, fn, pl in results:
-        if pl is not None:
-            y, u, v = R.resize_picture(pl[0], pl[1], pl[2], size[0], size[1], hs, vs)
-            if layout == PLANAR:
-                pl = [y, u, v]
-            elif layout == SEMI:
-                pl = [y, B.interleave(u, v)]
-            else:
-                pl = [Q.convert(y, u, v, layout, hs, vs).reshape(y.shape[0], 4 * y.shape[1])]
-        out.append((code, fn, pl))
-    return out
-
-
-def same(want, got):
-    npl = max((len(pl) for _, _, pl in want if pl is not None), default=0)
-    same_results(want, got, planes=range(npl))
-
-
 def equals_oracle(hip, packets, fmt, layout, size, pitch, offset=0, mode=0, sharp=False):
-    got = decode_steps(hip, [packets], [dict(layout=layout, pitch=pitch, offset=offset, size=size)], modes=[mode], sharp=[sharp])[0]
+    got = decode_steps(hip, [packets], Sized([dict(layout=layout, pitch=pitch, offset=offset, size=size)]), modes=[mode], sharp=[sharp])[0]
     want = planar_oracle(packets, mode, sharp)
-    same(in_layout(want, layout, fmt, size), got)
+    same_results(in_layout(want, layout, fmt, size), got)
     return want, got
 
 
@@ -215,7 +81,7 @@ def test_both_forms_are_reached_by_the_cases_above():
     seen = set()
     for w, h, ow, oh in CASES:
         for layout in LAYOUTS:
-            dims = [d for d in expected_dims(A.mk_meta(w, h, A.SUBSAMP_420), layout, ow, oh) if d[1]]
+            dims = [d for d in expected_dims(A.mk_meta(w, h, A.SUBSAMP_420), layout, (ow, oh)) if d[1]]
             for pitch, offset in VARIANTS:
                 seen.add((layout, documented_wide(dims, layout, pitch, offset)))
     assert seen == {(layout, wide) for layout in LAYOUTS for wide in (True, False)} - {(BGRA709, False), (RGBAFULL, False)}
@@ -289,10 +155,10 @@ def test_draw_info_and_postsharp(layout, mode, sharp):
         assert all(not np.array_equal(a[2][0], b[2][0]) for a, b in zip(plain, want) if a[2] is not None)
     assert npics(got) == 4
     first = next(i for i, r in enumerate(plain) if r[2] is not None)
-    once = decode_steps(hip, [packets], [dict(layout=layout, pitch=aligned, offset=0, size=size)], modes=[lambda t: mode if t <= first else 0],
+    once = decode_steps(hip, [packets], Sized([dict(layout=layout, pitch=aligned, offset=0, size=size)]), modes=[lambda t: mode if t <= first else 0],
                         sharp=[lambda t: sharp and t <= first])[0]
     mixed = [w_ if i <= first else p for i, (w_, p) in enumerate(zip(want, plain))]
-    same(in_layout(mixed, layout, "420", size), once)
+    same_results(in_layout(mixed, layout, "420", size), once)
 
 
 # ---- 5. one mixed step ---------------------------------------------------------------------------------------------------------------
@@ -307,14 +173,14 @@ def mixed_step(hip):
              dict(layout=RGBAFULL, pitch=tight, offset=0, size=(9, 5))]           # joins two steps late: no metadata beside decoders with pictures
     delay = [0, 0, 0, 0, 2]
     reset_every(hip)
-    got = decode_steps(hip, streams, specs, delay=delay)
+    got = decode_steps(hip, streams, Sized(specs), delay=delay)
     assert resize_forms(hip)[1] >= 4 and sum(scale_forms(hip)) >= 4  # (the sized planar surface at an odd address: its rounds' general form)
     for k, (pk, spec, fmt) in enumerate(zip(streams, specs, fmts)):
-        same(in_layout(planar_oracle(pk), spec["layout"], fmt, spec["size"]), got[k])
+        same_results(in_layout(planar_oracle(pk), spec["layout"], fmt, spec["size"]), got[k])
         if spec["size"] is None:  # byte-identical to the plain call's
-            same(plain_steps(hip, [pk], [dict(layout=spec["layout"], pitch=spec["pitch"], offset=spec["offset"])])[0], got[k])
+            same_results(decode_steps(hip, [pk], Surfaces([dict(layout=spec["layout"], pitch=spec["pitch"], offset=spec["offset"])]))[0], got[k])
         else:
-            same(decode_steps(hip, [pk], [spec], single=True)[0], got[k])  # ... to the one-decoder call's
+            same_results(decode_steps(hip, [pk], Sized([spec]), single=True)[0], got[k])  # ... to the one-decoder call's
 
 
 def test_sized_scaled_and_plain_entries_in_one_step():
@@ -337,15 +203,15 @@ def test_sized_scaled_and_plain_entries_in_one_step_device_parser():
 def test_own_size_is_the_plain_delivery_and_frame_sized_is_the_batch_call(layout):
     hip = bind(A.load_hip())
     packets = stream(50, 38, "420", 4, 2)
-    plain = plain_steps(hip, [packets], [dict(layout=layout, pitch=plus1, offset=1)], modes=[7], sharp=[True])[0]
+    plain = decode_steps(hip, [packets], Surfaces([dict(layout=layout, pitch=plus1, offset=1)]), modes=[7], sharp=[True])[0]
     reset_every(hip)
-    own = decode_steps(hip, [packets], [dict(layout=layout, pitch=plus1, offset=1, size=(50, 38))], modes=[7], sharp=[True])[0]
+    own = decode_steps(hip, [packets], Sized([dict(layout=layout, pitch=plus1, offset=1, size=(50, 38))]), modes=[7], sharp=[True])[0]
     assert resize_forms(hip) == (0, 0)
-    same(plain, own)
-    batch = decode_steps(hip, [packets], [dict(layout=layout, pitch=plus1, offset=1, size=(33, 21))], modes=[7], sharp=[True])[0]
-    one = decode_steps(hip, [packets], [dict(layout=layout, pitch=plus1, offset=1, size=(33, 21))], modes=[7], sharp=[True], single=True)[0]
+    same_results(plain, own)
+    batch = decode_steps(hip, [packets], Sized([dict(layout=layout, pitch=plus1, offset=1, size=(33, 21))]), modes=[7], sharp=[True])[0]
+    one = decode_steps(hip, [packets], Sized([dict(layout=layout, pitch=plus1, offset=1, size=(33, 21))]), modes=[7], sharp=[True], single=True)[0]
     assert npics(batch) == 4
-    same(batch, one)
+    same_results(batch, one)
 
 
 # ---- 7. the staging picture grows on one decoder -------------------------------------------------------------------------------------------
@@ -438,7 +304,7 @@ def test_refused_calls_consume_nothing(layout):
     assert hip.dsv2hip_dec_batch_surface_sized(2, decp, bufs, arr, ows, ohs, fns, rets) == 2
     assert list(rets) == [A.DEC_GOT_META] * 2
     dims = sized_dims(hip, decs[0], layout, *size)
-    assert dims == expected_dims(decs[0].vidmeta, layout, *size)
+    assert dims == expected_dims(decs[0].vidmeta, layout, size)
     rb = [d[0] for d in dims]
     surfs = [OutSurf(dims, layout, aligned) for _ in decs]
     nplanes = len(surfs[0].t)
@@ -504,7 +370,7 @@ def test_refused_calls_consume_nothing(layout):
             pic = rets[i] == A.DEC_OK and had_meta[i]
             got[i].append((rets[i], fns[i] if pic else None, surfs[i].planes() if pic else None))
     for i in range(2):
-        same(want, got[i])
+        same_results(want, got[i])
         hip.dsv_dec_free(C.byref(decs[i]))
 
 
@@ -522,11 +388,10 @@ def test_sizes_beyond_what_32_bit_sums_hold_are_refused(w, h):
     packet, the decoder, fn / ret and the surface as they were; the accepted neighbours get their plane sizes.  (A plane side above
     32 768 cannot be reached through a packet, the decoder taking metadata of up to 16 384 a side: tests/test_egress_resize_cpu.py
     pins that bound, as every other, on the rule the calls refuse by.)"""
-    from test_gpu_robustness import _meta_packet
     hip = bind(A.load_hip())
     dec = A.DECODER()
     buf, fn = A.BUF(), C.c_uint32(0)
-    mk_buf(hip, buf, _meta_packet((w, h, A.SUBSAMP_420, 30, 1, 1, 1, 1)))
+    mk_buf(hip, buf, meta_packet((w, h, A.SUBSAMP_420, 30, 1, 1, 1, 1)))
     assert hip.dsv2hip_dec_surface_frame_sized(C.byref(dec), C.byref(buf), C.byref(OUTSURF()), 0, 0, C.byref(fn)) == A.DEC_GOT_META
     assert (dec.vidmeta.width, dec.vidmeta.height, dec.vidmeta.subsamp) == (w, h, A.SUBSAMP_420)
     picture = stream(64, 48, "420", 4, 2)[1]
@@ -547,7 +412,7 @@ def test_sizes_beyond_what_32_bit_sums_hold_are_refused(w, h):
         for layout in LAYOUTS:
             dims = sized_dims(hip, dec, layout, ow, oh)
             if accepted:
-                assert dims == expected_dims(dec.vidmeta, layout, ow, oh), (layout, ow, oh)
+                assert dims == expected_dims(dec.vidmeta, layout, (ow, oh)), (layout, ow, oh)
                 continue
             assert dims is None, (layout, ow, oh)
             sf.c.layout = layout
@@ -567,7 +432,7 @@ def test_sizes_beyond_what_32_bit_sums_hold_are_refused(w, h):
 def test_sized_nv12_goes_straight_into_an_encoder_of_that_geometry():
     """A 64x48 4:2:0 stream delivered sized to 48x32 into a pitched NV12 device surface whose pointers and pitches go straight to
     dsv2hip_enc_surface_frame of a 48x32 encoder: the packets are the reference encoder's on the oracle's planes."""
-    ref, hip = A.load_ref(), bind_enc(bind(A.load_hip()))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, size = 64, 48, (48, 32)
     packets = stream(w, h, "420", 4, 4)
     sized = [R.resize_picture(pl[0], pl[1], pl[2], size[0], size[1], 1, 1) for _, _, pl in planar_oracle(packets) if pl is not None]

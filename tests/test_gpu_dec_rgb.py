@@ -7,7 +7,6 @@ several passes, draw_info and postsharp, RGB and YUV surfaces and two geometries
 byte is 255, no byte outside the rows is written, a refused call consumes nothing, and the surface feeds
 dsv2hip_enc_surface_frame without a host copy."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -18,14 +17,10 @@ import rgb_csc as R
 import yuv_rgb as Q
 from codec_run import configure_encoder, encode_stream
 from edge_cases import packet_bound_holds
-from test_gpu_dec_device_out import format_stream, mk_buf, npics, same_results
-from test_gpu_dec_drawinfo import stream
-from test_gpu_dec_surface import GUARD, LEAD, NO_FN, OUTSURF, PLANAR, SEMI, packets_of, surface_decode, surface_dims
-from test_gpu_dec_surface import bind as bind_surface
-from test_gpu_dec_surface import forms as uv_forms
-from test_gpu_enc_rgb import bind as bind_enc
-from test_gpu_enc_surface import SURFACE
-from test_gpu_formats import FMT
+from codec_run import FMT
+from dec_out import (OutSurf, Surfaces, aligned, decode_steps, fixed, format_stream, in_layout as as_rgb, is_rgb, npics, packets_of, planar_oracle, plus1,
+                     same_results, same_rgb, saturated_stream, stream, tight)
+from hipabi import OUTSURF, PLANAR, SEMI, SURFACE, bind, dec_rgb_forms as rgb_forms, dec_uv_forms as uv_forms, mk_buf, reset_dec_forms as reset_forms, surface_dims
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
@@ -33,180 +28,8 @@ ORDER = {"bgra": Q.BGRA, "rgba": Q.RGBA}
 CSC_IDS = ["bt601", "bt709", "bt601_full", "bt709_full"]
 
 
-def bind(hip):
-    bind_surface(hip)
-    hip.dsv2hip_dec_rgb_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_dec_rgb_stats.restype = None
-    return hip
-
-
-def rgb_forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_dec_rgb_stats(out, int(reset))
-    return out[0], out[1]
-
-
-def reset_forms(hip):
-    rgb_forms(hip, reset=True)
-    uv_forms(hip, reset=True)
-
-
-def is_rgb(layout):
-    return (layout & ~0x300) in (Q.BGRA, Q.RGBA)
-
-
-def tight(rb):
-    return rb
-
-
-def plus1(rb):
-    return rb + 1
-
-
-def aligned(rb):
-    return (rb + 15) // 16 * 16 + 16
-
-
-def fixed(pitch):
-    return lambda rb: pitch
-
-
-class OutSurf:
-    """One decoder's surface of any layout: per plane a tensor of LEAD guard bytes, `offset` more, rows pitch(row bytes) apart (the
-    last one without padding), LEAD guard bytes; cap[c] is exactly what the rows need.  (test_gpu_dec_surface.Surf with the pitch
-    as a function.)"""
-
-    def __init__(self, dims, layout, pitch, offset=0):
-        self.layout, self.dims = layout, [d for d in dims if d[1]]
-        self.c = OUTSURF()
-        self.c.layout = layout
-        self.t, self.inside, self.start, self.pitches = [], [], LEAD + offset, []
-        for i, (rb, rows) in enumerate(self.dims):
-            p = pitch(rb)
-            need = (rows - 1) * p + rb
-            t = torch.empty(self.start + need + LEAD, dtype=torch.uint8, device="cuda")
-            assert t.data_ptr() % 16 == 0
-            mask = np.zeros(t.numel(), dtype=bool)
-            for y in range(rows):
-                mask[self.start + y * p:self.start + y * p + rb] = True
-            self.t.append(t)
-            self.inside.append(mask)
-            self.pitches.append(p)
-            self.c.plane[i], self.c.pitch[i], self.c.cap[i] = t.data_ptr() + self.start, p, need
-
-    def arm(self):
-        for t in self.t:
-            t.fill_(GUARD)
-
-    def planes(self):
-        """the delivered planes; asserts that every byte outside the rows -- in front of plane[0], between the rows, behind the last
-        row -- still holds the guard value"""
-        out = []
-        for t, mask, (rb, rows), p in zip(self.t, self.inside, self.dims, self.pitches):
-            a = t.cpu().numpy()
-            assert np.all(a[~mask] == GUARD), "bytes outside the rows were written"
-            out.append(np.stack([a[self.start + y * p:self.start + y * p + rb] for y in range(rows)]))
-        return out
-
-    def untouched(self):
-        return all(bool(torch.all(t == GUARD)) for t in self.t)
-
-
-def expected_dims(md, layout):
-    if is_rgb(layout):
-        return [(4 * md.width, md.height), (0, 0), (0, 0)]
-    hs, vs = A.format_shifts(md.subsamp)
-    cw, ch = (md.width + (1 << hs) - 1) >> hs, (md.height + (1 << vs) - 1) >> vs
-    return [(md.width, md.height), (2 * cw, ch), (0, 0)] if layout == SEMI else [(md.width, md.height), (cw, ch), (cw, ch)]
-
-
-def decode_steps(hip, streams, specs, modes=None, sharp=None):
-    """Lockstep steps over one decoder per stream, pictures delivered into surfaces: spec = dict(layout, pitch, offset) per stream,
-    any layout.  Per stream: [(return code, frame number or None, planes or None)] per packet (test_gpu_dec_surface.surface_decode);
-    an RGB surface's planes are [h x 4w bytes].  The guards are checked after every step."""
-    bind(hip)
-    n = len(streams)
-    modes, sharp = modes or [0] * n, sharp or [False] * n
-    decs = [A.DECODER() for _ in range(n)]
-    surfs = [None] * n
-    res = [[] for _ in range(n)]
-    done = [False] * n
-    for t in range(max(len(s) for s in streams)):
-        live = [k for k in range(n) if t < len(streams[k]) and not done[k]]
-        m = len(live)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
-        bufs, arr, had_meta = (A.BUF * m)(), (OUTSURF * m)(), []
-        for i, k in enumerate(live):
-            decs[k].draw_info = modes[k]
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k])) == 0
-            mk_buf(hip, bufs[i], streams[k][t])
-            dims = surface_dims(hip, decs[k], specs[k]["layout"])
-            had_meta.append(dims is not None)
-            if dims is None:
-                assert decs[k].got_metadata == 0  # (its entry stays all zeros)
-                continue
-            assert dims == expected_dims(decs[k].vidmeta, specs[k]["layout"])
-            if surfs[k] is None:
-                surfs[k] = OutSurf(dims, **specs[k])
-            surfs[k].arm()
-            arr[i] = surfs[k].c
-        fns, rets = (C.c_uint32 * m)(), (C.c_int * m)()
-        torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        assert hip.dsv2hip_dec_batch_surface(m, decp, bufs, arr, fns, rets) == m
-        for i, k in enumerate(live):
-            planes = None
-            if surfs[k] is not None and had_meta[i]:
-                if rets[i] == A.DEC_OK:
-                    planes = surfs[k].planes()
-                else:
-                    assert surfs[k].untouched()
-            if planes is None and rets[i] == A.DEC_OK:
-                assert fns[i] == NO_FN
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-            done[k] = rets[i] == A.DEC_EOS
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res
-
-
-@functools.lru_cache(maxsize=None)
-def planar_oracle(packets, mode=0, sharp=False):
-    """the same packets through another decoder of the library into a tight PLANAR surface, under the same switches (shared, never
-    modified): [(return code, frame number, [Y, U, V])]"""
-    got = surface_decode(A.load_hip(), [packets], [dict(layout=PLANAR, pitch="tight", offset=0)], modes=[mode], sharp=[sharp])[0]
-    for _, _, pl in got:
-        for p in pl or ():
-            p.setflags(write=False)
-    return tuple(got)
-
-
-def as_rgb(results, layout, fmt):
-    """planar results as the surface's one plane of h x 4w bytes"""
-    _, hs, vs = FMT[fmt]
-    out = []
-    for code, fn, pl in results:
-        if pl is not None:
-            h, w = pl[0].shape
-            pl = [Q.convert(pl[0], pl[1], pl[2], layout, hs, vs).reshape(h, 4 * w)]
-        out.append((code, fn, pl))
-    return out
-
-
-def same_rgb(want, got):
-    """test_gpu_dec_device_out.same_results on the one plane, with the first differing byte named; alpha is part of the comparison"""
-    assert [r[:2] for r in want] == [r[:2] for r in got]
-    for (_, fn, pw), (_, _, pg) in zip(want, got):
-        assert (pw is None) == (pg is None)
-        if pw is not None:
-            assert pw[0].shape == pg[0].shape
-            bad = np.argwhere(pw[0] != pg[0])
-            assert bad.size == 0, "frame %d: byte %d of pixel (x=%d, y=%d) is %d, the conversion gives %d (%d bytes differ)" % (
-                fn, bad[0][1] % 4, bad[0][1] // 4, bad[0][0], pg[0][tuple(bad[0])], pw[0][tuple(bad[0])], len(bad))
-            assert np.all(pg[0][:, 3::4] == 255)
-
-
 def rgb_equals_oracle(hip, packets, fmt, layout, pitch, offset=0, mode=0, sharp=False):
-    got = decode_steps(hip, [packets], [dict(layout=layout, pitch=pitch, offset=offset)], modes=[mode], sharp=[sharp])[0]
+    got = decode_steps(hip, [packets], Surfaces([dict(layout=layout, pitch=pitch, offset=offset)]), modes=[mode], sharp=[sharp])[0]
     want = planar_oracle(packets, mode, sharp)
     same_rgb(as_rgb(want, layout, fmt), got)
     return want, got
@@ -270,41 +93,6 @@ def test_smallest_pictures(w, h, fmt, form):
 
 
 # ---- 4. saturation -----------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def saturated_planes():
-    """64x48 at full resolution (Y, U, V each 48 x 64): the eight corners of the YUV cube in 8x8 tiles; a ramp 0..255 of each of Y, U
-    and V against the extremes of the other two (3 x 8 rows); the limited-range extremes 16 / 235 (Y) and 16 / 240 (U, V) in 8x8
-    tiles; 8 rows of a smooth gradient"""
-    y, u, v = (np.full((48, 64), 128, dtype=np.uint8) for _ in range(3))
-    for k in range(8):
-        sl = (slice(0, 8), slice(8 * k, 8 * k + 8))
-        y[sl], u[sl], v[sl] = 255 * (k & 1), 255 * ((k >> 1) & 1), 255 * ((k >> 2) & 1)
-        sl = (slice(32, 40), slice(8 * k, 8 * k + 8))
-        y[sl], u[sl], v[sl] = (16, 235)[k & 1], (16, 240)[(k >> 1) & 1], (16, 240)[(k >> 2) & 1]
-    ramp = np.arange(64) * 255 // 63
-    for c, pl in enumerate((y, u, v)):
-        rows = slice(8 + 8 * c, 16 + 8 * c)
-        for other in (y, u, v):
-            other[rows, :32], other[rows, 32:] = 0, 255
-        pl[rows] = ramp
-    y[40:] = np.arange(64) * 3 + 20
-    u[40:] = (np.arange(8) * 20 + 30)[:, None]
-    v[40:] = 220 - np.arange(64) * 3
-    return y, u, v
-
-
-@functools.lru_cache(maxsize=None)
-def saturated_stream(fmt):
-    """the picture twice (an I and a P picture), lossless, by the reference encoder; returns (packets, the planes in the format)"""
-    code, hs, vs = FMT[fmt]
-    y, u, v = saturated_planes()
-    planes = (y, np.ascontiguousarray(u[::1 << vs, ::1 << hs]), np.ascontiguousarray(v[::1 << vs, ::1 << hs]))
-    frame = b"".join(p.tobytes() for p in planes)
-    packets = tuple(encode_stream(A.load_ref(), [frame, frame], 64, 48, code, eos=True, qp=100, gop=12)[0])
-    packet_bound_holds(packets, 64, 48, code)
-    return packets, planes
-
-
 @pytest.mark.parametrize("fmt", ["444", "420"])
 @pytest.mark.parametrize("csc", Q.CSC, ids=CSC_IDS)
 def test_saturation_reaches_both_clamps(csc, fmt):
@@ -338,7 +126,7 @@ def test_only_the_rows_are_written_and_alpha_is_255(form):
     w, h = (352, 288) if form == "wide" else (354, 290)
     spec = dict(layout=Q.RGBA | Q.FULL, pitch=aligned if form == "wide" else plus1, offset=0 if form == "wide" else 3)
     packets = packets_of(w, h, "420", 3)
-    got = decode_steps(hip, [packets], [spec])[0]
+    got = decode_steps(hip, [packets], Surfaces([spec]))[0]
     same_rgb(as_rgb(planar_oracle(packets), spec["layout"], "420"), got)
     pics = [pl[0] for _, _, pl in got if pl is not None]
     assert len(pics) == 3 and all(p.shape == (h, 4 * w) and np.all(p[:, 3::4] == 255) for p in pics)
@@ -368,12 +156,12 @@ def mixed_step(hip):
              dict(layout=rgb709f, pitch=plus1, offset=1),           # the second geometry: a round of its own, in the general form
              dict(layout=PLANAR, pitch=tight, offset=0)]
     reset_forms(hip)
-    got = decode_steps(hip, streams, specs)
+    got = decode_steps(hip, streams, Surfaces(specs))
     # CIF: 9 rounds with two aligned RGB surfaces each; 354x290: 3 rounds with an RGB surface at an odd address
     assert rgb_forms(hip) == (9, 3)
     assert uv_forms(hip)[0] == 9
     for k, (pk, spec, fmt) in enumerate(zip(streams, specs, fmts)):
-        alone = decode_steps(hip, [pk], [spec])[0]
+        alone = decode_steps(hip, [pk], Surfaces([spec]))[0]
         planes = range(len(alone[1][2]))
         same_results(alone, got[k], planes=planes)  # every output equals its single-decoder result
         want = planar_oracle(pk)
@@ -545,7 +333,7 @@ def test_rgba_surface_goes_straight_into_the_encoder():
     """A CIF stream decoded into a pitched RGBA device surface whose pointer and pitch go straight to dsv2hip_enc_surface_frame
     with the same layout: the packets are the reference encoder's on the planar pictures that the encoder's conversion
     (tests/rgb_csc.py) defines on this conversion's pixels."""
-    ref, hip = A.load_ref(), bind_enc(bind(A.load_hip()))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, layout = 352, 288, Q.RGBA | Q.BT709
     packets = stream(w, h, "420", 5, 4)
     pixels = [pl[0].reshape(h, w, 4) for _, _, pl in as_rgb(planar_oracle(packets), layout, "420") if pl is not None]

@@ -17,61 +17,18 @@ import box_reduce as B
 import dsvabi as A
 import yuv_rgb as Q
 from codec_run import configure_encoder, encode_stream
-from edge_cases import packet_bound_holds, stream_frames
-from test_gpu_dec_device_out import format_stream, lockstep, mk_buf, npics, same_results
-from test_gpu_dec_drawinfo import stream
-from test_gpu_dec_rgb import OutSurf, aligned, is_rgb, planar_oracle, plus1, reset_forms, rgb_forms, tight
-from test_gpu_dec_rgb import bind as bind_rgb
-from test_gpu_dec_surface import NO_FN, OUTSURF, PLANAR, SEMI, surface_dims
-from test_gpu_dec_surface import forms as uv_forms
-from test_gpu_enc_surface import SURFACE
-from test_gpu_enc_surface import bind as bind_enc
-from test_gpu_formats import FMT
+from edge_cases import packet_bound_holds
+from codec_run import FMT
+from dec_out import (OutSurf, Surfaces, aligned, base_of, content_stream, decode_steps, expected_dims, format_stream, in_layout, is_rgb, npics, planar_oracle, plus1,
+                     same_results, shift_of, stream, tight)
+from hipabi import (EIGHTH, HALF, OUTSURF, PLANAR, QUARTER, SCALE, SEMI, SURFACE, bind, dec_rgb_forms as rgb_forms, dec_scale_forms as scale_forms,
+                    dec_uv_forms as uv_forms, mk_buf, reset_dec_forms as reset_all, surface_dims)
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
-HALF, QUARTER, EIGHTH = 0x1000, 0x2000, 0x3000
-SCALE = {0: 0, 1: HALF, 2: QUARTER, 3: EIGHTH}
 BGRA709, RGBAFULL = Q.BGRA | Q.BT709, Q.RGBA | Q.FULL
 LAYOUTS = [PLANAR, SEMI, BGRA709, RGBAFULL]
 LAYOUT_IDS = ["planar", "semiplanar", "bgra709", "rgba601full"]
-
-
-def bind(hip):
-    bind_rgb(hip)
-    hip.dsv2hip_dec_scale_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_dec_scale_stats.restype = None
-    return hip
-
-
-def scale_forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_dec_scale_stats(out, int(reset))
-    return out[0], out[1]
-
-
-def reset_all(hip):
-    reset_forms(hip)
-    scale_forms(hip, reset=True)
-
-
-def shift_of(layout):
-    return (layout >> 12) & 3
-
-
-def base_of(layout):
-    return layout & ~0x3000
-
-
-def expected_dims(md, layout):
-    """include/dsv2_hip.h: dsv_mk_frame's plane sizes for (ceil(w / n), ceil(h / n)) in the stream's format, as the layout's rows"""
-    s, base = shift_of(layout), base_of(layout)
-    w, h = B.reduced_size(md.width, s), B.reduced_size(md.height, s)
-    if is_rgb(base):
-        return [(4 * w, h), (0, 0), (0, 0)]
-    hs, vs = A.format_shifts(md.subsamp)
-    cw, ch = (w + (1 << hs) - 1) >> hs, (h + (1 << vs) - 1) >> vs
-    return [(w, h), (2 * cw, ch), (0, 0)] if base == SEMI else [(w, h), (cw, ch), (cw, ch)]
 
 
 def documented_wide(dims, layout, pitch, offset):
@@ -82,93 +39,10 @@ def documented_wide(dims, layout, pitch, offset):
     return all(offset % 8 == 0 and pitch(rb) % 8 == 0 and rb % (16 >> s) == 0 for rb, _ in straight)
 
 
-def decode_steps(hip, streams, specs, modes=None, sharp=None, delay=None, schedule=None, single=False):
-    """test_gpu_dec_rgb.decode_steps for layouts with a scale: lockstep steps over one decoder per stream, spec = dict(layout, pitch,
-    offset) per stream; stream k hands in its first packet at step delay[k] (so a decoder without metadata can stand beside decoders
-    that deliver pictures); modes / sharp entries may be functions of the stream's packet index.  Per stream: [(return code, frame
-    number or None, planes or None)] per packet.  The reported sizes and the guards are checked at every step.  schedule:
-    test_gpu_dec_device_out.lockstep()'s, in place of delay; single: one dsv2hip_dec_surface_frame per packet in place of the step's
-    batch call."""
-    bind(hip)
-    n = len(streams)
-    modes, sharp = modes or [0] * n, sharp or [False] * n
-    decs = [A.DECODER() for _ in range(n)]
-    surfs = [None] * n
-    res = [[] for _ in range(n)]
-    done = [False] * n
-    for step in lockstep(streams, schedule, delay):
-        pkt = {k: t for k, t in step if not done[k]}
-        live = list(pkt)
-        m = len(live)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
-        bufs, arr, had_meta = (A.BUF * m)(), (OUTSURF * m)(), []
-        for i, k in enumerate(live):
-            at = pkt[k]
-            decs[k].draw_info = modes[k](at) if callable(modes[k]) else modes[k]
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k](at) if callable(sharp[k]) else sharp[k])) == 0
-            mk_buf(hip, bufs[i], streams[k][at])
-            dims = surface_dims(hip, decs[k], specs[k]["layout"])
-            had_meta.append(dims is not None)
-            if dims is None:
-                assert decs[k].got_metadata == 0  # (its entry stays all zeros)
-                continue
-            assert dims == expected_dims(decs[k].vidmeta, specs[k]["layout"])
-            if surfs[k] is None:
-                surfs[k] = OutSurf(dims, **specs[k])
-            surfs[k].arm()
-            arr[i] = surfs[k].c
-        fns, rets = (C.c_uint32 * m)(), (C.c_int * m)()
-        torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        if single:
-            for i in range(m):
-                fn = C.c_uint32(0)
-                rets[i] = hip.dsv2hip_dec_surface_frame(decp[i], C.byref(bufs[i]), C.byref(arr[i]), C.byref(fn))
-                fns[i] = fn.value
-        else:
-            assert hip.dsv2hip_dec_batch_surface(m, decp, bufs, arr, fns, rets) == m
-        for i, k in enumerate(live):
-            planes = None
-            if surfs[k] is not None and had_meta[i]:
-                if rets[i] == A.DEC_OK:
-                    planes = surfs[k].planes()  # (guards checked after every step)
-                else:
-                    assert surfs[k].untouched()
-            if planes is None and rets[i] == A.DEC_OK:
-                assert fns[i] == NO_FN
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-            done[k] = rets[i] == A.DEC_EOS
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res
-
-
-def in_layout(results, layout, fmt):
-    """full-size planar results ([Y, U, V] per picture) as the planes of `layout`: reduced, then interleaved or converted"""
-    s, base = shift_of(layout), base_of(layout)
-    _, hs, vs = FMT[fmt]
-    out = []
-    for code, fn, pl in results:
-        if pl is not None:
-            y, u, v = B.reduce_picture(pl[0], pl[1], pl[2], s)
-            if base == PLANAR:
-                pl = [y, u, v]
-            elif base == SEMI:
-                pl = [y, B.interleave(u, v)]
-            else:
-                pl = [Q.convert(y, u, v, base, hs, vs).reshape(y.shape[0], 4 * y.shape[1])]
-        out.append((code, fn, pl))
-    return out
-
-
-def same(want, got):
-    npl = max((len(pl) for _, _, pl in want if pl is not None), default=0)
-    same_results(want, got, planes=range(npl))
-
-
 def equals_oracle(hip, packets, fmt, layout, pitch, offset=0, mode=0, sharp=False):
-    got = decode_steps(hip, [packets], [dict(layout=layout, pitch=pitch, offset=offset)], modes=[mode], sharp=[sharp])[0]
+    got = decode_steps(hip, [packets], Surfaces([dict(layout=layout, pitch=pitch, offset=offset)]), modes=[mode], sharp=[sharp])[0]
     want = planar_oracle(packets, mode, sharp)
-    same(in_layout(want, layout, fmt), got)
+    same_results(in_layout(want, layout, fmt), got)
     return want, got
 
 
@@ -257,12 +131,6 @@ def test_every_chroma_format(fmt, s):
 
 
 # ---- 4. saturated content -------------------------------------------------------------------------------------------------------------
-def content_stream(kind, w, h, qp):
-    packets = tuple(encode_stream(A.load_ref(), stream_frames(w, h, A.SUBSAMP_420, kind, n=3), w, h, A.SUBSAMP_420, eos=True, qp=qp, gop=2)[0])
-    packet_bound_holds(packets, w, h, A.SUBSAMP_420)
-    return packets
-
-
 # white and black lossless; the checkerboard at 66x34 and quantiser 30: finer, or smaller, the reference encoder's packets of this
 # content leave the bound inside which it is defined (tests/edge_cases.py)
 CONTENT = [("white", 16, 16, 100), ("white", 34, 18, 100), ("black", 16, 16, 100), ("black", 34, 18, 100), ("checker", 66, 34, 30)]
@@ -303,10 +171,10 @@ def test_draw_info_and_postsharp(layout, mode, sharp):
     assert all(not np.array_equal(a[2][0], b[2][0]) for a, b in zip(red_plain, red_want) if a[2] is not None)  # visible at half size
     assert npics(got) == 4
     first = next(i for i, r in enumerate(plain) if r[2] is not None)
-    once = decode_steps(hip, [packets], [dict(layout=lay, pitch=aligned, offset=0)], modes=[lambda t: mode if t <= first else 0],
+    once = decode_steps(hip, [packets], Surfaces([dict(layout=lay, pitch=aligned, offset=0)]), modes=[lambda t: mode if t <= first else 0],
                         sharp=[lambda t: sharp and t <= first])[0]
     mixed = [w_ if i <= first else p for i, (w_, p) in enumerate(zip(want, plain))]
-    same(in_layout(mixed, lay, "420"), once)
+    same_results(in_layout(mixed, lay, "420"), once)
 
 
 # ---- 6. one mixed step ---------------------------------------------------------------------------------------------------------------
@@ -321,12 +189,12 @@ def mixed_step(hip):
              dict(layout=SEMI | QUARTER, pitch=tight, offset=0)]           # joins two steps late: no metadata beside decoders with pictures
     delay = [0, 0, 0, 0, 2]
     reset_all(hip)
-    got = decode_steps(hip, streams, specs, delay=delay)
+    got = decode_steps(hip, streams, Surfaces(specs), delay=delay)
     assert scale_forms(hip)[1] >= 4  # (the half-size planar surface at an odd address forces its rounds' general form)
     for k, (pk, spec, fmt) in enumerate(zip(streams, specs, fmts)):
-        alone = decode_steps(hip, [pk], [spec])[0]
-        same(alone, got[k])  # every output equals its single-decoder result
-        same(in_layout(planar_oracle(pk), spec["layout"], fmt), got[k])
+        alone = decode_steps(hip, [pk], Surfaces([spec]))[0]
+        same_results(alone, got[k])  # every output equals its single-decoder result
+        same_results(in_layout(planar_oracle(pk), spec["layout"], fmt), got[k])
 
 
 def test_mixed_scales_layouts_and_geometries_in_one_step():
@@ -504,13 +372,13 @@ def test_refused_calls_consume_nothing(layout):
             pic = rets[i] == A.DEC_OK and had_meta[i]
             got[i].append((rets[i], fns[i] if pic else None, surfs[i].planes() if pic else None))
     for i in range(2):
-        same(want, got[i])
+        same_results(want, got[i])
         hip.dsv_dec_free(C.byref(decs[i]))
 
 
 def test_the_encoder_still_refuses_a_scaled_layout():
     """dsv2hip_enc_surface_frame / _batch_surface know no scale: such a layout is an unknown value, refused with the encoder untouched"""
-    hip = bind_enc(bind(A.load_hip()))
+    hip = bind(A.load_hip())
     w, h = 32, 24
     enc = A.ENCODER()
     configure_encoder(hip, enc, A.mk_meta(w, h, A.SUBSAMP_420), qp=50, gop=48)
@@ -534,7 +402,7 @@ def test_half_size_nv12_goes_straight_into_an_encoder_of_the_reduced_geometry():
     """A 64x48 4:2:0 stream decoded at half size into a pitched NV12 device surface whose pointers and pitches go straight to
     dsv2hip_enc_surface_frame of a 32x24 encoder: the packets are the reference encoder's on the host copy of the same reduced
     planes."""
-    ref, hip = A.load_ref(), bind_enc(bind(A.load_hip()))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, layout = 64, 48, SEMI | HALF
     packets = stream(w, h, "420", 4, 4)
     reduced = [B.reduce_picture(pl[0], pl[1], pl[2], 1) for _, _, pl in planar_oracle(packets) if pl is not None]

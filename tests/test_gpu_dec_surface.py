@@ -4,7 +4,6 @@ decoder's pictures, bit for bit -- both forms of the chroma interleave, every ch
 draw_info and postsharp, both parsers, mixed surfaces and geometries in one step -- no byte outside the rows is written, a
 refused call consumes nothing, and the surfaces feed dsv2hip_enc_batch_surface without a host copy."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -12,183 +11,38 @@ import torch
 
 import dsvabi as A
 from codec_run import configure_encoder, encode_stream
-from test_gpu_dec_device_out import bind as bind_device, format_stream, lockstep, mk_buf, npics, same_results
-from test_gpu_dec_drawinfo import decode, stream
-from test_gpu_dec_postsharp import expected as expected_sharp
-from test_gpu_enc_surface import SURFACE, bind as bind_enc
-from test_gpu_formats import FMT as FMT5
-from test_oracle_fmt import chroma_dims, orc_to420
+import dec_out as D
+import yuv_rgb as Q
+from codec_run import FMT as FMT5
+from dec_out import (OutSurf, Surfaces, aligned, chroma_dims, decode, decode_steps, device_decode, expected_dims, expected_sharp, frame_decode, in_layout,
+                     npics, packets_of, plus1, same_results, stream, tight)
+from hipabi import EIGHTH, HALF, OUTSURF, PLANAR, QUARTER, SEMI, SURFACE, bind, dec_uv_forms as forms, mk_buf, surface_dims
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
-PLANAR, SEMI = 0, 1
-GUARD = 0xA5
-LEAD = 64  # guard bytes in front of and behind every plane
-NO_FN = 0xFFFFFFFF
-
-
-class OUTSURF(C.Structure):
-    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("cap", C.c_size_t * 3), ("layout", C.c_int)]
-
-
-def bind(hip):
-    P = C.POINTER
-    bind_device(hip)
-    hip.dsv2hip_dec_surface_dims.argtypes = [P(A.DECODER), C.c_int, P(C.c_size_t), P(C.c_int)]
-    hip.dsv2hip_dec_surface_dims.restype = C.c_int
-    hip.dsv2hip_dec_batch_surface.argtypes = [C.c_int, P(P(A.DECODER)), P(A.BUF), P(OUTSURF), P(C.c_uint32), P(C.c_int)]
-    hip.dsv2hip_dec_batch_surface.restype = C.c_int
-    hip.dsv2hip_dec_surface_frame.argtypes = [P(A.DECODER), P(A.BUF), P(OUTSURF), P(C.c_uint32)]
-    hip.dsv2hip_dec_surface_frame.restype = C.c_int
-    hip.dsv2hip_dec_surface_stats.argtypes = [P(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_dec_surface_stats.restype = None
-    return hip
-
-
-def forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_dec_surface_stats(out, int(reset))
-    return out[0], out[1]
-
-
-def surface_dims(hip, dec, layout):
-    """[(row bytes, rows)] of the planes of `layout` as the decoder reports them, or None (no metadata yet)"""
-    rb, rows = (C.c_size_t * 3)(), (C.c_int * 3)()
-    if hip.dsv2hip_dec_surface_dims(C.byref(dec), layout, rb, rows) != 0:
-        return None
-    return [(rb[c], rows[c]) for c in range(3)]
+PITCH = {"tight": tight, "align256": lambda rb: (rb + 255) // 256 * 256, "plus3": lambda rb: rb + 3}
 
 
 def dims_of(subsamp, w, h, layout):
-    """the same from the format: dsv_mk_frame's plane sizes"""
-    cw, ch = chroma_dims(subsamp, w, h)
-    return [(w, h), (2 * cw, ch), (0, 0)] if layout == SEMI else [(w, h), (cw, ch), (cw, ch)]
+    """the plane sizes of a picture of the format: dsv_mk_frame's"""
+    return expected_dims(A.mk_meta(w, h, subsamp), layout)
 
 
-PITCH = {"tight": lambda rb: rb, "align256": lambda rb: (rb + 255) // 256 * 256, "plus3": lambda rb: rb + 3}
-
-
-class Surf:
-    """One decoder's surface: per plane a tensor of LEAD guard bytes, `offset` more, rows `pitch` apart (the last one without
-    padding), LEAD guard bytes; cap[c] is exactly what the rows need."""
-
-    def __init__(self, dims, layout, pitch, offset):
-        self.layout, self.dims = layout, [d for d in dims if d[1]]
-        self.c = OUTSURF()
-        self.c.layout = layout
-        self.t, self.inside, self.start, self.pitches = [], [], LEAD + offset, []
-        for i, (rb, rows) in enumerate(self.dims):
-            p = PITCH[pitch](rb)
-            need = (rows - 1) * p + rb
-            t = torch.empty(self.start + need + LEAD, dtype=torch.uint8, device="cuda")
-            assert t.data_ptr() % 16 == 0
-            mask = np.zeros(t.numel(), dtype=bool)
-            for y in range(rows):
-                mask[self.start + y * p:self.start + y * p + rb] = True
-            self.t.append(t)
-            self.inside.append(mask)
-            self.pitches.append(p)
-            self.c.plane[i], self.c.pitch[i], self.c.cap[i] = t.data_ptr() + self.start, p, need
-
-    def arm(self):
-        for t in self.t:
-            t.fill_(GUARD)
-
-    def planes(self):
-        """the delivered planes (semiplanar: [Y, UV]); asserts that every byte outside the rows still holds the guard value"""
-        out = []
-        for t, mask, (rb, rows), p in zip(self.t, self.inside, self.dims, self.pitches):
-            a = t.cpu().numpy()
-            assert np.all(a[~mask] == GUARD), "bytes outside the rows were written"
-            out.append(np.stack([a[self.start + y * p:self.start + y * p + rb] for y in range(rows)]))
-        return out
-
-    def untouched(self):
-        return all(bool(torch.all(t == GUARD)) for t in self.t)
-
-
-def surface_decode(hip, streams, specs, modes=None, out420p=None, sharp=None):
-    """Lockstep steps over one decoder per stream, pictures delivered into surfaces: spec = dict(layout, pitch, offset) per stream.
-    Per stream: [(return code, frame number or None, planes or None)] per packet, as test_gpu_dec_device_out.device_decode gives,
-    the planes those of the layout ([Y, U, V] or [Y, UV]).  modes / sharp entries may be functions of the packet's index."""
-    bind(hip)
-    n = len(streams)
-    modes, out420p, sharp = modes or [0] * n, out420p or [False] * n, sharp or [False] * n
-    decs = [A.DECODER() for _ in range(n)]
-    for d, o in zip(decs, out420p):
-        if o:
-            assert hip.dsv2hip_dec_set_out420p(C.byref(d), 1) == 0
-    surfs = [None] * n
-    res = [[] for _ in range(n)]
-    done = [False] * n
-    for t in range(max(len(s) for s in streams)):
-        live = [k for k in range(n) if t < len(streams[k]) and not done[k]]
-        m = len(live)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k in live])
-        bufs, arr, had_meta = (A.BUF * m)(), (OUTSURF * m)(), []
-        for i, k in enumerate(live):
-            decs[k].draw_info = modes[k](t) if callable(modes[k]) else modes[k]
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k](t) if callable(sharp[k]) else sharp[k])) == 0
-            mk_buf(hip, bufs[i], streams[k][t])
-            dims = surface_dims(hip, decs[k], specs[k]["layout"])
-            had_meta.append(dims is not None)
-            if dims is None:
-                assert decs[k].got_metadata == 0  # (its entry stays all zeros)
-                continue
-            md = decs[k].vidmeta
-            assert dims == dims_of(A.SUBSAMP_420 if out420p[k] else md.subsamp, md.width, md.height, specs[k]["layout"])
-            if surfs[k] is None:
-                surfs[k] = Surf(dims, **specs[k])
-            surfs[k].arm()
-            arr[i] = surfs[k].c
-        fns, rets = (C.c_uint32 * m)(), (C.c_int * m)()
-        torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        assert hip.dsv2hip_dec_batch_surface(m, decp, bufs, arr, fns, rets) == m
-        for i, k in enumerate(live):
-            planes = None
-            if surfs[k] is not None and had_meta[i]:
-                if rets[i] == A.DEC_OK:
-                    planes = surfs[k].planes()  # (guards checked after every step)
-                else:
-                    assert surfs[k].untouched()
-            if planes is None and rets[i] == A.DEC_OK:
-                assert fns[i] == NO_FN
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-            done[k] = rets[i] == A.DEC_EOS
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res
-
-
-def interleave(u, v):
-    return np.stack([u, v], axis=-1).reshape(u.shape[0], 2 * u.shape[1])
-
-
-def in_layout(results, layout):
-    """reference results ([Y, U, V] per picture) as the planes of `layout`"""
-    if layout == PLANAR:
-        return results
-    return [(code, fn, None if pl is None else [pl[0], interleave(pl[1], pl[2])]) for code, fn, pl in results]
+def named(specs):
+    """Surfaces over spec = dict(layout, pitch, offset) per stream, the pitch by its name in PITCH"""
+    return Surfaces([dict(sp, pitch=PITCH[sp["pitch"]]) for sp in specs])
 
 
 def same(want, got, layout):
-    same_results(in_layout(want, layout), got, planes=(0, 1) if layout == SEMI else (0, 1, 2))
+    same_results(in_layout(want, layout), got)
 
 
-def packets_of(w, h, fmt, nfr, gop=48):
-    return stream(w, h, fmt, nfr, gop) if fmt in ("420", "444") else format_stream(fmt, w, h, nfr)
-
-
-@functools.lru_cache(maxsize=None)
 def reference(w, h, fmt, nfr, gop=48, to420=False):
-    """the reference decoder's results on the stream (shared, never modified); to420: chroma through the oracle's -out420p chain"""
-    want = decode(A.load_ref(), packets_of(w, h, fmt, nfr, gop), 0)
+    """the reference decoder's results on the stream (dec_out.reference: shared, never modified); to420: chroma through the oracle's
+    -out420p chain"""
+    want = D.reference(packets_of(w, h, fmt, nfr, gop), to420=(FMT5[fmt][0], w, h) if to420 else None)
     assert npics(want) == nfr and want[0][0] == A.DEC_GOT_META and want[-1][0] == A.DEC_EOS
-    if to420:
-        orc = A.load_oracle()
-        want = [(code, fn, None if pl is None else [pl[0]] + [orc_to420(orc, np.ascontiguousarray(pl[c]), FMT5[fmt][0], w, h) for c in (1, 2)])
-                for code, fn, pl in want]
-    return tuple(want)
+    return want
 
 
 def is_wide(row_bytes, pitch, offset):
@@ -210,7 +64,7 @@ def test_equals_reference_and_writes_nothing_else(w, h, fmt, nfr, gop, layout, p
     if gop == 4:
         assert len(packets) > nfr + 2  # (a metadata packet per GOP: I and P pictures both occur)
     forms(hip, reset=True)
-    got = surface_decode(hip, [packets], [dict(layout=layout, pitch=pitch, offset=offset)])[0]
+    got = decode_steps(hip, [packets], named([dict(layout=layout, pitch=pitch, offset=offset)]))[0]
     same(reference(w, h, fmt, nfr, gop), got, layout)
     if layout == PLANAR:
         assert forms(hip) == (0, 0)
@@ -228,7 +82,7 @@ def test_equals_reference_and_writes_nothing_else(w, h, fmt, nfr, gop, layout, p
 @pytest.mark.parametrize("fmt", ["422", "411", "410"])
 def test_other_chroma_formats(fmt, layout):
     hip = bind(A.load_hip())
-    got = surface_decode(hip, [packets_of(330, 250, fmt, 3)], [dict(layout=layout, pitch="plus3", offset=0)])[0]
+    got = decode_steps(hip, [packets_of(330, 250, fmt, 3)], named([dict(layout=layout, pitch="plus3", offset=0)]))[0]
     same(reference(330, 250, fmt, 3), got, layout)
 
 
@@ -240,7 +94,7 @@ def test_out420p_into_nv12(w, h, fmt, pitch):
     both (354 -> 177 pairs from 354 samples, 330x250 -> 165 x 125 from 165 / 83 wide, 250 / 63 tall planes)."""
     hip = bind(A.load_hip())
     forms(hip, reset=True)
-    got = surface_decode(hip, [packets_of(w, h, fmt, 3)], [dict(layout=SEMI, pitch=pitch, offset=0)], out420p=[True])[0]
+    got = decode_steps(hip, [packets_of(w, h, fmt, 3)], named([dict(layout=SEMI, pitch=pitch, offset=0)]), out420p=[True])[0]
     same(reference(w, h, fmt, 3, to420=True), got, SEMI)
     assert got[1][2][1].shape == ((h + 1) // 2, 2 * ((w + 1) // 2))
     assert forms(hip) == (0, 3)  # (odd row bytes / 2: 354 and 330 are no multiples of 16)
@@ -258,7 +112,7 @@ def test_draw_info_and_postsharp_into_pitched_nv12(every):
     sharp = True if every else (lambda k: k % 2 == 1)
     want = expected_sharp(ref, packets, mode=mode, sharp=sharp)
     plain = reference(352, 288, "420", 9, 4)
-    got = surface_decode(hip, [packets], [dict(layout=SEMI, pitch="align256", offset=0)], modes=[mode], sharp=[sharp])[0]
+    got = decode_steps(hip, [packets], named([dict(layout=SEMI, pitch="align256", offset=0)]), modes=[mode], sharp=[sharp])[0]
     same(want, got, SEMI)
     same_results(in_layout(plain, SEMI), got, planes=(1,))  # chroma: the undrawn decode's
     touched = [k for k, (a, b) in enumerate(zip(plain, got)) if a[2] is not None and not np.array_equal(a[2][0], b[2][0])]
@@ -272,7 +126,7 @@ def mixed_step(hip):
     cif, c444, hd = stream(352, 288, "420", 9, 4), stream(354, 290, "444", 3, 48), stream(1280, 720, "420", 3, 48)
     specs = [dict(layout=PLANAR, pitch="tight", offset=0), dict(layout=SEMI, pitch="align256", offset=0),
              dict(layout=SEMI, pitch="plus3", offset=1), dict(layout=PLANAR, pitch="align256", offset=0)]
-    got = surface_decode(hip, [cif, cif, c444, hd], specs, out420p=[False, False, True, False])
+    got = decode_steps(hip, [cif, cif, c444, hd], named(specs), out420p=[False, False, True, False])
     same(reference(352, 288, "420", 9, 4), got[0], PLANAR)
     same(reference(352, 288, "420", 9, 4), got[1], SEMI)
     same(reference(354, 290, "444", 3, to420=True), got[2], SEMI)
@@ -300,11 +154,10 @@ def test_mixed_surfaces_and_geometries_in_one_step_device_parser():
 def test_packed_equals_planar_tight(w, h, fmt, out420p):
     """dsv2hip_dec_batch_device and dsv2hip_dec_batch_surface with pitch {w, cw, cw} on the same packets; the sizes
     dsv2hip_dec_surface_dims reports add up to dsv2hip_dec_picture_bytes."""
-    from test_gpu_dec_device_out import device_decode
     hip = bind(A.load_hip())
     packets = packets_of(w, h, fmt, 3)
     packed = device_decode(hip, [packets], out420p=[out420p])[0]
-    got = surface_decode(hip, [packets], [dict(layout=PLANAR, pitch="tight", offset=0)], out420p=[out420p])[0]
+    got = decode_steps(hip, [packets], named([dict(layout=PLANAR, pitch="tight", offset=0)]), out420p=[out420p])[0]
     assert npics(packed) == 3
     same_results(packed, got)
     dec = A.DECODER()
@@ -377,7 +230,7 @@ def test_refused_calls_consume_nothing(layout):
     assert rets[0] == A.DEC_GOT_META and dec.got_metadata == 1
     dims = surface_dims(hip, dec, layout)
     assert dims == dims_of(A.SUBSAMP_420, 352, 288, layout)
-    surf = Surf(dims, layout, "align256", 0)
+    surf = OutSurf(dims, layout, PITCH["align256"], 0)
     surf.arm()
     torch.cuda.synchronize()
     mk_buf(hip, bufs[0], packets[1])
@@ -423,7 +276,7 @@ def test_transcode_through_surfaces_without_the_host():
     """Two CIF streams decoded into pitched NV12 surfaces whose pointers and pitches go straight to dsv2hip_enc_batch_surface: the
     packets are the reference encoder's on the reference decoder's pictures.  dsv2hip_dec_surface_frame gives the batch call's
     pictures."""
-    ref, hip = A.load_ref(), bind_enc(bind(A.load_hip()))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, ns = 352, 288, 2
     streams = [stream(w, h, "420", 5, 4, seed=70 + s) for s in range(ns)]
     refpics = [[r for r in decode(ref, pk, 0) if r[2] is not None] for pk in streams]
@@ -433,7 +286,7 @@ def test_transcode_through_surfaces_without_the_host():
     encs, decs = [A.ENCODER() for _ in range(ns)], [A.DECODER() for _ in range(ns)]
     for e in encs:
         configure_encoder(hip, e, meta, qp=50, gop=48)
-    surfs = [Surf(dims_of(A.SUBSAMP_420, w, h, SEMI), SEMI, "align256", 0) for _ in range(ns)]
+    surfs = [OutSurf(dims_of(A.SUBSAMP_420, w, h, SEMI), SEMI, PITCH["align256"], 0) for _ in range(ns)]
 
     def as_input(sf):
         c = SURFACE()
@@ -483,7 +336,7 @@ def test_transcode_through_surfaces_without_the_host():
     # one decoder, one call per packet
     dec = A.DECODER()
     one = []
-    sf = Surf(dims_of(A.SUBSAMP_420, w, h, SEMI), SEMI, "align256", 0)
+    sf = OutSurf(dims_of(A.SUBSAMP_420, w, h, SEMI), SEMI, PITCH["align256"], 0)
     sf.arm()
     torch.cuda.synchronize()
     for pk in streams[0]:
@@ -503,44 +356,6 @@ def test_transcode_through_surfaces_without_the_host():
 
 
 # ---- 9. every way out side by side -------------------------------------------------------------------------------------------
-def frame_decode(hip, streams, modes, sharp, out420p=None, schedule=None, single=False):
-    """dsv2hip_dec_batch over one decoder per stream into pinned frames, draw_info, postsharp and out420p per decoder: per stream
-    [(return code, frame number or None, [Y, U, V] or None)] per packet.  schedule: test_gpu_dec_device_out.lockstep()'s; single:
-    one dsv_dec per packet in place of the step's batch call."""
-    from test_gpu_dec_batch import bind as bind_batch, planes_of
-    bind_batch(bind(hip))
-    n = len(streams)
-    decs = [A.DECODER() for _ in range(n)]
-    for d, mode, s in zip(decs, modes, sharp):
-        d.draw_info = mode
-        assert hip.dsv2hip_dec_set_postsharp(C.byref(d), int(s)) == 0
-    for d, o in zip(decs, out420p or ()):
-        assert hip.dsv2hip_dec_set_out420p(C.byref(d), int(o)) == 0
-    res = [[] for _ in range(n)]
-    for step in lockstep(streams, schedule):
-        m = len(step)
-        decp = (C.POINTER(A.DECODER) * m)(*[C.pointer(decs[k]) for k, _ in step])
-        bufs, outs, fns, rets = (A.BUF * m)(), (C.POINTER(A.FRAME) * m)(), (C.c_uint32 * m)(), (C.c_int * m)()
-        for i, (k, t) in enumerate(step):
-            mk_buf(hip, bufs[i], streams[k][t])
-        if single:
-            for i in range(m):
-                fp, fn = C.POINTER(A.FRAME)(), C.c_uint32(0)
-                rets[i] = hip.dsv_dec(decp[i], C.byref(bufs[i]), C.byref(fp), C.byref(fn))
-                outs[i], fns[i] = fp, fn.value
-        else:
-            assert hip.dsv2hip_dec_batch(m, decp, bufs, outs, fns, rets) == m
-        for i, (k, _) in enumerate(step):
-            planes = None
-            if rets[i] == A.DEC_OK and outs[i]:
-                planes = planes_of(outs[i])
-                hip.dsv_frame_ref_dec(outs[i])
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res
-
-
 def test_every_delivery_in_one_round():
     """Ten decoders of one geometry (66x34 4:2:0) on the same I P P stream, one lockstep step per picture, each with another way out:
     pinned frames (plain, sharpened, drawn on and sharpened), the packed device buffer, a planar surface at an odd pitch and address,
@@ -549,10 +364,6 @@ def test_every_delivery_in_one_round():
     settings delivers alone, which the tests above and those of the other ways out pin to the reference.  The ABI has one entry
     point per kind of destination, so a step is three calls: the three pinned frames share a round, the six surfaces share one,
     and the packed buffer has its own.  This guards the packing of several pictures' jobs into one round's tables."""
-    from test_gpu_dec_device_out import device_decode
-    from test_gpu_dec_rgb import aligned, plus1, tight
-    from test_gpu_dec_scale import BGRA709, EIGHTH, HALF, QUARTER, decode_steps
-    import yuv_rgb as Q
     hip = bind(A.load_hip())
     packets = stream(66, 34, "420", 3, 48, seed=71)
     assert [pk[5] & 1 for pk in packets if pk[5] & 0x04] == [0, 1, 1]  # (dsv.h: packet type at byte 5, picture = 0x04, bit 0 = predicted)
@@ -560,7 +371,7 @@ def test_every_delivery_in_one_round():
     surfaces = [(dict(layout=PLANAR, pitch=plus1, offset=1), 0, False),
                 (dict(layout=SEMI, pitch=aligned, offset=0), 0, False),
                 (dict(layout=SEMI | HALF, pitch=tight, offset=0), 7, True),
-                (dict(layout=BGRA709, pitch=aligned, offset=0), 0, False),
+                (dict(layout=Q.BGRA | Q.BT709, pitch=aligned, offset=0), 0, False),
                 (dict(layout=Q.RGBA | QUARTER, pitch=tight, offset=0), 0, True),
                 (dict(layout=PLANAR | EIGHTH, pitch=tight, offset=0), 0, False)]
 
@@ -568,7 +379,7 @@ def test_every_delivery_in_one_round():
         """the three calls of a step sequence over the chosen decoders of each kind"""
         return (frame_decode(hip, [packets] * len(fr), [m for m, _ in fr], [s for _, s in fr]) if fr else [],
                 device_decode(hip, [packets]) if packed else [],
-                decode_steps(hip, [packets] * len(sf), [spec for spec, _, _ in sf], modes=[m for _, m, _ in sf], sharp=[s for _, _, s in sf]) if sf else [])
+                decode_steps(hip, [packets] * len(sf), Surfaces([spec for spec, _, _ in sf]), modes=[m for _, m, _ in sf], sharp=[s for _, _, s in sf]) if sf else [])
 
     got_frames, got_packed, got_surfaces = steps(frames, True, surfaces)
     assert all(npics(r) == 3 for r in got_frames + got_packed + got_surfaces)

@@ -7,7 +7,6 @@ the rows is written, a refused call touches nothing, the statistics count what t
 a DSV2HIP_SURFACE_RGBP surface without a host copy.  Float planes are read back through torch as integers of the element's width and
 compared as bit patterns."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -17,205 +16,22 @@ import dsvabi as A
 import rgb3_csc as R3
 import tensor_out as T
 import yuv_rgb as Q
-from codec_run import configure_encoder, encode_stream
+from codec_run import FMT, configure_encoder, encode_stream
 from edge_cases import stream_inverse_is_undefined
-from test_gpu_dec_device_out import format_stream, lockstep, mk_buf, npics
-from test_gpu_dec_drawinfo import decode, stream
-from test_gpu_dec_postsharp import ref_sharpen
-from test_gpu_dec_resize import bind as bind_sized
-from test_gpu_dec_resize import reset_every, resize_forms, sized_dims
-from test_gpu_dec_rgb import planar_oracle, rgb_forms, saturated_stream
-from test_gpu_dec_surface import GUARD, LEAD, NO_FN
-from test_gpu_enc_rgb import bind as bind_enc
-from test_gpu_enc_surface import SURFACE
-from test_gpu_formats import FMT
+from dec_out import (OutTensor, Tensors, aligned, decode_steps, format_stream, npics, planar_oracle, plus1, reference, saturated_stream, stream,
+                     tensor_expected as expected, tight)
+from hipabi import (OUTTENSOR, SURFACE, bind, dec_resize_forms as resize_forms, dec_rgb_forms as rgb_forms, dec_tensor_forms as tensor_forms, mk_buf,
+                    reset_dec_forms as reset_forms, sized_dims, tensor_dims)
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
 DECP = C.POINTER(A.DECODER)
-TORCH_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32}
-
-
-class OUTTENSOR(C.Structure):
-    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("cap", C.c_size_t * 3), ("dtype", C.c_int), ("csc", C.c_int), ("out_w", C.c_int),
-                ("out_h", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
-
-
-def bind(hip):
-    bind_sized(hip)
-    hip.dsv2hip_dec_tensor_dims.argtypes = [DECP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
-    hip.dsv2hip_dec_tensor_dims.restype = C.c_int
-    hip.dsv2hip_dec_batch_tensor.argtypes = [C.c_int, C.POINTER(DECP), C.POINTER(A.BUF), C.POINTER(OUTTENSOR), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
-    hip.dsv2hip_dec_batch_tensor.restype = C.c_int
-    hip.dsv2hip_dec_tensor_frame.argtypes = [DECP, C.POINTER(A.BUF), C.POINTER(OUTTENSOR), C.POINTER(C.c_uint32)]
-    hip.dsv2hip_dec_tensor_frame.restype = C.c_int
-    hip.dsv2hip_dec_tensor_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_dec_tensor_stats.restype = None
-    return hip
-
-
-def tensor_forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_dec_tensor_stats(out, int(reset))
-    return out[0], out[1]
-
-
-def reset_forms(hip):
-    reset_every(hip)
-    tensor_forms(hip, reset=True)
-
-
-def tensor_dims(hip, dec, dtype, ow=0, oh=0):
-    """(row bytes, rows) of one plane as the decoder reports them, or None"""
-    rb, rows = C.c_size_t(0), C.c_int(0)
-    if hip.dsv2hip_dec_tensor_dims(C.byref(dec) if dec is not None else None, dtype, ow, oh, C.byref(rb), C.byref(rows)) != 0:
-        return None
-    return rb.value, rows.value
-
-
-def tight(rb, elem):
-    return rb
-
-
-def plus1(rb, elem):
-    return rb + elem
-
-
-def aligned(rb, elem):
-    return (rb + 15) // 16 * 16 + 16
 
 
 def spec(dtype, csc=0, pitch=tight, offset=0, consts=T.UNIT, size=None):
     """a tensor: element type, CSC bits, pitch as a function of (row bytes, element size), pointer offset in ELEMENTS behind a 16-byte
     boundary, (scale[3], bias[3]), delivered size or None"""
     return dict(dtype=dtype, csc=csc, pitch=pitch, offset=offset, consts=consts, size=size)
-
-
-class OutTensor:
-    """One decoder's tensor: the three planes in ONE allocation of bytes -- LEAD guard bytes, `offset` elements more, then per plane its
-    rows pitch apart (the last one without padding) and at least LEAD guard bytes up to the next plane, which starts at the same offset
-    behind a 16-byte boundary; cap[c] is exactly what the rows need."""
-
-    def __init__(self, dims, dtype, csc, pitch, offset, consts, size):
-        rb, rows = dims
-        self.dtype, self.elem, self.rb, self.rows = dtype, T.ELEM[dtype], rb, rows
-        self.p = pitch(rb, self.elem)
-        need = (rows - 1) * self.p + rb
-        apart = (need + 15) // 16 * 16 + LEAD
-        self.starts = [LEAD + offset * self.elem + c * apart for c in range(3)]
-        self.t = torch.empty(self.starts[2] + need + LEAD, dtype=torch.uint8, device="cuda")
-        assert self.t.data_ptr() % 16 == 0
-        self.inside = np.zeros(self.t.numel(), dtype=bool)
-        self.c = OUTTENSOR()
-        self.c.dtype, self.c.csc = dtype, csc
-        self.c.out_w, self.c.out_h = size or (0, 0)
-        for c, start in enumerate(self.starts):
-            for y in range(rows):
-                self.inside[start + y * self.p:start + y * self.p + rb] = True
-            self.c.plane[c], self.c.pitch[c], self.c.cap[c] = self.t.data_ptr() + start, self.p, need
-            self.c.scale[c], self.c.bias[c] = consts[0][c], consts[1][c]
-
-    def wide(self):
-        """include/dsv2_hip.h at dsv2hip_dec_tensor_stats: pointers and pitch multiples of four elements, width of 4"""
-        return all(s % (4 * self.elem) == 0 for s in self.starts) and self.p % (4 * self.elem) == 0 and (self.rb // self.elem) % 4 == 0
-
-    def arm(self):
-        self.t.fill_(GUARD)
-
-    def planes(self):
-        """[R, G, B] as bit patterns (tensor_out.BITS), read back through torch as integers of the element's width; asserts that
-        every byte outside the rows -- in front, in the padding, between the planes, behind the last row -- still holds the guard"""
-        a = self.t.cpu().numpy()
-        assert np.all(a[~self.inside] == GUARD), "bytes outside the rows were written"
-        out = []
-        for start in self.starts:
-            rows = torch.as_strided(self.t, (self.rows, self.rb), (self.p, 1), start).contiguous()
-            out.append(rows.view(TORCH_INT[self.elem]).cpu().numpy().view(T.BITS[self.dtype]))
-        return out
-
-    def untouched(self):
-        return bool(torch.all(self.t == GUARD))
-
-
-def decode_steps(hip, streams, specs, modes=None, sharp=None, delay=None, single=False):
-    """Lockstep steps over one decoder per stream, pictures delivered into tensors (spec() per stream).  Per stream: [(return code,
-    frame number or None, [R, G, B] or None)] per packet.  The reported sizes and the guards are checked at every step.  single: one
-    dsv2hip_dec_tensor_frame per packet in place of the step's batch call.  Returns (results, the tensors)."""
-    bind(hip)
-    n = len(streams)
-    modes, sharp = modes or [0] * n, sharp or [False] * n
-    decs = [A.DECODER() for _ in range(n)]
-    tens = [None] * n
-    res = [[] for _ in range(n)]
-    done = [False] * n
-    for step in lockstep(streams, None, delay):
-        pkt = {k: t for k, t in step if not done[k]}
-        live = list(pkt)
-        m = len(live)
-        decp = (DECP * m)(*[C.pointer(decs[k]) for k in live])
-        bufs, arr, had_meta = (A.BUF * m)(), (OUTTENSOR * m)(), []
-        for i, k in enumerate(live):
-            decs[k].draw_info = modes[k]
-            assert hip.dsv2hip_dec_set_postsharp(C.byref(decs[k]), int(sharp[k])) == 0
-            mk_buf(hip, bufs[i], streams[k][pkt[k]])
-            dims = tensor_dims(hip, decs[k], specs[k]["dtype"], *(specs[k]["size"] or (0, 0)))
-            had_meta.append(dims is not None)
-            if dims is None:
-                assert decs[k].got_metadata == 0  # (its entry stays all zeros)
-                continue
-            ow, oh = specs[k]["size"] or (decs[k].vidmeta.width, decs[k].vidmeta.height)
-            assert dims == (ow * T.ELEM[specs[k]["dtype"]], oh)
-            if tens[k] is None:
-                tens[k] = OutTensor(dims, **specs[k])
-            tens[k].arm()
-            arr[i] = tens[k].c
-        fns, rets = (C.c_uint32 * m)(), (C.c_int * m)()
-        torch.cuda.synchronize()  # (the guard fills run on torch's stream, the decoder on its own)
-        if single:
-            for i in range(m):
-                fn = C.c_uint32(0)
-                rets[i] = hip.dsv2hip_dec_tensor_frame(decp[i], C.byref(bufs[i]), C.byref(arr[i]), C.byref(fn))
-                fns[i] = fn.value
-        else:
-            assert hip.dsv2hip_dec_batch_tensor(m, decp, bufs, arr, fns, rets) == m
-        for i, k in enumerate(live):
-            planes = None
-            if tens[k] is not None and had_meta[i]:
-                if rets[i] == A.DEC_OK:
-                    planes = tens[k].planes()  # (guards checked after every step)
-                else:
-                    assert tens[k].untouched()
-            if planes is None and rets[i] == A.DEC_OK:
-                assert fns[i] == NO_FN
-            res[k].append((rets[i], fns[i] if planes is not None else None, planes))
-            done[k] = rets[i] == A.DEC_EOS
-    for d in decs:
-        hip.dsv_dec_free(C.byref(d))
-    return res, tens
-
-
-@functools.lru_cache(maxsize=None)
-def reference(packets, mode=0, sharp=False):
-    """the REFERENCE decoder's results on the packets (shared, never modified): [(return code, frame number, [Y, U, V] or None)], drawn on
-    by the reference under `mode`, the luma then sharpened by the reference's dsv_post_process under `sharp`"""
-    ref = A.load_ref()
-    out = []
-    for code, fn, pl in decode(ref, packets, mode):
-        if pl is not None:
-            pl = [np.ascontiguousarray(p) for p in pl]
-            if sharp:
-                pl[0] = ref_sharpen(ref, pl[0])
-            for p in pl:
-                p.setflags(write=False)
-        out.append((code, fn, pl))
-    return tuple(out)
-
-
-def expected(results, fmt, sp):
-    """reference results as the tensor of spec `sp`"""
-    _, hs, vs = FMT[fmt]
-    return [(code, fn if pl is not None else None, None if pl is None else T.tensor(pl[0], pl[1], pl[2], sp["csc"], hs, vs, sp["dtype"], sp["consts"][0], sp["consts"][1], sp["size"]))
-            for code, fn, pl in results]
 
 
 def same(want, got, what=""):
@@ -234,11 +50,12 @@ def same(want, got, what=""):
 def equals_reference(hip, packets, fmt, specs, mode=0, sharp=False, single=False):
     """one decoder per spec, all on the same packets, in one step sequence"""
     n = len(specs)
-    got, tens = decode_steps(hip, [packets] * n, specs, modes=[mode] * n, sharp=[sharp] * n, single=single)
+    to = Tensors(specs)
+    got = decode_steps(hip, [packets] * n, to, modes=[mode] * n, sharp=[sharp] * n, single=single)
     ref = reference(packets, mode, sharp)
     for k, sp in enumerate(specs):
         same(expected(ref, fmt, sp), got[k], "%s %s" % (T.NAMES[sp["dtype"]], fmt))
-    return ref, got, tens
+    return ref, got, to.held
 
 
 CONSTS = {T.U8: T.UNIT, T.F16: T.IMAGENET, T.BF16: T.IMAGENET, T.F32: T.IMAGENET}
@@ -294,7 +111,7 @@ def test_rows_of_more_than_one_pass_one_block_high():
     own = planar_oracle(packets)
     for pitch in (tight, plus1):
         specs = [spec(dt, Q.BT709, pitch, 0, CONSTS[dt]) for dt in T.DTYPES]
-        got, _ = decode_steps(hip, [packets] * 4, specs)
+        got = decode_steps(hip, [packets] * 4, Tensors(specs))
         for k, sp in enumerate(specs):
             same(expected(own, "420", sp), got[k], T.NAMES[sp["dtype"]])
 
@@ -423,12 +240,12 @@ def mixed_step(hip):
              spec(T.F32, Q.BT709, plus1, 3, T.UNIT)]                # a late joiner
     delay = [0, 0, 0, 0, 0, 2]
     reset_forms(hip)
-    got, tens = decode_steps(hip, streams, specs, delay=delay)
+    got = decode_steps(hip, streams, Tensors(specs), delay=delay)
     assert tensor_forms(hip)[0] == 3  # 36x20: three rounds of aligned tensors; 34x18 (w % 4 == 2): always the general form
     assert tensor_forms(hip)[1] >= 3 and rgb_forms(hip) == (0, 0)
     for k, (pk, sp, fmt) in enumerate(zip(streams, specs, fmts)):
         same(expected(reference(pk), fmt, sp), got[k], "decoder %d" % k)
-        alone, _ = decode_steps(hip, [pk], [sp])
+        alone = decode_steps(hip, [pk], Tensors([sp]))
         same(alone[0], got[k], "decoder %d alone" % k)
 
 
@@ -616,7 +433,7 @@ def test_uint8_tensor_goes_straight_into_the_encoder_as_rgbp():
     """A stream decoded into a pitched uint8 tensor whose plane pointers and pitches go straight to dsv2hip_enc_surface_frame as a
     DSV2HIP_SURFACE_RGBP surface: the packets are the reference encoder's on the planar picture that the encoder's conversion
     (tests/rgb3_csc.py) defines on the oracle's bytes."""
-    ref, hip = A.load_ref(), bind_enc(bind(A.load_hip()))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, csc = 64, 48, Q.BT709
     packets = stream(w, h, "420", 4, 4)
     sp = spec(T.U8, csc, aligned, 0)

@@ -9,6 +9,7 @@ encoded through the plain call.
 The reference streams and the cases are tests/enc_resize_cases.py's; tests/test_ingest_resize_ref.py checks each stream's two
 conditions without a GPU."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -16,94 +17,46 @@ import torch
 
 import area_resize as AR
 import dsvabi as A
+import enc_in as EI
 import enc_resize_cases as K
 import ingest_resize as IR
 import rgb_csc as R
-import test_gpu_enc_scale as ES
-from codec_run import configure_encoder, encode_stream
+from codec_run import FMT, configure_encoder, encode_stream
 from edge_cases import packet_bound_holds
-from test_gpu_dec_device_out import mk_buf
-from test_gpu_dec_drawinfo import stream
-from test_gpu_dec_rgb import OutSurf, planar_oracle
-from test_gpu_dec_rgb import aligned as aligned_out
-from test_gpu_dec_rgb import bind as bind_dec
-from test_gpu_dec_resize import bind as bind_dec_sized
-from test_gpu_enc_rgb import encoders, rgb_content, rgb_forms
-from test_gpu_enc_surface import PLANAR, SEMI, SURFACE, content, copy_of, same_packets, take_packets
-from test_gpu_enc_surface import forms as yuv_forms
-from test_gpu_formats import FMT
+from dec_out import OutSurf, aligned as aligned_out, planar_oracle, stream
+from enc_in import content, copy_of, encode_steps, encoders, is_rgb, kind_of, rgb_content, same_packets, take_packets
+from hipabi import (HALF, PLANAR, SEMI, SURFACE, bind, enc_resize_forms as resize_forms, enc_rgb_forms as rgb_forms, enc_scale_forms as scale_forms,
+                    enc_yuv_forms as yuv_forms, mk_buf, reset_enc_forms as reset_all)
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
 CFG, NFR, SEED = K.CFG, K.NFR, K.SEED
 BGRA709, RGBAFULL, LAYOUTS, LAYOUT_IDS, VARIANTS = K.BGRA709, K.RGBAFULL, K.LAYOUTS, K.LAYOUT_IDS, K.VARIANTS
-is_rgb, kind_of = K.is_rgb, K.kind_of
 
 
-def bind(hip):
-    P = C.POINTER
-    ES.bind(hip)
-    hip.dsv2hip_enc_batch_surface_sized.argtypes = [C.c_int, P(P(A.ENCODER)), P(SURFACE), P(C.c_int), P(C.c_int), P(A.BUF), P(C.c_int)]
-    hip.dsv2hip_enc_batch_surface_sized.restype = C.c_int
-    hip.dsv2hip_enc_surface_frame_sized.argtypes = [P(A.ENCODER), P(SURFACE), C.c_int, C.c_int, P(A.BUF)]
-    hip.dsv2hip_enc_surface_frame_sized.restype = C.c_int
-    hip.dsv2hip_enc_sized_dims.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_size_t), P(C.c_int)]
-    hip.dsv2hip_enc_sized_dims.restype = C.c_int
-    hip.dsv2hip_enc_resize_stats.argtypes = [P(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_enc_resize_stats.restype = None
-    return hip
-
-
-def resize_forms(hip, reset=False):
-    out = (C.c_ulonglong * 4)()
-    hip.dsv2hip_enc_resize_stats(out, int(reset))
-    return tuple(out)
-
-
-def reset_all(hip):
-    resize_forms(hip, reset=True)
-    ES.reset_all(hip)
+sized_steps = functools.partial(encode_steps, nfr=NFR, call="dsv2hip_enc_batch_surface_sized")
 
 
 def source(sw, sh, name, layout, variant, t, offset=None, s=0):
     """picture t of the content made at sw x sh as a device surface; s: the scale value of its layout (0: a sized or plain entry)"""
     if is_rgb(layout):
-        return ES.rgb_source(rgb_content(sw, sh, NFR, SEED)[t], layout, s, variant, offset)
-    return ES.yuv_source(content(sw, sh, name, NFR, SEED)[t], sw, sh, name, layout, s, variant, offset)
+        return EI.rgb_source(rgb_content(sw, sh, NFR, SEED)[t], layout, s, variant, offset)
+    return EI.yuv_source(content(sw, sh, name, NFR, SEED)[t], sw, sh, name, layout, s, variant, offset)
 
 
 def documented_wide(sw, sh, name, layout, variant, offset=None):
     """include/dsv2_hip.h at dsv2hip_enc_resize_stats: YUV -- every sized source plane's pointer, pitch and SOURCE row bytes are
     multiples of 4; RGB -- pointer and pitch multiples of 4.  (The tensors start 16-byte aligned and the guard in front is 64 bytes.)"""
     _, hs, vs = FMT[name]
-    off = ES.offset_of(variant) if offset is None else offset
+    off = EI.offset_of(variant) if offset is None else offset
     if is_rgb(layout):
-        return off % 4 == 0 and ES.pitch_of(4 * sw, variant) % 4 == 0
-    return all(off % 4 == 0 and ES.pitch_of(rb, variant) % 4 == 0 and rb % 4 == 0 for rb, _ in IR.source_dims(sw, sh, hs, vs, layout))
-
-
-def encode_steps(hip, encs, make, nfr=NFR, expect=0):
-    """nfr lockstep steps through dsv2hip_enc_batch_surface_sized; make(k, t) = (surface, src_w, src_h) of stream k at step t.  Every
-    surface, its guard and its padding bytes are compared with what was put there after every step."""
-    n = len(encs)
-    encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(e) for e in encs])
-    bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)()
-    got = [[] for _ in range(n)]
-    for t in range(nfr):
-        made = [make(k, t) for k in range(n)]
-        arr = (SURFACE * n)(*[m[0].c for m in made])
-        sws, shs = (C.c_int * n)(*[m[1] for m in made]), (C.c_int * n)(*[m[2] for m in made])
-        torch.cuda.synchronize()  # (the tensors are built on torch's stream, the encoder runs on its own)
-        assert hip.dsv2hip_enc_batch_surface_sized(n, encp, arr, sws, shs, bufs, nbufs) == expect
-        take_packets(hip, bufs, nbufs, got)
-        for m in made:
-            m[0].check_untouched()
-    return got
+        return off % 4 == 0 and EI.pitch_of(4 * sw, variant) % 4 == 0
+    return all(off % 4 == 0 and EI.pitch_of(rb, variant) % 4 == 0 and rb % 4 == 0 for rb, _ in IR.source_dims(sw, sh, hs, vs, layout))
 
 
 def encode_sized(hip, sw, sh, w, h, name, layout, variant, offset=None, cfg=CFG, s=0):
     encs = encoders(hip, w, h, name, 1, cfg)
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, name, layout, variant, t, offset, s), sw, sh))
+    got = sized_steps(hip, encs, lambda k, t: (source(sw, sh, name, layout, variant, t, offset, s), sw, sh))
     hip.dsv_enc_free(C.byref(encs[0]))
     return got[0]
 
@@ -118,7 +71,7 @@ def parity_case(sw, sh, w, h, name, layout, variant, offset=None):
     wide = documented_wide(sw, sh, name, layout, variant, offset)
     at = (2 if is_rgb(layout) else 0) + (0 if wide else 1)
     assert resize_forms(hip) == tuple(NFR if i == at else 0 for i in range(4))
-    assert ES.scale_forms(hip) == (0, 0, 0, 0) and rgb_forms(hip) == (0, 0) and yuv_forms(hip) == (0, 0)  # (sized entries count here only)
+    assert scale_forms(hip) == (0, 0, 0, 0) and rgb_forms(hip) == (0, 0) and yuv_forms(hip) == (0, 0)  # (sized entries count here only)
 
 
 # ---- 1. every 4:2:0 source x layout x pitch / alignment ------------------------------------------------------------------------------
@@ -151,7 +104,7 @@ def constant_yuv(sw, sh, value):
 
 def steps_of_one_picture(hip, make, w, h, cfg, name="420"):
     encs = encoders(hip, w, h, name, 1, cfg)
-    got = encode_steps(hip, encs, lambda k, t: make())
+    got = sized_steps(hip, encs, lambda k, t: make())
     hip.dsv_enc_free(C.byref(encs[0]))
     return got[0]
 
@@ -165,7 +118,7 @@ def test_constant_sources_lossless(value, sw, sh):
     want = K.constant_reference(value, value)
     for layout in (PLANAR, SEMI):
         frame = constant_yuv(sw, sh, value)
-        got = steps_of_one_picture(hip, lambda: (ES.yuv_source(frame, sw, sh, "420", layout, 0, "plus1"), sw, sh), 16, 16, K.LOSSLESS)
+        got = steps_of_one_picture(hip, lambda: (EI.yuv_source(frame, sw, sh, "420", layout, 0, "plus1"), sw, sh), 16, 16, K.LOSSLESS)
         same_packets(want, got, LAYOUT_IDS[layout])
     px = np.full((sh, sw, 4), value, dtype=np.uint8)
     px[..., 3] = 77
@@ -174,7 +127,7 @@ def test_constant_sources_lossless(value, sw, sh):
         flat = [np.full((16, 16), one[0][0, 0], dtype=np.uint8)] + [np.full((8, 8), 128, dtype=np.uint8)] * 2
         assert one[1][0, 0] == 128 and one[2][0, 0] == 128
         assert all(np.array_equal(a, b) for a, b in zip(IR.convert_sized(px, layout, 16, 16, 1, 1), flat))
-        got = steps_of_one_picture(hip, lambda: (ES.rgb_source(px, layout, 0, "tight"), sw, sh), 16, 16, K.LOSSLESS)
+        got = steps_of_one_picture(hip, lambda: (EI.rgb_source(px, layout, 0, "tight"), sw, sh), 16, 16, K.LOSSLESS)
         same_packets(K.constant_reference(int(one[0][0, 0]), 128), got, LAYOUT_IDS[layout])
 
 
@@ -183,10 +136,10 @@ def test_checkerboard_99x51_into_66x34():
     hip = bind(A.load_hip())
     sw, sh, w, h = K.CHECKER
     frame = IR.packed(K.checker_planes())
-    got = steps_of_one_picture(hip, lambda: (ES.yuv_source(frame, sw, sh, "420", PLANAR, 0, "plus1"), sw, sh), w, h, K.CHECKER_CFG)
+    got = steps_of_one_picture(hip, lambda: (EI.yuv_source(frame, sw, sh, "420", PLANAR, 0, "plus1"), sw, sh), w, h, K.CHECKER_CFG)
     same_packets(K.checker_reference("yuv"), got, "planar")
     px = K.checker_pixels()
-    got = steps_of_one_picture(hip, lambda: (ES.rgb_source(px, BGRA709, 0, "aligned"), sw, sh), w, h, K.CHECKER_CFG)
+    got = steps_of_one_picture(hip, lambda: (EI.rgb_source(px, BGRA709, 0, "aligned"), sw, sh), w, h, K.CHECKER_CFG)
     same_packets(K.checker_reference(BGRA709), got, "bgra709")
 
 
@@ -203,15 +156,15 @@ def test_mixed_step():
         layout, sw, sh, how = K.MIXED[k]
         return (source(sw, sh, "420", layout, "aligned", t, None, 1 if how == "half" else 0), sw, sh)
 
-    got = encode_steps(hip, encs, make)
+    got = sized_steps(hip, encs, make)
     for e in encs:
         hip.dsv_enc_free(C.byref(e))
     assert yuv_forms(hip) == (0, NFR) and rgb_forms(hip) == (0, NFR)  # (rows of 34 bytes / 34 pixels: the plain general forms)
-    assert ES.scale_forms(hip) == (0, NFR, 0, 0)
+    assert scale_forms(hip) == (0, NFR, 0, 0)
     assert resize_forms(hip) == (0, NFR, NFR, 0)  # (35-byte rows: general; an aligned BGRA surface: wide)
     for k, (layout, sw, sh, how) in enumerate(K.MIXED):
         if how == "half":
-            want = ES.reference(sw, sh, "420", 1, kind_of(layout))
+            want = EI.scaled_reference(sw, sh, "420", 1, kind_of(layout))
         else:
             want = K.reference(sw, sh, 34, 18, "420", kind_of(layout))
         same_packets(want, got[k], "stream %d" % k)
@@ -235,7 +188,7 @@ def test_own_size_gives_the_packets_and_counters_of_the_plain_calls(layout):
     got = encode_sized(hip, w, h, w, h, "420", layout, "plus1")
     same_packets(want[0], got)
     same_packets(K.reference(w, h, w, h, "420", kind_of(layout)), got)
-    assert resize_forms(hip) == (0, 0, 0, 0) and ES.scale_forms(hip) == (0, 0, 0, 0)
+    assert resize_forms(hip) == (0, 0, 0, 0) and scale_forms(hip) == (0, 0, 0, 0)
     assert (rgb_forms(hip), yuv_forms(hip)) == (((0, NFR), (0, 0)) if is_rgb(layout) else ((0, 0), (0, NFR)))
 
 
@@ -263,10 +216,10 @@ def test_twice_the_encoders_size_equals_scale_half(layout):
     sw, sh, w, h = 68, 36, 34, 18
     reset_all(hip)
     sized = encode_sized(hip, sw, sh, w, h, "420", layout, "aligned")
-    assert sum(resize_forms(hip)) == NFR and sum(ES.scale_forms(hip)) == 0
+    assert sum(resize_forms(hip)) == NFR and sum(scale_forms(hip)) == 0
     half = encode_sized(hip, sw, sh, w, h, "420", layout, "aligned", s=1)
-    assert sum(resize_forms(hip)) == NFR and sum(ES.scale_forms(hip)) == NFR  # (a scale value: the scaled call's entry and counters)
-    want = ES.reference(sw, sh, "420", 1, kind_of(layout))
+    assert sum(resize_forms(hip)) == NFR and sum(scale_forms(hip)) == NFR  # (a scale value: the scaled call's entry and counters)
+    want = EI.scaled_reference(sw, sh, "420", 1, kind_of(layout))
     same_packets(want, half, "SCALE_HALF through the sized call")
     same_packets(want, sized, "sized")
 
@@ -303,7 +256,7 @@ REFUSALS = ([("source_8w_plus_1", PLANAR, set_size(8 * 34 + 1, 27)), ("source_w_
              ("src_h_negative", RGBAFULL, set_size(51, -27)),
              ("layout_0x4000", PLANAR, lambda c, size: setattr(c, "layout", c.layout | 0x4000)), ("layout_0x1010", R.RGBA, set_layout(0x1010)),
              ("planar_bt709", PLANAR, set_layout(PLANAR | R.BT709)), ("layout_2", PLANAR, set_layout(2)),
-             ("half_of_another_size", SEMI, set_layout(SEMI | ES.SCALE[1]))] +
+             ("half_of_another_size", SEMI, set_layout(SEMI | HALF))] +
             [("pitch_short_planar_%d" % p, PLANAR, short_pitch(p, (51, 26, 26)[p])) for p in range(3)] +
             [("pitch_short_semiplanar_%d" % p, SEMI, short_pitch(p, (51, 52)[p])) for p in range(2)] +
             [("pitch_short_rgb", BGRA709, short_pitch(0, 204))] +
@@ -339,11 +292,11 @@ def test_refused_source_touches_nothing(what, layout, spoil):
     state = bytes(C.string_at(C.byref(encs[1]), C.sizeof(encs[1])))
     assert hip.dsv2hip_enc_surface_frame_sized(C.byref(encs[1]), C.byref(bad), size[0], size[1], (A.BUF * 4)()) == 0
     assert bytes(C.string_at(C.byref(encs[1]), C.sizeof(encs[1]))) == state
-    assert resize_forms(hip) == (0, 0, 0, 0) and ES.scale_forms(hip) == (0, 0, 0, 0)
+    assert resize_forms(hip) == (0, 0, 0, 0) and scale_forms(hip) == (0, 0, 0, 0)
     for g in good:
         g.check_untouched()
     layouts = [PLANAR, layout]
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, "420", layouts[k], "aligned", t), sw, sh))
+    got = sized_steps(hip, encs, lambda k, t: (source(sw, sh, "420", layouts[k], "aligned", t), sw, sh))
     for e in encs:
         hip.dsv_enc_free(C.byref(e))
     for k in range(2):
@@ -396,7 +349,7 @@ def test_refused_arguments():
     assert nbufs[0] == 77
     # the scaled call with s = 0 and another source size stays refused
     assert hip.dsv2hip_enc_batch_surface_scaled(1, encp, arr, sws, shs, bufs, nbufs) == -1 and nbufs[0] == 77
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, "420", SEMI, "aligned", t), sw, sh))
+    got = sized_steps(hip, encs, lambda k, t: (source(sw, sh, "420", SEMI, "aligned", t), sw, sh))
     hip.dsv_enc_free(C.byref(encs[0]))
     same_packets(K.reference(sw, sh, w, h, "420", "yuv"), got[0])
 
@@ -413,7 +366,7 @@ def test_refused_on_a_uyvy_encoder():
     refused(hip, encs, [sf.c], [(sw, sh)])
     assert hip.dsv2hip_enc_surface_frame_sized(C.byref(encs[0]), C.byref(sf.c), sw, sh, (A.BUF * 4)()) == 0
     assert hip.dsv2hip_enc_set_uyvy_input(C.byref(encs[0]), 0) == 0
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, name, SEMI, "aligned", t), sw, sh))
+    got = sized_steps(hip, encs, lambda k, t: (source(sw, sh, name, SEMI, "aligned", t), sw, sh))
     hip.dsv_enc_free(C.byref(encs[0]))
     same_packets(K.reference(sw, sh, w, h, name, "yuv"), got[0])
 
@@ -423,7 +376,7 @@ def test_full_size_decode_into_the_sized_call_equals_sized_decode_into_the_plain
     """A 64x48 4:2:0 stream decoded at FULL size into a pitched NV12 device surface that goes to dsv2hip_enc_surface_frame_sized of a
     42x30 encoder, against the same stream decoded at 42x30 into a PLANAR surface (dsv2hip_dec_surface_frame_sized) that goes to the
     plain call, and against the reference encoder on the host's resampling of the decoded planes."""
-    ref, hip = A.load_ref(), bind_dec_sized(bind_dec(bind(A.load_hip())))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, ow, oh, cfg = 64, 48, 42, 30, dict(qp=50, gop=48)
     packets = stream(w, h, "420", 4, 4)
     full = [pl for _, _, pl in planar_oracle(packets) if pl is not None]
@@ -502,4 +455,4 @@ def test_sized_dims_are_the_oracles_shapes_and_refuse_what_the_calls_refuse():
     for layout in (0x4000, 0x1010, 0x1012, PLANAR | R.BT709, 0x2):
         assert sized_dims(hip, 51, 27, 34, 18, A.SUBSAMP_420, layout)[0] == -1
     # a scale value: the scaled call's rule
-    assert sized_dims(hip, 67, 35, 34, 18, A.SUBSAMP_420, SEMI | ES.SCALE[1])[0] == 0 and sized_dims(hip, 51, 27, 34, 18, A.SUBSAMP_420, SEMI | ES.SCALE[1])[0] == -1
+    assert sized_dims(hip, 67, 35, 34, 18, A.SUBSAMP_420, SEMI | HALF)[0] == 0 and sized_dims(hip, 51, 27, 34, 18, A.SUBSAMP_420, SEMI | HALF)[0] == -1

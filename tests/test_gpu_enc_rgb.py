@@ -5,7 +5,6 @@ half outside them (lossless, so every LSB of the conversion reaches the packets)
 and YUV surfaces mixed in one step; alpha and padding are never pixels, the surface is never written, a refused call touches
 nothing."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -13,109 +12,15 @@ import torch
 
 import dsvabi as A
 import rgb_csc as R
-from codec_run import configure_encoder, decode_stream, encode_stream
+from codec_run import FMT
 from edge_cases import stream_inverse_is_undefined
-from test_gpu_enc_surface import (CIF_NV12, CIF_PLANAR, GUARD, LEAD, PLANAR, SURFACE, Surface, content, copy_of, encode_steps, packed_batch,
-                                  reference, refused, same_packets)
-from test_gpu_enc_surface import bind as bind_surface
-from test_gpu_enc_surface import forms as yuv_forms
-from test_gpu_formats import FMT
+from enc_in import (CFG, CIF_NV12, CIF_PLANAR, CSC_IDS, LOSSLESS, RgbSurface, Surface, content, copy_of, encode_steps, encoders, oracle_frames, packed_batch, planes_equal_oracle,
+                    reference, refused, rgb_content, rgb_ref_packets as ref_packets, rgb_reference, same_packets, saturated_pictures)
+from hipabi import PLANAR, bind, enc_rgb_forms as rgb_forms, enc_yuv_forms as yuv_forms, reset_enc_forms as reset_forms
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
-CFG = dict(qp=60, gop=12)
-LOSSLESS = dict(qp=100, gop=12)
 ORDER = {"bgra": R.BGRA, "rgba": R.RGBA}
-CSC_IDS = ["bt601", "bt709", "bt601_full", "bt709_full"]
-
-
-def bind(hip):
-    bind_surface(hip)
-    hip.dsv2hip_enc_rgb_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_enc_rgb_stats.restype = None
-    return hip
-
-
-def rgb_forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_enc_rgb_stats(out, int(reset))
-    return out[0], out[1]
-
-
-def reset_forms(hip):
-    rgb_forms(hip, reset=True)
-    yuv_forms(hip, reset=True)
-
-
-@functools.lru_cache(maxsize=None)
-def rgb_content(w, h, nfr, seed):
-    """nfr pictures, h x w x 4 uint8: smooth moving gradients in the three colour bytes plus noise, the alpha byte random"""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    out = []
-    for t in range(nfr):
-        c = [(np.sin((xx + 3 * t) / 17.0) + np.cos((yy + 2 * t) / 11.0)) * 50 + 128,
-             np.sin((xx - 2 * t + yy) / 23.0) * 90 + 128,
-             np.cos((yy + 4 * t) / 19.0) * 70 + np.sin(xx / 31.0) * 40 + 120]
-        px = np.stack(c + [np.zeros((h, w))], axis=-1) + rng.integers(-3, 4, (h, w, 4))
-        px = px.clip(0, 255).astype(np.uint8)
-        px[..., 3] = rng.integers(0, 256, (h, w))
-        px.setflags(write=False)
-        out.append(px)
-    return tuple(out)
-
-
-def oracle_frames(pictures, layout, name):
-    _, hs, vs = FMT[name]
-    return [R.planar_bytes(p, layout, hs, vs) for p in pictures]
-
-
-def ref_packets(pictures, layout, name, cfg):
-    """the real reference encoder on the planar pictures the conversion defines"""
-    h, w = pictures[0].shape[:2]
-    return encode_stream(A.load_ref(), oracle_frames(pictures, layout, name), w, h, FMT[name][0], eos=False, **cfg)[0]
-
-
-@functools.lru_cache(maxsize=None)
-def rgb_reference(w, h, name, nfr, seed, layout, lossless=False):
-    return tuple(ref_packets(rgb_content(w, h, nfr, seed), layout, name, LOSSLESS if lossless else CFG))
-
-
-class RgbSurface:
-    """One picture as a device tensor: LEAD guard bytes, `offset` more, rows of 4 * w bytes `pitch` apart (the last one without
-    padding), LEAD guard bytes.  Guard and padding hold `fill` (None: noise); `alpha` (not None) replaces the picture's alpha
-    bytes.  plane[1..2] and pitch[1..2] stay NULL / 0: an RGB surface has none.  `check_untouched` compares every byte."""
-
-    def __init__(self, pixels, layout, pitch, offset=0, fill=GUARD, alpha=None):
-        h, w = pixels.shape[:2]
-        assert pitch >= 4 * w
-        if alpha is not None:
-            pixels = pixels.copy()
-            pixels[..., 3] = alpha
-        start = LEAD + offset
-        size = start + (h - 1) * pitch + 4 * w + LEAD
-        if fill is None:
-            t = torch.from_numpy(np.random.default_rng(size).integers(0, 256, size, dtype=np.uint8)).cuda()
-        else:
-            t = torch.full((size,), fill, dtype=torch.uint8, device="cuda")
-        assert t.data_ptr() % 16 == 0
-        torch.as_strided(t, (h, 4 * w), (pitch, 1), start).copy_(torch.from_numpy(pixels.reshape(h, 4 * w).copy()).cuda())
-        self.t, self.was = t, t.clone()
-        self.c = SURFACE()
-        self.c.layout = layout
-        self.c.plane[0] = t.data_ptr() + start
-        self.c.pitch[0] = pitch
-
-    def check_untouched(self):
-        assert torch.equal(self.t, self.was), "the encoder wrote into a surface"
-
-
-def encoders(hip, w, h, name, n, cfg):
-    meta = A.mk_meta(w, h, FMT[name][0])
-    encs = [A.ENCODER() for _ in range(n)]
-    for e in encs:
-        configure_encoder(hip, e, meta, **cfg)
-    return encs
 
 
 def encode_rgb(hip, pictures, layout, name, cfg=CFG, **surface):
@@ -133,19 +38,6 @@ def odd_pitch(w):
 
 def aligned_pitch(w):
     return ((4 * w + 15) & ~15) + 16
-
-
-def planes_equal_oracle(packets, pictures, layout, name):
-    """the product's packets through the REFERENCE decoder: with a lossless stream its pictures are the oracle's planes, sample for sample"""
-    _, hs, vs = FMT[name]
-    dec = decode_stream(A.load_ref(), packets)
-    assert len(dec) == len(pictures)
-    for t, (fn, *planes) in enumerate(dec):
-        for c, (got, want) in enumerate(zip(planes, R.convert(pictures[t], layout, hs, vs))):
-            assert got.shape == want.shape
-            bad = np.argwhere(got != want)
-            assert bad.size == 0, "frame %d plane %d: sample (x=%d, y=%d) is %d, the conversion gives %d" % (
-                t, c, bad[0][1], bad[0][0], got[tuple(bad[0])], want[tuple(bad[0])])
 
 
 # ---- 1. wide form -------------------------------------------------------------------------------------------------------
@@ -210,25 +102,6 @@ def test_smallest_pictures_lossless(w, h, name, form):
 
 
 # ---- 4. presets and saturation ----------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def saturated_pictures():
-    """64x48: the 8 corners of the colour cube in 8x8 tiles, 16 rows of noise, a sweep 0..255 of each primary (12 rows), 12 rows
-    of noise; the second picture has other noise"""
-    out = []
-    for t in range(2):
-        rng = np.random.default_rng(70 + t)
-        px = rng.integers(0, 256, (48, 64, 4), dtype=np.uint8)
-        for k in range(8):
-            px[0:8, 8 * k:8 * k + 8, 0:3] = [255 * (k & 1), 255 * ((k >> 1) & 1), 255 * ((k >> 2) & 1)]
-        sweep = np.zeros((768, 3), dtype=np.uint8)
-        for c in range(3):
-            sweep[256 * c:256 * c + 256, c] = np.arange(256)
-        px[24:36, :, 0:3] = sweep.reshape(12, 64, 3)
-        px.setflags(write=False)
-        out.append(px)
-    return tuple(out)
-
-
 @pytest.mark.parametrize("name", ["444", "420"])
 @pytest.mark.parametrize("csc", R.CSC, ids=CSC_IDS)
 def test_presets_and_saturation_lossless(csc, name):

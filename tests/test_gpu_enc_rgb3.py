@@ -4,7 +4,7 @@ tests/rgb_csc.py on the picture widened to four bytes) -- both forms of both kin
 presets, the five chroma formats, the smallest pictures and footprints half outside them (lossless, so every LSB of the conversion
 reaches the packets), saturated colours, rows of several passes, torch tensors read in place, every kind of surface mixed in one
 step; padding is never a pixel, the surface is never written, a refused call touches nothing.  The shapes are those of
-tests/test_gpu_enc_rgb.py, whose pictures, encoders and references are shared."""
+tests/test_gpu_enc_rgb.py; the pictures, encoders and references of both are tests/enc_in.py's."""
 import ctypes as C
 
 import numpy as np
@@ -15,42 +15,18 @@ import dsvabi as A
 import rgb3_csc as R3
 import rgb_csc as R
 from edge_cases import stream_inverse_is_undefined
-from test_gpu_dec_device_out import format_stream, mk_buf
-from test_gpu_dec_rgb import OutSurf, aligned as aligned_out, planar_oracle
-from test_gpu_dec_rgb import bind as bind_dec
-from test_gpu_dec_resize import bind as bind_dec_sized
-from test_gpu_dec_surface import OUTSURF, PLANAR as OUT_PLANAR, surface_dims
-from test_gpu_enc_resize import bind as bind_sized
-from test_gpu_enc_rgb import (CFG, CSC_IDS, LOSSLESS, RgbSurface, encoders, oracle_frames, planes_equal_oracle, ref_packets, reset_forms, rgb_content,
-                              rgb_forms, rgb_reference, saturated_pictures)
-from test_gpu_enc_rgb import bind as bind_rgb
-from test_gpu_enc_surface import (CIF_NV12, GUARD, LEAD, PLANAR, SURFACE, Surface, content, copy_of, encode_steps, packed_batch, reference, refused,
-                                  same_packets)
-from test_gpu_enc_surface import forms as yuv_forms
-from test_gpu_formats import FMT
+from codec_run import FMT
+from dec_out import OutSurf, aligned as aligned_out, format_stream, planar_oracle
+from enc_in import (CFG, CIF_NV12, CSC_IDS, LOSSLESS, Rgb3Surface, RgbSurface, Surface, TensorSurface, content, copy_of, encode_steps, encoders, oracle_frames,
+                    packed_batch, pixels_of, planes_equal_oracle, reference, refused, rgb_content, rgb_ref_packets as ref_packets, rgb_reference, same_packets,
+                    saturated_pictures)
+from hipabi import (OUTSURF, PLANAR, SURFACE, bind, enc_rgb3_forms as rgb3_forms, enc_rgb_forms as rgb_forms, enc_yuv_forms as yuv_forms, mk_buf,
+                    reset_enc_forms as reset_all, surface_dims)
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
 BGR, RGB, RGBP = R3.BGR, R3.RGB, R3.RGBP
 ORDERS = ["bgr", "rgb", "rgbp"]
-
-
-def bind(hip):
-    bind_rgb(hip)
-    hip.dsv2hip_enc_rgb3_stats.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_enc_rgb3_stats.restype = None
-    return hip
-
-
-def rgb3_forms(hip, reset=False):
-    out = (C.c_ulonglong * 4)()
-    hip.dsv2hip_enc_rgb3_stats(out, int(reset))
-    return tuple(out)
-
-
-def reset_all(hip):
-    rgb3_forms(hip, reset=True)
-    reset_forms(hip)
 
 
 def counts(layout, wide, steps=3):
@@ -62,15 +38,6 @@ def counts(layout, wide, steps=3):
 def four(layout):
     """the four-byte layout that names the colours of rgb_content's bytes 0..2 read as a surface of `layout`"""
     return (R.BGRA if R3.order_of(layout) == BGR else R.RGBA) | (layout & 0x300)
-
-
-def pixels_of(px4, layout):
-    """bytes 0..2 of an h x w x 4 picture as the surface of `layout` holds them: in memory order (BGR / RGB), or as three planes that are
-    R, G, B (RGBP).  The oracle on it is the four-byte oracle on px4 under four(layout), whatever px4's alpha: the references are shared
-    with tests/test_gpu_enc_rgb.py."""
-    if R3.order_of(layout) == RGBP:
-        return np.ascontiguousarray(px4[..., :3].transpose(2, 0, 1))
-    return np.ascontiguousarray(px4[..., :3])
 
 
 def expected(pictures4, layout, name):
@@ -85,40 +52,6 @@ def expected(pictures4, layout, name):
 def reference3(w, h, name, nfr, seed, layout, lossless=False):
     expected(rgb_content(w, h, nfr, seed), layout, name)
     return rgb_reference(w, h, name, nfr, seed, four(layout), lossless)
-
-
-class Rgb3Surface:
-    """One picture as device tensors, one per source plane (one: BGR / RGB, three: RGBP): LEAD guard bytes, `offset` more, rows `pitch`
-    apart (the last one without padding), LEAD guard bytes.  Guard and padding hold `fill` (None: noise).  pitch / offset: a value, or
-    one per plane.  plane[1..2] and pitch[1..2] of a packed surface stay NULL / 0.  `check_untouched` compares every byte."""
-
-    def __init__(self, px4, layout, pitch, offset=0, fill=GUARD):
-        pixels = pixels_of(px4, layout)
-        planes = list(pixels) if R3.order_of(layout) == RGBP else [pixels.reshape(pixels.shape[0], -1)]
-        pitches = pitch if isinstance(pitch, tuple) else (pitch,) * len(planes)
-        offsets = offset if isinstance(offset, tuple) else (offset,) * len(planes)
-        self.t, self.was = [], []
-        self.c = SURFACE()
-        self.c.layout = layout
-        for i, pl in enumerate(planes):
-            rows, rb = pl.shape
-            assert pitches[i] >= rb
-            start = LEAD + offsets[i]
-            size = start + (rows - 1) * pitches[i] + rb + LEAD
-            if fill is None:
-                t = torch.from_numpy(np.random.default_rng(size + i).integers(0, 256, size, dtype=np.uint8)).cuda()
-            else:
-                t = torch.full((size,), fill, dtype=torch.uint8, device="cuda")
-            assert t.data_ptr() % 16 == 0
-            torch.as_strided(t, (rows, rb), (pitches[i], 1), start).copy_(torch.from_numpy(np.ascontiguousarray(pl)).cuda())
-            self.t.append(t)
-            self.was.append(t.clone())
-            self.c.plane[i] = t.data_ptr() + start
-            self.c.pitch[i] = pitches[i]
-
-    def check_untouched(self):
-        for t, was in zip(self.t, self.was):
-            assert torch.equal(t, was), "the encoder wrote into a surface"
 
 
 def row_bytes(w, layout):
@@ -251,28 +184,6 @@ def test_padding_is_never_a_pixel_and_nothing_is_written(w, h, form, order):
 
 
 # ---- 6. straight from torch ----------------------------------------------------------------------------------------------------------
-class TensorSurface:
-    """a view of a torch uint8 tensor as a surface, read in place: h x w x 3 (element strides (pitch, 3, 1)) or 3 x h x w (strides
-    (plane, pitch, 1)); `check_untouched` compares every byte of the tensor the view belongs to"""
-
-    def __init__(self, view, whole, layout):
-        self.whole, self.was = whole, whole.clone()
-        self.c = SURFACE()
-        self.c.layout = layout
-        if R3.order_of(layout) == RGBP:
-            assert view.shape[0] == 3 and view.stride(2) == 1
-            for c in range(3):
-                self.c.plane[c] = view[c].data_ptr()
-                self.c.pitch[c] = view.stride(1)
-        else:
-            assert view.shape[2] == 3 and view.stride(2) == 1 and view.stride(1) == 3
-            self.c.plane[0] = view.data_ptr()
-            self.c.pitch[0] = view.stride(0)
-
-    def check_untouched(self):
-        assert torch.equal(self.whole, self.was), "the encoder wrote into a tensor"
-
-
 @pytest.mark.parametrize("crop", [False, True], ids=["contiguous", "crop"])
 @pytest.mark.parametrize("order", ["bgr", "rgbp"], ids=["hwc", "chw"])
 def test_straight_from_torch(order, crop):
@@ -436,7 +347,6 @@ def test_refused_by_the_scaled_and_sized_calls_at_the_encoders_own_size(order):
     exactly the encoder's picture (where a BGRA surface is the plain call's job): -1 / 0, nothing touched; the plain call then encodes
     the same surface from frame 0."""
     hip = bind(A.load_hip())
-    bind_sized(hip)
     w, h, name = 352, 288, "420"
     layout = R3.ORDER[order] | R.BT709
     encs = encoders(hip, w, h, name, 1, CFG)
@@ -460,9 +370,7 @@ def test_refused_by_the_decoder():
     / dsv2hip_dec_surface_frame refuse a surface that names one -- here a 4:4:4 stream's PLANAR surface, three planes of w x h bytes,
     which has room for each of them -- with the packet, the decoder, fn / ret and the surface as they were; the same packets then
     decode into that surface as PLANAR."""
-    hip = A.load_hip()
-    bind_dec(hip)
-    bind_dec_sized(hip)
+    hip = bind(A.load_hip())
     packets = format_stream("444", 34, 18, 3)
     want = planar_oracle(packets)
     dec = A.DECODER()
@@ -470,9 +378,9 @@ def test_refused_by_the_decoder():
     bufs, arr, fns, rets = (A.BUF * 1)(), (OUTSURF * 1)(), (C.c_uint32 * 1)(), (C.c_int * 1)()
     mk_buf(hip, bufs[0], packets[0])
     assert hip.dsv2hip_dec_batch_surface(1, decp, bufs, arr, fns, rets) == 1 and rets[0] == A.DEC_GOT_META
-    dims = surface_dims(hip, dec, OUT_PLANAR)
+    dims = surface_dims(hip, dec, PLANAR)
     assert dims == [(34, 18)] * 3
-    sf = OutSurf(dims, OUT_PLANAR, aligned_out)
+    sf = OutSurf(dims, PLANAR, aligned_out)
     sf.arm()
     torch.cuda.synchronize()
     mk_buf(hip, bufs[0], packets[1])

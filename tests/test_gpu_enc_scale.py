@@ -21,22 +21,17 @@ import ingest_scale as S
 import rgb_csc as R
 from codec_run import configure_encoder, encode_stream
 from edge_cases import content_planes, packet_bound_holds
-from test_gpu_dec_device_out import mk_buf
-from test_gpu_dec_drawinfo import stream
-from test_gpu_dec_rgb import OutSurf, planar_oracle
-from test_gpu_dec_rgb import aligned as aligned_out
-from test_gpu_dec_rgb import bind as bind_dec
-from test_gpu_enc_rgb import RgbSurface, encoders, rgb_content, rgb_forms
-from test_gpu_enc_rgb import bind as bind_rgb
-from test_gpu_enc_surface import PLANAR, SEMI, SURFACE, Surface, content, copy_of, same_packets, take_packets
-from test_gpu_enc_surface import forms as yuv_forms
-from test_gpu_formats import FMT
+from codec_run import FMT
+from dec_out import OutSurf, aligned as aligned_out, planar_oracle, stream
+from enc_in import (LADDER_CFG, LADDER_LOSSLESS, LADDER_NFR, LADDER_SEED, content, copy_of, encode_steps, encoders, is_rgb, kind_of, offset_of, pitch_of,
+                    ref_packets, rgb_content, rgb_source, same_packets, scaled_pictures as oracle_pictures, scaled_reference as reference, take_packets,
+                    yuv_source)
+from hipabi import (PLANAR, SEMI, SURFACE, bind, enc_rgb_forms as rgb_forms, enc_scale_forms as scale_forms, enc_yuv_forms as yuv_forms, mk_buf,
+                    reset_enc_forms as reset_all)
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
 
-CFG = dict(qp=60, gop=4)
-LOSSLESS = dict(qp=100, gop=4)
-NFR, SEED = 4, 5
+CFG, LOSSLESS, NFR, SEED = LADDER_CFG, LADDER_LOSSLESS, LADDER_NFR, LADDER_SEED
 SCALE = S.SCALE
 BGRA709, RGBAFULL = R.BGRA | R.BT709, R.RGBA | R.FULL
 LAYOUTS = [PLANAR, SEMI, BGRA709, RGBAFULL]
@@ -44,91 +39,8 @@ LAYOUT_IDS = {PLANAR: "planar", SEMI: "semiplanar", BGRA709: "bgra709", RGBAFULL
 VARIANTS = ["tight", "plus1", "aligned"]
 
 
-def bind(hip):
-    P = C.POINTER
-    bind_rgb(hip)
-    hip.dsv2hip_enc_batch_surface_scaled.argtypes = [C.c_int, P(P(A.ENCODER)), P(SURFACE), P(C.c_int), P(C.c_int), P(A.BUF), P(C.c_int)]
-    hip.dsv2hip_enc_batch_surface_scaled.restype = C.c_int
-    hip.dsv2hip_enc_surface_frame_scaled.argtypes = [P(A.ENCODER), P(SURFACE), C.c_int, C.c_int, P(A.BUF)]
-    hip.dsv2hip_enc_surface_frame_scaled.restype = C.c_int
-    hip.dsv2hip_enc_scaled_dims.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_int), P(C.c_int), P(C.c_size_t), P(C.c_int)]
-    hip.dsv2hip_enc_scaled_dims.restype = C.c_int
-    hip.dsv2hip_enc_scale_stats.argtypes = [P(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_enc_scale_stats.restype = None
-    return hip
-
-
-def scale_forms(hip, reset=False):
-    out = (C.c_ulonglong * 4)()
-    hip.dsv2hip_enc_scale_stats(out, int(reset))
-    return tuple(out)
-
-
-def reset_all(hip):
-    scale_forms(hip, reset=True)
-    rgb_forms(hip, reset=True)
-    yuv_forms(hip, reset=True)
-
-
-def is_rgb(layout):
-    return (layout & 0xff) in (R.BGRA, R.RGBA)
-
-
-def kind_of(layout):
-    """which oracle a layout's pictures come from: the YUV content for both YUV layouts, the RGB content through the layout's conversion"""
-    return layout if is_rgb(layout) else "yuv"
-
-
-# ---- the oracle's pictures and the reference's packets on them: made once, shared, never changed --------------------------------
-@functools.lru_cache(maxsize=None)
-def oracle_pictures(sw, sh, name, s, kind):
-    """the encoder's pictures (packed planar bytes) for the content made at the SOURCE size with seed 5"""
-    _, hs, vs = FMT[name]
-    if kind == "yuv":
-        return tuple(S.packed(S.reduce_yuv(S.split_planar(f, sw, sh, hs, vs), s)) for f in content(sw, sh, name, NFR, SEED))
-    return tuple(S.packed(S.convert_scaled(px, kind, hs, vs, s)) for px in rgb_content(sw, sh, NFR, SEED))
-
-
-def conditions(packets, w, h, name):
-    """both conditions of a case.  (4:1:1 and "4:1:0": the reference gives their packets the buffer of 4:2:0, dsv_encoder.c:1062-1066.)"""
-    packet_bound_holds(packets, w, h, FMT[name][0] if name in ("444", "422", "420") else A.SUBSAMP_420)
-    kinds = {pk[5] & 1 for pk in packets if pk[5] & 0x04}  # (dsv.h: packet type at byte 5, picture = 0x04, bit 0 = predicted)
-    assert kinds == {0, 1}, "broken test case: I and P pictures do not both occur"
-
-
-def ref_packets(pictures, w, h, name, cfg):
-    packets = tuple(encode_stream(A.load_ref(), list(pictures), w, h, FMT[name][0], eos=False, **cfg)[0])
-    conditions(packets, w, h, name)
-    return packets
-
-
-@functools.lru_cache(maxsize=None)
-def reference(sw, sh, name, s, kind):
-    return ref_packets(oracle_pictures(sw, sh, name, s, kind), S.up(sw, s), S.up(sh, s), name, CFG)
-
-
 # ---- sources ----------------------------------------------------------------------------------------------------------------------
-def pitch_of(rb, variant):
-    return {"tight": rb, "plus1": rb + 1, "aligned": ((rb + 15) & ~15) + 16}[variant]
-
-
-def offset_of(variant):
-    return 1 if variant == "plus1" else 0
-
-
-def yuv_source(frame, sw, sh, name, layout, s, variant, offset=None):
-    """a packed planar picture of sw x sh as a planar / semiplanar device surface whose layout says the scale"""
-    _, hs, vs = FMT[name]
-    rbs = [rb for rb, _ in S.source_dims(sw, sh, hs, vs, layout)]
-    off = offset_of(variant) if offset is None else offset
-    sf = Surface(frame, sw, sh, name, layout, tuple(pitch_of(rb, variant) for rb in rbs), offsets=(off, off, off))
-    sf.c.layout = layout | SCALE[s]
-    return sf
-
-
-def rgb_source(pixels, layout, s, variant, offset=None):
-    sw = pixels.shape[1]
-    return RgbSurface(pixels, layout | SCALE[s], pitch_of(4 * sw, variant), offset=offset_of(variant) if offset is None else offset)
+scaled_steps = functools.partial(encode_steps, nfr=NFR, call="dsv2hip_enc_batch_surface_scaled")
 
 
 def source(sw, sh, name, layout, s, variant, t, offset=None):
@@ -147,29 +59,10 @@ def documented_wide(sw, sh, name, layout, variant, offset=None):
     return all(off % 16 == 0 and pitch_of(rb, variant) % 16 == 0 and rb % 16 == 0 for rb, _ in S.source_dims(sw, sh, hs, vs, layout))
 
 
-def encode_steps(hip, encs, make, nfr=NFR, expect=0):
-    """nfr lockstep steps through dsv2hip_enc_batch_surface_scaled; make(k, t) = (surface, src_w, src_h) of stream k at step t.  Every
-    surface, its guard and its padding bytes are compared with what was put there after every step."""
-    n = len(encs)
-    encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(e) for e in encs])
-    bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)()
-    got = [[] for _ in range(n)]
-    for t in range(nfr):
-        made = [make(k, t) for k in range(n)]
-        arr = (SURFACE * n)(*[m[0].c for m in made])
-        sws, shs = (C.c_int * n)(*[m[1] for m in made]), (C.c_int * n)(*[m[2] for m in made])
-        torch.cuda.synchronize()  # (the tensors are built on torch's stream, the encoder runs on its own)
-        assert hip.dsv2hip_enc_batch_surface_scaled(n, encp, arr, sws, shs, bufs, nbufs) == expect
-        take_packets(hip, bufs, nbufs, got)
-        for m in made:
-            m[0].check_untouched()
-    return got
-
-
 def encode_scaled(hip, sw, sh, name, layout, s, variant, offset=None, cfg=CFG):
     """one encoder of the reduced geometry over the NFR source pictures; frees the encoder"""
     encs = encoders(hip, S.up(sw, s), S.up(sh, s), name, 1, cfg)
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, name, layout, s, variant, t, offset), sw, sh))
+    got = scaled_steps(hip, encs, lambda k, t: (source(sw, sh, name, layout, s, variant, t, offset), sw, sh))
     hip.dsv_enc_free(C.byref(encs[0]))
     return got[0]
 
@@ -245,7 +138,7 @@ def constant_yuv(sw, sh, value):
 
 def steps_of_one_picture(hip, make, w, h, cfg, name="420"):
     encs = encoders(hip, w, h, name, 1, cfg)
-    got = encode_steps(hip, encs, lambda k, t: make())
+    got = scaled_steps(hip, encs, lambda k, t: make())
     hip.dsv_enc_free(C.byref(encs[0]))
     return got[0]
 
@@ -301,7 +194,7 @@ def test_mixed_step():
     hip = bind(A.load_hip())
     encs = encoders(hip, 34, 18, "420", len(MIXED), CFG)
     reset_all(hip)
-    got = encode_steps(hip, encs, lambda k, t: (source(MIXED[k][1], MIXED[k][2], "420", MIXED[k][0], MIXED[k][3], "aligned", t),) + MIXED[k][1:3])
+    got = scaled_steps(hip, encs, lambda k, t: (source(MIXED[k][1], MIXED[k][2], "420", MIXED[k][0], MIXED[k][3], "aligned", t),) + MIXED[k][1:3])
     for e in encs:
         hip.dsv_enc_free(C.byref(e))
     assert yuv_forms(hip) == (0, NFR) and rgb_forms(hip) == (0, NFR)  # (rows of 34 bytes / 34 pixels: the general forms)
@@ -417,7 +310,7 @@ def test_refused_source_touches_nothing(what, layout, spoil):
     assert hip.dsv2hip_enc_surface_frame_scaled(C.byref(encs[1]), C.byref(bad), size[0], size[1], (A.BUF * 4)()) == 0
     assert bytes(C.string_at(C.byref(encs[1]), C.sizeof(encs[1]))) == state
     layouts = [PLANAR, layout]
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, "420", layouts[k], s, "aligned", t), sw, sh))
+    got = scaled_steps(hip, encs, lambda k, t: (source(sw, sh, "420", layouts[k], s, "aligned", t), sw, sh))
     for e in encs:
         hip.dsv_enc_free(C.byref(e))
     for k in range(2):
@@ -441,7 +334,7 @@ def test_refused_arguments():
     one = hip.dsv2hip_enc_surface_frame_scaled
     assert one(None, arr, sw, sh, bufs) == 0 and one(C.byref(encs[0]), None, sw, sh, bufs) == 0 and one(C.byref(encs[0]), arr, sw, sh, None) == 0
     assert nbufs[0] == 77
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, "420", SEMI, s, "aligned", t), sw, sh))
+    got = scaled_steps(hip, encs, lambda k, t: (source(sw, sh, "420", SEMI, s, "aligned", t), sw, sh))
     hip.dsv_enc_free(C.byref(encs[0]))
     same_packets(reference(sw, sh, "420", s, "yuv"), got[0])
 
@@ -458,7 +351,7 @@ def test_refused_on_a_uyvy_encoder():
     refused(hip, encs, [sf.c], [(sw, sh)])
     assert hip.dsv2hip_enc_surface_frame_scaled(C.byref(encs[0]), C.byref(sf.c), sw, sh, (A.BUF * 4)()) == 0
     assert hip.dsv2hip_enc_set_uyvy_input(C.byref(encs[0]), 0) == 0
-    got = encode_steps(hip, encs, lambda k, t: (source(sw, sh, name, SEMI, s, "aligned", t), sw, sh))
+    got = scaled_steps(hip, encs, lambda k, t: (source(sw, sh, name, SEMI, s, "aligned", t), sw, sh))
     hip.dsv_enc_free(C.byref(encs[0]))
     same_packets(reference(sw, sh, name, s, "yuv"), got[0])
 
@@ -472,7 +365,7 @@ def test_refused_with_an_encoder_of_another_geometry():
     torch.cuda.synchronize()
     refused(hip, encs, [sf.c for sf in first], geo)
     for k, (sw, sh) in enumerate(geo):
-        got = encode_steps(hip, [encs[k]], lambda _, t: (source(sw, sh, "420", BGRA709, 1, "aligned", t), sw, sh))
+        got = scaled_steps(hip, [encs[k]], lambda _, t: (source(sw, sh, "420", BGRA709, 1, "aligned", t), sw, sh))
         hip.dsv_enc_free(C.byref(encs[k]))
         same_packets(reference(sw, sh, "420", 1, BGRA709), got[0], "%dx%d" % (sw, sh))
 
@@ -482,7 +375,7 @@ def test_full_size_decode_into_the_scaled_call_equals_half_size_decode_into_the_
     """A 64x48 4:2:0 stream decoded at FULL size into a pitched NV12 device surface that goes to dsv2hip_enc_surface_frame_scaled of a
     32x24 encoder at half size: the packets of test_gpu_dec_scale.test_half_size_nv12_goes_straight_into_an_encoder_of_the_reduced_
     geometry (decode at half size, plain encode) and of the reference encoder on the host copy of the reduced planes."""
-    ref, hip = A.load_ref(), bind_dec(bind(A.load_hip()))
+    ref, hip = A.load_ref(), bind(A.load_hip())
     w, h, cfg = 64, 48, dict(qp=50, gop=48)
     packets = stream(w, h, "420", 4, 4)
     full = [pl for _, _, pl in planar_oracle(packets) if pl is not None]

@@ -3,48 +3,17 @@
 of the ingest kernel, rows wider than one workgroup pass, mixed surfaces in one step -- padding is never read as pixels, the
 surface is never written, and a refused call touches nothing."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 import dsvabi as A
-from codec_run import configure_encoder, encode_stream
-from test_gpu_formats import FMT, frames as plain_frames
+from codec_run import FMT
+from enc_in import CIF_NV12, CIF_PLANAR, Surface, content, copy_of, dims, encode_steps, encoders, packed_batch, reference, refused, same_packets, take_packets
+from hipabi import BGR, BGRA, BT709, HALF, PLANAR, RGBA, RGBP, SEMI, SURFACE, bind, enc_yuv_forms as forms
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
-
-PLANAR, SEMI = 0, 1
-GUARD = 0xA5
-LEAD = 64  # guard bytes in front of and behind every plane
-CFG = dict(qp=60, gop=12)
-
-
-class SURFACE(C.Structure):
-    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3), ("layout", C.c_int)]
-
-
-def bind(hip):
-    P = C.POINTER
-    hip.dsv2hip_enc_batch_surface.argtypes = [C.c_int, P(P(A.ENCODER)), P(SURFACE), P(A.BUF), P(C.c_int)]
-    hip.dsv2hip_enc_batch_surface.restype = C.c_int
-    hip.dsv2hip_enc_surface_frame.argtypes = [P(A.ENCODER), P(SURFACE), P(A.BUF)]
-    hip.dsv2hip_enc_surface_frame.restype = C.c_int
-    hip.dsv2hip_enc_surface_stats.argtypes = [P(C.c_ulonglong), C.c_int]
-    hip.dsv2hip_enc_surface_stats.restype = None
-    hip.dsv2hip_enc_batch.argtypes = [C.c_int, P(P(A.ENCODER)), P(C.c_void_p), P(A.BUF), P(C.c_int)]
-    hip.dsv2hip_enc_batch.restype = C.c_int
-    hip.dsv2hip_enc_set_uyvy_input.argtypes = [P(A.ENCODER), C.c_int]
-    hip.dsv2hip_enc_set_uyvy_input.restype = C.c_int
-    return hip
-
-
-def dims(w, h, name):
-    """(format code, [(row bytes, rows)] of Y, U, V)"""
-    code, hs, vs = FMT[name]
-    cw, ch = (w + (1 << hs) - 1) >> hs, (h + (1 << vs) - 1) >> vs
-    return code, [(w, h), (cw, ch), (cw, ch)]
 
 
 def row_bytes(w, h, name, layout):
@@ -53,106 +22,15 @@ def row_bytes(w, h, name, layout):
     return [d[0][0], 2 * d[1][0]] if layout == SEMI else [p[0] for p in d]
 
 
-@functools.lru_cache(maxsize=None)
-def content(w, h, name, nfr, seed):
-    _, hs, vs = FMT[name]
-    return tuple(plain_frames(w, h, hs, vs, nfr, seed))
-
-
-@functools.lru_cache(maxsize=None)
-def reference(w, h, name, nfr, seed):
-    return tuple(encode_stream(A.load_ref(), list(content(w, h, name, nfr, seed)), w, h, FMT[name][0], eos=False, **CFG)[0])
-
-
-class Surface:
-    """One picture as device tensors, one per source plane: LEAD guard bytes, `offset` more, rows `pitch` apart (the last one
-    without padding), LEAD guard bytes.  Guard and padding hold `fill`; `check_untouched` compares every byte with what was put."""
-
-    def __init__(self, frame, w, h, name, layout, pitches, offsets=(0, 0, 0), fill=GUARD):
-        _, d = dims(w, h, name)
-        flat = np.frombuffer(frame, dtype=np.uint8)
-        planes, at = [], 0
-        for pw, ph in d:
-            planes.append(flat[at:at + pw * ph].reshape(ph, pw))
-            at += pw * ph
-        assert at == flat.size
-        if layout == SEMI:
-            planes = [planes[0], np.stack([planes[1], planes[2]], axis=-1).reshape(d[1][1], 2 * d[1][0])]
-        self.t, self.was = [], []
-        self.c = SURFACE()
-        self.c.layout = layout
-        for i, pl in enumerate(planes):
-            rows, rb = pl.shape
-            assert pitches[i] >= rb
-            start = LEAD + offsets[i]
-            t = torch.full((start + (rows - 1) * pitches[i] + rb + LEAD,), fill, dtype=torch.uint8, device="cuda")
-            assert t.data_ptr() % 16 == 0
-            torch.as_strided(t, (rows, rb), (pitches[i], 1), start).copy_(torch.from_numpy(pl.copy()).cuda())
-            self.t.append(t)
-            self.was.append(t.clone())
-            self.c.plane[i] = t.data_ptr() + start
-            self.c.pitch[i] = pitches[i]
-
-    def check_untouched(self):
-        for t, was in zip(self.t, self.was):
-            assert torch.equal(t, was), "the encoder wrote into a surface"
-
-
-def new_encoders(hip, w, h, name, n):
-    meta = A.mk_meta(w, h, FMT[name][0])
-    encs = [A.ENCODER() for _ in range(n)]
-    for e in encs:
-        configure_encoder(hip, e, meta, **CFG)
-    return encs
-
-
-def take_packets(hip, bufs, nbufs, got):
-    for s in range(len(got)):
-        assert 0 <= nbufs[s] <= 4
-        for i in range(nbufs[s]):
-            b = bufs[4 * s + i]
-            got[s].append(bytes(C.string_at(b.data, b.len)))
-            hip.dsv_buf_free(C.byref(b))
-
-
-def encode_steps(hip, encs, make_surface, nfr):
-    """nfr lockstep steps over encs; make_surface(s, t) builds stream s's surface of step t.  Returns the packets per stream."""
-    n = len(encs)
-    encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(e) for e in encs])
-    bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)()
-    got = [[] for _ in range(n)]
-    for t in range(nfr):
-        surfs = [make_surface(s, t) for s in range(n)]
-        arr = (SURFACE * n)(*[sf.c for sf in surfs])
-        torch.cuda.synchronize()  # (the tensors are built on torch's stream, the encoder runs on its own)
-        assert hip.dsv2hip_enc_batch_surface(n, encp, arr, bufs, nbufs) == 0
-        take_packets(hip, bufs, nbufs, got)
-        for sf in surfs:
-            sf.check_untouched()
-    return got
-
-
 def encode_with(hip, w, h, name, specs, nfr=3, seed0=5):
     """One encoder per spec = dict(layout, pitches, offsets, fill), stream s encoding content(seed0 + s); frees the encoders."""
     code = dims(w, h, name)[0]
     assert code == FMT[name][0]
-    encs = new_encoders(hip, w, h, name, len(specs))
+    encs = encoders(hip, w, h, name, len(specs))
     got = encode_steps(hip, encs, lambda s, t: Surface(content(w, h, name, nfr, seed0 + s)[t], w, h, name, **specs[s]), nfr)
     for e in encs:
         hip.dsv_enc_free(C.byref(e))
     return got
-
-
-def same_packets(want, got, what=""):
-    assert len(want) == len(got), "%s: %d packets, the reference has %d" % (what, len(got), len(want))
-    for i, (a, b) in enumerate(zip(want, got)):
-        assert a == b, "%s: packet %d differs" % (what, i)
-
-
-def forms(hip, reset=False):
-    out = (C.c_ulonglong * 2)()
-    hip.dsv2hip_enc_surface_stats(out, int(reset))
-    return out[0], out[1]
 
 
 def odd_pitch(rb):
@@ -160,8 +38,6 @@ def odd_pitch(rb):
 
 
 # ---- 1. parity, wide form ---------------------------------------------------------------------------------------------
-CIF_PLANAR = dict(layout=PLANAR, pitches=(512, 256, 256))
-CIF_NV12 = dict(layout=SEMI, pitches=(512, 512))
 
 
 @pytest.mark.parametrize("spec", [CIF_PLANAR, CIF_NV12], ids=["planar", "nv12"])
@@ -217,21 +93,6 @@ def test_padding_is_never_read_and_nothing_is_written(w, h, spec):
 
 
 # ---- 5. one step, mixed surfaces ----------------------------------------------------------------------------------------
-def packed_batch(hip, w, h, name, frames):
-    """dsv2hip_enc_batch on the packed picture, one stream"""
-    enc = new_encoders(hip, w, h, name, 1)[0]
-    encp = (C.POINTER(A.ENCODER) * 1)(C.pointer(enc))
-    bufs, nbufs = (A.BUF * 4)(), (C.c_int * 1)()
-    got = [[]]
-    for fb in frames:
-        dev = torch.from_numpy(np.frombuffer(fb, dtype=np.uint8).copy()).cuda()
-        torch.cuda.synchronize()
-        assert hip.dsv2hip_enc_batch(1, encp, (C.c_void_p * 1)(dev.data_ptr()), bufs, nbufs) == 0
-        take_packets(hip, bufs, nbufs, got)
-    hip.dsv_enc_free(C.byref(enc))
-    return got[0]
-
-
 @pytest.mark.parametrize("aligned", [False, True], ids=["general_step", "wide_step"])
 def test_mixed_surfaces_in_one_step(aligned):
     """Five encoders with different content in one call per frame: packed as a surface (pitch = width), planar pitched, NV12,
@@ -274,26 +135,6 @@ REFUSALS = ([("pitch_short_planar_%d" % p, PLANAR, break_pitch(PLANAR, p)) for p
             [("layout_2_planar", PLANAR, bad_layout), ("layout_2_semiplanar", SEMI, bad_layout)])
 
 
-def refused(hip, encs, cs, single=True):
-    """the batch call on surfaces cs returns -1 and leaves nbufs alone; the one-frame call on each pair returns 0"""
-    n = len(encs)
-    encp = (C.POINTER(A.ENCODER) * n)(*[C.pointer(e) for e in encs])
-    bufs, nbufs = (A.BUF * (4 * n))(), (C.c_int * n)(*[77 + k for k in range(n)])
-    state = [bytes(C.string_at(C.byref(e), C.sizeof(e))) for e in encs]
-    assert hip.dsv2hip_enc_batch_surface(n, encp, (SURFACE * n)(*cs), bufs, nbufs) == -1
-    assert list(nbufs) == [77 + k for k in range(n)]
-    if single:
-        assert sum(hip.dsv2hip_enc_surface_frame(C.byref(e), C.byref(c), bufs) for e, c in zip(encs, cs)) == 0
-    assert [bytes(C.string_at(C.byref(e), C.sizeof(e))) for e in encs] == state
-    return encp, bufs, nbufs
-
-
-def copy_of(c):
-    d = SURFACE()
-    C.memmove(C.byref(d), C.byref(c), C.sizeof(c))
-    return d
-
-
 @pytest.mark.parametrize("what,layout,spoil", REFUSALS, ids=[r[0] for r in REFUSALS])
 def test_refused_surface_touches_nothing(what, layout, spoil):
     """Two encoders, the second one's surface spoiled: -1 (0 from the one-frame call), nbufs as the test set it; the same
@@ -301,7 +142,7 @@ def test_refused_surface_touches_nothing(what, layout, spoil):
     hip = bind(A.load_hip())
     w, h, name = 352, 288, "420"
     spec = CIF_NV12 if layout == SEMI else CIF_PLANAR
-    encs = new_encoders(hip, w, h, name, 2)
+    encs = encoders(hip, w, h, name, 2)
     good = [Surface(content(w, h, name, 3, 5 + s)[0], w, h, name, **spec) for s in range(2)]
     bad = copy_of(good[1].c)
     spoil(bad, w, h, name)
@@ -320,7 +161,7 @@ def test_refused_arguments():
     """n <= 0, NULL arrays, a NULL encoder, a NULL surface: refused, and the encoder still starts at frame 0"""
     hip = bind(A.load_hip())
     w, h, name = 352, 288, "420"
-    encs = new_encoders(hip, w, h, name, 1)
+    encs = encoders(hip, w, h, name, 1)
     sf = Surface(content(w, h, name, 3, 5)[0], w, h, name, **CIF_NV12)
     torch.cuda.synchronize()
     encp, bufs, nbufs = (C.POINTER(A.ENCODER) * 1)(C.pointer(encs[0])), (A.BUF * 4)(), (C.c_int * 1)(77)
@@ -353,7 +194,7 @@ def test_refused_on_a_uyvy_encoder():
     frame 0."""
     hip = bind(A.load_hip())
     w, h, name = 176, 144, "422"
-    encs = new_encoders(hip, w, h, name, 1)
+    encs = encoders(hip, w, h, name, 1)
     assert hip.dsv2hip_enc_set_uyvy_input(C.byref(encs[0]), 1) == 0
     spec = dict(layout=SEMI, pitches=(256, 256))
     sf = Surface(content(w, h, name, 3, 5)[0], w, h, name, **spec)
@@ -369,7 +210,7 @@ def test_refused_with_an_encoder_of_another_geometry():
     """352x288 and 176x144 in one call: -1; each then encodes on its own from frame 0."""
     hip = bind(A.load_hip())
     geo = [(352, 288), (176, 144)]
-    encs = [new_encoders(hip, w, h, "420", 1)[0] for w, h in geo]
+    encs = [encoders(hip, w, h, "420", 1)[0] for w, h in geo]
     spec = [CIF_NV12, dict(layout=SEMI, pitches=(256, 256))]
     first = [Surface(content(w, h, "420", 3, 5)[0], w, h, "420", **spec[k]) for k, (w, h) in enumerate(geo)]
     torch.cuda.synchronize()
@@ -381,7 +222,6 @@ def test_refused_with_an_encoder_of_another_geometry():
 
 
 # ---- 7. every way in, side by side ---------------------------------------------------------------------------------------------
-BGRA, RGBA, BGR, RGBP, BT709, HALF = 0x10, 0x11, 0x20, 0x22, 0x100, 0x1000
 # (call, layout, the picture in the surface, its planes as (row bytes, rows)) for nine 34x18 4:2:0 encoders
 WAYS_IN = [("plain", PLANAR, (34, 18), [(34, 18), (17, 9), (17, 9)]),
            ("plain", SEMI, (34, 18), [(34, 18), (34, 9)]),
@@ -392,20 +232,6 @@ WAYS_IN = [("plain", PLANAR, (34, 18), [(34, 18), (17, 9), (17, 9)]),
            ("scaled", RGBA | HALF, (67, 35), [(268, 35)]),
            ("sized", PLANAR, (35, 19), [(35, 19), (18, 10), (18, 10)]),
            ("sized", BGRA | BT709, (51, 27), [(204, 27)])]
-
-
-def bind_all_calls(hip):
-    P = C.POINTER
-    bind(hip)
-    for call in ("scaled", "sized"):
-        f = getattr(hip, "dsv2hip_enc_batch_surface_" + call)
-        f.argtypes, f.restype = [C.c_int, P(P(A.ENCODER)), P(SURFACE), P(C.c_int), P(C.c_int), P(A.BUF), P(C.c_int)], C.c_int
-        f = getattr(hip, "dsv2hip_enc_surface_frame_" + call)
-        f.argtypes, f.restype = [P(A.ENCODER), P(SURFACE), C.c_int, C.c_int, P(A.BUF)], C.c_int
-    for name in ("surface", "rgb", "scale", "resize", "rgb3"):
-        f = getattr(hip, "dsv2hip_enc_%s_stats" % name)
-        f.argtypes, f.restype = [P(C.c_ulonglong), C.c_int], None
-    return hip
 
 
 def all_forms(hip, reset=False):
@@ -422,7 +248,7 @@ def test_every_ingest_in_one_session():
     with NV12 and RGBA at half size from 67x35 and the sized call with planar from 35x19 and BGRA-709 from 51x27.  Every stream's packets
     are those of a fresh encoder fed the same surfaces alone through the matching one-frame call, and each of the five form counters
     counts its own kind and no other: tight pitches and 16-byte aligned planes, so only the sized RGB ingest (pitch 204) is wide."""
-    hip = bind_all_calls(A.load_hip())
+    hip = bind(A.load_hip())
     w, h, nfr = 34, 18, 3
     rng = np.random.RandomState(34)
     surfs = []  # [stream][frame]: (SURFACE, its tensors)
@@ -441,7 +267,7 @@ def test_every_ingest_in_one_session():
         surfs.append(per_frame)
     torch.cuda.synchronize()
     groups = {call: [s for s, way in enumerate(WAYS_IN) if way[0] == call] for call in ("plain", "scaled", "sized")}
-    encs = new_encoders(hip, w, h, "420", len(WAYS_IN))
+    encs = encoders(hip, w, h, "420", len(WAYS_IN))
     got = [[] for _ in WAYS_IN]
     all_forms(hip, reset=True)
     for t in range(nfr):
@@ -464,7 +290,7 @@ def test_every_ingest_in_one_session():
     for e in encs:
         hip.dsv_enc_free(C.byref(e))
     for s, (call, _, (sw, sh), _) in enumerate(WAYS_IN):
-        enc = new_encoders(hip, w, h, "420", 1)[0]
+        enc = encoders(hip, w, h, "420", 1)[0]
         alone, bufs = [[]], (A.BUF * 4)()
         for t in range(nfr):
             c = surfs[s][t][0]

@@ -16,7 +16,7 @@ import long_motion as L
 import mixed_steps as M
 from codec_run import encode_stream
 from hme_common import assert_fields_equal
-from test_gpu_dec_mixed_rounds import PARSE_IDS, parse_mode
+from hipabi import PARSE_IDS, parse_mode
 from test_oracle_bmc import clone
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import dsvabi as A
-from codec_run import encode_stream
+from codec_run import encode_stream, meta_packet as _meta_packet
 from conftest import load_pkg
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
@@ -77,20 +77,6 @@ def _feed(hip, dec, pk):
     if code == A.DEC_OK and fp:
         hip.dsv_frame_ref_dec(fp)
     return code
-
-
-def _ueg(v):
-    """bit string of the interleaved exp-Golomb code (bs.c:132)"""
-    v += 1
-    nb = v.bit_length() - 1
-    return "".join("0" + str((v >> i) & 1) for i in range(nb - 1, -1, -1)) + "1"
-
-
-def _meta_packet(fields):
-    bits = "".join(_ueg(f) for f in fields) + "0"
-    bits += "0" * (-len(bits) % 8)
-    body = bytes(int(bits[i:i + 8], 2) for i in range(0, len(bits), 8))
-    return b"DSV2" + bytes([8, 0x00]) + bytes(8) + body
 
 
 def test_hostile_packets_return_errors_not_crashes():

@@ -8,7 +8,6 @@ matrix of the validity rule, and dsv2hip_enc_sized_dims (the library loads witho
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,9 +17,8 @@ import dsvabi as A
 import ingest_resize as IR
 import ingest_scale as S
 import rgb_csc as R
-from test_egress_resize_cpu import SHAPES
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 FMT = {"444": (0, 0), "422": (1, 0), "420": (1, 1), "411": (2, 0), "410": (2, 2)}
 SUBSAMP = {"444": 0x0, "422": 0x4, "420": 0x5, "411": 0x8, "410": 0xA}
 UYVY = 0x14
@@ -29,19 +27,9 @@ UYVY = 0x14
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     """builds tools/ingest_resize_check.cpp with the sanitizers, runs its whole sweep and returns the directory of its dumped cases"""
-    work = tmp_path_factory.mktemp("ingest_resize")
-    exe, out = str(work / "ingest_resize_check"), work / "dump"
-    out.mkdir()
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "ingest_resize_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--dump", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert "in the wide form" in r.stdout and "cases of the validity rule equal its restatement" in r.stdout
-    return str(out)
+    out, dump = build_and_run("tools/ingest_resize_check.cpp", tmp_path_factory.mktemp("ingest_resize"), ["--dump", "{dump}"], timeout=900)
+    assert "in the wide form" in out and "cases of the validity rule equal its restatement" in out
+    return dump
 
 
 def same_bytes(name, got, want):
@@ -88,7 +76,7 @@ def test_the_sweep_ran_the_promised_cases(dump_dir):
         f = line.split()
         rec = (f[1], f[2], f[3], tuple(int(v) for v in f[4:8]), int(f[8]), int(f[9]), int(f[10]))
         (yuv if f[0] == "yuv" else rgb).add(rec)
-    for shape in SHAPES:
+    for shape in AR.SWEEP_SHAPES:
         for layout in ("planar", "semi"):
             # (the documented rule: the wide form needs every source plane's row bytes to be a multiple of 4)
             can_wide = all(rb % 4 == 0 for rb, _ in S.source_dims(shape[0], shape[1], 1, 1, S.SEMI if layout == "semi" else S.PLANAR))
@@ -96,7 +84,7 @@ def test_the_sweep_ran_the_promised_cases(dump_dir):
             assert forms == ({"wide", "general"} if can_wide else {"general"}), (shape, layout)
             assert {(r[5], r[6]) for r in yuv if r[1] == layout and r[3] == shape and r[4] == -1} == set(itertools.product(range(3), range(4)))
             assert {r[4] for r in yuv if r[1] == layout and r[3] == shape} == {-1, 0, 1, 254, 255}
-    assert sum(all(rb % 4 == 0 for rb, _ in S.source_dims(c[0], c[1], 1, 1, S.SEMI)) for c in SHAPES) >= 4
+    assert sum(all(rb % 4 == 0 for rb, _ in S.source_dims(c[0], c[1], 1, 1, S.SEMI)) for c in AR.SWEEP_SHAPES) >= 4
     assert any(r[3][2] > 256 for r in yuv) and any(r[3][2] > 256 for r in rgb)  # a row of more than one workgroup
     assert {r[2] for r in yuv} == set(FMT) and {r[2] for r in rgb} == set(FMT)
     assert {r[1] for r in rgb} == {"%s%03x" % (o, c) for o in ("bgra", "rgba") for c in (0x000, 0x100, 0x200, 0x300)}

@@ -6,7 +6,6 @@ GPU), that the scaled and sized grammars know nothing of the three layouts.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +13,8 @@ import pytest
 import dsvabi as A
 import rgb3_csc as R3
 import rgb_csc as R
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 FMT = {"444": (0, 0), "422": (1, 0), "420": (1, 1), "411": (2, 0), "410": (2, 2)}
 SUBSAMP = {name: 4 * hs + vs for name, (hs, vs) in FMT.items()}  # DSV_SUBSAMP_*: the two shifts
 
@@ -23,19 +22,9 @@ SUBSAMP = {name: 4 * hs + vs for name, (hs, vs) in FMT.items()}  # DSV_SUBSAMP_*
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     """builds tools/ingest_rgb3_check.cpp with the sanitizers, runs its whole sweep and returns the directory of its dumped cases"""
-    work = tmp_path_factory.mktemp("ingest_rgb3")
-    exe, out = str(work / "ingest_rgb3_check"), work / "dump"
-    out.mkdir()
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "ingest_rgb3_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--dump", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=60)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert "in the wide form" in r.stdout
-    return str(out)
+    out, dump = build_and_run("tools/ingest_rgb3_check.cpp", tmp_path_factory.mktemp("ingest_rgb3"), ["--dump", "{dump}"], timeout=60)
+    assert "in the wide form" in out
+    return dump
 
 
 def test_kernel_body_sweep_is_clean_and_equals_the_numpy_oracle(dump_dir):

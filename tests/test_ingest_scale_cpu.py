@@ -7,7 +7,6 @@ colours, the refusal matrix of the validity rule, and dsv2hip_enc_scaled_dims (t
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,8 +15,8 @@ import box_reduce as B
 import dsvabi as A
 import ingest_scale as S
 import rgb_csc as R
+from sanitized_tool import build_and_run
 
-HIPCC = "/opt/rocm/bin/hipcc"
 FMT = {"444": (0, 0), "422": (1, 0), "420": (1, 1), "411": (2, 0), "410": (2, 2)}
 SUBSAMP = {"444": 0x0, "422": 0x4, "420": 0x5, "411": 0x8, "410": 0xA}
 UYVY = 0x14
@@ -26,19 +25,9 @@ UYVY = 0x14
 @pytest.fixture(scope="module")
 def dump_dir(tmp_path_factory):
     """builds tools/ingest_scale_check.cpp with the sanitizers, runs its whole sweep and returns the directory of its dumped cases"""
-    work = tmp_path_factory.mktemp("ingest_scale")
-    exe, out = str(work / "ingest_scale_check"), work / "dump"
-    out.mkdir()
-    # (host code only, and the sanitizers named for the host side alone: nothing sanitized is ever built for the GPU)
-    cmd = [HIPCC, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I", os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc"), os.path.join(A.ROOT, "tools", "ingest_scale_check.cpp"), "-o", exe]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, "--dump", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    assert "in the wide form" in r.stdout and "cases of the validity rule equal its restatement" in r.stdout
-    return str(out)
+    out, dump = build_and_run("tools/ingest_scale_check.cpp", tmp_path_factory.mktemp("ingest_scale"), ["--dump", "{dump}"], timeout=900)
+    assert "in the wide form" in out and "cases of the validity rule equal its restatement" in out
+    return dump
 
 
 def same_bytes(name, got, want):

@@ -16,9 +16,8 @@ import pytest
 import dsvabi as A
 from codec_run import encode_stream
 from conftest import load_pkg
+from sanitized_tool import HIPCC, run
 
-HIPCC = "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(A.ROOT, "digital-subband-video-2_amd", "csrc")
 pytestmark = [pytest.mark.skipif(not os.path.exists(A.REF_SO), reason="oracle/_ref not built"),
               pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")]
 
@@ -48,10 +47,8 @@ def test_parser_survives_damaged_packets(tmp_path, fuzz_bin, w, h, subsamp, fmt,
     packets = encode_stream(ref, [v.frame_bytes(t) for t in range(6)], w, h, subsamp, eos=True, qp=qp, gop=gop)[0]
     path = str(tmp_path / "packets.bin")
     write_packets(path, [packets])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([fuzz_bin, path, "400", "11"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
-    rep = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run(fuzz_bin, [path, "400", "11"], timeout=900, abort_on_error=1)
+    rep = json.loads(out.strip().splitlines()[-1])
     assert rep["clean_pictures"] == 6 and rep["clean_planes_ok"] == 18 and rep["clean_planes_bad"] == 0
     # the damaged copies really went through the parser, and through both of its outcomes
     assert rep["damaged_parsed"] > 1000 and rep["damaged_refused"] > 0 and rep["damaged_planes_bad"] > 0

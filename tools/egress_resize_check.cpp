@@ -23,43 +23,23 @@
 
 #include "egress_resize.h"
 
+#include "check_support.h"
+
 using namespace dsv2;
 
 namespace {
 
-constexpr uint8_t kGuard = 0xA5;
-constexpr int kLead = 64; // guard bytes in front of and behind the destination
+using support::kGuard;
+using support::kLead; // guard bytes in front of and behind the destination
 
-struct Plane {
-    uint8_t *alloc, *org;
-    size_t bytes;
-    int stride, w, h;
-    std::vector<uint8_t> was;
+struct Plane : support::Plane {
     // bordered: as dframe_alloc lays a plane out (32-pixel border, stride a multiple of 16, 16-byte aligned origin); else as the
     // decoder stages a luma plane: no border, stride = w rounded up to 16, h rows.  constant >= 0: the visible pixels hold that value
     // (border and padding keep their noise)
-    Plane(int w_, int h_, bool bordered, unsigned seed, int constant = -1) : w(w_), h(h_)
+    Plane(int w_, int h_, bool bordered, unsigned seed, int constant = -1)
+        : support::Plane(w_, h_, bordered ? kBorder : 0, seed, support::noise_extremes, constant)
     {
-        const int b = bordered ? kBorder : 0;
-        stride = (w + 2 * b + 15) & ~15;
-        bytes = (size_t) stride * (size_t) (h + 2 * b);
-        alloc = (uint8_t *) aligned_alloc(16, bytes);
-        for (size_t i = 0; i < bytes; i++) { // (a quarter of the samples are 0 or 255)
-            seed = seed * 1664525u + 1013904223u;
-            alloc[i] = (seed >> 30) == 0 ? ((seed & 0x10000) ? 255 : 0) : (uint8_t) (seed >> 20);
-        }
-        org = alloc + (size_t) b * stride + b;
-        if (constant >= 0) {
-            for (int y = 0; y < h; y++) {
-                memset(org + (size_t) y * stride, constant, (size_t) w);
-            }
-        }
-        was.assign(alloc, alloc + bytes);
     }
-    ~Plane() { free(alloc); }
-    Plane(const Plane &) = delete;
-    int at(int x, int y) const { return org[(size_t) y * stride + x]; }
-    bool unchanged() const { return memcmp(was.data(), alloc, bytes) == 0; }
 };
 
 long long gcd_of(long long x, long long y) { return y ? gcd_of(y, x % y) : x; }
@@ -303,10 +283,7 @@ long dump_allowed()
 
 int main(int argc, char **argv)
 {
-    if (argc == 3 && strcmp(argv[1], "--dump") == 0) {
-        g_dump = argv[2];
-    } else if (argc != 1) {
-        fprintf(stderr, "usage: %s [--dump DIR]\n", argv[0]);
+    if (!support::dump_option(argc, argv, &g_dump)) {
         return 2;
     }
     const long divisions = check_divisions();

@@ -19,54 +19,33 @@
 
 #include "egress_rgb.h"
 
+#include "check_support.h"
+
 using namespace dsv2;
 
 namespace {
 
-constexpr uint8_t kGuard = 0xA5;
-constexpr int kLead = 64; // guard bytes in front of and behind the surface
+using support::kFmtName;
+using support::kGuard;
+using support::kHs;
+using support::kLead; // guard bytes in front of and behind the surface
+using support::kPreset;
+using support::preset_of;
+using support::kVs;
 
 // ---- the conversion, restated: one pixel at a time, in the header's own terms ---------------------------------------------------
-const long kPreset[4][6] = {{298, 16, 409, -100, -208, 516}, {298, 16, 459, -55, -136, 541}, {256, 0, 359, -88, -183, 454}, {256, 0, 403, -48, -120, 475}};
-int preset_of(int csc) { return ((csc & 0x200) ? 2 : 0) + ((csc & 0x100) ? 1 : 0); }
-
-long floor_shift8(long v) { return v >= 0 ? v / 256 : -((-v + 255) / 256); }
-uint8_t clamp255(long v) { return (uint8_t) (v < 0 ? 0 : v > 255 ? 255 : v); }
-
 void expect_pixel(int csc, bool bgra, int Y, int U, int V, uint8_t out[4])
 {
-    const long *p = kPreset[preset_of(csc)];
-    const long C = p[0] * (Y - p[1]), D = U - 128, E = V - 128;
-    const uint8_t R = clamp255(floor_shift8(C + p[2] * E + 128)), G = clamp255(floor_shift8(C + p[3] * D + p[4] * E + 128)),
-                  B = clamp255(floor_shift8(C + p[5] * D + 128));
-    out[0] = bgra ? B : R, out[1] = G, out[2] = bgra ? R : B, out[3] = 255;
+    uint8_t rgb[3];
+    support::expect_pixel(csc, Y, U, V, rgb);
+    out[0] = rgb[bgra ? 2 : 0], out[1] = rgb[1], out[2] = rgb[bgra ? 0 : 2], out[3] = 255;
 }
 
 // ---- source planes: an exact-size heap block each ---------------------------------------------------------------------------------
-struct Plane {
-    uint8_t *alloc, *org;
-    size_t bytes;
-    int stride, w, h;
-    std::vector<uint8_t> was;
+struct Plane : support::Plane {
     // bordered: as dframe_alloc lays a plane out (32-pixel border, stride a multiple of 16, 16-byte aligned origin); else as the
     // decoder stages a luma plane: no border, stride = w rounded up to 16, h rows
-    Plane(int w_, int h_, bool bordered, unsigned seed) : w(w_), h(h_)
-    {
-        const int b = bordered ? kBorder : 0;
-        stride = (w + 2 * b + 15) & ~15;
-        bytes = (size_t) stride * (size_t) (h + 2 * b);
-        alloc = (uint8_t *) aligned_alloc(16, bytes);
-        for (size_t i = 0; i < bytes; i++) { // (border and padding hold noise too)
-            seed = seed * 1664525u + 1013904223u;
-            alloc[i] = (seed >> 29) == 0 ? ((seed & 0x10000) ? 255 : 0) : (seed >> 28) == 2 ? ((seed & 0x10000) ? 235 : 16) : (uint8_t) (seed >> 20);
-        }
-        org = alloc + (size_t) b * stride + b;
-        was.assign(alloc, alloc + bytes);
-    }
-    ~Plane() { free(alloc); }
-    Plane(const Plane &) = delete;
-    int at(int x, int y) const { return org[(size_t) y * stride + x]; }
-    bool unchanged() const { return memcmp(was.data(), alloc, bytes) == 0; }
+    Plane(int w_, int h_, bool bordered, unsigned seed) : support::Plane(w_, h_, bordered ? kBorder : 0, seed, support::noise_range_ends) {}
 };
 
 template <bool WIDE> void run_grid(const RgbOutJob &j)
@@ -85,8 +64,6 @@ template <bool WIDE> void run_grid(const RgbOutJob &j)
     }
 }
 
-const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
-const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
 long g_cases = 0, g_wide = 0;
 const char *g_dump = nullptr;
 
@@ -187,10 +164,7 @@ void named(int w, int h, int fmt, int csc, bool bgra, int pitch_kind, int offset
 
 int main(int argc, char **argv)
 {
-    if (argc == 3 && strcmp(argv[1], "--dump") == 0) {
-        g_dump = argv[2];
-    } else if (argc != 1) {
-        fprintf(stderr, "usage: %s [--dump DIR]\n", argv[0]);
+    if (!support::dump_option(argc, argv, &g_dump)) {
         return 2;
     }
     static const int cscs[4] = {0x000, 0x100, 0x200, 0x300};

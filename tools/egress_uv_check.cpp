@@ -13,28 +13,16 @@
 
 #include "egress_uv.h"
 
+#include "check_support.h"
+
 using namespace dsv2;
 
 namespace {
 
-constexpr uint8_t kGuard = 0xA5;
+using support::kGuard;
 
-struct Plane { // as dframe_alloc lays one out: 32-pixel border, stride a multiple of 16, 16-byte aligned origin
-    uint8_t *alloc, *org;
-    int stride, w, h;
-    Plane(int w_, int h_, unsigned seed) : w(w_), h(h_)
-    {
-        stride = (w + 2 * kBorder + 15) & ~15;
-        const size_t bytes = (size_t) stride * (size_t) (h + 2 * kBorder);
-        alloc = (uint8_t *) aligned_alloc(16, (bytes + 15) & ~(size_t) 15);
-        for (size_t i = 0; i < bytes; i++) { // (the border holds noise too: a non-reference picture's is never extended)
-            seed = seed * 1664525u + 1013904223u;
-            alloc[i] = (uint8_t) (seed >> 24);
-        }
-        org = alloc + (size_t) kBorder * stride + kBorder;
-    }
-    ~Plane() { free(alloc); }
-    int at(int x, int y) const { return org[(size_t) y * stride + x]; }
+struct Plane : support::Plane { // as dframe_alloc lays one out: 32-pixel border, stride a multiple of 16, 16-byte aligned origin
+    Plane(int w_, int h_, unsigned seed) : support::Plane(w_, h_, kBorder, seed, support::noise_plain) {}
 };
 
 int imin(int a, int b) { return a < b ? a : b; }

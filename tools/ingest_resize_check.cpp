@@ -23,52 +23,25 @@
 #include "ingest_plan.h"
 #include "ingest_resize.h"
 
+#include "check_support.h"
+
 using namespace dsv2;
 
 namespace {
 
-constexpr uint8_t kGuard = 0xA5;
-constexpr int kGuardBytes = 64;
+using support::ceil_shift;
+using support::dump_rows;
+using support::kGuard;
+using support::kMatrix;
+using support::preset_of;
+constexpr int kGuardBytes = support::kLead;
 
-const int kMatrix[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},
-                           {47, 157, 16, -26, -86, 112, 112, -102, -10},
-                           {77, 150, 29, -43, -85, 128, 128, -107, -21},
-                           {54, 183, 19, -29, -99, 128, 128, -116, -12}};
-int preset_of(int csc) { return ((csc & 0x200) ? 2 : 0) + ((csc & 0x100) ? 1 : 0); }
-int ceil_shift(int v, int s) { return (v + (1 << s) - 1) >> s; }
+
 long gcd_of(long x, long y) { return y ? gcd_of(y, x % y) : x; }
 
 // ---- planes as dframe_alloc lays them out (32-pixel border, stride a multiple of 16, 16-byte aligned origin), 64 guard bytes round them
-struct Plane {
-    uint8_t *alloc, *first, *org;
-    size_t bytes;
-    int stride, w, h;
-    Plane(int w_, int h_) : w(w_), h(h_)
-    {
-        stride = (w + 2 * kBorder + 15) & ~15;
-        bytes = (size_t) stride * (size_t) (h + 2 * kBorder) + 2 * kGuardBytes;
-        alloc = (uint8_t *) aligned_alloc(16, (bytes + 15) & ~(size_t) 15);
-        memset(alloc, kGuard, bytes);
-        first = alloc + kGuardBytes;
-        org = first + (size_t) kBorder * stride + kBorder;
-    }
-    ~Plane() { free(alloc); }
-    Plane(const Plane &) = delete;
-    // every byte is the guard value except the w x h samples, which are want(x, y)
-    template <class F> bool equals(F want, long *bad_x, long *bad_y, int *got, int *expected) const
-    {
-        for (size_t i = 0; i < bytes; i++) {
-            const long at = (long) i - kGuardBytes;
-            long y = at >= 0 ? at / stride - kBorder : -1000, x = at >= 0 ? at % stride - kBorder : -1000;
-            const bool inside = at >= 0 && x >= 0 && x < w && y >= 0 && y < h;
-            const int e = inside ? want((int) x, (int) y) : kGuard;
-            if (alloc[i] != e) {
-                *bad_x = x, *bad_y = y, *got = alloc[i], *expected = e;
-                return false;
-            }
-        }
-        return true;
-    }
+struct Plane : support::GuardedPlane {
+    Plane(int w_, int h_) : support::GuardedPlane(w_, h_, kBorder, kGuardBytes) {}
 };
 
 // an exact-size source block: `offset` bytes, then rows of rb bytes `pitch` apart, nothing behind the last row
@@ -101,28 +74,15 @@ struct SourceBlock {
     SourceBlock(const SourceBlock &) = delete;
 };
 
-const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+using support::kHs;
+using support::kVs;
 const int kSubsamp[5] = {DSV_SUBSAMP_444, DSV_SUBSAMP_422, DSV_SUBSAMP_420, DSV_SUBSAMP_411, DSV_SUBSAMP_410};
-const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
+using support::kFmtName;
 long g_cases[2] = {0, 0}, g_wide[2] = {0, 0}, g_planes = 0;
 const char *g_dump = nullptr;
 FILE *g_case_list = nullptr;
 
-void dump_rows(FILE *f, const uint8_t *p, size_t pitch, size_t rb, int rows)
-{
-    for (int y = 0; y < rows; y++) {
-        fwrite(p + (size_t) y * pitch, 1, rb, f);
-    }
-}
-FILE *dump_open(const char *name, const char *ext)
-{
-    FILE *f = fopen((std::string(g_dump) + "/" + name + ext).c_str(), "wb");
-    if (!f) {
-        fprintf(stderr, "cannot write into %s\n", g_dump);
-        exit(1);
-    }
-    return f;
-}
+FILE *dump_open(const char *name, const char *ext) { return support::dump_open(g_dump, name, ext); }
 
 // ---- the resampling, restated: the overlap of [lo0, hi0) and [lo1, hi1) --------------------------------------------------------
 long overlap(long lo0, long hi0, long lo1, long hi1)

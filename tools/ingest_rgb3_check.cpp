@@ -22,67 +22,24 @@
 #include "ingest_plan.h"
 #include "ingest_rgb3.h"
 
+#include "check_support.h"
+
 using namespace dsv2;
 
 namespace {
 
-constexpr uint8_t kGuard = 0xA5;
+using support::expect_chroma;
+using support::expect_luma;
+using support::kGuard;
+using support::Picture;
 enum Order { BGR = 0, RGB = 1, RGBP = 2 };
 const char *const kOrderName[3] = {"bgr", "rgb", "rgbp"};
 
-// ---- the conversion, restated: one sample at a time, signed arithmetic, coordinates clamped -----------------------------------
-const int kMatrix[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},
-                           {47, 157, 16, -26, -86, 112, 112, -102, -10},
-                           {77, 150, 29, -43, -85, 128, 128, -107, -21},
-                           {54, 183, 19, -29, -99, 128, 128, -116, -12}};
-int preset_of(int csc) { return ((csc & 0x200) ? 2 : 0) + ((csc & 0x100) ? 1 : 0); }
-
-struct Picture { // the surface's pixels as R, G, B triples, whatever its layout
-    int w, h;
-    std::vector<int> rgb;
-    const int *at(int x, int y) const
-    {
-        x = x < w - 1 ? x : w - 1;
-        y = y < h - 1 ? y : h - 1;
-        return &rgb[3 * ((size_t) y * w + x)];
-    }
-};
-
-int expect_luma(const Picture &p, int csc, int x, int y)
-{
-    const int *m = kMatrix[preset_of(csc)], *c = p.at(x, y);
-    const int ybase = (csc & 0x200) ? 0 : 16;
-    return (m[0] * c[0] + m[1] * c[1] + m[2] * c[2] + 128 + 256 * ybase) >> 8;
-}
-
-int expect_chroma(const Picture &p, int csc, int row, int hs, int vs, int cx, int cy)
-{
-    const int *m = kMatrix[preset_of(csc)] + 3 * row;
-    long sum = 0;
-    for (int dy = 0; dy < 1 << vs; dy++) {
-        for (int dx = 0; dx < 1 << hs; dx++) {
-            const int *c = p.at((cx << hs) + dx, (cy << vs) + dy);
-            sum += m[0] * c[0] + m[1] * c[1] + m[2] * c[2];
-        }
-    }
-    const long v = (sum + (32896L << (hs + vs))) >> (8 + hs + vs);
-    return (int) (v < 255 ? v : 255);
-}
+// (the conversion, restated one sample at a time: check_support.h)
 
 // ---- planes as dframe_alloc lays them out: 32-pixel border, stride a multiple of 16, 16-byte aligned origin ---------------------
-struct Plane {
-    uint8_t *alloc, *org;
-    size_t bytes;
-    int stride, w, h;
-    Plane(int w_, int h_) : w(w_), h(h_)
-    {
-        stride = (w + 2 * kBorder + 15) & ~15;
-        bytes = (size_t) stride * (size_t) (h + 2 * kBorder);
-        alloc = (uint8_t *) aligned_alloc(16, bytes);
-        memset(alloc, kGuard, bytes);
-        org = alloc + (size_t) kBorder * stride + kBorder;
-    }
-    ~Plane() { free(alloc); }
+struct Plane : support::GuardedPlane {
+    Plane(int w_, int h_) : support::GuardedPlane(w_, h_, kBorder, 0) {}
 };
 
 // a source plane: `offset` bytes, then h rows of rb bytes `pitch` apart, and not one byte more
@@ -123,9 +80,10 @@ template <class F> void run_grid(int h, F thread)
     }
 }
 
-const int kHs[5] = {0, 1, 1, 2, 2}, kVs[5] = {0, 0, 1, 0, 2};
+using support::kHs;
+using support::kVs;
 const int kSubsamp[5] = {DSV_SUBSAMP_444, DSV_SUBSAMP_422, DSV_SUBSAMP_420, DSV_SUBSAMP_411, DSV_SUBSAMP_410};
-const char *const kFmtName[5] = {"444", "422", "420", "411", "410"};
+using support::kFmtName;
 long g_cases = 0, g_wide[2] = {0, 0};
 const char *g_dump = nullptr;
 
@@ -263,10 +221,7 @@ void check(int w, int h, int fmt, int csc, Order order, int pitch_kind, int offs
 
 int main(int argc, char **argv)
 {
-    if (argc == 3 && strcmp(argv[1], "--dump") == 0) {
-        g_dump = argv[2];
-    } else if (argc != 1) {
-        fprintf(stderr, "usage: %s [--dump DIR]\n", argv[0]);
+    if (!support::dump_option(argc, argv, &g_dump)) {
         return 2;
     }
     static const int cscs[4] = {0x000, 0x100, 0x200, 0x300};
