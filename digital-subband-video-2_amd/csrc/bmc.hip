@@ -2415,7 +2415,6 @@ void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool
 // One job per picture (TensorOutJob, dev.h), fetched by value and pinned to scalar registers; k_egress_rgb's shape: 64 x 4 threads
 // cover 16 rows and walk the row in passes of 256 pixels.  The thread's work is egress_tensor.h's egress_tensor_rows (which
 // tools/egress_tensor_check.cpp runs on the CPU); the job's element type is uniform over the workgroup.
-__device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float, uni(__builtin_bit_cast(int, v))); }
 template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_tensor(const TensorOutJob *__restrict__ tab)
 {
     DSV2_KERNEL_PRIO();

@@ -62,6 +62,7 @@ template <class T> __device__ __forceinline__ T *uni_ptr(T *p)
     return (T *) (((unsigned long long) hi << 32) | lo);
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uni(float v) { return __builtin_bit_cast(float, uni(__builtin_bit_cast(int, v))); }
 __device__ __forceinline__ DPlane uni(const DPlane &p) { return DPlane{uni_ptr(p.data), uni(p.stride), uni(p.w), uni(p.h)}; }
 
 template <class T> __device__ __forceinline__ T job_of(const T *tab, unsigned i)
@@ -278,6 +279,30 @@ inline bool tensor_job_wide(const TensorOutJob &j)
     }
     return (bits & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
 }
+struct TensorInJob { // one picture that is three planes R, G, B of a caller's float tensor (dsv2hip_in_tensor: binary16, bfloat16 or binary32
+                     // elements) on its way into the three bordered source planes: taken through the job's per-plane scale and bias, clamped and
+                     // rounded to bytes, then converted as a planar RGB surface is (ingest_tensor.h, frame.hip: k_ingest_tensor); 152 bytes,
+                     // fetched by value through the scalar cache like Rgb3Job, whose destination side it shares.  (A uint8 tensor is an Rgb3Job.)
+    const uint8_t *src[3]; // device memory, element aligned: row y of R, G, B at src[c] + y * pitch[c], w elements of it read
+    size_t pitch[3];       // bytes, multiples of the element size
+    uint8_t *dst[3];       // Y, U, V planes from dframe_alloc
+    int ystride, cstride;  // RgbJob's, as w, h, hs, vs and the quads
+    int w, h;
+    int hs, vs;
+    int dtype;             // kTensorF16, kTensorBF16, kTensorF32
+    uint32_t ycoef, upos, uneg, vpos, vneg; // the planar kind's: R G B in bytes 0..2 of a pixel dword
+    uint32_t yoff;
+    float scale[3], bias[3]; // the byte of element e of plane c is rint(min(max(fl32(fl32(e * scale[c]) + bias[c]), 0), 255)), 0 for a NaN
+};
+// every plane's pointer and pitch multiples of four elements and w of 4: a thread's four elements of a row arrive as one vector load
+inline bool tensor_in_job_wide(const TensorInJob &j)
+{
+    uintptr_t bits = 0;
+    for (int c = 0; c < 3; c++) {
+        bits |= ((uintptr_t) j.src[c]) | (uintptr_t) j.pitch[c];
+    }
+    return (bits & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
+}
 struct ScaleOutJob { // one plane of a decoded picture on its way out at half, quarter or eighth size (dsv2hip_out_surface, DSV2HIP_SCALE_*): the box
                      // average of include/dsv2_hip.h (egress_scale.h, bmc.hip: k_egress_scale) into a plane of the caller's surface, or into the
                      // decoder's staging picture that k_egress_uv / k_egress_rgb then read; 40 bytes, fetched by value through the scalar cache
@@ -365,6 +390,9 @@ inline bool rgb3_job_wide(const Rgb3Job &j)
     }
     return (m & 3) == 0;
 }
+// n float tensors of h rows (TensorInJob above; the element types may differ from job to job); wide: every job's plane pointers and
+// pitches are multiples of four elements and w of 4 (tensor_in_job_wide)
+void ingest_tensor_batch(hipStream_t s, const TensorInJob *d_jobs, int n, int h, bool wide);
 // Half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled): the records of k_ingest_surface_scaled and
 // k_ingest_rgb_scaled (frame.hip, ingest_scale.h), in tables of their own behind the two above.
 struct ScaledSurfaceJob { // one SOURCE plane of a caller's surface, box-averaged (the decoder's REDUCTION, include/dsv2_hip.h) on its way into a

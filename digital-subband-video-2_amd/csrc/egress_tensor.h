@@ -24,41 +24,14 @@
 #pragma once
 
 #include "egress_rgb.h"
+#include "tensor_num.h"
 
 namespace dsv2 {
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// (tensor_affine, tensor_f32_bits, tensor_f16_pair, tensor_bf16_bits and u32x2: tensor_num.h, shared with ingest_tensor.h)
 
-__host__ __device__ __forceinline__ float tensor_affine(float v, float scale, float bias)
-{
-#pragma clang fp contract(off)
-    const float p = v * scale;
-    return p + bias;
-}
-__host__ __device__ __forceinline__ uint32_t tensor_f32_bits(float f) { return __builtin_bit_cast(uint32_t, f); }
-typedef float tensor_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 tensor_f16x2 __attribute__((ext_vector_type(2)));
-// two binary32 values as a pair of binary16 in one dword, lo in bits 0 .. 15: one v_cvt_pk_f16_f32 on gfx950
-__host__ __device__ __forceinline__ uint32_t tensor_f16_pair(float lo, float hi)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(tensor_f32x2{lo, hi}, tensor_f16x2));
-}
-__host__ __device__ __forceinline__ uint32_t tensor_bf16_bits(float f)
-{
-    const uint32_t b = tensor_f32_bits(f);
-    return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-}
-
-// A row number all lanes share, handed on as a value the compiler knows nothing about (lane_offset's scalar counterpart): the twelve
-// destination rows of a pass -- four rows of three planes -- are then addressed where they are stored, a scalar multiply-add each,
-// instead of living in 24 scalar registers across the loop next to the job's 34 (the first build of this file spilled them).
-__host__ __device__ __forceinline__ int row_number(int y)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(y));
-#endif
-    return y;
-}
+// (row_number: tensor_num.h -- the twelve destination rows of a pass are addressed where they are stored; the first build of this
+// file kept them in 24 scalar registers across the loop next to the job's 34 and spilled them)
 
 // the conversion's terms with byte 0 = R, byte 1 = G, byte 2 = B
 __host__ __device__ __forceinline__ RgbTerms tensor_terms(const TensorOutJob &j)

@@ -1519,7 +1519,7 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 // pyramids and source pre-pass still enqueued on the stream)
 static std::atomic<int> g_fail_next_step{0};
 // steps whose ingest of a launch class ran in the wide / the general form: [2 * class + (wide ? 0 : 1)] (dsv2hip_enc_surface_stats,
-// _rgb_stats, _scale_stats, _resize_stats, _rgb3_stats, each over its one or two classes)
+// _rgb_stats, _scale_stats, _resize_stats, _rgb3_stats, _tensor_stats, each over its one or two classes)
 static std::atomic<unsigned long long> g_ingest_steps[2 * enc_ingest::kClasses];
 
 // workgroups per (picture, plane) of the entropy coder's chunk kernels; each walks its share of the plane's 1 024-symbol chunks
@@ -1712,9 +1712,10 @@ struct Ingest {
     Tab<SizedSurfaceJob> sized_surf;
     Tab<SizedRgbJob> sized_rgb;
     Tab<Rgb3Job> rgb3[2];
-    size_t room[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0}; // entries the step's plans need of each table
-    int n[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool wide[enc_ingest::kClasses] = {true, true, true, true, true, true, true, true}; // IngestPlan's, over the step
+    Tab<TensorInJob> tensor;
+    size_t room[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // entries the step's plans need of each table
+    int n[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool wide[enc_ingest::kClasses] = {true, true, true, true, true, true, true, true, true}; // IngestPlan's, over the step
     int scaled_row_bytes = 0, scaled_rgb_sw = 0;
     void count(const std::vector<enc_ingest::IngestPlan> &plans)
     {
@@ -1735,6 +1736,7 @@ struct Ingest {
         sized_rgb = Tab<SizedRgbJob>(tabs, room[SIZED_RGB]);
         rgb3[0] = Tab<Rgb3Job>(tabs, room[RGB3_PACKED]);
         rgb3[1] = Tab<Rgb3Job>(tabs, room[RGB3_PLANAR]);
+        tensor = Tab<TensorInJob>(tabs, room[TENSOR_IN]);
     }
     template <class T> void append(Tab<T> &t, int cl, const T *jobs, const enc_ingest::IngestPlan &p)
     {
@@ -1753,6 +1755,7 @@ struct Ingest {
         append(sized_rgb, SIZED_RGB, p.sized_rgb, p);
         append(rgb3[0], RGB3_PACKED, p.rgb3, p);
         append(rgb3[1], RGB3_PLANAR, p.rgb3, p);
+        append(tensor, TENSOR_IN, p.tensor, p);
         scaled_row_bytes = std::max(scaled_row_bytes, p.scaled_row_bytes);
         scaled_rgb_sw = std::max(scaled_rgb_sw, p.scaled_rgb_sw);
     }
@@ -1790,6 +1793,9 @@ struct Ingest {
             if (ran(RGB3_PACKED + kind)) {
                 ingest_rgb3_batch(bs, rgb3[kind].d, n[RGB3_PACKED + kind], h, kind == kRgb3Planar, wide[RGB3_PACKED + kind]);
             }
+        }
+        if (ran(TENSOR_IN)) {
+            ingest_tensor_batch(bs, tensor.d, n[TENSOR_IN], h, wide[TENSOR_IN]);
         }
     }
 };
@@ -2714,20 +2720,24 @@ static bool accept_surface(enc_ingest::Call call, const DSV_ENCODER *enc, const 
     return enc_ingest::accept(call, enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, uyvy_input, sf, src_w, src_h, out);
 }
 
-/* dsv2hip_enc_batch for surfaces; surf[k] is read during the call only.  Refused as a whole with -1, nothing touched, for what
- * dsv2hip_enc_batch refuses or a surface accept() does not pass.  src_w, src_h: of the scaled and the sized call */
-static int surface_batch(enc_ingest::Call call, int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs,
-                         int *nbufs)
+static bool accept_tensor(const DSV_ENCODER *enc, const dsv2hip_in_tensor &t, enc_ingest::Source *out)
 {
-    const bool plain = call == enc_ingest::CALL_PLAIN;
-    if (n <= 0 || !encs || !surf || (!plain && (!src_w || !src_h)) || !bufs || !nbufs) {
+    const bool uyvy_input = enc->ref && ((const EncImpl *) enc->ref)->input_uyvy;
+    return enc_ingest::accept_tensor(enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, uyvy_input, t, out);
+}
+
+/* dsv2hip_enc_batch for pictures that accept_k(k, &source) admits: surfaces or tensors, read during the call only.  Refused as a whole
+ * with -1, nothing touched, for what dsv2hip_enc_batch refuses, a missing argument (have_args) or an entry accept_k does not pass. */
+extern "C++" { // (templates: this stretch of the file has C linkage)
+template <class Accept> static int source_batch(int n, DSV_ENCODER **encs, bool have_args, DSV_BUF *bufs, int *nbufs, Accept accept_k)
+{
+    if (n <= 0 || !encs || !have_args || !bufs || !nbufs) {
         return -1;
     }
     std::vector<Job> jobs((size_t) n);
     for (int k = 0; k < n; k++) {
         memset(&jobs[(size_t) k], 0, sizeof(Job));
-        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) ||
-            !accept_surface(call, encs[k], surf[k], plain ? 0 : src_w[k], plain ? 0 : src_h[k], &jobs[(size_t) k].source)) {
+        if (!enc_usable(encs[k]) || step_key(encs[k]) != step_key(encs[0]) || !accept_k(k, &jobs[(size_t) k].source)) {
             return -1;
         }
         jobs[(size_t) k].enc = encs[k];
@@ -2740,18 +2750,43 @@ static int surface_batch(enc_ingest::Call call, int n, DSV_ENCODER **encs, const
     return ok ? 0 : -1; // a failed step: every nbufs[k] is 0, the encoders are dead
 }
 
-/* dsv2hip_enc_device_frame for one surface: a step of its own; 0 packets where the batch call would return -1 */
-static int surface_frame(enc_ingest::Call call, DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
+/* dsv2hip_enc_device_frame for one such picture: a step of its own; 0 packets where the batch call would return -1 */
+template <class Accept> static int source_frame(DSV_ENCODER *enc, bool have_args, DSV_BUF *bufs, Accept accept_one)
 {
     Job jb;
     memset(&jb, 0, sizeof(jb));
-    if (surf == NULL || bufs == NULL || !enc_usable(enc) || !accept_surface(call, enc, *surf, src_w, src_h, &jb.source)) {
+    if (!have_args || bufs == NULL || !enc_usable(enc) || !accept_one(&jb.source)) {
         return 0;
     }
     jb.enc = enc;
     jb.bufs = bufs;
     enc_batch(&jb, 1);
     return jb.nbuf;
+}
+} // extern "C++"
+
+/* the three surface calls; src_w, src_h: of the scaled and the sized call */
+static int surface_batch(enc_ingest::Call call, int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, const int *src_w, const int *src_h, DSV_BUF *bufs,
+                         int *nbufs)
+{
+    const bool plain = call == enc_ingest::CALL_PLAIN;
+    return source_batch(n, encs, surf && (plain || (src_w && src_h)), bufs, nbufs, [&](int k, enc_ingest::Source *out) {
+        return accept_surface(call, encs[k], surf[k], plain ? 0 : src_w[k], plain ? 0 : src_h[k], out);
+    });
+}
+static int surface_frame(enc_ingest::Call call, DSV_ENCODER *enc, const dsv2hip_surface *surf, int src_w, int src_h, DSV_BUF *bufs)
+{
+    return source_frame(enc, surf != NULL, bufs, [&](enc_ingest::Source *out) { return accept_surface(call, enc, *surf, src_w, src_h, out); });
+}
+
+/* the tensor calls (include/dsv2_hip.h: PLANAR RGB FLOAT TENSORS AS ENCODER INPUT): the same steps, another acceptance rule */
+int dsv2hip_enc_batch_tensor(int n, DSV_ENCODER **encs, const dsv2hip_in_tensor *t, DSV_BUF *bufs, int *nbufs)
+{
+    return source_batch(n, encs, t != NULL, bufs, nbufs, [&](int k, enc_ingest::Source *out) { return accept_tensor(encs[k], t[k], out); });
+}
+int dsv2hip_enc_tensor_frame(DSV_ENCODER *enc, const dsv2hip_in_tensor *t, DSV_BUF *bufs)
+{
+    return source_frame(enc, t != NULL, bufs, [&](enc_ingest::Source *out) { return accept_tensor(enc, *t, out); });
 }
 
 int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs)
@@ -2822,6 +2857,7 @@ void dsv2hip_enc_rgb_stats(unsigned long long *out2, int reset) { ingest_stats(e
 void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::SCALED_SURF, 2, out4, reset); }
 void dsv2hip_enc_resize_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::SIZED_SURF, 2, out4, reset); }
 void dsv2hip_enc_rgb3_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::RGB3_PACKED, 2, out4, reset); }
+void dsv2hip_enc_tensor_stats(unsigned long long *out2, int reset) { ingest_stats(enc_ingest::TENSOR_IN, 1, out2, reset); }
 
 /* the same with the pictures in HOST memory (packed planar Y, U, V).  host_planar[k]: stream k's picture of this
  * step; host_next (may be NULL, entries may be NULL): the picture stream k will bring to the NEXT call -- it is

@@ -11,6 +11,7 @@
 #include "dev.h"
 #include "ingest_rgb.h"
 #include "ingest_rgb3.h"
+#include "ingest_tensor.h"
 #include "ingest_scale.h"
 #include "ingest_resize.h"
 #include "prio.h"
@@ -514,6 +515,53 @@ void ingest_rgb3_batch(hipStream_t s, const Rgb3Job *d_jobs, int n, int h, bool 
         DSV2_LAUNCH((k_ingest_rgb3<kRgb3Packed, true>), grid, block, 0, s, d_jobs);
     } else {
         DSV2_LAUNCH((k_ingest_rgb3<kRgb3Packed, false>), grid, block, 0, s, d_jobs);
+    }
+}
+
+// ---- planar RGB float tensors (dsv2hip_in_tensor: binary16, bfloat16, binary32), taken to bytes and converted on the way in -----
+// One TensorInJob per picture, fetched by value and pinned to scalar registers as above -- the six constants too; the thread's work
+// is ingest_tensor.h's ingest_tensor_rows (which tools/ingest_tensor_check.cpp runs on the CPU), k_ingest_rgb3's decomposition with
+// another fetch.  The job's element type is uniform over the workgroup; a launch may hold jobs of all three.
+template <bool WIDE> __global__ __launch_bounds__(256) void k_ingest_tensor(const TensorInJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const TensorInJob jl = job_of(tab, blockIdx.y);
+    const auto uni_pitch = [](size_t p) { return ((size_t) (unsigned) uni((int) (p >> 32)) << 32) | (unsigned) uni((int) p); };
+    const TensorInJob j{{uni_ptr(jl.src[0]), uni_ptr(jl.src[1]), uni_ptr(jl.src[2])},
+                        {uni_pitch(jl.pitch[0]), uni_pitch(jl.pitch[1]), uni_pitch(jl.pitch[2])},
+                        {uni_ptr(jl.dst[0]), uni_ptr(jl.dst[1]), uni_ptr(jl.dst[2])},
+                        uni(jl.ystride),
+                        uni(jl.cstride),
+                        uni(jl.w),
+                        uni(jl.h),
+                        uni(jl.hs),
+                        uni(jl.vs),
+                        uni(jl.dtype),
+                        (uint32_t) uni((int) jl.ycoef),
+                        (uint32_t) uni((int) jl.upos),
+                        (uint32_t) uni((int) jl.uneg),
+                        (uint32_t) uni((int) jl.vpos),
+                        (uint32_t) uni((int) jl.vneg),
+                        (uint32_t) uni((int) jl.yoff),
+                        {uni(jl.scale[0]), uni(jl.scale[1]), uni(jl.scale[2])},
+                        {uni(jl.bias[0]), uni(jl.bias[1]), uni(jl.bias[2])}};
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    ingest_tensor_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void ingest_tensor_batch(hipStream_t s, const TensorInJob *d_jobs, int n, int h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kSurfaceRows - 1) / kSurfaceRows, n), block(64, 4);
+    if (wide) {
+        DSV2_LAUNCH(k_ingest_tensor<true>, grid, block, 0, s, d_jobs);
+    } else {
+        DSV2_LAUNCH(k_ingest_tensor<false>, grid, block, 0, s, d_jobs);
     }
 }
 

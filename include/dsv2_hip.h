@@ -890,6 +890,59 @@ int  dsv2hip_dec_tensor_dims(DSV_DECODER *dec, int dtype, int out_w, int out_h, 
 int  dsv2hip_dec_batch_tensor(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_tensor *t, DSV_FNUM *fn, int *ret);
 int  dsv2hip_dec_tensor_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_tensor *t, DSV_FNUM *fn);
 void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset);
+/* PLANAR RGB FLOAT TENSORS AS ENCODER INPUT, f16 / bf16 / f32 -- what a model or a renderer produces: a diffusion decoder, a
+ * super-resolution network, a neural renderer, a simulator emit float [3, h, w] in device memory, usually normalised.  The encoder
+ * reads it in place: no kernel of the caller's in front (de-normalise, clamp, round, store uint8[3, h, w]) whose rounding every
+ * caller would pick for themselves.  The counterpart of the out-tensor calls above; the element types are their enum.
+ * A contiguous torch [3, h, w] tensor is plane[c] = data_ptr + c * h * w * elem, pitch[c] = w * elem (elem = 2, 2, 4); a batch
+ * [n, 3, h, w] is n descriptors.  The planes are named by POINTER: plane[0] is read as R, plane[1] as G, plane[2] as B, and a B-G-R
+ * producer passes them in the other order (scale[c] / bias[c] belong to plane[c]).  Planes may lie anywhere, also in different
+ * allocations.
+ * Semantics are those of dsv2hip_enc_batch_surface / dsv2hip_enc_surface_frame: 4 buffer slots per stream, their return values, t[k]
+ * copied by value (it may go once the call returns).  The tensor is only read, and only inside its rows -- no byte of padding, no byte
+ * behind the last row; it is never written.  The picture has the encoder's size.  One step may mix element types, presets, constants,
+ * tensor geometries (pointers, pitches, and so the form) and whatever else dsv2hip_enc_batch_surface lets the streams of a step
+ * differ in; a refused call touches nothing: no encoder, buffer, nbufs or tensor.
+ * THE CONTRACT.  For element e of plane c -- a binary16 or bfloat16 element widened EXACTLY to binary32 --
+ *
+ *   g = fl32( fl32( e * scale[c] ) + bias[c] )
+ *   v = 0                              where g is a NaN
+ *       rint( min( max(g, 0), 255 ) )  else, ties to even, as a byte
+ *
+ * g is two IEEE binary32 operations, each rounded to nearest even, NOT fused into one multiply-add.  So +inf gives 255, -inf and -0
+ * give 0, a tie k + 0.5 goes to the even neighbour (0.5 -> 0, 1.5 -> 2, 2.5 -> 2, 254.5 -> 254, 255.5 -> 255).  Subnormal elements and
+ * intermediates take part with their value: nothing is flushed to zero.  In numpy: np.rint(np.clip(g, 0, 255)) with g = e.astype(
+ * np.float32) * np.float32(s) + np.float32(b), after replacing NaNs by 0.  The packets are exactly those of
+ * dsv2hip_enc_batch_surface on a DSV2HIP_SURFACE_RGBP | csc surface that holds the bytes v: THE CONVERSION above, character for
+ * character.
+ * The inverse of the decoder's constants is scale' = 1 / scale, bias' = -bias / scale, folded by the caller; for torchvision's
+ * ToTensor + Normalize(mean, std) that is scale' = 255 * std, bias' = 255 * mean.  ROUND TRIP: a byte delivered by
+ * dsv2hip_dec_batch_tensor under scale = 1 / 255, bias = 0 or under the ImageNet constants (mean 0.485, 0.456, 0.406, std 0.229, 0.224,
+ * 0.225) comes back as the same byte under these inverse constants, for F32, F16 and BF16 alike -- checked for all 256 bytes of every
+ * channel (tests/test_ingest_tensor_cpu.py).  That is a checked fact about these constants, NOT a theorem: with other constants, a
+ * BF16 or F16 element (8 or 11 significant bits) need not come back as the byte it was made from.
+ * DSV2HIP_TENSOR_U8 is accepted and IS the planar RGB surface: the same records and kernel as DSV2HIP_SURFACE_RGBP | csc, scale and
+ * bias ignored (they may hold anything); it counts in dsv2hip_enc_rgb3_stats, not in dsv2hip_enc_tensor_stats.
+ * Refused as a whole (the batch call returns -1, the one-frame call 0 packets): everything dsv2hip_enc_batch_surface refuses for an
+ * RGB layout (an encoder with dsv2hip_enc_set_uyvy_input on, a stream format outside the five, encoders of different step keys ...);
+ * an unknown dtype; a csc bit outside the two; a NULL plane; a plane pointer or a pitch that is not a multiple of the element size; a
+ * pitch below w * elem; a scale[c] or bias[c] that is not finite (float dtypes only).
+ * Out of scope: interleaved [h, w, 3] float tensors; the scaled and the sized route (they remain the surface calls' own, as for
+ * three-byte and planar RGB); tensors and surfaces in one call; 10-bit; host memory; any change to what the surface calls accept.
+ * dsv2hip_enc_tensor_stats: out2[0] / out2[1] = lockstep steps of this process whose float tensor ingest ran in the wide form (every
+ * plane pointer and pitch of every float tensor of the step a multiple of four elements and w a multiple of 4 -- any contiguous torch
+ * tensor with w % 4 == 0: a thread's four elements of a row arrive as one 8 / 16-byte load) / in the general form so far; reset != 0
+ * clears the counts afterwards. */
+typedef struct dsv2hip_in_tensor {
+    const void *plane[3];   /* device memory: the R, G and B planes, named by pointer */
+    size_t pitch[3];        /* bytes from one row to the next */
+    int    dtype;           /* DSV2HIP_TENSOR_* (the decoder's enum, reused) */
+    int    csc;             /* any subset of DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE */
+    float  scale[3], bias[3]; /* for plane[c]; ignored (may hold anything) for U8 */
+} dsv2hip_in_tensor;
+int  dsv2hip_enc_batch_tensor(int n, DSV_ENCODER **encs, const dsv2hip_in_tensor *t, DSV_BUF *bufs, int *nbufs);
+int  dsv2hip_enc_tensor_frame(DSV_ENCODER *enc, const dsv2hip_in_tensor *t, DSV_BUF *bufs);
+void dsv2hip_enc_tensor_stats(unsigned long long *out2, int reset);   /* steps in the wide / in the general form */
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the
