@@ -52,28 +52,4 @@ void intra_filter_batch(hipStream_t s, const McJob *d_tab, int n, int luma_w, in
 // dsv_post_process (bmc.c:340): de-gradient sharpen of every interior 4x4 cell
 void post_process_plane(hipStream_t s, const DPlane &dp);
 
-// decoder egress: n planes (device table) copied out of the reconstruction into the delivered picture, the sharpened ones
-// through dsv_post_process on the way.  wide: every job's width is a multiple of 16 and its destination and destination
-// stride are 16-byte aligned (16-byte loads and stores); else any width and alignment.  any_sharp: some job has `sharp` set.
-// max_h: the tallest plane.
-void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool wide, bool any_sharp);
-// ... into a semiplanar surface: n pictures' chroma (device table), U and V interleaved into one plane, converted to 4:2:0 on
-// the way where the job's mode says so.  wide: every job's destination and pitch are multiples of 16 and its cw of 8
-// (uv_job_wide); any_conv: some job has mode != 0.  max_ch: the most rows delivered.
-void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch, bool wide, bool any_conv);
-// ... into packed four-byte RGB surfaces: n pictures of h rows (device table), converted on the way (egress_rgb.h).  wide: every
-// job's destination and pitch are multiples of 16 and its w of 4 (rgb_out_job_wide).
-void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide);
-// ... into the three planes R, G, B of callers' tensors: n pictures of at most h rows (device table), converted on the way
-// (egress_tensor.h).  wide: every job's plane pointers and pitches are multiples of four elements and its w of 4 (tensor_job_wide).
-void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h, bool wide);
-// ... at half, quarter or eighth size: n planes (device table) box-averaged on the way (egress_scale.h) into a caller's plane or the
-// decoder's staging picture.  wide: every job's destination and pitch are multiples of 8 and its row is writable up to a multiple of
-// 16 >> shift bytes (scale_job_wide).  max_oh: the most rows delivered.
-void egress_scale_batch(hipStream_t s, const ScaleOutJob *d_jobs, int n, int max_oh, bool wide);
-// ... at a size the caller names: n planes (device table) area-averaged on the way (egress_resize.h) into a caller's plane or the
-// decoder's staging picture.  wide: every job's destination and pitch are multiples of 4 and its row is writable up to a multiple of
-// 4 bytes (resize_job_wide).  max_ow, max_oh: the most samples a row and the most rows delivered.
-void egress_resize_batch(hipStream_t s, const ResizeOutJob *d_jobs, int n, int max_ow, int max_oh, bool wide);
-
 } // namespace dsv2

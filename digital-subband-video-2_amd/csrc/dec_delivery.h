@@ -9,7 +9,7 @@
 #include <math.h>
 #include <stddef.h>
 
-#include "dev.h"
+#include "io_jobs.h"
 #include "surface_layout.h"
 
 namespace dsv2 {
@@ -121,14 +121,14 @@ inline OutTarget target_packed(void *buf, const size_t row_bytes[3], const int r
 }
 
 // the YUV -> RGB conversion of include/dsv2_hip.h for a layout's DSV2HIP_CSC_* bits: ky, ybase, rv, gu, gv, bu
-inline void rgb_out_coefs(RgbOutJob &j, int csc)
+inline RgbOutCoefs rgb_out_coefs(int csc)
 {
     static const int preset[4][6] = {{298, 16, 409, -100, -208, 516},  // BT601 (limited)
                                      {298, 16, 459, -55, -136, 541},   // BT709 (limited)
                                      {256, 0, 359, -88, -183, 454},    // BT601 | FULL
                                      {256, 0, 403, -48, -120, 475}};   // BT709 | FULL
     const int *p = preset[((csc & DSV2HIP_CSC_FULL_RANGE) ? 2 : 0) + ((csc & DSV2HIP_CSC_BT709) ? 1 : 0)];
-    j.ky = p[0], j.ybase = p[1], j.rv = p[2], j.gu = p[3], j.gv = p[4], j.bu = p[5];
+    return RgbOutCoefs{p[0], p[1], p[2], p[3], p[4], p[5]};
 }
 
 // ---- what one picture contributes to a round --------------------------------------------------------------------------------------------
@@ -147,18 +147,18 @@ struct DeliveryPlan {
     int n_copy = 0, n_to420 = 0, n_eg = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb = 0, n_overlay = 0;
     bool sharpen_overlaid = false; // that plane is also sharpened in place, behind the overlay (a drawn-on picture under postsharp)
     // what the round needs to pick its kernels' forms
-    bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (bmc.hip: k_egress)
-    bool scl_wide = true;                  // every reduction job allows the unconditional vector store (bmc.hip: k_egress_scale)
+    bool eg_wide = true, eg_sharp = false; // every egress job allows the 16-byte form / some egress job sharpens (egress.hip: k_egress)
+    bool scl_wide = true;                  // every reduction job allows the unconditional vector store (egress.hip: k_egress_scale)
     int scl_rows = 0;                      // the most rows a reduction job delivers
-    bool rsz_wide = true;                  // every resampling job allows the unconditional dword store (bmc.hip: k_egress_resize)
+    bool rsz_wide = true;                  // every resampling job allows the unconditional dword store (egress.hip: k_egress_resize)
     int rsz_rows = 0, rsz_cols = 0;        // the most rows / samples a row a resampling job delivers
-    bool uv_wide = true, uv_conv = false;  // the interleave job allows the 16-byte form / converts to 4:2:0 (bmc.hip: k_egress_uv)
+    bool uv_wide = true, uv_conv = false;  // the interleave job allows the 16-byte form / converts to 4:2:0 (egress.hip: k_egress_uv)
     int uv_rows = 0;                       // the chroma rows it delivers ("4:1:0" to 4:2:0: more than the source has)
-    bool rgb_wide = true;                  // the RGB job allows the 16-byte form (bmc.hip: k_egress_rgb)
+    bool rgb_wide = true;                  // the RGB job allows the 16-byte form (egress.hip: k_egress_rgb)
     // (behind everything the plans of the other targets hold: theirs are what they were)
     TensorOutJob ten[1];
     int n_ten = 0;
-    bool ten_wide = true;                  // the tensor job allows the unconditional vector stores (bmc.hip: k_egress_tensor)
+    bool ten_wide = true;                  // the tensor job allows the unconditional vector stores (egress.hip: k_egress_tensor)
 };
 
 // A sharpened and / or drawn-on picture that leaves reduced, as RGB or as a tensor has no delivered full-size luma plane for the overlay and the
@@ -243,34 +243,25 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
             p.uv_wide = uv_job_wide(uj);
             p.uv_rows = src[1].h;
         } else if (t.kind == OutTarget::RGB) {
-            RgbOutJob &rj = p.rgb[p.n_rgb++] = RgbOutJob{src[0].data, src[1].data, src[2].data, t.plane[0], src[0].stride, src[1].stride, t.pitch[0],
-                                                         src[0].w, src[0].h, hs, vs, 0, 0, 0, 0, 0, 0, t.bgra};
-            rgb_out_coefs(rj, t.csc);
+            const RgbOutJob &rj = p.rgb[p.n_rgb++] = RgbOutJob{src[0].data, src[1].data, src[2].data, t.plane[0], src[0].stride, src[1].stride, t.pitch[0],
+                                                               src[0].w, src[0].h, hs, vs, rgb_out_coefs(t.csc), t.bgra};
             p.rgb_wide = rgb_out_job_wide(rj);
         } else if (t.kind == OutTarget::TENSOR) {
-            TensorOutJob &tj = p.ten[p.n_ten++] = TensorOutJob{src[0].data,
-                                                               src[1].data,
-                                                               src[2].data,
-                                                               {t.plane[0], t.plane[1], t.plane[2]},
-                                                               src[0].stride,
-                                                               src[1].stride,
-                                                               {t.pitch[0], t.pitch[1], t.pitch[2]},
-                                                               src[0].w,
-                                                               src[0].h,
-                                                               hs,
-                                                               vs,
-                                                               0,
-                                                               0,
-                                                               0,
-                                                               0,
-                                                               0,
-                                                               0,
-                                                               t.dtype,
-                                                               {t.scale[0], t.scale[1], t.scale[2]},
-                                                               {t.bias[0], t.bias[1], t.bias[2]}};
-            RgbOutJob coefs{};
-            rgb_out_coefs(coefs, t.csc);
-            tj.ky = coefs.ky, tj.ybase = coefs.ybase, tj.rv = coefs.rv, tj.gu = coefs.gu, tj.gv = coefs.gv, tj.bu = coefs.bu;
+            const TensorOutJob &tj = p.ten[p.n_ten++] = TensorOutJob{src[0].data,
+                                                                     src[1].data,
+                                                                     src[2].data,
+                                                                     {t.plane[0], t.plane[1], t.plane[2]},
+                                                                     src[0].stride,
+                                                                     src[1].stride,
+                                                                     {t.pitch[0], t.pitch[1], t.pitch[2]},
+                                                                     src[0].w,
+                                                                     src[0].h,
+                                                                     hs,
+                                                                     vs,
+                                                                     rgb_out_coefs(t.csc),
+                                                                     t.dtype,
+                                                                     {t.scale[0], t.scale[1], t.scale[2]},
+                                                                     {t.bias[0], t.bias[1], t.bias[2]}};
             p.ten_wide = tensor_job_wide(tj);
         }
     } else if (!conv && !t.device() && !sharp_out) {

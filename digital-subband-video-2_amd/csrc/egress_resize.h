@@ -1,8 +1,8 @@
-// egress_resize.h -- what one thread of k_egress_resize (bmc.hip) does, as a function that also compiles for the host (the pattern of
+// egress_resize.h -- what one thread of k_egress_resize (egress.hip) does, as a function that also compiles for the host (the pattern of
 // egress_scale.h): the kernel is this function behind blockIdx / threadIdx, and tools/egress_resize_check.cpp sweeps the very same
 // code on the CPU under AddressSanitizer -- ratios, forms, pitches and offsets -- before it runs on a GPU.
 //
-// One ResizeOutJob (dev.h) = one plane of a decoded picture on its way out at a size the caller names.  A plane of pw x ph becomes
+// One ResizeOutJob (io_jobs.h) = one plane of a decoded picture on its way out at a size the caller names.  A plane of pw x ph becomes
 // ow x oh by the exact area average of include/dsv2_hip.h: with pw / ow = a / b and ph / oh = c / d in lowest terms, source pixel i
 // covers [i*b, (i+1)*b), output sample x covers [x*a, (x+1)*a), wx(x, i) is the length of their overlap (and wy(y, j) likewise), and
 //   out(x, y) = (SUM j SUM i  wy(y,j) * wx(x,i) * P(i, j)  +  D / 2) / D,   D = a * c
@@ -33,7 +33,7 @@ __host__ __device__ __forceinline__ uint32_t mulhi_u32(uint32_t x, uint32_t y)
     return (uint32_t) (((uint64_t) x * (uint64_t) y) >> 32);
 #endif
 }
-// n / den for any 32-bit n, with r = resize_recip(den) (dev.h): n * r / 2^32 lies below n / den by less than n / 2^32 < 1, so its
+// n / den for any 32-bit n, with r = resize_recip(den) (io_jobs.h): n * r / 2^32 lies below n / den by less than n / 2^32 < 1, so its
 // integer part is the quotient or one less
 __host__ __device__ __forceinline__ uint32_t resize_div(uint32_t n, uint32_t den, uint32_t r)
 {

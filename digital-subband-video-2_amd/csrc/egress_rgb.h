@@ -1,9 +1,9 @@
-// egress_rgb.h -- what one thread of k_egress_rgb (bmc.hip) does, as a function that also compiles for the host (the pattern of
+// egress_rgb.h -- what one thread of k_egress_rgb (egress.hip) does, as a function that also compiles for the host (the pattern of
 // egress_uv.h and ingest_rgb.h): the kernel is this function behind blockIdx / threadIdx, and tools/egress_rgb_check.cpp sweeps the
 // very same code on the CPU under AddressSanitizer -- forms, byte orders, presets, formats, widths, pitches and offsets -- before it
 // runs on a GPU.
 //
-// One RgbOutJob (dev.h) = one decoded picture on its way into a packed four-byte RGB surface (dsv2hip_out_surface, layout BGRA /
+// One RgbOutJob (io_jobs.h) = one decoded picture on its way into a packed four-byte RGB surface (dsv2hip_out_surface, layout BGRA /
 // RGBA), converted on the way by the integer formulas of include/dsv2_hip.h (the contract; restated at rgb_terms below).  The
 // mirror image of ingest_rgb.h: a thread owns FOUR pixels of FOUR consecutive rows -- a whole number of chroma footprints of every
 // format, so a chroma sample is read and its three products formed once for all the pixels it covers; rows below h are read again
@@ -49,12 +49,12 @@ struct RgbTerms { // a job's conversion, per byte of the pixel: byte k = clamp((
 __host__ __device__ __forceinline__ RgbTerms rgb_terms(const RgbOutJob &j)
 {
     RgbTerms t;
-    t.ky = j.ky;
-    t.cu[0] = j.bgra ? j.bu : 0, t.cv[0] = j.bgra ? 0 : j.rv; // byte 0: B or R
-    t.cu[1] = j.gu, t.cv[1] = j.gv;
-    t.cu[2] = j.bgra ? 0 : j.bu, t.cv[2] = j.bgra ? j.rv : 0; // byte 2: R or B
+    t.ky = j.csc.ky;
+    t.cu[0] = j.bgra ? j.csc.bu : 0, t.cv[0] = j.bgra ? 0 : j.csc.rv; // byte 0: B or R
+    t.cu[1] = j.csc.gu, t.cv[1] = j.csc.gv;
+    t.cu[2] = j.bgra ? 0 : j.csc.bu, t.cv[2] = j.bgra ? j.csc.rv : 0; // byte 2: R or B
     for (int k = 0; k < 3; k++) {
-        t.off[k] = 128 - j.ky * j.ybase - 128 * (t.cu[k] + t.cv[k]);
+        t.off[k] = 128 - j.csc.ky * j.csc.ybase - 128 * (t.cu[k] + t.cv[k]);
     }
     return t;
 }

@@ -1,8 +1,8 @@
-// egress_scale.h -- what one thread of k_egress_scale (bmc.hip) does, as a function that also compiles for the host (the pattern of
+// egress_scale.h -- what one thread of k_egress_scale (egress.hip) does, as a function that also compiles for the host (the pattern of
 // egress_uv.h and egress_rgb.h): the kernel is this function behind blockIdx / threadIdx, and tools/egress_scale_check.cpp sweeps the
 // very same code on the CPU under AddressSanitizer -- shifts, forms, widths, heights, pitches and offsets -- before it runs on a GPU.
 //
-// One ScaleOutJob (dev.h) = one plane of a decoded picture on its way out at half, quarter or eighth size.  With s = j.shift and
+// One ScaleOutJob (io_jobs.h) = one plane of a decoded picture on its way out at half, quarter or eighth size.  With s = j.shift and
 // n = 1 << s, a plane of pw x ph becomes ow = ceil(pw / n) by oh = ceil(ph / n), and (include/dsv2_hip.h, the contract)
 //   out(x, y) = (SUM j<n, i<n  P(min(x*n + i, pw-1), min(y*n + j, ph-1))  +  (1 << (2*s - 1))) >> (2*s)
 // one rounding over the whole footprint; a footprint across the right or bottom edge repeats the edge pixel.

@@ -1,8 +1,8 @@
-// egress_tensor.h -- what one thread of k_egress_tensor (bmc.hip) does, as a function that also compiles for the host (the pattern of
+// egress_tensor.h -- what one thread of k_egress_tensor (egress.hip) does, as a function that also compiles for the host (the pattern of
 // egress_rgb.h): the kernel is this function behind blockIdx / threadIdx, and tools/egress_tensor_check.cpp sweeps the very same code
 // on the CPU under AddressSanitizer -- forms, element types, presets, formats, widths, pitches and offsets -- before it runs on a GPU.
 //
-// One TensorOutJob (dev.h) = one decoded picture on its way into the three planes R, G, B of a caller's tensor (dsv2hip_out_tensor),
+// One TensorOutJob (io_jobs.h) = one decoded picture on its way into the three planes R, G, B of a caller's tensor (dsv2hip_out_tensor),
 // converted on the way by the integer formulas of include/dsv2_hip.h (egress_rgb.h's rgb_terms, mad24 and rgb_sum16 with the byte
 // order fixed to R, G, B) and, for a float element type, taken through the job's per-plane scale and bias.  k_egress_rgb's shape: a
 // thread owns FOUR pixels of FOUR consecutive rows -- a whole number of chroma footprints of every format; rows below h are read again
@@ -37,7 +37,7 @@ namespace dsv2 {
 __host__ __device__ __forceinline__ RgbTerms tensor_terms(const TensorOutJob &j)
 {
     RgbOutJob r{};
-    r.ky = j.ky, r.ybase = j.ybase, r.rv = j.rv, r.gu = j.gu, r.gv = j.gv, r.bu = j.bu, r.bgra = 0;
+    r.csc = j.csc, r.bgra = 0;
     return rgb_terms(r);
 }
 

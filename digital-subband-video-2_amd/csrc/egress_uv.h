@@ -1,13 +1,13 @@
-// egress_uv.h -- what one thread of k_egress_uv (bmc.hip) does, as a function that also compiles for the host: the kernel is
+// egress_uv.h -- what one thread of k_egress_uv (egress.hip) does, as a function that also compiles for the host: the kernel is
 // this function behind blockIdx / threadIdx, and tools/egress_uv_check.cpp sweeps the very same code on the CPU under
 // AddressSanitizer -- widths, pitches, offsets and modes -- before it ever runs on a GPU.
 //
-// One UvEgressJob (dev.h) = the two chroma planes of one decoded picture on their way into the interleaved plane of a
+// One UvEgressJob (io_jobs.h) = the two chroma planes of one decoded picture on their way into the interleaved plane of a
 // semiplanar surface (NV12 / NV16 / NV24: rows U0 V0 U1 V1 ...).  A thread owns VEC (U, V) pairs -- 2 * VEC destination bytes -- of
 // FOUR consecutive rows; every load is issued before the first store.
 //   VEC = 8, the wide form: destination pointer and pitch multiples of 16 and cw a multiple of 8 in every job of the launch (the
 //            host picks it per round): 8 bytes of U and 8 of V per row, zipped by four v_perm_b32 into one 16-byte store -- the
-//            inverse of k_ingest_surface's split (frame.hip).
+//            inverse of k_ingest_surface's split (ingest.hip).
 //   VEC = 4, the general form: any cw, pitch and alignment.  Whole dwords are read from the sources (x is a multiple of 4 and
 //            the planes' origins and strides of 16; the up to three bytes past the row lie in the 32-pixel border); a destination
 //            dword is stored as one only where it is aligned and lies whole inside the row, else byte by byte inside the row:
@@ -20,7 +20,7 @@
 //            whose cost is its byte loads, not its branches, and the switch is uniform over the launch's workgroup.
 #pragma once
 
-#include "dev.h"
+#include "io_jobs.h"
 
 namespace dsv2 {
 

@@ -137,7 +137,7 @@ inline bool accept_tensor(int enc_w, int enc_h, int subsamp, bool uyvy_input, co
 
 // The conversion of include/dsv2_hip.h for an RGB surface of `layout` as the RGB ingest kernels take it: each row of the preset's matrix as
 // byte quads in the surface's channel order (a fourth byte weighs 0), chroma rows split into positive parts and magnitudes of negative ones
-template <class RgbJobT> inline void rgb_job_coefs(RgbJobT &j, int layout)
+inline RgbInCoefs rgb_job_coefs(int layout)
 {
     static const int presets[4][9] = {{66, 129, 25, -38, -74, 112, 112, -94, -18},   // BT601 (limited)
                                       {47, 157, 16, -26, -86, 112, 112, -102, -10},  // BT709 (limited)
@@ -155,10 +155,7 @@ template <class RgbJobT> inline void rgb_job_coefs(RgbJobT &j, int layout)
             q[row][v < 0] |= (uint32_t) (v < 0 ? -v : v) << at;
         }
     }
-    j.ycoef = q[0][0];
-    j.upos = q[1][0], j.uneg = q[1][1];
-    j.vpos = q[2][0], j.vneg = q[2][1];
-    j.yoff = 128u + (full ? 0u : 256u * 16u);
+    return RgbInCoefs{q[0][0], q[1][0], q[1][1], q[2][0], q[2][1], 128u + (full ? 0u : 256u * 16u)};
 }
 
 // ---- what one picture contributes to a step ---------------------------------------------------------------------------------------------
@@ -177,7 +174,7 @@ struct IngestPlan {
     TensorInJob tensor[1];
     int n[kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // records per class: a surface brings those of ONE class, a PACKED picture none
     // what the step needs to pick its kernels' forms and grids
-    bool wide[kClasses] = {true, true, true, true, true, true, true, true, true}; // every record of the class allows the wide form (dev.h: *_job_wide)
+    bool wide[kClasses] = {true, true, true, true, true, true, true, true, true}; // every record of the class allows the wide form (io_jobs.h: *_job_wide)
     int scaled_row_bytes = 0; // SCALED_SURF: the most bytes a source row of a record holds
     int scaled_rgb_sw = 0;    // SCALED_RGB: the source's width
 };
@@ -200,37 +197,35 @@ inline IngestPlan plan_ingest(const DFrame &f, const Source &s)
     if (s.kind == Source::TENSOR) { // (the plain route alone)
         TensorInJob &j = p.tensor[p.n[TENSOR_IN]++];
         j = TensorInJob{{s.plane[0], s.plane[1], s.plane[2]}, {s.pitch[0], s.pitch[1], s.pitch[2]}, {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride,
-                        dp[0].w, dp[0].h, hs, vs, s.dtype, 0, 0, 0, 0, 0, 0, {s.scale[0], s.scale[1], s.scale[2]}, {s.bias[0], s.bias[1], s.bias[2]}};
-        rgb_job_coefs(j, DSV2HIP_SURFACE_RGBA | (s.layout & 0x300)); // (R is byte 0 of a pixel dword, as for the planar kind)
+                        dp[0].w, dp[0].h, hs, vs, s.dtype,
+                        rgb_job_coefs(DSV2HIP_SURFACE_RGBA | (s.layout & 0x300)), // (R is byte 0 of a pixel dword, as for the planar kind)
+                        {s.scale[0], s.scale[1], s.scale[2]}, {s.bias[0], s.bias[1], s.bias[2]}};
         p.wide[TENSOR_IN] = tensor_in_job_wide(j);
     } else if (s.kind == Source::RGB3 || s.kind == Source::RGBP) { // (the plain route alone)
         const int kind = s.kind == Source::RGBP ? kRgb3Planar : kRgb3Packed, cl = RGB3_PACKED + kind;
         Rgb3Job &j = p.rgb3[p.n[cl]++];
         j = Rgb3Job{{s.plane[0], nullptr, nullptr}, {s.pitch[0], 0, 0}, {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride,
-                    dp[0].w, dp[0].h, hs, vs, kind, 0, 0, 0, 0, 0, 0};
+                    dp[0].w, dp[0].h, hs, vs, kind,
+                    rgb_job_coefs(kind == kRgb3Planar ? DSV2HIP_SURFACE_RGBA | (s.layout & 0x300) : s.layout)}; // (planar: R is byte 0 of a pixel dword)
         for (int c = 1; c < 3 && kind == kRgb3Planar; c++) {
             j.src[c] = s.plane[c], j.pitch[c] = s.pitch[c];
         }
-        rgb_job_coefs(j, kind == kRgb3Planar ? DSV2HIP_SURFACE_RGBA | (s.layout & 0x300) : s.layout); // (planar: R is byte 0 of a pixel dword)
         p.wide[cl] = rgb3_job_wide(j);
     } else if (s.kind == Source::RGB4 && s.route == Source::SIZED) {
         SizedRgbJob &j = p.sized_rgb[p.n[SIZED_RGB]++];
         j = SizedRgbJob{s.plane[0], s.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h, dp[1].w, dp[1].h,
                         ingest_resize::sized_ratio(s.src_w, s.src_h, dp[0].w, dp[0].h, true),
-                        ingest_resize::sized_ratio(s.src_w, s.src_h, dp[1].w, dp[1].h, true), 0, 0, 0, 0, 0, 0};
-        rgb_job_coefs(j, s.layout);
+                        ingest_resize::sized_ratio(s.src_w, s.src_h, dp[1].w, dp[1].h, true), rgb_job_coefs(s.layout)};
         p.wide[SIZED_RGB] = sized_rgb_job_wide(j);
     } else if (s.kind == Source::RGB4 && s.route == Source::REDUCED) {
         ScaledRgbJob &j = p.scaled_rgb[p.n[SCALED_RGB]++];
         j = ScaledRgbJob{s.plane[0], s.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, s.src_w, s.src_h, hs, vs, s.shift,
-                         0, 0, 0, 0, 0, 0};
-        rgb_job_coefs(j, s.layout);
+                         rgb_job_coefs(s.layout)};
         p.wide[SCALED_RGB] = scaled_rgb_job_wide(j);
         p.scaled_rgb_sw = s.src_w;
     } else if (s.kind == Source::RGB4) {
         RgbJob &j = p.rgb[p.n[RGB]++];
-        j = RgbJob{s.plane[0], s.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h, hs, vs, 0, 0, 0, 0, 0, 0};
-        rgb_job_coefs(j, s.layout);
+        j = RgbJob{s.plane[0], s.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h, hs, vs, rgb_job_coefs(s.layout)};
         p.wide[RGB] = rgb_job_wide(j);
     } else if (s.route == Source::SIZED) {
         for (int c = 0; c < 3; c++) { // (an interleaved plane: two records, its U and its V half)

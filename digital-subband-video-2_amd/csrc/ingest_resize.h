@@ -1,5 +1,5 @@
 // ingest_resize.h -- ingest at any larger size (dsv2hip_enc_batch_surface_sized): what one thread of k_ingest_sized and
-// k_ingest_rgb_sized (frame.hip) does, as functions that also compile for the host (the pattern of ingest_scale.h and
+// k_ingest_rgb_sized (ingest.hip) does, as functions that also compile for the host (the pattern of ingest_scale.h and
 // egress_resize.h), and the device-free rule that says which source an encoder takes (ingest_resize::plan_sized_source,
 // sized_surface_fits).  tools/ingest_resize_check.cpp sweeps the very same code on the CPU under AddressSanitizer -- ratios, forms,
 // layouts, pitches and offsets -- before it runs on a GPU.
@@ -188,7 +188,7 @@ template <bool WIDE> __host__ __device__ __forceinline__ void ingest_sized_rgb_q
         uint32_t w = 0;
         for (int k = 0; k < 4 && x0 + k < j.ow; k++) {
             sized_rgb_sums<WIDE>(j, j.ql, gy, x0 + k, aligned, S);
-            w |= resize_div(sized_rgb_weigh(j.ycoef, S) + j.yoff * j.ql.D, j.ql.D << 8, j.ql.rD) << (8 * k);
+            w |= resize_div(sized_rgb_weigh(j.csc.ycoef, S) + j.csc.yoff * j.ql.D, j.ql.D << 8, j.ql.rD) << (8 * k);
         }
         sized_store_quad(j.dst[0] + (size_t) gy * (size_t) j.ystride, x0, j.ow, w);
     } else {
@@ -197,8 +197,8 @@ template <bool WIDE> __host__ __device__ __forceinline__ void ingest_sized_rgb_q
         for (int k = 0; k < 4 && x0 + k < j.cw; k++) {
             sized_rgb_sums<WIDE>(j, j.qc, cy, x0 + k, aligned, S);
             const uint32_t bias = 32896u * j.qc.D;
-            const uint32_t u = resize_div(sized_rgb_weigh(j.upos, S) + bias - sized_rgb_weigh(j.uneg, S), j.qc.D << 8, j.qc.rD);
-            const uint32_t v = resize_div(sized_rgb_weigh(j.vpos, S) + bias - sized_rgb_weigh(j.vneg, S), j.qc.D << 8, j.qc.rD);
+            const uint32_t u = resize_div(sized_rgb_weigh(j.csc.upos, S) + bias - sized_rgb_weigh(j.csc.uneg, S), j.qc.D << 8, j.qc.rD);
+            const uint32_t v = resize_div(sized_rgb_weigh(j.csc.vpos, S) + bias - sized_rgb_weigh(j.csc.vneg, S), j.qc.D << 8, j.qc.rD);
             wu |= (u < 255u ? u : 255u) << (8 * k), wv |= (v < 255u ? v : 255u) << (8 * k);
         }
         sized_store_quad(j.dst[1] + (size_t) cy * (size_t) j.cstride, x0, j.cw, wu);

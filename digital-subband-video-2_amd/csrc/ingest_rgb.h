@@ -1,8 +1,8 @@
-// ingest_rgb.h -- what one thread of k_ingest_rgb (frame.hip) does, as a function that also compiles for the host (the pattern of
+// ingest_rgb.h -- what one thread of k_ingest_rgb (ingest.hip) does, as a function that also compiles for the host (the pattern of
 // egress_uv.h): the kernel is this function behind blockIdx / threadIdx, and tools/ingest_rgb_check.cpp sweeps the very same code
 // on the CPU under AddressSanitizer -- forms, byte orders, presets, formats, widths, pitches and offsets -- before it runs on a GPU.
 //
-// One RgbJob (dev.h) = one packed four-byte RGB surface (dsv2hip_surface, layout BGRA / RGBA) on its way into the three bordered
+// One RgbJob (io_jobs.h) = one packed four-byte RGB surface (dsv2hip_surface, layout BGRA / RGBA) on its way into the three bordered
 // source planes, converted on the way by the integer formulas of include/dsv2_hip.h (the contract; restated at rgb_chroma below).
 // A thread owns FOUR pixels of FOUR consecutive rows -- a whole number of chroma footprints of every format (the widest is 4 pixels,
 // the tallest 4 rows), so neither LDS nor another lane is needed; rows below h and pixels right of w are read again from the last
@@ -131,8 +131,8 @@ template <int HS, int VS, bool WIDE> __host__ __device__ __forceinline__ void rg
         if (y0 + r >= h) {
             break;
         }
-        const uint32_t y01 = perm_b32(dot4_u8(px[r][1], j.ycoef, j.yoff), dot4_u8(px[r][0], j.ycoef, j.yoff), 0x00000501u);
-        const uint32_t y23 = perm_b32(dot4_u8(px[r][3], j.ycoef, j.yoff), dot4_u8(px[r][2], j.ycoef, j.yoff), 0x00000501u);
+        const uint32_t y01 = perm_b32(dot4_u8(px[r][1], j.csc.ycoef, j.csc.yoff), dot4_u8(px[r][0], j.csc.ycoef, j.csc.yoff), 0x00000501u);
+        const uint32_t y23 = perm_b32(dot4_u8(px[r][3], j.csc.ycoef, j.csc.yoff), dot4_u8(px[r][2], j.csc.ycoef, j.csc.yoff), 0x00000501u);
         const uint32_t o = perm_b32(y23, y01, 0x05040100u);
         uint8_t *yrow = j.dst[0] + (size_t) (y0 + r) * (size_t) j.ystride;
         if (WIDE || x + 4 <= w) {
@@ -143,8 +143,8 @@ template <int HS, int VS, bool WIDE> __host__ __device__ __forceinline__ void rg
             }
         }
     }
-    rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[1], j.upos, j.uneg);
-    rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[2], j.vpos, j.vneg);
+    rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[1], j.csc.upos, j.csc.uneg);
+    rgb_chroma<HS, VS, WIDE>(j, px, x, y0, j.dst[2], j.csc.vpos, j.csc.vneg);
 }
 
 // rows y0 .. y0 + 3 (y0 a multiple of 4, below h) of job j, pixels x_first .. x_first + 3 (a multiple of 4) and on in steps of x_step,

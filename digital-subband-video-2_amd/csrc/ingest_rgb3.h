@@ -1,8 +1,8 @@
-// ingest_rgb3.h -- what one thread of k_ingest_rgb3 (frame.hip) does, as a function that also compiles for the host (the pattern of
+// ingest_rgb3.h -- what one thread of k_ingest_rgb3 (ingest.hip) does, as a function that also compiles for the host (the pattern of
 // ingest_rgb.h): the kernel is this function behind blockIdx / threadIdx, and tools/ingest_rgb3_check.cpp sweeps the very same code
 // on the CPU under AddressSanitizer -- kinds, forms, byte orders, presets, formats, widths, pitches and offsets -- before it runs on a GPU.
 //
-// One Rgb3Job (dev.h) = one RGB surface WITHOUT a fourth byte (dsv2hip_surface) on its way into the three bordered source planes:
+// One Rgb3Job (io_jobs.h) = one RGB surface WITHOUT a fourth byte (dsv2hip_surface) on its way into the three bordered source planes:
 //   kRgb3Packed: BGR / RGB, three bytes a pixel in one plane (OpenCV's Mat, a numpy / torch uint8[h, w, 3]);
 //   kRgb3Planar: RGBP, one plane per colour (torch's uint8[3, h, w]).
 // The decomposition is k_ingest_rgb's: a thread owns FOUR pixels of FOUR consecutive rows, rows below h and pixels right of w are
@@ -41,7 +41,7 @@ template <int KIND, bool WIDE, int HS, int VS> __host__ __device__ __forceinline
     constexpr bool PLANAR = KIND == kRgb3Planar;
     const int w = j.w, h = j.h;
     // what rgb_emit reads of a job: destination, geometry, coefficients
-    const RgbJob o{nullptr, 0, {j.dst[0], j.dst[1], j.dst[2]}, j.ystride, j.cstride, w, h, j.hs, j.vs, j.ycoef, j.upos, j.uneg, j.vpos, j.vneg, j.yoff};
+    const RgbJob o{nullptr, 0, {j.dst[0], j.dst[1], j.dst[2]}, j.ystride, j.cstride, w, h, j.hs, j.vs, j.csc};
     for (int xi = x_first; xi < w; xi += x_step) {
         const int x = lane_offset(xi);
         uint32_t px[4][4];

@@ -1,5 +1,5 @@
 // ingest_scale.h -- half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled): what the threads of
-// k_ingest_surface_scaled and k_ingest_rgb_scaled (frame.hip) do, as functions that also compile for the host (the pattern of
+// k_ingest_surface_scaled and k_ingest_rgb_scaled (ingest.hip) do, as functions that also compile for the host (the pattern of
 // ingest_rgb.h and egress_scale.h), and the device-free rule that says which source an encoder takes (ingest_scale::plan_source, surface_fits).
 // tools/ingest_scale_check.cpp sweeps the very same code on the CPU under AddressSanitizer -- shifts, forms, formats, byte orders,
 // presets, widths, heights, pitches and offsets -- before it runs on a GPU.
@@ -261,8 +261,8 @@ template <bool WIDE, int S> __host__ __device__ __forceinline__ void ingest_rgb_
                 uint32_t a = 0, b = 0; // luma: pixels 0, 1 / 2, 3
 #pragma unroll
                 for (int r = 0; r < N; r++) {
-                    a = dot4_u8(px[r][1], j.ycoef, dot4_u8(px[r][0], j.ycoef, a));
-                    b = dot4_u8(px[r][3], j.ycoef, dot4_u8(px[r][2], j.ycoef, b));
+                    a = dot4_u8(px[r][1], j.csc.ycoef, dot4_u8(px[r][0], j.csc.ycoef, a));
+                    b = dot4_u8(px[r][3], j.csc.ycoef, dot4_u8(px[r][2], j.csc.ycoef, b));
                 }
                 ys0[li] = S == 1 ? a : a + b, ys1[li] = b;
                 uint32_t p0 = 0, n0 = 0, p1 = 0, n1 = 0, q0 = 0, m0 = 0, q1 = 0, m1 = 0; // U pos / neg, V pos / neg of pixels 0, 1 and of 2, 3
@@ -270,10 +270,10 @@ template <bool WIDE, int S> __host__ __device__ __forceinline__ void ingest_rgb_
                 for (int r = 0; r < N; r++) {
 #pragma unroll
                     for (int i = 0; i < 2; i++) {
-                        p0 = dot4_u8(px[r][i], j.upos, p0), n0 = dot4_u8(px[r][i], j.uneg, n0);
-                        q0 = dot4_u8(px[r][i], j.vpos, q0), m0 = dot4_u8(px[r][i], j.vneg, m0);
-                        p1 = dot4_u8(px[r][2 + i], j.upos, p1), n1 = dot4_u8(px[r][2 + i], j.uneg, n1);
-                        q1 = dot4_u8(px[r][2 + i], j.vpos, q1), m1 = dot4_u8(px[r][2 + i], j.vneg, m1);
+                        p0 = dot4_u8(px[r][i], j.csc.upos, p0), n0 = dot4_u8(px[r][i], j.csc.uneg, n0);
+                        q0 = dot4_u8(px[r][i], j.csc.vpos, q0), m0 = dot4_u8(px[r][i], j.csc.vneg, m0);
+                        p1 = dot4_u8(px[r][2 + i], j.csc.upos, p1), n1 = dot4_u8(px[r][2 + i], j.csc.uneg, n1);
+                        q1 = dot4_u8(px[r][2 + i], j.csc.vpos, q1), m1 = dot4_u8(px[r][2 + i], j.csc.vneg, m1);
                     }
                 }
                 if (cshift >= 2) {
@@ -292,7 +292,7 @@ template <bool WIDE, int S> __host__ __device__ __forceinline__ void ingest_rgb_
                 lanes.each([&](int li, int lane) {
                     const int x = xb + 4 * lane;
                     uint8_t *yrow = j.dst[0] + (size_t) oy * (size_t) j.ystride;
-                    const uint32_t yoff = j.yoff << (2 * S);
+                    const uint32_t yoff = j.csc.yoff << (2 * S);
                     if constexpr (S == 1) {
                         const uint32_t o[2] = {(ys0[li] + yoff) >> (8 + 2 * S), (ys1[li] + yoff) >> (8 + 2 * S)};
                         st_samples<2, false>(yrow, x >> 1, o, ow);
@@ -421,7 +421,7 @@ inline bool surface_fits(const Source &s, const dsv2hip_surface &sf, int enc_w, 
     return true;
 }
 
-// (the forms: scaled_surface_job_wide / scaled_rgb_job_wide in dev.h, the existing wide predicates applied to the SOURCE)
+// (the forms: scaled_surface_job_wide / scaled_rgb_job_wide in io_jobs.h, the existing wide predicates applied to the SOURCE)
 
 } // namespace ingest_scale
 } // namespace dsv2

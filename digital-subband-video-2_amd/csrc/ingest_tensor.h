@@ -1,9 +1,9 @@
-// ingest_tensor.h -- what one thread of k_ingest_tensor (frame.hip) does, as a function that also compiles for the host (the pattern of
+// ingest_tensor.h -- what one thread of k_ingest_tensor (ingest.hip) does, as a function that also compiles for the host (the pattern of
 // ingest_rgb3.h): the kernel is this function behind blockIdx / threadIdx, and tools/ingest_tensor_check.cpp sweeps the very same code
 // on the CPU under AddressSanitizer -- forms, element types, presets, formats, widths, pitches, offsets and constants -- before it runs
 // on a GPU.
 //
-// One TensorInJob (dev.h) = one picture that is the three planes R, G, B of a caller's float tensor (dsv2hip_in_tensor: binary16,
+// One TensorInJob (io_jobs.h) = one picture that is the three planes R, G, B of a caller's float tensor (dsv2hip_in_tensor: binary16,
 // bfloat16 or binary32 elements) on its way into the three bordered source planes.  The decomposition is k_ingest_rgb3's: a thread
 // owns FOUR pixels of FOUR consecutive rows, rows below h and pixels right of w are read again from the last row / pixel and never
 // stored.  Only the fetch is new -- load, widen, scale and bias, clamp, round, pack: once the thread holds its px[4][4] pixel dwords
@@ -112,7 +112,7 @@ __host__ __device__ __forceinline__ void ingest_tensor_rows_fmt(const TensorInJo
     constexpr int ROWS = !WIDE ? 1 : DT == kTensorF32 ? 2 : 4; // rows whose loads are in flight together
     const int w = j.w, h = j.h;
     // what rgb_emit reads of a job: destination, geometry, coefficients
-    const RgbJob o{nullptr, 0, {j.dst[0], j.dst[1], j.dst[2]}, j.ystride, j.cstride, w, h, j.hs, j.vs, j.ycoef, j.upos, j.uneg, j.vpos, j.vneg, j.yoff};
+    const RgbJob o{nullptr, 0, {j.dst[0], j.dst[1], j.dst[2]}, j.ystride, j.cstride, w, h, j.hs, j.vs, j.csc};
     for (int xi = x_first; xi < w; xi += x_step) {
         const int x = lane_offset(xi);
         uint32_t px[4][4];

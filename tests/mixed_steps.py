@@ -132,7 +132,7 @@ SHORT_LIST = 5  # the stream of alternating() that starts with symbol lists too 
 def alternating():
     """6 streams; streams 3 and 4 are defined by their RGB pictures; stream 5 joins at step 1, one frame short.  352x288: chroma
     rows of 176 bytes -- at 176x144 they have 88, no multiple of 16, and no step with a planar surface could take the wide form of
-    the surface ingest (csrc/dev.h: surface_job_wide)."""
+    the surface ingest (csrc/io_jobs.h: surface_job_wide)."""
     streams = [table_stream(s, nframes=9 if s == SHORT_LIST else 10, layout=RGB_LAYOUTS.get(s % 5), w=352, h=288) for s in range(6)]
     return streams, [[s for s in ((k + t) % 6 for k in range(6)) if s != SHORT_LIST or t >= 1] for t in range(10)]  # (rotated by one slot a step)
 

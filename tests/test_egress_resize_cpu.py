@@ -64,7 +64,7 @@ def test_kernel_body_sweep_is_clean_and_equals_the_numpy_oracle(dump_dir):
 
 
 def test_the_bounds_of_the_call_equal_the_oracles(dump_dir):
-    """resize_allowed (dev.h), which the three sized calls refuse by, at and around every bound -- ratio 8 and 1 per axis, sizes that are
+    """resize_allowed (io_jobs.h), which the three sized calls refuse by, at and around every bound -- ratio 8 and 1 per axis, sizes that are
     not positive, a side of 32 768, D = 2^24 -- against the oracle's restatement; both verdicts occur, for each kind of bound"""
     rows = [[int(v) for v in line.split()] for line in open(os.path.join(dump_dir, "allowed.txt"))]
     assert len(rows) >= 40

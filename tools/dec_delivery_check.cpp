@@ -2,14 +2,14 @@
 // kind x scale x out420p x postsharp x draw_info x pointer offset x pitch, over FAKE addresses -- the reconstruction, the two staging
 // areas and the target are disjoint ranges of one synthetic address space, and nothing is ever dereferenced.  Meant to be built with
 // AddressSanitizer and UndefinedBehaviorSanitizer (the planner is handed no staging area it says it does not need: a look at one faults).
-// For every case the program works out, by its own interval arithmetic over the footprints dev.h documents for each job record,
+// For every case the program works out, by its own interval arithmetic over the footprints io_jobs.h documents for each job record,
 //   coverage  the bytes written by the jobs whose destination is the target are exactly the visible rows of the target's planes as
 //             dsv2hip_dec_surface_dims documents them (a pinned frame: its planes' rows, or under the whole-frame copy its block), no
 //             byte twice, nothing else outside the staging areas -- where a row may be written up to its stride;
 //   order     every byte read from a staging area was written by a job of a strictly earlier launch class (whole-frame copy, 4:2:0
 //             conversion, egress, overlay, sharpening in place, reduction, chroma interleave, RGB conversion); overlay and sharpening touch
 //             a staged plane only between the egress that fills it and the reduction / conversion that reads it;
-//   form      the plan's wide / sharp / conv / rows facts are those of dev.h's *_job_wide predicates applied to its jobs;
+//   form      the plan's wide / sharp / conv / rows facts are those of io_jobs.h's *_job_wide predicates applied to its jobs;
 //   counts    the job counts are those of the table below (restated as data), every row of which some case must hit;
 //   sources   the reconstruction is never written, and the luma is read from it -- or from the staged copy if and only if the picture
 //             is sharpened or drawn on and leaves reduced or as RGB.
@@ -238,7 +238,7 @@ Region region_of(const Case &c, const World &W, const Rows &r)
     return NOWHERE;
 }
 
-// ---- a plan's jobs with the footprints dev.h documents ----------------------------------------------------------------------------------
+// ---- a plan's jobs with the footprints io_jobs.h documents ----------------------------------------------------------------------------------
 struct Access {
     int cls;
     const char *what;
@@ -378,8 +378,8 @@ void check(const Case &c)
     for (int i = 0; i < p.n_rgb; i++) {
         const RgbOutJob &j = p.rgb[i];
         const bool bgra = ((c.w + c.offset) & 1) == 0;
-        if (j.hs != hs || j.vs != vs || (j.bgra != 0) != bgra || j.ky != (bgra ? 298 : 256) || j.w != cdiv(c.w, c.shift) || j.h != cdiv(c.h, c.shift)) {
-            fail(c, "rgb job: hs %d vs %d bgra %d ky %d %dx%d", j.hs, j.vs, j.bgra, j.ky, j.w, j.h);
+        if (j.hs != hs || j.vs != vs || (j.bgra != 0) != bgra || j.csc.ky != (bgra ? 298 : 256) || j.w != cdiv(c.w, c.shift) || j.h != cdiv(c.h, c.shift)) {
+            fail(c, "rgb job: hs %d vs %d bgra %d ky %d %dx%d", j.hs, j.vs, j.bgra, j.csc.ky, j.w, j.h);
         }
     }
     // sources and destinations by region
@@ -481,7 +481,7 @@ void check(const Case &c)
             }
         }
     }
-    // form: dev.h's predicates over the jobs
+    // form: io_jobs.h's predicates over the jobs
     bool eg_wide = true, eg_sharp = false, scl_wide = true, uv_wide = true, uv_conv = false, rgb_wide = true;
     int scl_rows = 0, uv_rows = 0;
     for (int i = 0; i < p.n_eg; i++) {

@@ -190,7 +190,7 @@ void check_tensor(const Case &c)
     const TensorOutJob &j = p.ten[0];
     const int *co = kCoef[((tn.csc & DSV2HIP_CSC_FULL_RANGE) ? 2 : 0) + ((tn.csc & DSV2HIP_CSC_BT709) ? 1 : 0)];
     bool ok = j.sy == src[0].data && j.su == src[1].data && j.sv == src[2].data && j.ystride == src[0].stride && j.cstride == src[1].stride && j.w == dw && j.h == dh &&
-              j.hs == hs && j.vs == vs && j.dtype == c.dtype && j.ky == co[0] && j.ybase == co[1] && j.rv == co[2] && j.gu == co[3] && j.gv == co[4] && j.bu == co[5];
+              j.hs == hs && j.vs == vs && j.dtype == c.dtype && j.csc.ky == co[0] && j.csc.ybase == co[1] && j.csc.rv == co[2] && j.csc.gu == co[3] && j.csc.gv == co[4] && j.csc.bu == co[5];
     for (int k = 0; k < 3; k++) {
         ok = ok && j.dst[k] == tn.plane[k] && (size_t) j.dpitch[k] == pitch;
         ok = ok && (elem == 1 || (j.scale[k] == tn.scale[k] && j.bias[k] == tn.bias[k]));
@@ -295,8 +295,8 @@ template <class Plan> void print_plan(const Old &c, const Plan &p, bool luma, bo
     }
     for (int i = 0; i < p.n_rgb; i++) {
         const RgbOutJob &j = p.rgb[i];
-        printf(" rgb %llx %llx %llx %llx %d %d %d %d %d %d %d %d %d %d %d %d %d %d", at(j.sy), at(j.su), at(j.sv), at(j.dst), j.ystride, j.cstride, j.dpitch, j.w, j.h, j.hs, j.vs, j.ky,
-               j.ybase, j.rv, j.gu, j.gv, j.bu, j.bgra);
+        printf(" rgb %llx %llx %llx %llx %d %d %d %d %d %d %d %d %d %d %d %d %d %d", at(j.sy), at(j.su), at(j.sv), at(j.dst), j.ystride, j.cstride, j.dpitch, j.w, j.h, j.hs, j.vs, j.csc.ky,
+               j.csc.ybase, j.csc.rv, j.csc.gu, j.csc.gv, j.csc.bu, j.bgra);
     }
     for (int i = 0; i < p.n_overlay; i++) {
         printf(" ov %llx %d %d %d", at(p.overlay[i].data), p.overlay[i].stride, p.overlay[i].w, p.overlay[i].h);
@@ -326,7 +326,7 @@ bool same(const UvEgressJob &a, const UvEgressJob &b)
 bool same(const RgbOutJob &a, const RgbOutJob &b)
 {
     return a.sy == b.sy && a.su == b.su && a.sv == b.sv && a.dst == b.dst && a.ystride == b.ystride && a.cstride == b.cstride && a.dpitch == b.dpitch && a.w == b.w &&
-           a.h == b.h && a.hs == b.hs && a.vs == b.vs && a.ky == b.ky && a.ybase == b.ybase && a.rv == b.rv && a.gu == b.gu && a.gv == b.gv && a.bu == b.bu && a.bgra == b.bgra;
+           a.h == b.h && a.hs == b.hs && a.vs == b.vs && a.csc.ky == b.csc.ky && a.csc.ybase == b.csc.ybase && a.csc.rv == b.csc.rv && a.csc.gu == b.csc.gu && a.csc.gv == b.csc.gv && a.csc.bu == b.csc.bu && a.bgra == b.bgra;
 }
 template <class T> bool same_jobs(const T *a, int na, const T *b, int nb)
 {

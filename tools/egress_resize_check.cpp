@@ -11,7 +11,7 @@
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         -I digital-subband-video-2_amd/csrc tools/egress_resize_check.cpp -o egress_resize_check && ./egress_resize_check [--dump DIR]
 // --dump DIR writes, for the named cases, NAME.src (the source plane, packed) and NAME.out (the resampled plane, packed), and
-// allowed.txt: resize_allowed's verdict (dev.h: the bounds of the call) on sizes at and around every bound, refused ones included, a
+// allowed.txt: resize_allowed's verdict (io_jobs.h: the bounds of the call) on sizes at and around every bound, refused ones included, a
 // line "pw ph ow oh verdict" each, which the test compares with the oracle's restatement of the bounds.
 #include <stdio.h>
 #include <stdlib.h>
@@ -64,7 +64,7 @@ uint8_t expect_sample(const Plane &p, int ow, int oh, int x, int y)
     return (uint8_t) ((sum + D / 2) / D);
 }
 
-// the kernel's grid (bmc.hip): a thread per four samples of a row, threads past the plane return
+// the kernel's grid (egress.hip): a thread per four samples of a row, threads past the plane return
 template <bool WIDE> void run_grid(const ResizeOutJob &j)
 {
     for (int y = 0; y < ((j.oh + 3) & ~3); y++) {

@@ -88,7 +88,7 @@ void check(const Plane &Y, const Plane &U, const Plane &V, int fmt, int csc, boo
     memset(alloc, kGuard, bytes);
     uint8_t *dst = alloc + start;
     const long *p = kPreset[preset_of(csc)];
-    const RgbOutJob j{Y.org, U.org, V.org, dst, Y.stride, U.stride, (int) pitch, w, h, hs, vs, (int) p[0], (int) p[1], (int) p[2], (int) p[3], (int) p[4], (int) p[5], bgra};
+    const RgbOutJob j{Y.org, U.org, V.org, dst, Y.stride, U.stride, (int) pitch, w, h, hs, vs, {(int) p[0], (int) p[1], (int) p[2], (int) p[3], (int) p[4], (int) p[5]}, bgra};
     const bool wide = rgb_out_job_wide(j) && !force_general;
     wide ? run_grid<true>(j) : run_grid<false>(j);
     g_cases++;

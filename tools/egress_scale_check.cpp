@@ -28,7 +28,7 @@ namespace {
 
 using support::kGuard;
 using support::kLead;                    // guard bytes in front of and behind the destination
-constexpr int kLanes = 8, kRows = 32;  // k_egress_scale's workgroup (bmc.hip): threads along a row, output rows
+constexpr int kLanes = 8, kRows = 32;  // k_egress_scale's workgroup (egress.hip): threads along a row, output rows
 
 struct Plane : support::Plane {
     // bordered: as dframe_alloc lays a plane out (32-pixel border, stride a multiple of 16, 16-byte aligned origin); else as the

@@ -135,7 +135,7 @@ void check(const Plane &Y, const Plane &U, const Plane &V, int fmt, int csc, int
     const float *k = kConst[konst];
     TensorOutJob j{};
     j.sy = Y.org, j.su = U.org, j.sv = V.org, j.ystride = Y.stride, j.cstride = U.stride, j.w = w, j.h = h, j.hs = hs, j.vs = vs;
-    j.ky = (int) p[0], j.ybase = (int) p[1], j.rv = (int) p[2], j.gu = (int) p[3], j.gv = (int) p[4], j.bu = (int) p[5], j.dtype = dtype;
+    j.csc = RgbOutCoefs{(int) p[0], (int) p[1], (int) p[2], (int) p[3], (int) p[4], (int) p[5]}, j.dtype = dtype;
     for (int c = 0; c < 3; c++) {
         if (posix_memalign((void **) &alloc[c], 16, bytes) != 0) {
             abort();

@@ -2,14 +2,14 @@
 // size x source kind x (call, route) x pointer offset x pitch, over FAKE addresses -- the encoder's source planes and the planes of the
 // caller's surface are disjoint ranges of one synthetic address space, and nothing is ever dereferenced or launched.  Meant to be built
 // with AddressSanitizer and UndefinedBehaviorSanitizer.  For every case the program works out, by its own interval arithmetic over the
-// footprints dev.h documents for each job record,
+// footprints io_jobs.h documents for each job record,
 //   acceptance  the call takes or refuses the surface as the table below says (and refuses it on an encoder with UYVY input on);
 //   counts      a taken picture brings the records of ONE launch class, as many as the second table says (restated as data);
 //   coverage    the visible w x h of each of the encoder's three source planes is written by exactly one record, and nothing else is;
 //   reads       what a record reads is exactly the samples that feed the plane(s) it writes -- the whole rows of a plane, the pairs of an
 //               interleaved plane, or its U or its V bytes alone, of the SOURCE's size -- and lies inside (rows - 1) * pitch + row_bytes
 //               of a plane the layout has;
-//   form        the plan's wide flags, the scaled class's largest row bytes and source width are dev.h's *_job_wide predicates and the
+//   form        the plan's wide flags, the scaled class's largest row bytes and source width are io_jobs.h's *_job_wide predicates and the
 //               extents of its records.
 // tests/test_enc_ingest_cpu.py builds and runs it:
 //   hipcc -x hip --cuda-host-only -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
@@ -125,7 +125,7 @@ struct Access { // what one record reads and writes
 int cdiv(int v, int shift) { return (v + (1 << shift) - 1) >> shift; }
 long gcd_of(long x, long y) { return y ? gcd_of(y, x % y) : x; }
 
-// the footprints dev.h documents, record type by record type
+// the footprints io_jobs.h documents, record type by record type
 Access access_of(const SurfaceJob &j)
 {
     Access a{{foot(j.src, j.pitch, 1, j.dst2 ? 2 * j.w : j.w, j.h)}, {foot(j.dst, (U64) j.dstride, 1, j.w, j.h)}};
@@ -280,7 +280,7 @@ void check_plan(const Case &c, const DFrame &f, const SourcePlanes &s, const Ing
             fail(c, "%d records of class %d; the table says %d of class %d alone", p.n[cl], cl, row->n, row->cl);
         }
     }
-    // the records' footprints, and the form facts restated from dev.h's predicates
+    // the records' footprints, and the form facts restated from io_jobs.h's predicates
     std::vector<Access> acc;
     bool wide = true;
     int row_bytes = 0, rgb_sw = 0;

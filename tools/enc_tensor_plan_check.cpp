@@ -187,8 +187,8 @@ void check_tensor(const Case &c)
         const int preset = ((tn.csc & DSV2HIP_CSC_FULL_RANGE) ? 2 : 0) + ((tn.csc & DSV2HIP_CSC_BT709) ? 1 : 0);
         const int *m = kQuads[preset];
         bool ok = j.ystride == f.p[0].stride && j.cstride == f.p[1].stride && j.w == c.w && j.h == c.h && j.hs == hs && j.vs == vs && j.dtype == c.dtype &&
-                  j.ycoef == quad(m, false) && j.upos == quad(m + 3, false) && j.uneg == quad(m + 3, true) && j.vpos == quad(m + 6, false) && j.vneg == quad(m + 6, true) &&
-                  j.yoff == 128u + (preset >= 2 ? 0u : 4096u) && quad(m, true) == 0;
+                  j.csc.ycoef == quad(m, false) && j.csc.upos == quad(m + 3, false) && j.csc.uneg == quad(m + 3, true) && j.csc.vpos == quad(m + 6, false) && j.csc.vneg == quad(m + 6, true) &&
+                  j.csc.yoff == 128u + (preset >= 2 ? 0u : 4096u) && quad(m, true) == 0;
         for (int k = 0; k < 3; k++) {
             ok = ok && j.src[k] == tn.plane[k] && j.pitch[k] == tn.pitch[k] && j.dst[k] == f.p[k].data && j.scale[k] == tn.scale[k] && j.bias[k] == tn.bias[k];
             // reads: h rows of w elements, the last one ending inside what the caller described
@@ -213,7 +213,7 @@ struct Way {
 const Way kWays[12] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {1, 2, 0}, {1, 3, 0}, {2, 0, 0}, {2, 0, 1}, {2, 0, 2}, {2, 0, 3}, {2, 1, 0}, {2, 2, 0}, {2, 3, 0}};
 
 void print_ratio(const SizedRatio &q) { printf(" %u %u %u %u %u %u %u %u", q.a, q.b, q.c, q.d, q.D, q.rD, q.rb, q.rd); }
-template <class J> void print_quads(const J &j) { printf(" %x %x %x %x %x %x", j.ycoef, j.upos, j.uneg, j.vpos, j.vneg, j.yoff); }
+template <class J> void print_quads(const J &j) { printf(" %x %x %x %x %x %x", j.csc.ycoef, j.csc.upos, j.csc.uneg, j.csc.vpos, j.csc.vneg, j.csc.yoff); }
 // the members an IngestPlan had before tensors, as text (addresses are the synthetic ones)
 template <class Plan> void print_plan(const Plan &p)
 {
