@@ -3,7 +3,8 @@
 // tables; tools/dec_delivery_check.cpp compiles it for the host under AddressSanitizer + UndefinedBehaviorSanitizer and sweeps
 // target kind x scale x out420p x postsharp x draw_info x alignment over synthetic addresses (tests/test_dec_delivery_cpu.py);
 // tools/dec_delivery_sized_check.cpp does the same for sized targets (tests/test_dec_delivery_sized_cpu.py),
-// tools/dec_tensor_plan_check.cpp for tensor targets (tests/test_dec_tensor_plan_cpu.py).
+// tools/dec_tensor_plan_check.cpp for tensor targets (tests/test_dec_tensor_plan_cpu.py), tools/dec_hwc_plan_check.cpp for interleaved
+// tensor targets (tests/test_dec_hwc_plan_cpu.py).
 #pragma once
 
 #include <math.h>
@@ -25,7 +26,8 @@ struct OutTarget {
         PLANAR, // the caller's device planes Y, U, V (a packed buffer: pitch {w, cw, cw})
         SEMI,   // ... Y and one plane of interleaved U V rows (plane[2] unused)
         RGB,    // ... one plane of four-byte pixels, plane[0], converted on the way out (plane[1..2] unused)
-        TENSOR  // ... the planes R, G, B of a tensor (dsv2hip_out_tensor), converted on the way out; pitches in bytes
+        TENSOR, // ... the planes R, G, B of a tensor (dsv2hip_out_tensor), converted on the way out; pitches in bytes
+        HWC     // ... one interleaved [h, w, 3] tensor (dsv2hip_out_hwc), plane[0], converted on the way out (plane[1..2] unused)
     } kind = FRAME;
     uint8_t *plane[3] = {nullptr, nullptr, nullptr};
     int pitch[3] = {0, 0, 0};
@@ -34,12 +36,12 @@ struct OutTarget {
     int shift = 0;  // device targets: every plane at 1 / 2^shift of its size, box-averaged on the way out (egress_scale.h); 0 .. 3
     int ow = 0, oh = 0; // device targets: the picture at this size, every plane area-averaged on the way out (egress_resize.h); 0 x 0: not
                         // sized.  Never together with a shift
-    int csc = 0;    // RGB, TENSOR: the DSV2HIP_CSC_* bits
-    bool bgra = false; // RGB: bytes in memory B G R A, else R G B A
-    int dtype = 0;  // TENSOR: DSV2HIP_TENSOR_*
-    float scale[3] = {0, 0, 0}, bias[3] = {0, 0, 0}; // TENSOR, float element types: the per-plane constants
+    int csc = 0;    // RGB, TENSOR, HWC: the DSV2HIP_CSC_* bits
+    bool bgra = false; // RGB: bytes in memory B G R A, else R G B A; HWC: elements B G R, else R G B
+    int dtype = 0;  // TENSOR, HWC: DSV2HIP_TENSOR_*
+    float scale[3] = {0, 0, 0}, bias[3] = {0, 0, 0}; // TENSOR, HWC, float element types: the per-plane / per-element constants
     bool device() const { return kind != FRAME; }
-    bool converted() const { return kind == RGB || kind == TENSOR; } // leaves through a YUV -> RGB conversion, which reads every plane in place
+    bool converted() const { return kind == RGB || kind == TENSOR || kind == HWC; } // leaves through a YUV -> RGB conversion, which reads every plane in place
     bool sized() const { return ow != 0; }
     bool reduced() const { return shift != 0 || sized(); } // leaves through the reduction or the resampling
 };
@@ -106,6 +108,35 @@ inline bool target_tensor(const dsv2hip_out_tensor &tn, size_t row_bytes, int ro
     return true;
 }
 
+// A caller's interleaved tensor whose element type, CSC bits and size dsv2hip_dec_hwc_dims accepted with these rows: false for an order
+// that is not exactly DSV2HIP_SURFACE_RGB or _BGR, a NULL pointer or one not aligned to its element, a pitch that is no multiple of the
+// element, below the row's bytes or beyond an int, a capacity that does not hold the rows, or (float element types) a constant that is
+// not finite.
+inline bool target_hwc(const dsv2hip_out_hwc &hw, size_t row_bytes, int rows, OutTarget *out)
+{
+    OutTarget t;
+    t.kind = OutTarget::HWC;
+    t.dtype = hw.dtype, t.csc = hw.csc;
+    const size_t elem = (size_t) tensor_elem(hw.dtype);
+    if ((hw.order != DSV2HIP_SURFACE_RGB && hw.order != DSV2HIP_SURFACE_BGR) || !hw.data || ((uintptr_t) hw.data) % elem || hw.pitch % elem ||
+        hw.pitch < row_bytes || hw.pitch > (size_t) INT32_MAX || hw.cap < (size_t) (rows - 1) * hw.pitch + row_bytes) {
+        return false;
+    }
+    t.bgra = hw.order == DSV2HIP_SURFACE_BGR;
+    if (hw.dtype != DSV2HIP_TENSOR_U8) {
+        for (int k = 0; k < 3; k++) {
+            if (!isfinite(hw.scale[k]) || !isfinite(hw.bias[k])) {
+                return false;
+            }
+            t.scale[k] = hw.scale[k], t.bias[k] = hw.bias[k];
+        }
+    }
+    t.plane[0] = (uint8_t *) hw.data;
+    t.pitch[0] = (int) hw.pitch;
+    *out = t;
+    return true;
+}
+
 // the packed buffer of dsv2hip_dec_batch_device: the planar surface with pitch {w, cw, cw}, plane behind plane
 inline OutTarget target_packed(void *buf, const size_t row_bytes[3], const int rows[3])
 {
@@ -133,7 +164,7 @@ inline RgbOutCoefs rgb_out_coefs(int csc)
 
 // ---- what one picture contributes to a round --------------------------------------------------------------------------------------------
 // The jobs by launch class, in the order the round launches the classes: whole-frame copy, 4:2:0 conversion, egress, overlay, sharpening
-// in place, reduction, resampling, chroma interleave, RGB conversion, tensor conversion.  A job of a later class may read what a job of an earlier one wrote -- the
+// in place, reduction, resampling, chroma interleave, RGB conversion, tensor conversion, interleaved tensor conversion.  A job of a later class may read what a job of an earlier one wrote -- the
 // decoder's two staging areas -- and nothing else is shared between them.
 struct DeliveryPlan {
     CopyJob copy[1];
@@ -159,15 +190,19 @@ struct DeliveryPlan {
     TensorOutJob ten[1];
     int n_ten = 0;
     bool ten_wide = true;                  // the tensor job allows the unconditional vector stores (egress.hip: k_egress_tensor)
+    // (and behind those the interleaved tensor's)
+    HwcOutJob hwc[1];
+    int n_hwc = 0;
+    bool hwc_wide = true;                  // the interleaved tensor job allows the unconditional vector stores (egress.hip: k_egress_hwc)
 };
 
-// A sharpened and / or drawn-on picture that leaves reduced, as RGB or as a tensor has no delivered full-size luma plane for the overlay and the
+// A sharpened and / or drawn-on picture that leaves reduced, as RGB or as a tensor (planar or interleaved) has no delivered full-size luma plane for the overlay and the
 // sharpening to act on: its luma goes through the egress kernel into DecImpl's staged luma plane (w x h, 16-byte aligned origin and stride)
 inline bool needs_staged_luma(const OutTarget &t, bool sharp, int draw)
 {
     return t.device() && (t.reduced() || t.converted()) && (sharp || draw);
 }
-// the reduced planes that k_egress_uv / k_egress_rgb / k_egress_tensor then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
+// the reduced planes that k_egress_uv / k_egress_rgb / k_egress_tensor / k_egress_hwc then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
 inline bool needs_staged_scaled(const OutTarget &t) { return t.device() && t.reduced() && t.kind != OutTarget::PLANAR; }
 // ... which a sized picture needs at up to the picture's own size, a shifted one at half size
 inline bool needs_staged_full(const OutTarget &t) { return needs_staged_scaled(t) && t.sized(); }
@@ -263,6 +298,25 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
                                                                      {t.scale[0], t.scale[1], t.scale[2]},
                                                                      {t.bias[0], t.bias[1], t.bias[2]}};
             p.ten_wide = tensor_job_wide(tj);
+        } else if (t.kind == OutTarget::HWC) {
+            const HwcOutJob &hj = p.hwc[p.n_hwc++] = HwcOutJob{src[0].data,
+                                                               src[1].data,
+                                                               src[2].data,
+                                                               t.plane[0],
+                                                               src[0].stride,
+                                                               src[1].stride,
+                                                               t.pitch[0],
+                                                               src[0].w,
+                                                               src[0].h,
+                                                               hs,
+                                                               vs,
+                                                               rgb_out_coefs(t.csc),
+                                                               t.bgra,
+                                                               t.dtype,
+                                                               {t.scale[0], t.scale[1], t.scale[2]},
+                                                               {t.bias[0], t.bias[1], t.bias[2]},
+                                                               0};
+            p.hwc_wide = hwc_job_wide(hj);
         }
     } else if (!conv && !t.device() && !sharp_out) {
         p.copy[p.n_copy++] = CopyJob{recon.alloc, t.frame_alloc, recon.bytes};

@@ -227,6 +227,7 @@ thread_local DecClock t_dec_clock;
 std::atomic<unsigned long long> g_uv_rounds[2]; // device rounds whose chroma interleave ran in the wide / the general form (dsv2hip_dec_surface_stats)
 std::atomic<unsigned long long> g_rgb_rounds[2]; // ... whose RGB egress ran in the wide / the general form (dsv2hip_dec_rgb_stats)
 std::atomic<unsigned long long> g_tensor_rounds[2]; // ... whose tensor conversion ran in the wide / the general form (dsv2hip_dec_tensor_stats)
+std::atomic<unsigned long long> g_hwc_rounds[2]; // ... whose interleaved tensor conversion ran in the wide / the general form (dsv2hip_dec_hwc_stats)
 std::atomic<unsigned long long> g_scale_rounds[2]; // ... whose reduction ran in the wide / the general form (dsv2hip_dec_scale_stats)
 std::atomic<unsigned long long> g_resize_rounds[2]; // ... whose resampling ran in the wide / the general form (dsv2hip_dec_resize_stats)
 
@@ -352,23 +353,25 @@ struct Delivery {
     Tab<UvEgressJob> uv;
     Tab<RgbOutJob> rgb;
     Tab<TensorOutJob> ten;
-    size_t room[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // entries the round's plans need of each table, in the order above
-    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb = 0, n_ten = 0;
+    Tab<HwcOutJob> hwc;
+    size_t room[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // entries the round's plans need of each table, in the order above
+    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb = 0, n_ten = 0, n_hwc = 0;
     bool eg_wide = true, eg_sharp = false, scl_wide = true, rsz_wide = true, uv_wide = true, uv_conv = false, rgb_wide = true, ten_wide = true; // DeliveryPlan's, over the round
+    bool hwc_wide = true;
     int scl_rows = 0, rsz_rows = 0, rsz_cols = 0, uv_rows = 0;
     bool ov_vectors = false;         // some overlay job draws motion vectors
     std::vector<DPlane> sharp_drawn; // luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
     size_t count(const std::vector<DeliveryPlan> &plans) // the arena bytes the tables of these plans take
     {
         for (const DeliveryPlan &p : plans) {
-            const int n[9] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_rsz, p.n_uv, p.n_rgb, p.n_ten};
-            for (int k = 0; k < 9; k++) {
+            const int n[10] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_rsz, p.n_uv, p.n_rgb, p.n_ten, p.n_hwc};
+            for (int k = 0; k < 10; k++) {
                 room[k] += (size_t) n[k];
             }
         }
         return room[0] * sizeof(CopyJob) + room[1] * sizeof(To420Job) + room[2] * sizeof(EgressJob) + room[3] * sizeof(OverlayJob) +
                room[4] * sizeof(ScaleOutJob) + room[5] * sizeof(ResizeOutJob) + room[6] * sizeof(UvEgressJob) + room[7] * sizeof(RgbOutJob) +
-               room[8] * sizeof(TensorOutJob) + 9 * 16;
+               room[8] * sizeof(TensorOutJob) + 9 * 16 + (room[9] ? room[9] * sizeof(HwcOutJob) + 16 : 0);
     }
     void take(TableArena &tabs)
     {
@@ -381,6 +384,7 @@ struct Delivery {
         uv = Tab<UvEgressJob>(tabs, room[6]);
         rgb = Tab<RgbOutJob>(tabs, room[7]);
         ten = Tab<TensorOutJob>(tabs, room[8]);
+        hwc = Tab<HwcOutJob>(tabs, room[9]);
     }
     template <class T> static void append(Tab<T> &t, int &n, const T *jobs, int count)
     {
@@ -398,12 +402,14 @@ struct Delivery {
         append(uv, n_uv, p.uv, p.n_uv);
         append(rgb, n_rgb, p.rgb, p.n_rgb);
         append(ten, n_ten, p.ten, p.n_ten);
+        append(hwc, n_hwc, p.hwc, p.n_hwc);
         eg_wide = eg_wide && p.eg_wide, eg_sharp = eg_sharp || p.eg_sharp;
         scl_wide = scl_wide && p.scl_wide, scl_rows = std::max(scl_rows, p.scl_rows);
         rsz_wide = rsz_wide && p.rsz_wide, rsz_rows = std::max(rsz_rows, p.rsz_rows), rsz_cols = std::max(rsz_cols, p.rsz_cols);
         uv_wide = uv_wide && p.uv_wide, uv_conv = uv_conv || p.uv_conv, uv_rows = std::max(uv_rows, p.uv_rows);
         rgb_wide = rgb_wide && p.rgb_wide;
         ten_wide = ten_wide && p.ten_wide;
+        hwc_wide = hwc_wide && p.hwc_wide;
         if (p.n_overlay) {
             oj.dst = p.overlay[0];
             ov.h[n_ov++] = oj;
@@ -442,6 +448,10 @@ struct Delivery {
         if (n_ten) { // (the same place in the order)
             egress_tensor_batch(bs, ten.d, n_ten, h, ten_wide);
             g_tensor_rounds[ten_wide ? 0 : 1]++;
+        }
+        if (n_hwc) { // (the same place in the order, behind the planar tensors)
+            egress_hwc_batch(bs, hwc.d, n_hwc, h, hwc_wide);
+            g_hwc_rounds[hwc_wide ? 0 : 1]++;
         }
     }
 };
@@ -1190,6 +1200,65 @@ int dsv2hip_dec_tensor_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_ten
     return ret;
 }
 
+// Element size, CSC bits and size of an interleaved tensor delivery as dsv2hip_dec_hwc_dims documents them: tensor_dims' with three
+// elements a pixel
+static bool hwc_dims(DSV_DECODER *d, int dtype, int out_w, int out_h, size_t *row_bytes, int *rows, int *ow, int *oh)
+{
+    if (!tensor_dims(d, dtype, out_w, out_h, row_bytes, rows, ow, oh)) {
+        return false;
+    }
+    *row_bytes *= 3;
+    return true;
+}
+
+int dsv2hip_dec_hwc_dims(DSV_DECODER *d, int dtype, int out_w, int out_h, size_t *row_bytes, int *rows)
+{
+    int ow, oh;
+    if (!row_bytes || !rows) {
+        return -1;
+    }
+    return hwc_dims(d, dtype, out_w, out_h, row_bytes, rows, &ow, &oh) ? 0 : -1;
+}
+
+// dsv2hip_dec_batch_tensor's mirror for interleaved tensors
+int dsv2hip_dec_batch_hwc(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_hwc *hws, DSV_FNUM *fn, int *ret)
+{
+    if (n <= 0 || !decs || !bufs || !hws || !fn || !ret) {
+        return -1;
+    }
+    std::vector<DecJob> jobs((size_t) n);
+    for (int k = 0; k < n; k++) {
+        if (!decs[k]) {
+            return -1;
+        }
+        if (!decs[k]->got_metadata) {
+            continue;
+        }
+        const dsv2hip_out_hwc &hw = hws[k];
+        size_t rb;
+        int rows, ow, oh;
+        if ((hw.csc & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE)) || !hwc_dims(decs[k], hw.dtype, hw.out_w, hw.out_h, &rb, &rows, &ow, &oh)) {
+            return -1;
+        }
+        OutTarget &t = jobs[(size_t) k].target;
+        if (!target_hwc(hw, rb, rows, &t)) {
+            return -1;
+        }
+        t.ow = ow, t.oh = oh;
+    }
+    return dec_batch_run(jobs, decs, bufs, nullptr, fn, ret);
+}
+
+int dsv2hip_dec_hwc_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_hwc *t, DSV_FNUM *fn)
+{
+    int ret = DSV_DEC_ERROR;
+    if (dsv2hip_dec_batch_hwc(1, &d, buf, t, fn, &ret) != 1) {
+        return -1;
+    }
+    return ret;
+}
+
+void dsv2hip_dec_hwc_stats(unsigned long long *out2, int reset) { read_rounds(g_hwc_rounds, out2, reset); }
 void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds, out2, reset); }
 void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset) { read_rounds(g_tensor_rounds, out2, reset); }
 void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset) { read_rounds(g_scale_rounds, out2, reset); }

@@ -8,6 +8,7 @@
 #include "degrad.h"
 #include "egress_rgb.h"
 #include "egress_tensor.h"
+#include "egress_hwc.h"
 #include "egress_resize.h"
 #include "egress_scale.h"
 #include "egress_uv.h"
@@ -180,6 +181,30 @@ void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h
     }
     const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
     DSV2_LAUNCH_FORM(wide, k_egress_tensor<true>, k_egress_tensor<false>, grid, block, 0, s, d_jobs);
+}
+
+// ---- decoder egress into an interleaved [h, w, 3] tensor, R G B or B G R: uint8, binary16, bfloat16 or binary32 elements ---------------
+// One job per picture (HwcOutJob, io_jobs.h), fetched by value and pinned to scalar registers as above; k_egress_rgb's grid: 64 x 4
+// threads cover 16 rows and walk the row in passes of 256 pixels.  The thread's work is egress_hwc.h's egress_hwc_rows (which
+// tools/egress_hwc_check.cpp runs on the CPU); the job's element type is uniform over the workgroup.
+template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_hwc(const HwcOutJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const HwcOutJob j = pin(job_of(tab, blockIdx.y));
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    egress_hwc_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void egress_hwc_batch(hipStream_t s, const HwcOutJob *d_jobs, int n, int h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
+    DSV2_LAUNCH_FORM(wide, k_egress_hwc<true>, k_egress_hwc<false>, grid, block, 0, s, d_jobs);
 }
 
 // ---- decoder egress at half, quarter or eighth size: the box average of include/dsv2_hip.h ------------------------------------------

@@ -109,6 +109,26 @@ inline bool tensor_job_wide(const TensorOutJob &j)
     }
     return (bits & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
 }
+struct HwcOutJob { // one decoded picture on its way into an interleaved [h, w, 3] tensor (dsv2hip_out_hwc: uint8, binary16, bfloat16 or binary32
+                   // elements, R G B or B G R), converted on the way (egress_hwc.h, egress.hip: k_egress_hwc); 120 bytes.  It shares
+                   // RgbOutJob's source side and its byte-order word.
+    const uint8_t *sy, *su, *sv; // RgbOutJob's
+    uint8_t *dst;                // device memory, element aligned: pixel x of row y at dst + y * dpitch + 3 * x * elem, 3 * w elements written
+    int ystride, cstride;
+    int dpitch;                  // bytes, a multiple of the element size
+    int w, h;                    // of the picture
+    int hs, vs;                  // the stream's chroma shifts
+    RgbOutCoefs csc;
+    int bgra;                    // the element order: non-zero B G R, zero R G B (RgbOutJob's word: which of R and B is element 0)
+    int dtype;                   // kTensor*
+    float scale[3], bias[3];     // float dtypes: element k of every pixel holds fl32(fl32(byte * scale[k]) + bias[k]), in memory order
+    int unused;                  // (a whole number of 8-byte words: the table's records stay pointer aligned)
+};
+// pointer and pitch multiples of four elements and w of 4: a thread's twelve elements of a row leave as whole vector stores
+inline bool hwc_job_wide(const HwcOutJob &j)
+{
+    return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
+}
 struct TensorInJob { // one picture that is three planes R, G, B of a caller's float tensor (dsv2hip_in_tensor: binary16, bfloat16 or binary32
                      // elements) on its way into the three bordered source planes: taken through the job's per-plane scale and bias, clamped and
                      // rounded to bytes, then converted as a planar RGB surface is (ingest_tensor.h, ingest.hip: k_ingest_tensor); 152 bytes.
@@ -296,6 +316,9 @@ void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool
 // ... into the three planes R, G, B of callers' tensors: n pictures of at most h rows (device table), converted on the way
 // (egress_tensor.h).  wide: every job's plane pointers and pitches are multiples of four elements and its w of 4 (tensor_job_wide).
 void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h, bool wide);
+// ... into callers' interleaved [h, w, 3] tensors: n pictures of at most h rows (device table), converted on the way (egress_hwc.h).
+// wide: every job's pointer and pitch are multiples of four elements and its w of 4 (hwc_job_wide).
+void egress_hwc_batch(hipStream_t s, const HwcOutJob *d_jobs, int n, int h, bool wide);
 // ... at half, quarter or eighth size: n planes (device table) box-averaged on the way (egress_scale.h) into a caller's plane or the
 // decoder's staging picture.  wide: every job's destination and pitch are multiples of 8 and its row is writable up to a multiple of
 // 16 >> shift bytes (scale_job_wide).  max_oh: the most rows delivered.
@@ -319,6 +342,7 @@ DSV2_IO_RECORD(EgressJob, 40);
 DSV2_IO_RECORD(UvEgressJob, 56);
 DSV2_IO_RECORD(RgbOutJob, 88);
 DSV2_IO_RECORD(TensorOutJob, 136);
+DSV2_IO_RECORD(HwcOutJob, 120);
 DSV2_IO_RECORD(ScaleOutJob, 40);
 DSV2_IO_RECORD(ResizeOutJob, 72);
 #undef DSV2_IO_RECORD
@@ -326,5 +350,7 @@ static_assert(offsetof(RgbJob, csc) == 64 && offsetof(Rgb3Job, csc) == 100 && of
                   offsetof(SizedRgbJob, csc) == 112,
               "the ingest quads stay where the six words were");
 static_assert(offsetof(RgbOutJob, csc) == 60 && offsetof(TensorOutJob, csc) == 84, "the egress constants stay where the six ints were");
+static_assert(offsetof(HwcOutJob, csc) == offsetof(RgbOutJob, csc) && offsetof(HwcOutJob, bgra) == offsetof(RgbOutJob, bgra),
+              "the interleaved tensor's record begins as the RGB surface's");
 
 } // namespace dsv2

@@ -869,7 +869,7 @@ void dsv2hip_dec_resize_stats(unsigned long long *out2, int reset);
  * (rows - 1) * pitch[c] + row_bytes; scale[c] or bias[c] not finite (float dtypes only); dsv2hip_dec_set_out420p on; exactly one of
  * out_w / out_h zero; a size dsv2hip_dec_sized_dims refuses for an RGB layout.
  * MEMORY: as an RGB surface's -- a drawn-on or sharpened picture stages its luma, a sized one its resampled planes.
- * Out of scope: interleaved [h, w, 3] out tensors; the DSV2HIP_SCALE_* presets (a size covers them where it divides; THE RESAMPLING
+ * Out of scope: interleaved [h, w, 3] out tensors (they have the calls of INTERLEAVED RGB TENSORS below); the DSV2HIP_SCALE_* presets (a size covers them where it divides; THE RESAMPLING
  * says where the two differ); tensors and surfaces in one step; enlargement; any change to what the surface calls accept.
  * dsv2hip_dec_tensor_stats: out2[0] / out2[1] = device rounds of this process whose tensor conversion ran in the wide form (every
  * plane pointer and pitch of every tensor of the round a multiple of four elements and the delivered width a multiple of 4 -- any
@@ -890,6 +890,58 @@ int  dsv2hip_dec_tensor_dims(DSV_DECODER *dec, int dtype, int out_w, int out_h, 
 int  dsv2hip_dec_batch_tensor(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_tensor *t, DSV_FNUM *fn, int *ret);
 int  dsv2hip_dec_tensor_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_tensor *t, DSV_FNUM *fn);
 void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset);
+/* INTERLEAVED RGB TENSORS, u8 / f16 / bf16 / f32 -- what most image consumers take: an OpenCV Mat / GpuMat (BGR24), numpy, PIL, TF and
+ * JAX pictures (uint8[h, w, 3], float NHWC), torch's channels_last memory format ([n, 3, h, w] that is [n, h, w, 3] in memory).  The
+ * picture leaves the decoder with three elements a pixel, full size or at any smaller size, without a four-byte surface or a planar
+ * tensor and a second pass of the caller's (drop alpha, permute) in between.  The out-surface calls keep refusing 0x20 / 0x21 and
+ * dsv2hip_out_tensor has no layout field, so the interleaved tensor has a descriptor and entry points of its own.
+ * A contiguous torch [h, w, 3] tensor, or a channels_last [1, 3, h, w] one, is data = data_ptr, pitch = 3 * w * elem; an OpenCV
+ * GpuMat of CV_8UC3 is data = mat.data, pitch = mat.step, order DSV2HIP_SURFACE_BGR.
+ * Semantics are those of dsv2hip_dec_batch_tensor: ret[k], fn[k], packet consumption and decoder state are dsv_dec's; t[k] is copied;
+ * only the row_bytes = 3 * out_w * elem of each of the rows are written -- padding, the bytes behind the last row and anything else
+ * never are; a decoder without metadata may pass anything (its entry is not looked at); draw_info and postsharp act on the full-size
+ * luma before everything else; one step may mix element types, orders, sizes, presets, constants and stream geometries; a refused call
+ * touches nothing: no packet, decoder, fn, ret or tensor.
+ * SIZE.  As the planar tensor's: out_w == 0 && out_h == 0 is the picture's own size, else the rules of DELIVERY AT ANY SMALLER SIZE;
+ * out_w == w && out_h == h is the plain delivery and counts in no resize statistic.  dsv2hip_dec_hwc_dims reports row_bytes =
+ * 3 * out_w * elem and rows = out_h (the picture's own size for 0 x 0), and -1 wherever the batch call would refuse for dtype, size or
+ * decoder.
+ * THE CONTRACT.  The bytes R, G, B of pixel (x, y) are THE CONVERSION (csc: any subset of DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE)
+ * of the planar picture the same decoder delivers under the same draw_info / postsharp settings -- for a sized tensor, of the planes
+ * resampled by THE RESAMPLING.  Element k of a pixel is the channel `order` puts there: DSV2HIP_SURFACE_RGB R, G, B;
+ * DSV2HIP_SURFACE_BGR B, G, R.  A U8 tensor in BGR order therefore holds exactly bytes 0, 1, 2 of the BGRA surface of the same call,
+ * one in RGB order those of the RGBA surface; scale and bias are ignored for it and may hold anything.  For a float dtype element k of
+ * every pixel holds, for its byte v, f = fl32( fl32( (float) v * scale[k] ) + bias[k] ), not fused, rounded to F16 / BF16 exactly as
+ * the planar tensor's elements are.  The constants belong to MEMORY POSITIONS: a BGR consumer with ImageNet's constants passes them
+ * in B, G, R order.
+ * Refused as a whole with -1, for a decoder that has metadata: an unknown dtype; an order that is not exactly DSV2HIP_SURFACE_RGB or
+ * DSV2HIP_SURFACE_BGR (0x22, the four-byte layouts and CSC bits in `order` included); a csc bit outside the two; a NULL data; data or
+ * pitch not a multiple of the element size; a pitch below row_bytes or beyond INT_MAX; cap < (rows - 1) * pitch + row_bytes; scale[k]
+ * or bias[k] not finite (float dtypes only); dsv2hip_dec_set_out420p on; exactly one of out_w / out_h zero; a size
+ * dsv2hip_dec_sized_dims refuses for an RGB layout.
+ * MEMORY: as an RGB surface's -- a drawn-on or sharpened picture stages its luma, a sized one its resampled planes.
+ * Out of scope: a fourth channel (the BGRA / RGBA surfaces are that); the DSV2HIP_SCALE_* presets (a size covers them where it
+ * divides); interleaved tensors together with surfaces or planar tensors in one call; enlargement; out420p; host memory; any change to
+ * what the surface or planar-tensor calls accept; the encoder's float interleaved input.
+ * dsv2hip_dec_hwc_stats: out2[0] / out2[1] = device rounds of this process whose interleaved conversion ran in the wide form (data and
+ * pitch of every interleaved tensor of the round multiples of four elements and the delivered width a multiple of 4 -- any contiguous
+ * torch [h, w, 3] or channels_last [1, 3, h, w] tensor with w % 4 == 0: a thread's twelve elements of a row leave as whole vector
+ * stores) / in the general form so far; reset != 0 clears the counts afterwards.  Sized tensors also count in
+ * dsv2hip_dec_resize_stats, as any sized picture; nothing counts in dsv2hip_dec_rgb_stats or dsv2hip_dec_tensor_stats. */
+typedef struct dsv2hip_out_hwc {
+    void  *data;      /* device memory: pixel (x, y) at data + y * pitch + 3 * x * elem */
+    size_t pitch;     /* bytes from one row to the next */
+    size_t cap;       /* bytes the caller owns from data on */
+    int    dtype;     /* DSV2HIP_TENSOR_* (the planar tensor's enum, reused) */
+    int    order;     /* DSV2HIP_SURFACE_RGB: elements R G B;  DSV2HIP_SURFACE_BGR: B G R */
+    int    csc;       /* any subset of DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE */
+    int    out_w, out_h;          /* 0, 0: the picture's own size; else DELIVERY AT ANY SMALLER SIZE */
+    float  scale[3], bias[3];     /* for ELEMENT k of every pixel, in memory order; ignored for U8 */
+} dsv2hip_out_hwc;
+int  dsv2hip_dec_hwc_dims(DSV_DECODER *dec, int dtype, int out_w, int out_h, size_t *row_bytes, int *rows);
+int  dsv2hip_dec_batch_hwc(int n, DSV_DECODER **decs, DSV_BUF *bufs, const dsv2hip_out_hwc *t, DSV_FNUM *fn, int *ret);
+int  dsv2hip_dec_hwc_frame(DSV_DECODER *dec, DSV_BUF *buf, const dsv2hip_out_hwc *t, DSV_FNUM *fn);
+void dsv2hip_dec_hwc_stats(unsigned long long *out2, int reset);
 /* PLANAR RGB FLOAT TENSORS AS ENCODER INPUT, f16 / bf16 / f32 -- what a model or a renderer produces: a diffusion decoder, a
  * super-resolution network, a neural renderer, a simulator emit float [3, h, w] in device memory, usually normalised.  The encoder
  * reads it in place: no kernel of the caller's in front (de-normalise, clamp, round, store uint8[3, h, w]) whose rounding every
