@@ -2,9 +2,8 @@
 // call and of any allocation.  decoder.cpp plans every picture of a round with it before it sizes and fills the round's job
 // tables; tools/dec_delivery_check.cpp compiles it for the host under AddressSanitizer + UndefinedBehaviorSanitizer and sweeps
 // target kind x scale x out420p x postsharp x draw_info x alignment over synthetic addresses (tests/test_dec_delivery_cpu.py);
-// tools/dec_delivery_sized_check.cpp does the same for sized targets (tests/test_dec_delivery_sized_cpu.py),
-// tools/dec_tensor_plan_check.cpp for tensor targets (tests/test_dec_tensor_plan_cpu.py), tools/dec_hwc_plan_check.cpp for interleaved
-// tensor targets (tests/test_dec_hwc_plan_cpu.py).
+// tools/dec_delivery_sized_check.cpp does the same for sized targets (tests/test_dec_delivery_sized_cpu.py), tools/dec_plan_check.cpp
+// for planar and interleaved tensor targets (tests/test_dec_plan_cpu.py).
 #pragma once
 
 #include <math.h>
@@ -164,8 +163,8 @@ inline RgbOutCoefs rgb_out_coefs(int csc)
 
 // ---- what one picture contributes to a round --------------------------------------------------------------------------------------------
 // The jobs by launch class, in the order the round launches the classes: whole-frame copy, 4:2:0 conversion, egress, overlay, sharpening
-// in place, reduction, resampling, chroma interleave, RGB conversion, tensor conversion, interleaved tensor conversion.  A job of a later class may read what a job of an earlier one wrote -- the
-// decoder's two staging areas -- and nothing else is shared between them.
+// in place, reduction, resampling, chroma interleave, RGB conversion (one launch per layout: packed, planar, interleaved).  A job of a
+// later class may read what a job of an earlier one wrote -- the decoder's two staging areas -- and nothing else is shared between them.
 struct DeliveryPlan {
     CopyJob copy[1];
     To420Job to420[3];
@@ -185,15 +184,7 @@ struct DeliveryPlan {
     int rsz_rows = 0, rsz_cols = 0;        // the most rows / samples a row a resampling job delivers
     bool uv_wide = true, uv_conv = false;  // the interleave job allows the 16-byte form / converts to 4:2:0 (egress.hip: k_egress_uv)
     int uv_rows = 0;                       // the chroma rows it delivers ("4:1:0" to 4:2:0: more than the source has)
-    bool rgb_wide = true;                  // the RGB job allows the 16-byte form (egress.hip: k_egress_rgb)
-    // (behind everything the plans of the other targets hold: theirs are what they were)
-    TensorOutJob ten[1];
-    int n_ten = 0;
-    bool ten_wide = true;                  // the tensor job allows the unconditional vector stores (egress.hip: k_egress_tensor)
-    // (and behind those the interleaved tensor's)
-    HwcOutJob hwc[1];
-    int n_hwc = 0;
-    bool hwc_wide = true;                  // the interleaved tensor job allows the unconditional vector stores (egress.hip: k_egress_hwc)
+    bool rgb_wide = true;                  // the RGB job allows the wide form (egress.hip: k_egress_rgb; its layout: rgb[0].layout)
 };
 
 // A sharpened and / or drawn-on picture that leaves reduced, as RGB or as a tensor (planar or interleaved) has no delivered full-size luma plane for the overlay and the
@@ -202,7 +193,7 @@ inline bool needs_staged_luma(const OutTarget &t, bool sharp, int draw)
 {
     return t.device() && (t.reduced() || t.converted()) && (sharp || draw);
 }
-// the reduced planes that k_egress_uv / k_egress_rgb / k_egress_tensor / k_egress_hwc then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
+// the reduced planes that k_egress_uv / k_egress_rgb then read go into DecImpl's staged scaled picture (16-byte aligned origins and strides)
 inline bool needs_staged_scaled(const OutTarget &t) { return t.device() && t.reduced() && t.kind != OutTarget::PLANAR; }
 // ... which a sized picture needs at up to the picture's own size, a shifted one at half size
 inline bool needs_staged_full(const OutTarget &t) { return needs_staged_scaled(t) && t.sized(); }
@@ -277,46 +268,26 @@ inline DeliveryPlan plan_delivery(const DFrame &recon, int out_format, const Out
                 UvEgressJob{src[1].data, src[2].data, t.plane[1], t.pitch[1], src[1].stride, src[1].w, src[1].h, src[1].w, src[1].h, 0};
             p.uv_wide = uv_job_wide(uj);
             p.uv_rows = src[1].h;
-        } else if (t.kind == OutTarget::RGB) {
-            const RgbOutJob &rj = p.rgb[p.n_rgb++] = RgbOutJob{src[0].data, src[1].data, src[2].data, t.plane[0], src[0].stride, src[1].stride, t.pitch[0],
-                                                               src[0].w, src[0].h, hs, vs, rgb_out_coefs(t.csc), t.bgra};
-            p.rgb_wide = rgb_out_job_wide(rj);
-        } else if (t.kind == OutTarget::TENSOR) {
-            const TensorOutJob &tj = p.ten[p.n_ten++] = TensorOutJob{src[0].data,
-                                                                     src[1].data,
-                                                                     src[2].data,
-                                                                     {t.plane[0], t.plane[1], t.plane[2]},
-                                                                     src[0].stride,
-                                                                     src[1].stride,
-                                                                     {t.pitch[0], t.pitch[1], t.pitch[2]},
-                                                                     src[0].w,
-                                                                     src[0].h,
-                                                                     hs,
-                                                                     vs,
-                                                                     rgb_out_coefs(t.csc),
-                                                                     t.dtype,
-                                                                     {t.scale[0], t.scale[1], t.scale[2]},
-                                                                     {t.bias[0], t.bias[1], t.bias[2]}};
-            p.ten_wide = tensor_job_wide(tj);
-        } else if (t.kind == OutTarget::HWC) {
-            const HwcOutJob &hj = p.hwc[p.n_hwc++] = HwcOutJob{src[0].data,
+        } else if (t.converted()) { // one conversion job, its layout the target's (plane[1..2] and pitch[1..2]: null / 0 but for TENSOR)
+            const int layout = t.kind == OutTarget::RGB ? kRgbOutPacked : t.kind == OutTarget::TENSOR ? kRgbOutPlanar : kRgbOutInterleaved;
+            const RgbOutJob &rj = p.rgb[p.n_rgb++] = RgbOutJob{src[0].data,
                                                                src[1].data,
                                                                src[2].data,
-                                                               t.plane[0],
                                                                src[0].stride,
                                                                src[1].stride,
-                                                               t.pitch[0],
                                                                src[0].w,
                                                                src[0].h,
                                                                hs,
                                                                vs,
                                                                rgb_out_coefs(t.csc),
                                                                t.bgra,
+                                                               layout,
+                                                               {t.plane[0], t.plane[1], t.plane[2]},
+                                                               {t.pitch[0], t.pitch[1], t.pitch[2]},
                                                                t.dtype,
                                                                {t.scale[0], t.scale[1], t.scale[2]},
-                                                               {t.bias[0], t.bias[1], t.bias[2]},
-                                                               0};
-            p.hwc_wide = hwc_job_wide(hj);
+                                                               {t.bias[0], t.bias[1], t.bias[2]}};
+            p.rgb_wide = rgb_out_job_wide(rj);
         }
     } else if (!conv && !t.device() && !sharp_out) {
         p.copy[p.n_copy++] = CopyJob{recon.alloc, t.frame_alloc, recon.bytes};

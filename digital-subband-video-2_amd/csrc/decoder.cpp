@@ -225,9 +225,9 @@ struct DecClock { // DSV2_TRACE=2: wall-clock split of a lockstep decode step, p
 };
 thread_local DecClock t_dec_clock;
 std::atomic<unsigned long long> g_uv_rounds[2]; // device rounds whose chroma interleave ran in the wide / the general form (dsv2hip_dec_surface_stats)
-std::atomic<unsigned long long> g_rgb_rounds[2]; // ... whose RGB egress ran in the wide / the general form (dsv2hip_dec_rgb_stats)
-std::atomic<unsigned long long> g_tensor_rounds[2]; // ... whose tensor conversion ran in the wide / the general form (dsv2hip_dec_tensor_stats)
-std::atomic<unsigned long long> g_hwc_rounds[2]; // ... whose interleaved tensor conversion ran in the wide / the general form (dsv2hip_dec_hwc_stats)
+// ... whose RGB conversion of a layout (kRgbOut*) ran in the wide / the general form: dsv2hip_dec_rgb_stats (packed), _tensor_stats (planar),
+// _hwc_stats (interleaved)
+std::atomic<unsigned long long> g_rgb_rounds[kRgbOutLayouts][2];
 std::atomic<unsigned long long> g_scale_rounds[2]; // ... whose reduction ran in the wide / the general form (dsv2hip_dec_scale_stats)
 std::atomic<unsigned long long> g_resize_rounds[2]; // ... whose resampling ran in the wide / the general form (dsv2hip_dec_resize_stats)
 
@@ -351,27 +351,28 @@ struct Delivery {
     Tab<ScaleOutJob> scl;
     Tab<ResizeOutJob> rsz;
     Tab<UvEgressJob> uv;
-    Tab<RgbOutJob> rgb;
-    Tab<TensorOutJob> ten;
-    Tab<HwcOutJob> hwc;
-    size_t room[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // entries the round's plans need of each table, in the order above
-    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb = 0, n_ten = 0, n_hwc = 0;
-    bool eg_wide = true, eg_sharp = false, scl_wide = true, rsz_wide = true, uv_wide = true, uv_conv = false, rgb_wide = true, ten_wide = true; // DeliveryPlan's, over the round
-    bool hwc_wide = true;
+    Tab<RgbOutJob> rgb[kRgbOutLayouts]; // one table per layout, one launch each
+    size_t room[7 + kRgbOutLayouts] = {}; // entries the round's plans need of each table, in the order above
+    int n_copy = 0, n_to420 = 0, n_eg = 0, n_ov = 0, n_scl = 0, n_rsz = 0, n_uv = 0, n_rgb[kRgbOutLayouts] = {};
+    bool eg_wide = true, eg_sharp = false, scl_wide = true, rsz_wide = true, uv_wide = true, uv_conv = false; // DeliveryPlan's, over the round
+    bool rgb_wide[kRgbOutLayouts] = {true, true, true};
     int scl_rows = 0, rsz_rows = 0, rsz_cols = 0, uv_rows = 0;
     bool ov_vectors = false;         // some overlay job draws motion vectors
     std::vector<DPlane> sharp_drawn; // luma planes that are drawn on AND sharpened: sharpened in place behind the overlay
     size_t count(const std::vector<DeliveryPlan> &plans) // the arena bytes the tables of these plans take
     {
         for (const DeliveryPlan &p : plans) {
-            const int n[10] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_rsz, p.n_uv, p.n_rgb, p.n_ten, p.n_hwc};
-            for (int k = 0; k < 10; k++) {
+            const int n[7] = {p.n_copy, p.n_to420, p.n_eg, p.n_overlay, p.n_scl, p.n_rsz, p.n_uv};
+            for (int k = 0; k < 7; k++) {
                 room[k] += (size_t) n[k];
+            }
+            if (p.n_rgb) {
+                room[7 + p.rgb[0].layout] += (size_t) p.n_rgb;
             }
         }
         return room[0] * sizeof(CopyJob) + room[1] * sizeof(To420Job) + room[2] * sizeof(EgressJob) + room[3] * sizeof(OverlayJob) +
-               room[4] * sizeof(ScaleOutJob) + room[5] * sizeof(ResizeOutJob) + room[6] * sizeof(UvEgressJob) + room[7] * sizeof(RgbOutJob) +
-               room[8] * sizeof(TensorOutJob) + 9 * 16 + (room[9] ? room[9] * sizeof(HwcOutJob) + 16 : 0);
+               room[4] * sizeof(ScaleOutJob) + room[5] * sizeof(ResizeOutJob) + room[6] * sizeof(UvEgressJob) +
+               (room[7] + room[8] + room[9]) * sizeof(RgbOutJob) + 10 * 16; // (16: each table's alignment)
     }
     void take(TableArena &tabs)
     {
@@ -382,9 +383,9 @@ struct Delivery {
         scl = Tab<ScaleOutJob>(tabs, room[4]);
         rsz = Tab<ResizeOutJob>(tabs, room[5]);
         uv = Tab<UvEgressJob>(tabs, room[6]);
-        rgb = Tab<RgbOutJob>(tabs, room[7]);
-        ten = Tab<TensorOutJob>(tabs, room[8]);
-        hwc = Tab<HwcOutJob>(tabs, room[9]);
+        for (int l = 0; l < kRgbOutLayouts; l++) {
+            rgb[l] = Tab<RgbOutJob>(tabs, room[7 + l]);
+        }
     }
     template <class T> static void append(Tab<T> &t, int &n, const T *jobs, int count)
     {
@@ -400,16 +401,15 @@ struct Delivery {
         append(scl, n_scl, p.scl, p.n_scl);
         append(rsz, n_rsz, p.rsz, p.n_rsz);
         append(uv, n_uv, p.uv, p.n_uv);
-        append(rgb, n_rgb, p.rgb, p.n_rgb);
-        append(ten, n_ten, p.ten, p.n_ten);
-        append(hwc, n_hwc, p.hwc, p.n_hwc);
+        if (p.n_rgb) {
+            const int l = p.rgb[0].layout;
+            append(rgb[l], n_rgb[l], p.rgb, p.n_rgb);
+            rgb_wide[l] = rgb_wide[l] && p.rgb_wide;
+        }
         eg_wide = eg_wide && p.eg_wide, eg_sharp = eg_sharp || p.eg_sharp;
         scl_wide = scl_wide && p.scl_wide, scl_rows = std::max(scl_rows, p.scl_rows);
         rsz_wide = rsz_wide && p.rsz_wide, rsz_rows = std::max(rsz_rows, p.rsz_rows), rsz_cols = std::max(rsz_cols, p.rsz_cols);
         uv_wide = uv_wide && p.uv_wide, uv_conv = uv_conv || p.uv_conv, uv_rows = std::max(uv_rows, p.uv_rows);
-        rgb_wide = rgb_wide && p.rgb_wide;
-        ten_wide = ten_wide && p.ten_wide;
-        hwc_wide = hwc_wide && p.hwc_wide;
         if (p.n_overlay) {
             oj.dst = p.overlay[0];
             ov.h[n_ov++] = oj;
@@ -441,17 +441,11 @@ struct Delivery {
             egress_uv_batch(bs, uv.d, n_uv, uv_rows, uv_wide, uv_conv);
             g_uv_rounds[uv_wide ? 0 : 1]++;
         }
-        if (n_rgb) { // last: behind the overlay and the sharpening of the luma planes staged for it
-            egress_rgb_batch(bs, rgb.d, n_rgb, h, rgb_wide);
-            g_rgb_rounds[rgb_wide ? 0 : 1]++;
-        }
-        if (n_ten) { // (the same place in the order)
-            egress_tensor_batch(bs, ten.d, n_ten, h, ten_wide);
-            g_tensor_rounds[ten_wide ? 0 : 1]++;
-        }
-        if (n_hwc) { // (the same place in the order, behind the planar tensors)
-            egress_hwc_batch(bs, hwc.d, n_hwc, h, hwc_wide);
-            g_hwc_rounds[hwc_wide ? 0 : 1]++;
+        for (int l = 0; l < kRgbOutLayouts; l++) { // last, packed, planar, interleaved: behind the overlay and the sharpening of the luma planes staged for it
+            if (n_rgb[l]) {
+                egress_rgb_batch(bs, rgb[l].d, n_rgb[l], h, l, rgb_wide[l]);
+                g_rgb_rounds[l][rgb_wide[l] ? 0 : 1]++;
+            }
         }
     }
 };
@@ -1258,9 +1252,9 @@ int dsv2hip_dec_hwc_frame(DSV_DECODER *d, DSV_BUF *buf, const dsv2hip_out_hwc *t
     return ret;
 }
 
-void dsv2hip_dec_hwc_stats(unsigned long long *out2, int reset) { read_rounds(g_hwc_rounds, out2, reset); }
-void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds, out2, reset); }
-void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset) { read_rounds(g_tensor_rounds, out2, reset); }
+void dsv2hip_dec_hwc_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds[kRgbOutInterleaved], out2, reset); }
+void dsv2hip_dec_rgb_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds[kRgbOutPacked], out2, reset); }
+void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset) { read_rounds(g_rgb_rounds[kRgbOutPlanar], out2, reset); }
 void dsv2hip_dec_scale_stats(unsigned long long *out2, int reset) { read_rounds(g_scale_rounds, out2, reset); }
 void dsv2hip_dec_resize_stats(unsigned long long *out2, int reset) { read_rounds(g_resize_rounds, out2, reset); }
 void dsv2hip_dec_surface_stats(unsigned long long *out2, int reset) { read_rounds(g_uv_rounds, out2, reset); }

@@ -7,8 +7,6 @@
 #include "io_jobs.h"
 #include "degrad.h"
 #include "egress_rgb.h"
-#include "egress_tensor.h"
-#include "egress_hwc.h"
 #include "egress_resize.h"
 #include "egress_scale.h"
 #include "egress_uv.h"
@@ -134,12 +132,12 @@ void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch
     }
 }
 
-// ---- decoder egress into a packed four-byte RGB surface (BGRA / RGBA), converted on the way out ----------------------------------
+// ---- decoder egress as RGB, converted on the way out: packed four-byte surfaces (BGRA / RGBA), planar or interleaved tensors -------------
 // One job per picture (RgbOutJob, io_jobs.h), fetched by value and pinned to scalar registers (dev.h: job_of, pin) as k_ingest_rgb
 // (ingest.hip) does, whose shape this mirrors: 64 x 4 threads cover 16 rows -- every vertical chroma footprint, up to 4 rows, lies
 // inside one thread -- and walk the row in passes of 256 pixels.  The thread's work is egress_rgb.h's egress_rgb_rows (which
-// tools/egress_rgb_check.cpp runs on the CPU).
-template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_rgb(const RgbOutJob *__restrict__ tab)
+// tools/egress_rgb_check.cpp runs on the CPU); the layout is the kernel's, the job's element type is uniform over the workgroup.
+template <int LAYOUT, bool WIDE> __global__ __launch_bounds__(256) void k_egress_rgb(const RgbOutJob *__restrict__ tab)
 {
     DSV2_KERNEL_PRIO();
     const RgbOutJob j = pin(job_of(tab, blockIdx.y));
@@ -147,64 +145,27 @@ template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_rgb(const R
     if (y0 >= j.h) {
         return;
     }
-    egress_rgb_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+    egress_rgb_rows<LAYOUT, WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
 }
 
-void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide)
+template <int LAYOUT> static void egress_rgb_launch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide)
+{
+    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
+    DSV2_LAUNCH_FORM(wide, (k_egress_rgb<LAYOUT, true>), (k_egress_rgb<LAYOUT, false>), grid, block, 0, s, d_jobs);
+}
+
+void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, int layout, bool wide)
 {
     if (n <= 0) {
         return;
     }
-    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
-    DSV2_LAUNCH_FORM(wide, k_egress_rgb<true>, k_egress_rgb<false>, grid, block, 0, s, d_jobs);
-}
-
-// ---- decoder egress into the three planes R, G, B of a caller's tensor: uint8, binary16, bfloat16 or binary32 elements -----------------
-// One job per picture (TensorOutJob, io_jobs.h), fetched by value and pinned to scalar registers as above; k_egress_rgb's shape: 64 x 4
-// threads cover 16 rows and walk the row in passes of 256 pixels.  The thread's work is egress_tensor.h's egress_tensor_rows (which
-// tools/egress_tensor_check.cpp runs on the CPU); the job's element type is uniform over the workgroup.
-template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_tensor(const TensorOutJob *__restrict__ tab)
-{
-    DSV2_KERNEL_PRIO();
-    const TensorOutJob j = pin(job_of(tab, blockIdx.y));
-    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
-    if (y0 >= j.h) {
-        return;
+    if (layout == kRgbOutPacked) {
+        egress_rgb_launch<kRgbOutPacked>(s, d_jobs, n, h, wide);
+    } else if (layout == kRgbOutPlanar) {
+        egress_rgb_launch<kRgbOutPlanar>(s, d_jobs, n, h, wide);
+    } else {
+        egress_rgb_launch<kRgbOutInterleaved>(s, d_jobs, n, h, wide);
     }
-    egress_tensor_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
-}
-
-void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h, bool wide)
-{
-    if (n <= 0) {
-        return;
-    }
-    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
-    DSV2_LAUNCH_FORM(wide, k_egress_tensor<true>, k_egress_tensor<false>, grid, block, 0, s, d_jobs);
-}
-
-// ---- decoder egress into an interleaved [h, w, 3] tensor, R G B or B G R: uint8, binary16, bfloat16 or binary32 elements ---------------
-// One job per picture (HwcOutJob, io_jobs.h), fetched by value and pinned to scalar registers as above; k_egress_rgb's grid: 64 x 4
-// threads cover 16 rows and walk the row in passes of 256 pixels.  The thread's work is egress_hwc.h's egress_hwc_rows (which
-// tools/egress_hwc_check.cpp runs on the CPU); the job's element type is uniform over the workgroup.
-template <bool WIDE> __global__ __launch_bounds__(256) void k_egress_hwc(const HwcOutJob *__restrict__ tab)
-{
-    DSV2_KERNEL_PRIO();
-    const HwcOutJob j = pin(job_of(tab, blockIdx.y));
-    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
-    if (y0 >= j.h) {
-        return;
-    }
-    egress_hwc_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
-}
-
-void egress_hwc_batch(hipStream_t s, const HwcOutJob *d_jobs, int n, int h, bool wide)
-{
-    if (n <= 0) {
-        return;
-    }
-    const dim3 grid((h + kEgressRows - 1) / kEgressRows, n), block(64, 4);
-    DSV2_LAUNCH_FORM(wide, k_egress_hwc<true>, k_egress_hwc<false>, grid, block, 0, s, d_jobs);
 }
 
 // ---- decoder egress at half, quarter or eighth size: the box average of include/dsv2_hip.h ------------------------------------------

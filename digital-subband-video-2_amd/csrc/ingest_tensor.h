@@ -17,7 +17,7 @@
 // conversion, as every ingest here does; binary32 would hold 48 registers of raw data that way and takes its rows TWO at a time
 // (24 registers), the first pair converted to its eight pixel dwords before the second pair is asked for.
 // The element type is data of the job, one value for the whole workgroup: the switch on it stands outside the loops, around the
-// switch on the stream's format (egress_tensor.h).
+// switch on the stream's format (egress_rgb.h).
 // THE FLOAT CONTRACT (include/dsv2_hip.h): g = fl32(fl32(e * scale) + bias), two IEEE binary32 operations, NOT fused (tensor_num.h's
 // tensor_affine, shared with the decoder's side); the byte is 0 for a NaN, else rint(min(max(g, 0), 255)) with ties to even.  The clamp
 // stands BEFORE the conversion to an integer, which is undefined outside the integer's range on the host and need not saturate alike

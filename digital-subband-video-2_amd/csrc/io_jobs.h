@@ -72,62 +72,40 @@ struct UvEgressJob { // both chroma planes of a decoded picture on their way int
     int mode;               // To420Job's: 0 as decoded, 1 from 4:4:4, 2 from 4:2:2, 3 from 4:1:1, 4 from "4:1:0"
 };
 inline bool uv_job_wide(const UvEgressJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && j.cw % 8 == 0; }
-struct RgbOutJob { // one decoded picture on its way into a packed four-byte RGB surface (dsv2hip_out_surface, BGRA / RGBA), converted on the
-                   // way (egress_rgb.h, egress.hip: k_egress_rgb); 88 bytes
+constexpr int kTensorU8 = 0, kTensorF16 = 1, kTensorBF16 = 2, kTensorF32 = 3; // RgbOutJob::dtype, TensorInJob::dtype (DSV2HIP_TENSOR_*)
+inline int tensor_elem(int dtype) { return dtype == kTensorU8 ? 1 : dtype == kTensorF32 ? 4 : 2; } // bytes of an element
+// RgbOutJob::layout: where the converted picture goes -- a packed four-byte RGB surface (dsv2hip_out_surface, BGRA / RGBA), the three
+// planes R, G, B of a tensor (dsv2hip_out_tensor) or an interleaved [h, w, 3] tensor (dsv2hip_out_hwc); one launch takes one layout
+constexpr int kRgbOutPacked = 0, kRgbOutPlanar = 1, kRgbOutInterleaved = 2, kRgbOutLayouts = 3;
+struct RgbOutJob { // one decoded picture on its way out as RGB, converted on the way (egress_rgb.h, egress.hip: k_egress_rgb); 144 bytes.
+                   // What every layout reads comes first, the tensors' element type and constants last.
     const uint8_t *sy, *su, *sv; // pixel (0,0) of the luma and the chroma planes: 16-byte aligned origin and stride, rows readable up to the
                                  // next multiple of 4 bytes (dframe_alloc's border; the decoder's staged luma: its stride)
-    uint8_t *dst;                // device memory, any alignment: row y at dst + y * dpitch, 4 * w bytes of it written
     int ystride, cstride;        // of sy; of su and sv (the two chroma planes of a frame share their geometry)
-    int dpitch;
     int w, h;                    // of the picture
     int hs, vs;                  // the stream's chroma shifts
     RgbOutCoefs csc;
-    int bgra;                    // the surface's byte order: non-zero B G R A, zero R G B A
+    int bgra;                    // packed: the byte order, non-zero B G R A, zero R G B A; interleaved: the element order, non-zero B G R,
+                                 // zero R G B (which of R and B is byte / element 0); planar: 0 (the planes are R, G, B)
+    int layout;                  // kRgbOut*
+    uint8_t *dst[3];             // device memory.  Packed: any alignment, row y at dst[0] + y * dpitch[0], 4 * w bytes of it written.
+    int dpitch[3];               // Planar: element aligned, row y of R, G, B at dst[c] + y * dpitch[c], w elements of it written.
+                                 // Interleaved: element aligned, pixel x of row y at dst[0] + y * dpitch[0] + 3 * x * elem, 3 * w elements
+                                 // written.  Pitches in bytes, multiples of the element size.  Only planar uses dst[1..2], dpitch[1..2]
+    int dtype;                   // tensors: kTensor*; packed: kTensorU8
+    float scale[3], bias[3];     // float dtypes: plane c (planar) / element k of every pixel in memory order (interleaved) holds
+                                 // fl32(fl32(byte * scale) + bias), rounded to the element type
 };
-inline bool rgb_out_job_wide(const RgbOutJob &j) { return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & 15) == 0 && (j.w & 3) == 0; }
-constexpr int kTensorU8 = 0, kTensorF16 = 1, kTensorBF16 = 2, kTensorF32 = 3; // TensorOutJob::dtype (DSV2HIP_TENSOR_*)
-inline int tensor_elem(int dtype) { return dtype == kTensorU8 ? 1 : dtype == kTensorF32 ? 4 : 2; } // bytes of an element
-struct TensorOutJob { // one decoded picture on its way into three planes R, G, B of a caller's tensor (dsv2hip_out_tensor: uint8, binary16, bfloat16
-                      // or binary32 elements), converted on the way (egress_tensor.h, egress.hip: k_egress_tensor); 136 bytes.  It shares
-                      // RgbOutJob's source side.
-    const uint8_t *sy, *su, *sv; // RgbOutJob's
-    uint8_t *dst[3];             // device memory, element aligned: row y of R, G, B at dst[c] + y * dpitch[c], w elements of it written
-    int ystride, cstride;
-    int dpitch[3];               // bytes, multiples of the element size
-    int w, h;                    // of the picture
-    int hs, vs;                  // the stream's chroma shifts
-    RgbOutCoefs csc;
-    int dtype;                   // kTensor*
-    float scale[3], bias[3];     // float dtypes: plane c holds fl32(fl32(byte * scale[c]) + bias[c]), rounded to the element type
-};
-// every plane's pointer and pitch multiples of four elements and w of 4: a thread's four samples of a row leave as one vector store
-inline bool tensor_job_wide(const TensorOutJob &j)
+// Which launches may take the wide form: the destination pointers and pitches of the layout -- packed: multiples of 16 bytes; tensors:
+// of four elements, every plane's where planar -- and w a multiple of 4.  A thread's row then leaves as whole vector stores.
+inline bool rgb_out_job_wide(const RgbOutJob &j)
 {
     uintptr_t bits = 0;
-    for (int c = 0; c < 3; c++) {
+    for (int c = 0; c < (j.layout == kRgbOutPlanar ? 3 : 1); c++) {
         bits |= ((uintptr_t) j.dst[c]) | (uintptr_t) j.dpitch[c];
     }
-    return (bits & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
-}
-struct HwcOutJob { // one decoded picture on its way into an interleaved [h, w, 3] tensor (dsv2hip_out_hwc: uint8, binary16, bfloat16 or binary32
-                   // elements, R G B or B G R), converted on the way (egress_hwc.h, egress.hip: k_egress_hwc); 120 bytes.  It shares
-                   // RgbOutJob's source side and its byte-order word.
-    const uint8_t *sy, *su, *sv; // RgbOutJob's
-    uint8_t *dst;                // device memory, element aligned: pixel x of row y at dst + y * dpitch + 3 * x * elem, 3 * w elements written
-    int ystride, cstride;
-    int dpitch;                  // bytes, a multiple of the element size
-    int w, h;                    // of the picture
-    int hs, vs;                  // the stream's chroma shifts
-    RgbOutCoefs csc;
-    int bgra;                    // the element order: non-zero B G R, zero R G B (RgbOutJob's word: which of R and B is element 0)
-    int dtype;                   // kTensor*
-    float scale[3], bias[3];     // float dtypes: element k of every pixel holds fl32(fl32(byte * scale[k]) + bias[k]), in memory order
-    int unused;                  // (a whole number of 8-byte words: the table's records stay pointer aligned)
-};
-// pointer and pitch multiples of four elements and w of 4: a thread's twelve elements of a row leave as whole vector stores
-inline bool hwc_job_wide(const HwcOutJob &j)
-{
-    return ((((uintptr_t) j.dst) | (uintptr_t) j.dpitch) & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
+    const uintptr_t grain = j.layout == kRgbOutPacked ? 16 : (uintptr_t) (4 * tensor_elem(j.dtype));
+    return (bits & (grain - 1)) == 0 && (j.w & 3) == 0;
 }
 struct TensorInJob { // one picture that is three planes R, G, B of a caller's float tensor (dsv2hip_in_tensor: binary16, bfloat16 or binary32
                      // elements) on its way into the three bordered source planes: taken through the job's per-plane scale and bias, clamped and
@@ -310,15 +288,9 @@ void egress_batch(hipStream_t s, const EgressJob *d_jobs, int n, int max_h, bool
 // the way where the job's mode says so.  wide: every job's destination and pitch are multiples of 16 and its cw of 8
 // (uv_job_wide); any_conv: some job has mode != 0.  max_ch: the most rows delivered.
 void egress_uv_batch(hipStream_t s, const UvEgressJob *d_jobs, int n, int max_ch, bool wide, bool any_conv);
-// ... into packed four-byte RGB surfaces: n pictures of h rows (device table), converted on the way (egress_rgb.h).  wide: every
-// job's destination and pitch are multiples of 16 and its w of 4 (rgb_out_job_wide).
-void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, bool wide);
-// ... into the three planes R, G, B of callers' tensors: n pictures of at most h rows (device table), converted on the way
-// (egress_tensor.h).  wide: every job's plane pointers and pitches are multiples of four elements and its w of 4 (tensor_job_wide).
-void egress_tensor_batch(hipStream_t s, const TensorOutJob *d_jobs, int n, int h, bool wide);
-// ... into callers' interleaved [h, w, 3] tensors: n pictures of at most h rows (device table), converted on the way (egress_hwc.h).
-// wide: every job's pointer and pitch are multiples of four elements and its w of 4 (hwc_job_wide).
-void egress_hwc_batch(hipStream_t s, const HwcOutJob *d_jobs, int n, int h, bool wide);
+// ... as RGB, converted on the way (egress_rgb.h): n pictures of at most h rows (device table), every job of the given layout
+// (kRgbOut*: packed four-byte surfaces, planar or interleaved tensors).  wide: rgb_out_job_wide of every job.
+void egress_rgb_batch(hipStream_t s, const RgbOutJob *d_jobs, int n, int h, int layout, bool wide);
 // ... at half, quarter or eighth size: n planes (device table) box-averaged on the way (egress_scale.h) into a caller's plane or the
 // decoder's staging picture.  wide: every job's destination and pitch are multiples of 8 and its row is writable up to a multiple of
 // 16 >> shift bytes (scale_job_wide).  max_oh: the most rows delivered.
@@ -340,17 +312,14 @@ DSV2_IO_RECORD(SizedSurfaceJob, 64);
 DSV2_IO_RECORD(SizedRgbJob, 136);
 DSV2_IO_RECORD(EgressJob, 40);
 DSV2_IO_RECORD(UvEgressJob, 56);
-DSV2_IO_RECORD(RgbOutJob, 88);
-DSV2_IO_RECORD(TensorOutJob, 136);
-DSV2_IO_RECORD(HwcOutJob, 120);
+DSV2_IO_RECORD(RgbOutJob, 144);
 DSV2_IO_RECORD(ScaleOutJob, 40);
 DSV2_IO_RECORD(ResizeOutJob, 72);
 #undef DSV2_IO_RECORD
 static_assert(offsetof(RgbJob, csc) == 64 && offsetof(Rgb3Job, csc) == 100 && offsetof(TensorInJob, csc) == 100 && offsetof(ScaledRgbJob, csc) == 68 &&
                   offsetof(SizedRgbJob, csc) == 112,
               "the ingest quads stay where the six words were");
-static_assert(offsetof(RgbOutJob, csc) == 60 && offsetof(TensorOutJob, csc) == 84, "the egress constants stay where the six ints were");
-static_assert(offsetof(HwcOutJob, csc) == offsetof(RgbOutJob, csc) && offsetof(HwcOutJob, bgra) == offsetof(RgbOutJob, bgra),
-              "the interleaved tensor's record begins as the RGB surface's");
+static_assert(offsetof(RgbOutJob, layout) + 4 == offsetof(RgbOutJob, dst) && offsetof(RgbOutJob, dtype) == 116,
+              "what every layout reads first, the tensors' words behind it");
 
 } // namespace dsv2

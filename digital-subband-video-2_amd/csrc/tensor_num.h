@@ -1,4 +1,4 @@
-// tensor_num.h -- the arithmetic the two tensor conversions share (egress_tensor.h: bytes to elements; ingest_tensor.h: elements to
+// tensor_num.h -- the arithmetic the two tensor conversions share (egress_rgb.h, its tensor layouts: bytes to elements; ingest_tensor.h: elements to
 // bytes), for device and host alike: the affine step of THE FLOAT CONTRACT (include/dsv2_hip.h) and the elements' bit patterns.
 #pragma once
 

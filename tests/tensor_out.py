@@ -1,5 +1,5 @@
 """Planar RGB tensors as decoder output (dsv2hip_out_tensor of include/dsv2_hip.h) in numpy: the oracle of
-tests/test_gpu_dec_tensor.py, pinned to the kernel's text and to the C restatement by tests/test_egress_tensor_cpu.py.  Built on
+tests/test_gpu_dec_tensor.py, pinned to the kernel's text and to the C restatement by tests/test_egress_rgb_cpu.py.  Built on
 tests/yuv_rgb.py (THE CONVERSION) and tests/area_resize.py (THE RESAMPLING); what is its own is the float contract:
 
     f = fl32(fl32(float(v) * scale[c]) + bias[c])       two binary32 operations, not fused

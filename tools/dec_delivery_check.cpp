@@ -279,7 +279,7 @@ std::vector<Access> accesses_of(const DeliveryPlan &p)
         const RgbOutJob &j = p.rgb[i];
         const int cw = cdiv(j.w, j.hs), ch = cdiv(j.h, j.vs);
         v.push_back(Access{RGBOUT, "RGB conversion", {rows_of(j.sy, j.ystride, j.w, j.h), rows_of(j.su, j.cstride, cw, ch), rows_of(j.sv, j.cstride, cw, ch)},
-                           rows_of(j.dst, j.dpitch, 4 * (long) j.w, j.h)});
+                           rows_of(j.dst[0], j.dpitch[0], 4 * (long) j.w, j.h)});
     }
     return v;
 }
@@ -378,7 +378,7 @@ void check(const Case &c)
     for (int i = 0; i < p.n_rgb; i++) {
         const RgbOutJob &j = p.rgb[i];
         const bool bgra = ((c.w + c.offset) & 1) == 0;
-        if (j.hs != hs || j.vs != vs || (j.bgra != 0) != bgra || j.csc.ky != (bgra ? 298 : 256) || j.w != cdiv(c.w, c.shift) || j.h != cdiv(c.h, c.shift)) {
+        if (j.layout != kRgbOutPacked || j.hs != hs || j.vs != vs || (j.bgra != 0) != bgra || j.csc.ky != (bgra ? 298 : 256) || j.w != cdiv(c.w, c.shift) || j.h != cdiv(c.h, c.shift)) {
             fail(c, "rgb job: hs %d vs %d bgra %d ky %d %dx%d", j.hs, j.vs, j.bgra, j.csc.ky, j.w, j.h);
         }
     }

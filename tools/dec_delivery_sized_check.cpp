@@ -224,7 +224,7 @@ void check(const Case &c)
         const bool bgra = ((c.w + c.offset) & 1) == 0;
         if (r.sy != W.scaled[0].data || r.su != W.scaled[1].data || r.sv != W.scaled[2].data || r.ystride != W.scaled[0].stride || r.cstride != W.scaled[1].stride ||
             r.w != c.ow || r.h != c.oh || r.hs != DSV_FORMAT_H_SHIFT(c.fmt) || r.vs != DSV_FORMAT_V_SHIFT(c.fmt) || (r.bgra != 0) != bgra ||
-            r.csc.ky != (bgra ? 298 : 256) || !W.want[0].same(r.dst, r.dpitch, 4 * (long) r.w, r.h) || p.rgb_wide != rgb_out_job_wide(r)) {
+            r.csc.ky != (bgra ? 298 : 256) || r.layout != kRgbOutPacked || !W.want[0].same(r.dst[0], r.dpitch[0], 4 * (long) r.w, r.h) || p.rgb_wide != rgb_out_job_wide(r)) {
             fail(c, "the conversion does not read what the resampling staged, or does not write the target's rows");
         }
     }

@@ -6,9 +6,9 @@ tools/probe/egress_hwc.py [legs ...]                      (default: all seventee
 tools/probe/egress_hwc.py --summarise KERNEL_TRACE.csv    (the same legs as the traced run)
 1080p 4:2:0, 64 decoders in one lockstep group, 8 timed steps behind 3 warm-up steps, on the same streams, ImageNet's constants folded
 (in B, G, R order for a BGR tensor):
-  bgra            dsv2hip_dec_batch_surface, BGRA (BT.601, limited range), pitch 7680 (k_egress_rgb<wide>: 1.5 P bytes in, 4 P out)
-  ten_DT          dsv2hip_dec_batch_tensor into one [64, 3, h, w] tensor of element type DT (k_egress_tensor<wide>: 3 / 6 / 6 / 12 P out)
-  hwc_DT_rgb/bgr  dsv2hip_dec_batch_hwc into one [64, h, w, 3] tensor (k_egress_hwc<wide>: the same bytes in and out as ten_DT)
+  bgra            dsv2hip_dec_batch_surface, BGRA (BT.601, limited range), pitch 7680 (k_egress_rgb<packed, wide>: 1.5 P bytes in, 4 P out)
+  ten_DT          dsv2hip_dec_batch_tensor into one [64, 3, h, w] tensor of element type DT (k_egress_rgb<planar, wide>: 3 / 6 / 6 / 12 P out)
+  hwc_DT_rgb/bgr  dsv2hip_dec_batch_hwc into one [64, h, w, 3] tensor (k_egress_rgb<interleaved, wide>: the same bytes in and out as ten_DT)
   perm_DT         ten_DT, then torch's permute(0, 2, 3, 1).contiguous() of the whole batch -- one copy kernel for the 64 pictures,
                   the cheapest form of the caller's permute(1, 2, 0).contiguous() per picture
                   DT: u8, f16, bf16, f32
@@ -16,8 +16,9 @@ The legs are interleaved step by step in one process -- leg A's step t, leg B's 
 destinations of its own, so clock and load drift hit them alike.  Prints per leg the median and the minimum wall time of a step, and
 checks on the last step that every hwc leg holds its type's planar tensor transposed, element for element.  The kernels' own times:
 rocprofv3 --kernel-trace --output-format csv -- python tools/probe/egress_hwc.py, then --summarise on the trace: per leg the launches
-behind the warm-up ones (a launch of k_egress_tensor belongs to leg (its index mod the number of ten and perm legs), likewise
-k_egress_hwc and the copy kernel), mean, min - max and sigma in microseconds, and per element type the comparisons of DESIGN 5.24."""
+behind the warm-up ones (a launch of the planar layout belongs to leg (its index mod the number of ten and perm legs), likewise the
+interleaved layout and the copy kernel), mean, min - max and sigma in microseconds, and per element type the comparisons of DESIGN 5.24.
+Launches are told apart by layout, so the traces of builds before the layouts shared k_egress_rgb read alike."""
 import csv
 import ctypes as C
 import os
@@ -53,6 +54,16 @@ class OUTHWC(C.Structure):  # dsv2hip_out_hwc
                 ("out_w", C.c_int), ("out_h", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
+def layout_of(kernel):
+    """the layout an egress conversion kernel writes -- k_egress_rgb<0 / 1 / 2, WIDE>, or before DESIGN 5.25 k_egress_rgb<WIDE>,
+    k_egress_tensor<WIDE>, k_egress_hwc<WIDE> -- or None for any other kernel"""
+    for name, layout in (("k_egress_tensor<", "planar"), ("k_egress_hwc<", "interleaved"), ("k_egress_rgb<0,", "packed"), ("k_egress_rgb<1,", "planar"),
+                         ("k_egress_rgb<2,", "interleaved"), ("k_egress_rgb<true>", "packed"), ("k_egress_rgb<false>", "packed")):
+        if name in kernel.replace(", ", ","):
+            return layout
+    return None
+
+
 def summarise(path, legs):
     rows = list(csv.DictReader(open(path)))
     if rows and "Dispatch_Id" in rows[0]:
@@ -65,13 +76,14 @@ def summarise(path, legs):
     nt = nh = nc = 0
     for r in rows:
         k, us = r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-        if "k_egress_tensor" in k and planar:
+        layout = layout_of(k)
+        if layout == "planar" and planar:
             per[planar[nt % len(planar)]].append(us)
             nt += 1
-        elif "k_egress_hwc" in k and hwc:
+        elif layout == "interleaved" and hwc:
             per[hwc[nh % len(hwc)]].append(us)
             nh += 1
-        elif "k_egress_rgb" in k and "bgra" in per:
+        elif layout == "packed" and "bgra" in per:
             per["bgra"].append(us)
         elif "dsv2" not in k and perm and nt and ("elementwise" in k or "copy" in k.lower()):
             copies[perm[nc % len(perm)]].append(us)

@@ -3,8 +3,8 @@
 tools/probe/egress_rgb.py [packed] [bgra] [bgra_general]   (default: all three)
 1080p 4:2:0, 64 decoders in one lockstep group, 12 timed steps behind the warm-up steps, on the same streams:
   packed        dsv2hip_dec_batch_device: packed planar pictures (k_egress<16>: 1.5 P bytes in, 1.5 P out)
-  bgra          dsv2hip_dec_batch_surface, BGRA (BT.601, limited range), pitch 7680 (k_egress_rgb<wide>: 1.5 P bytes in, 4 P out)
-  bgra_general  the same one byte off alignment at pitch 7681 (k_egress_rgb<general>)
+  bgra          dsv2hip_dec_batch_surface, BGRA (BT.601, limited range), pitch 7680 (k_egress_rgb<packed, wide>: 1.5 P bytes in, 4 P out)
+  bgra_general  the same one byte off alignment at pitch 7681 (k_egress_rgb<packed, general>)
 The legs are interleaved step by step in one process -- leg A's step t, leg B's step t, leg C's step t, then step t + 1 -- each with
 decoders and destinations of its own, so clock and load drift hit them alike.  Prints per leg the median and the minimum wall
 time of a step, and of the span of its last stage (border extension + the picture's way out: dsv2hip_prof_read entry 7) per step

@@ -3,11 +3,12 @@
 DESIGN 5.21), the counterpart of tools/probe/egress_rgb.py:
 tools/probe/egress_tensor.py [bgra] [u8] [f16] [bf16] [f32]   (default: all five, in this order)
 1080p 4:2:0, 64 decoders in one lockstep group, 8 timed steps behind the warm-up steps, on the same streams:
-  bgra          dsv2hip_dec_batch_surface, BGRA (BT.601, limited range), pitch 7680 (k_egress_rgb<wide>: 1.5 P bytes in, 4 P out)
+  bgra          dsv2hip_dec_batch_surface, BGRA (BT.601, limited range), pitch 7680 (k_egress_rgb<packed, wide>: 1.5 P bytes in, 4 P out)
   u8 .. f32     dsv2hip_dec_batch_tensor into contiguous [3, h, w] tensors of the element type, ImageNet's constants folded
-                (k_egress_tensor<wide>: 1.5 P bytes in, 3 / 6 / 6 / 12 P out)
+                (k_egress_rgb<planar, wide>: 1.5 P bytes in, 3 / 6 / 6 / 12 P out)
 The legs are interleaved step by step in one process -- leg A's step t, leg B's step t, ... then step t + 1 -- each with decoders and
-destinations of its own, so clock and load drift hit them alike; every launch of k_egress_tensor in a kernel trace is then leg
+destinations of its own, so clock and load drift hit them alike; every launch of the planar layout in a kernel trace (k_egress_rgb<1, ...>;
+k_egress_tensor before DESIGN 5.25) is then leg
 (launch index mod number of tensor legs).  Prints per leg the median and the minimum wall time of a step, and of the span of its last
 stage (border extension + the picture's way out: dsv2hip_prof_read entry 7) per step and per picture.  The kernels' own times:
 rocprofv3 --kernel-trace -- python tools/probe/egress_tensor.py."""
