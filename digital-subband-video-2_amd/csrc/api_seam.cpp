@@ -7,6 +7,8 @@
 // Section 6 (dsv2hip_planeset_*) keeps operands resident in HBM for measurement.
 #include <string.h>
 
+#include <algorithm>
+#include <atomic>
 #include <mutex>
 
 #include <vector>
@@ -15,6 +17,8 @@
 #include "bmc.h"
 #include "hme.h"
 #include "quant.h"
+#include "entropy_gpu.h"
+#include "dec_parse_dev.h"
 
 using namespace dsv2;
 
@@ -90,6 +94,14 @@ struct SeamCtx {
     uint32_t *sym_pos = nullptr;
     int32_t *sym_val = nullptr;
     size_t sym_elems = 0;
+    // the device coders of dsv_encode_plane / dsv_decode_plane (dsv2hip_seam_set_gpu_entropy, dsv2hip_dec_set_parse_mode)
+    EntBuffers ent;
+    std::vector<uint8_t> ent_big;
+    int32_t *ent_ll = nullptr; // the three DC coefficients of an EntJob
+    JobTable parse_job;        // (a table of its own: the section's parse writes into the DequantJob that `jobs` holds)
+    int *parse_fail = nullptr;
+    uint8_t *pkt = nullptr;    // the section as the decoder stages a packet
+    size_t pkt_bytes = 0;
 
     void init()
     {
@@ -178,6 +190,9 @@ struct SeamCtx {
 };
 
 SeamCtx g_seam;
+// dsv_encode_plane codes on the device (dsv2hip_seam_set_gpu_entropy; DSV2_SEAM_GPU_ENTROPY=1 sets it when the library loads, for test
+// modules run unchanged in a process of their own)
+std::atomic<int> g_seam_gpu_entropy{getenv("DSV2_SEAM_GPU_ENTROPY") && atoi(getenv("DSV2_SEAM_GPU_ENTROPY")) != 0};
 
 // A DPlane for a lone host DSV_PLANE: device storage with the bordered layout, filled from
 // whatever host memory surrounds the plane when the host plane itself is bordered
@@ -321,10 +336,47 @@ void dsv_encode_plane(DSV_BS *bs, DSV_COEFS *src, int q, DSV_FMETA *fm)
     quant_steps(&j, cfg, q);
     quant_jobs(c.stream, c.jobs.put(c.stream, &j), 1, cfg);
     compact_jobs(c.stream, c.jobs.put(c.stream, &cj), 1, nscan);
+    const bool gpu_coder = g_seam_gpu_entropy.load() != 0;
+    const int plane = fm->cur_plane;
+    if (gpu_coder) { // the plane as plane `cur_plane` of a picture whose other two planes are empty
+        c.ent.ensure(c.comp.list_cap, ent_out_bytes(c.comp.list_cap, nscan), kEntMirrorBytes);
+        size_t qv_off[4];
+        ScanGeom scan[3] = {};
+        for (int k = 0; k < 4; k++) {
+            qv_off[k] = k > plane ? nscan : 0;
+        }
+        scan[plane] = g;
+        if (!c.ent_ll) {
+            HIPCHK(hipMalloc((void **) &c.ent_ll, 3 * sizeof(int32_t)));
+        }
+        int32_t ll[3] = {0, 0, 0};
+        ll[plane] = src->data[0]; // (the quantiser leaves the DC as it is: hzcc.c:599-602)
+        HIPCHK(hipMemcpyAsync(c.ent_ll, ll, sizeof(ll), hipMemcpyHostToDevice, c.stream));
+        const EntJob ej = c.ent.job(c.comp.d_pos, c.comp.d_val, cj.total, c.ent_ll, c.comp.list_cap);
+        entropy_gpu_jobs(c.stream, c.jobs.put(c.stream, &ej), 1, ent_geom(qv_off, scan), ent_chunk_slots());
+    }
     int nsym = 0;
     HIPCHK(hipMemcpyAsync(&nsym, cj.total, sizeof(int), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(src->data, dc.data, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
+    if (gpu_coder) {
+        unsigned pbytes[3];
+        bool late_copy = false;
+        const uint8_t *sections = ent_collect(c.ent, c.stream, c.ent_big, pbytes, &late_copy);
+        if (sections) {
+            if (late_copy) {
+                HIPCHK(hipStreamSynchronize(c.stream));
+            }
+            for (int k = 0; k < plane; k++) {
+                sections += pbytes[k]; // (the empty planes' sections: length, DC 0, no symbols, 0x55)
+            }
+            const unsigned at = (bs->pos + 7) >> 3; // dsv_bs_align (hzcc.c:594)
+            memcpy(bs->start + at, sections, pbytes[plane]);
+            bs->pos = (at + pbytes[plane]) * 8;
+            return;
+        }
+        // a flag of the coder's (or the tests' forced fall-back): the host codes the plane from the symbol list, as the encoder does
+    }
     std::vector<uint32_t> pos((size_t) nsym);
     std::vector<int32_t> val((size_t) nsym);
     if (nsym) {
@@ -336,6 +388,94 @@ void dsv_encode_plane(DSV_BS *bs, DSV_COEFS *src, int q, DSV_FMETA *fm)
     bs->pos = bw.pos;
 }
 
+int dsv2hip_seam_set_gpu_entropy(int on)
+{
+    if (on >= 0) {
+        g_seam_gpu_entropy.store(on != 0);
+    }
+    return g_seam_gpu_entropy.load();
+}
+
+// dsv_decode_plane with the section's symbols parsed on the device: the head on the host (dec_parse.h's parse_body does the same for
+// the decoder), the section staged as the decoder stages a packet, k_dec_parse
+// writing the symbol counts into the dequantiser's record, and a failed section's plane zeroed by the conditional fill
+static int decode_plane_on_device(SeamCtx &c, DSV_BS *bs, DSV_COEFS *dst, int q, DSV_FMETA *fm, const ScanGeom &g)
+{
+    const size_t n = (size_t) dst->width * dst->height;
+    BitReader br{bs->start, bs->pos};
+    br.align();
+    const unsigned plen = br.get_bits(32);
+    br.align();
+    if (!(plen > 0 && plen < (unsigned) g.w * g.h * sizeof(int32_t) * 2)) {
+        bs->pos = br.pos;
+        return 0; // "plane length was strange" (hzcc.c:645)
+    }
+    const unsigned start = br.byte_pos();
+    const int32_t LL = br.get_seg();
+    br.align();
+    const int runs = (int) br.get_bits(24);
+    br.align();
+    const size_t end = (size_t) start + plen;
+    // the packet: everything up to the section's end and the 8 bytes behind it -- where the reference, which has no packet length here,
+    // reads on when a damaged section's last code overruns (the end-of-plane byte of a length field one too small stands there)
+    const size_t len = end + 8;
+    const size_t staged = ((len + 64 + 15) & ~(size_t) 15) + 4096; // 16-byte aligned, 64 zero bytes behind it, a window of readable memory
+    if (staged > c.pkt_bytes) {
+        if (c.pkt) {
+            HIPCHK(hipFree(c.pkt));
+        }
+        HIPCHK(hipMalloc((void **) &c.pkt, staged));
+        c.pkt_bytes = staged;
+    }
+    HIPCHK(hipMemcpyAsync(c.pkt, bs->start, len, hipMemcpyHostToDevice, c.stream));
+    HIPCHK(hipMemsetAsync(c.pkt + len, 0, staged - len, c.stream));
+    const int cap = std::min(std::max(runs, 0), g.base[10]);
+    c.get_syms((size_t) (cap > 0 ? cap : 1));
+    if (!c.parse_fail) {
+        HIPCHK(hipMalloc((void **) &c.parse_fail, sizeof(int)));
+    }
+    // (one extra vector of coefficients: the fill works in 16-byte units)
+    DCoefs dc{c.get_coefs(n + 4), dst->width, dst->height};
+    HIPCHK(hipMemcpyAsync(dc.data, dst->data, n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+    QuantCfg cfg = make_quant_cfg(c, dst, fm);
+    DequantJob j{};
+    j.coefs = dc.data;
+    j.pos = c.sym_pos;
+    j.val = c.sym_val;
+    j.bd = cfg.bd;
+    j.LL = dst->data[0];
+    dequant_steps(&j, cfg, q);
+    const DequantJob *dj = c.jobs.put(c.stream, &j);
+    DecParseJob pj{};
+    pj.pkt = c.pkt;
+    pj.data_bitpos = br.pos;
+    pj.limit_bits = (uint32_t) ((len + 8) * 8);
+    pj.end_byte = (uint32_t) end;
+    pj.runs = runs;
+    pj.cap = cap;
+    pj.chroma = 0;
+    pj.pos = c.sym_pos;
+    pj.val = c.sym_val;
+    pj.seg_out = const_cast<int *>(dj->seg);
+    pj.fail = c.parse_fail;
+    DecScanBases sb;
+    for (int k = 0; k < 11; k++) {
+        sb.base[k] = g.base[k];
+    }
+    dec_parse_planes(c.stream, c.parse_job.put(c.stream, &pj), 1, sb, sb);
+    const int max_seg[4] = {cap, cap, cap, cap};
+    dequant_jobs(c.stream, dj, 1, max_seg, cfg);
+    const CopyJob zero{nullptr, dc.data, (n * sizeof(int32_t) + 15) & ~(size_t) 15};
+    zero_linear_if_batch(c.stream, c.parse_job.put(c.stream, &zero), c.parse_fail, 1, zero.bytes);
+    int fail = 0;
+    HIPCHK(hipMemcpyAsync(&fail, c.parse_fail, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipMemcpyAsync(dst->data, dc.data, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream));
+    dst->data[0] = LL; // hzcc.c:633
+    bs->pos = (unsigned) (end * 8);
+    return fail == 0;
+}
+
 int dsv_decode_plane(DSV_BS *bs, DSV_COEFS *dst, int q, DSV_FMETA *fm)
 {
     SeamCtx &c = g_seam;
@@ -344,6 +484,10 @@ int dsv_decode_plane(DSV_BS *bs, DSV_COEFS *dst, int q, DSV_FMETA *fm)
     size_t n = (size_t) dst->width * dst->height;
     ScanGeom g;
     make_scan(&g, dst->width, dst->height);
+    const int mode = dsv2hip_dec_parse_mode(); // the decoder's rule: 2 every picture, 1 the P pictures
+    if (mode >= 2 || (mode == 1 && fm->isP)) {
+        return decode_plane_on_device(c, bs, dst, q, fm, g);
+    }
     std::vector<uint32_t> pos((size_t) g.base[10]);
     std::vector<int32_t> val((size_t) g.base[10]);
     int seg_count[4];

@@ -144,7 +144,7 @@ void block_geometry(int w, int h, int ovx, int ovy, int *blk_w, int *blk_h, int 
 // Section buffer of the GPU entropy coder: 4 bits per coefficient (1.5 MB at 1080p: a 370 Mbit/s stream at 30 pictures a second),
 // at least 1 MB; 4 MB or that, whichever is more, for streams whose lists are sized for the worst case (lossless).  A picture
 // that does not fit raises the coder's "no room" flag and is coded on the host.
-static uint32_t ent_out_bytes(size_t list_symbols, size_t ncoef)
+uint32_t ent_out_bytes(size_t list_symbols, size_t ncoef)
 {
     const size_t half = (ncoef / 2 + 65535) & ~(size_t) 65535;
     return (uint32_t) std::max<size_t>(list_symbols >= ncoef ? (4u << 20) : (1u << 20), half);
@@ -237,7 +237,7 @@ void CodecDev::init(int format_, int w_, int h_, int blk_w_, int blk_h_, int pyr
         comp.ensure_lists(qv_off[3], list_symbols ? list_symbols : qv_off[3]);
         // (the plane sections of the packet assembled on the GPU: 4 MB section buffer, 1 MB pinned mirror -- far above any 1080p
         // picture at sane quality; larger ones are fetched by a copy)
-        ent.ensure(comp.list_cap, ent_out_bytes(comp.list_cap, qv_off[3]), 1u << 20);
+        ent.ensure(comp.list_cap, ent_out_bytes(comp.list_cap, qv_off[3]), kEntMirrorBytes);
     } else {
         HIPCHK(dev_alloc((void **) &qv, qv_off[3] * sizeof(int32_t)));
         scratch.ensure((size_t) cw[0] * ch[0], sbt_ll_elems(cw[0], ch[0]));

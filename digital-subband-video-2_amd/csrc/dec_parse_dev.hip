@@ -496,6 +496,7 @@ __global__ __launch_bounds__(64) void k_dec_parse(const DecParseJob *__restrict_
             truncated = true;
         }
         if (truncated || n >= J.cap) { // (n < cap always holds for cap = min(runs, total): belt and braces on untrusted input)
+            ok = truncated ? ok : 0;
             truncated = true;
             break;
         }
@@ -510,12 +511,10 @@ __global__ __launch_bounds__(64) void k_dec_parse(const DecParseJob *__restrict_
         c3 += seg >= 7;
         cur = (uint32_t) p + 1;
     }
-    if (!truncated) {
+    if (!truncated) { // (an overrun leaves the reference's loop unaligned, and the end-of-plane byte is looked for there: entropy.cpp)
         br.align();
-        if (br.get_bits(8) != 0x55) {
-            ok = 0;
-        }
-    } else {
+    }
+    if (br.get_bits(8) != 0x55) {
         ok = 0;
     }
     if (threadIdx.x == 0) {

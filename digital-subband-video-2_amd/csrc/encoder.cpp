@@ -2397,23 +2397,11 @@ static void collect_symbols(Step &st)
             late_copy = true;
         }
         if (kGpuEntropy && !overflow) {
-            const int *info = dv.ent.host_info;
-            if ((info[0] & ENT_FALLBACK_MASK) || kEntForceFallback) {
+            jb.gpu_bytes = ent_collect(dv.ent, bs, jb.im->big_bytes, jb.gpu_plane_bytes, &late_copy);
+            if (!jb.gpu_bytes) {
                 need_syms = true; // (state outside the tabulated range / no room: code this picture on the host)
                 if (trace_mode() & 2) {
-                    fprintf(stderr, "[batch] stream %d: GPU entropy coder fell back (flags %d)\n", k, info[0]);
-                }
-            } else {
-                for (int c = 0; c < 3; c++) {
-                    jb.gpu_plane_bytes[c] = (unsigned) info[ENT_INFO_PBYTES + c];
-                }
-                if (info[0] & ENT_NOT_MIRRORED) { // finished, but larger than the pinned mirror
-                    jb.im->big_bytes.resize((size_t) info[ENT_INFO_TOTAL]);
-                    HIPCHK(hipMemcpyAsync(jb.im->big_bytes.data(), dv.ent.out, (size_t) info[ENT_INFO_TOTAL], hipMemcpyDeviceToHost, bs));
-                    late_copy = true;
-                    jb.gpu_bytes = jb.im->big_bytes.data();
-                } else {
-                    jb.gpu_bytes = dv.ent.host_out;
+                    fprintf(stderr, "[batch] stream %d: GPU entropy coder fell back (flags %d)\n", k, dv.ent.host_info[0]);
                 }
             }
         }
@@ -2482,7 +2470,35 @@ Coalescer<Job> g_enc_queue; // dsv_enc callers share lockstep steps (batch.h)
 
 } // namespace
 
+namespace dsv2 {
 
+int ent_chunk_slots() { return kEntSlots; }
+
+// pictures (the seam: planes) for which the GPU coder itself raised flag 1 << i, i = 0 .. 3 (dsv2hip_enc_ent_flag_count)
+static std::atomic<long> g_ent_flags[4];
+
+const uint8_t *ent_collect(const EntBuffers &ent, hipStream_t s, std::vector<uint8_t> &big, unsigned plane_bytes[3], bool *late_copy)
+{
+    const int *info = ent.host_info;
+    for (int i = 0; i < 4; i++) {
+        g_ent_flags[i] += (info[0] >> i) & 1;
+    }
+    if ((info[0] & ENT_FALLBACK_MASK) || kEntForceFallback) {
+        return nullptr;
+    }
+    for (int c = 0; c < 3; c++) {
+        plane_bytes[c] = (unsigned) info[ENT_INFO_PBYTES + c];
+    }
+    if (info[0] & ENT_NOT_MIRRORED) { // finished, but larger than the pinned mirror
+        big.resize((size_t) info[ENT_INFO_TOTAL]);
+        HIPCHK(hipMemcpyAsync(big.data(), ent.out, (size_t) info[ENT_INFO_TOTAL], hipMemcpyDeviceToHost, s));
+        *late_copy = true;
+        return big.data();
+    }
+    return ent.host_out;
+}
+
+} // namespace dsv2
 
 extern "C" {
 
@@ -2649,6 +2665,15 @@ int dsv_enc(DSV_ENCODER *enc, DSV_FRAME *frame, DSV_BUF *bufs) // dsv_encoder.c:
  * microseconds leaders spent waiting for expected callers; reset != 0 clears the counts afterwards */
 void dsv2hip_test_fail_next_step(int how) { g_fail_next_step.store(how); }
 long dsv2hip_enc_list_growths(void) { return g_list_growths.load(); }
+long dsv2hip_enc_ent_flag_count(int flag)
+{
+    for (int i = 0; i < 4; i++) {
+        if (flag == 1 << i) {
+            return g_ent_flags[i].load();
+        }
+    }
+    return -1;
+}
 long dsv2hip_arena_fallbacks(void) { return dsv2::arena_fallbacks(); }
 
 void dsv2hip_enc_queue_stats(unsigned long long *out4, int reset)

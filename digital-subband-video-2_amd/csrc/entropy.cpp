@@ -452,13 +452,14 @@ int entropy_decode_plane(BitReader &br, int32_t *LL, uint32_t *pos, int32_t *val
         seg_count[seg == 0 ? 0 : 1 + (seg - 1) / 3]++;
         cur = (uint32_t) p + 1;
     }
+    // the reference leaves its symbol loop at an overrun without aligning (hzcc.c:490, :510, :527, :564 return past :582) and looks
+    // for the end-of-plane byte where it stands: a section whose length field is one too small, its last code ending on a byte
+    // boundary, still decodes -- without its last symbol -- and so does one overrun in 256 by chance
     if (!truncated) {
         br.align();
-        if (br.get_bits(8) != 0x55) {
-            ok = 0; // "bad eop" (hzcc.c:636)
-        }
-    } else {
-        ok = 0;
+    }
+    if (br.get_bits(8) != 0x55) {
+        ok = 0; // "bad eop" (hzcc.c:636)
     }
     br.seek(((uint64_t) start + plen) * 8);
     return ok;

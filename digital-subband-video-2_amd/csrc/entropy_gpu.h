@@ -1,6 +1,8 @@
 // entropy_gpu.h -- plane sections of the picture packet assembled on the GPU (entropy_gpu.hip)
 #pragma once
 
+#include <vector>
+
 #include "quant.h"
 
 namespace dsv2 {
@@ -53,5 +55,17 @@ struct EntBuffers { // per encoder instance
 
 // n streams of identical geometry; chunk_slots = workgroups per (stream, plane) that share that plane's chunks
 void entropy_gpu_jobs(hipStream_t s, const EntJob *d_jobs, int n, const EntGeom &g, int chunk_slots);
+
+// ---- what the callers of the coder share (the encoder's lockstep step and the stage seam's dsv_encode_plane) ----
+constexpr uint32_t kEntMirrorBytes = 1u << 20; // the pinned mirror of the finished sections (EntBuffers::ensure's host_bytes)
+// section buffer of a stream whose lists hold list_symbols of its ncoef scan positions (codec_dev.cpp)
+uint32_t ent_out_bytes(size_t list_symbols, size_t ncoef);
+int ent_chunk_slots(); // DSV2_ENT_SLOTS (encoder.cpp)
+// The verdict on one picture behind entropy_gpu_jobs, its info words arrived (the caller has waited for the stream).  Null: the host
+// codes the picture from the symbol list -- the coder raised a flag of ENT_FALLBACK_MASK, or the tests force it
+// (DSV2_GPU_ENTROPY_FORCE_FALLBACK).  Else the three sections back to back, plane_bytes[c] each: the pinned mirror, or -- larger than
+// the mirror -- `big`, filled by a copy enqueued on s (*late_copy set: wait for s before reading).  Counts every flag of 1 / 2 / 4 / 8
+// the coder itself raised (dsv2hip_enc_ent_flag_count).
+const uint8_t *ent_collect(const EntBuffers &ent, hipStream_t s, std::vector<uint8_t> &big, unsigned plane_bytes[3], bool *late_copy);
 
 } // namespace dsv2

@@ -28,8 +28,13 @@
 //   7 k_ent_out      the finished bytes and their sizes to pinned host memory
 //
 //
-// A state beyond 255 (k >= 32 at damp 3, never seen on real pictures) or a plane that outgrows its buffer raises a
-// flag; the host then codes that picture from the symbol list as before (entropy.cpp) -- same bytes either way.
+// A state beyond 255 behind a chunk (k >= 32 at damp 3; at the finest level, damp 5, some 256 symbols of |v| >= 65 on end take it
+// to 255 / 256 and of |v| >= 129 past it: tests/entropy_cases.py has the model, whether a chunk ends on 255 or on 256 hangs on the
+// parity of the symbols before it.  Real pictures do it: a 0/255 checkerboard of 352 x 288, lossless or at qp 97 - 99, reaches
+// states of 287 - 384 in all three planes of its I picture, in packets of half the reference's bound and less; 0/255 noise reaches
+// 275: tests/stream_sections.py) or a plane that outgrows its buffer raises a flag; the host
+// then codes that picture from the symbol list as before (entropy.cpp) -- same bytes either way.  dsv2hip_enc_ent_flag_count()
+// counts the flags raised.
 #include "entropy_gpu.h"
 #include "prio.h"
 

@@ -1020,6 +1020,22 @@ void dsv2hip_dec_queue_stats(unsigned long long *out4, int reset);
  * and coded on the host; the packets are the same).  Number of such enlargements in this process so far: a stream pays at most
  * one.  DSV2_COMPACT_CAP=<symbols> overrides the initial size. */
 long dsv2hip_enc_list_growths(void);
+/* The GPU entropy coder (csrc/entropy_gpu.hip) hands a picture to the host coder when it raises flag 1 (the adaptive Rice state left
+ * the tabulated range), 2 (its section buffer is too small) or 4 (a chunk of 1 024 symbols of 2^24 bits or more), and has the bytes
+ * fetched by a copy when it raises 8 (finished, but larger than the pinned mirror); the packets are the same.  Number of pictures of
+ * this process -- of planes, for dsv_encode_plane on the device coder -- for which the coder ITSELF raised `flag` (1, 2, 4 or 8) so
+ * far; the tests' forced fall-back (DSV2_GPU_ENTROPY_FORCE_FALLBACK) is not counted.  -1 for any other argument. */
+long dsv2hip_enc_ent_flag_count(int flag);
+/* Which entropy coder the stage seam's dsv_encode_plane (section 5) runs behind the quantiser: 0 (the default) the host coder of
+ * csrc/entropy.cpp, 1 the encoder's GPU coder with the encoder's own fall-back rule -- the plane as plane fm->cur_plane of a picture
+ * whose other planes are empty.  on < 0 changes nothing.  Returns the setting in force.  DSV2_SEAM_GPU_ENTROPY=1 makes 1 the setting a
+ * process starts with.  (dsv_decode_plane follows
+ * dsv2hip_dec_set_parse_mode: mode 2 parses every section on the device, mode 1 those of fm->isP pictures.  The seam has no packet
+ * length, so the device path takes the section and the 8 bytes behind it for the packet: bs->start must be readable for 8 bytes
+ * behind the section's end -- which the reference, and the host path, read too when a damaged section's last code overruns -- and
+ * where a damaged section makes the parse run on further than that, the device parser reads zeros where the other two read the
+ * caller's bytes.) */
+int dsv2hip_seam_set_gpu_entropy(int on);
 /* Device allocations that did not fit their instance's one-block arena (the block's size is an estimate): 0 unless the estimate has
  * drifted from the allocations it stands for. */
 long dsv2hip_arena_fallbacks(void);
