@@ -1,7 +1,8 @@
 // enc_ingest.h -- which kernels a picture enters the encoder through, reading and writing what: accepted per call and planned per
 // picture, free of any device call and of any allocation (the decoder's counterpart is dec_delivery.h).  encoder.cpp
 // passes every surface of the three surface calls through accept(), every tensor of the tensor calls through accept_tensor() (DESIGN
-// 5.22; tools/enc_tensor_plan_check.cpp sweeps those), and plans every picture of a step with plan_ingest() before it sizes
+// 5.22; tools/enc_tensor_plan_check.cpp sweeps those), every interleaved tensor of the hwc calls through accept_hwc() (DESIGN 5.26;
+// tools/enc_hwc_plan_check.cpp), and plans every picture of a step with plan_ingest() before it sizes
 // and fills the step's job tables.  tools/enc_ingest_check.cpp compiles this header for the host under AddressSanitizer +
 // UndefinedBehaviorSanitizer and sweeps format x size x kind x route x offset x pitch over synthetic addresses
 // (tests/test_enc_ingest_cpu.py); the four tools/ingest_*_check.cpp run the kernels' bodies on the records planned here.
@@ -24,8 +25,10 @@ struct Source { // (an aggregate without initialisers: it lives in the encoder's
         RGB4,   // ... one plane of four-byte pixels, BGRA / RGBA (plane[1..2] unused)
         RGB3,   // ... one plane of three-byte pixels, BGR / RGB
         RGBP,   // ... a plane per colour: R, G, B
-        TENSOR  // ... a plane per colour of binary16, bfloat16 or binary32 elements under per-plane constants (dsv2hip_in_tensor; the plain
+        TENSOR, // ... a plane per colour of binary16, bfloat16 or binary32 elements under per-plane constants (dsv2hip_in_tensor; the plain
                 // route alone).  A uint8 tensor is an RGBP.
+        HWC     // ... one plane of three such elements a pixel, R G B or B G R, under per-position constants (dsv2hip_in_hwc; the plain
+                // route alone; plane[0] / pitch[0]).  A uint8 one is an RGB3.
     } kind;
     enum Route {
         PLAIN,   // the picture in the surface has the encoder's size
@@ -36,11 +39,12 @@ struct Source { // (an aggregate without initialisers: it lives in the encoder's
     size_t pitch[3];
     int src_w, src_h; // of the picture IN THE SURFACE
     int shift;        // REDUCED: 1 .. 3
-    int layout;       // the RGB kinds: the layout without its scale value -- byte order and DSV2HIP_CSC_* bits (TENSOR: the bits alone)
-    int dtype;        // TENSOR: DSV2HIP_TENSOR_F16, _BF16 or _F32
-    float scale[3], bias[3]; // TENSOR: of plane[c]
+    int layout;       // the RGB kinds: the layout without its scale value -- byte order and DSV2HIP_CSC_* bits (TENSOR: the bits alone; HWC: the
+                      // element order, DSV2HIP_SURFACE_RGB or _BGR, and the bits)
+    int dtype;        // TENSOR, HWC: DSV2HIP_TENSOR_F16, _BF16 or _F32
+    float scale[3], bias[3]; // TENSOR: of plane[c]; HWC: of element k of every pixel
     bool surface() const { return kind != PACKED; }
-    bool rgb() const { return kind == RGB4 || kind == RGB3 || kind == RGBP || kind == TENSOR; }
+    bool rgb() const { return kind == RGB4 || kind == RGB3 || kind == RGBP || kind == TENSOR || kind == HWC; }
 };
 
 // One rule for the three calls: may an encoder of enc_w x enc_h in format subsamp take surface sf, which the caller says holds a picture
@@ -135,6 +139,38 @@ inline bool accept_tensor(int enc_w, int enc_h, int subsamp, bool uyvy_input, co
     return true;
 }
 
+// The same rule for an interleaved tensor (dsv2hip_enc_batch_hwc / _hwc_frame; always the plain route).  Refused: what accept_tensor
+// refuses, read for one pointer and pitch (the row holds 3 * w elements); an order that is not exactly DSV2HIP_SURFACE_RGB or
+// DSV2HIP_SURFACE_BGR.  A uint8 one IS the three-byte surface: it leaves as an RGB3 source, constants unread.
+inline bool accept_hwc(int enc_w, int enc_h, int subsamp, bool uyvy_input, const dsv2hip_in_hwc &t, Source *out)
+{
+    if ((t.csc & ~(DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE)) || (t.order != DSV2HIP_SURFACE_RGB && t.order != DSV2HIP_SURFACE_BGR)) {
+        return false;
+    }
+    if (t.dtype == DSV2HIP_TENSOR_U8) {
+        const dsv2hip_surface sf{{t.data, nullptr, nullptr}, {t.pitch, 0, 0}, t.order | t.csc};
+        return accept(CALL_PLAIN, enc_w, enc_h, subsamp, uyvy_input, sf, 0, 0, out);
+    }
+    if (uyvy_input || !ingest_scale::rgb_format(subsamp) || (t.dtype != DSV2HIP_TENSOR_F16 && t.dtype != DSV2HIP_TENSOR_BF16 && t.dtype != DSV2HIP_TENSOR_F32)) {
+        return false;
+    }
+    const size_t elem = (size_t) tensor_elem(t.dtype);
+    if (!t.data || ((uintptr_t) t.data | t.pitch) % elem != 0 || t.pitch / elem < 3 * (size_t) enc_w) {
+        return false;
+    }
+    Source s{};
+    s.kind = Source::HWC, s.route = Source::PLAIN, s.layout = t.order | t.csc, s.src_w = enc_w, s.src_h = enc_h, s.dtype = t.dtype;
+    s.plane[0] = (const uint8_t *) t.data, s.pitch[0] = t.pitch;
+    for (int k = 0; k < 3; k++) {
+        if (t.scale[k] - t.scale[k] != 0.0f || t.bias[k] - t.bias[k] != 0.0f) { // (finite: accept_tensor's test)
+            return false;
+        }
+        s.scale[k] = t.scale[k], s.bias[k] = t.bias[k];
+    }
+    *out = s;
+    return true;
+}
+
 // The conversion of include/dsv2_hip.h for an RGB surface of `layout` as the RGB ingest kernels take it: each row of the preset's matrix as
 // byte quads in the surface's channel order (a fourth byte weighs 0), chroma rows split into positive parts and magnitudes of negative ones
 inline RgbInCoefs rgb_job_coefs(int layout)
@@ -161,7 +197,7 @@ inline RgbInCoefs rgb_job_coefs(int layout)
 // ---- what one picture contributes to a step ---------------------------------------------------------------------------------------------
 // The launch classes, in the order the step launches them (behind the packed and the UYVY pictures' launches); a class has a job table
 // of its own in the step, a form counter pair, and one launch for all the step's records of it.
-enum Class { SURF, RGB, SCALED_SURF, SCALED_RGB, SIZED_SURF, SIZED_RGB, RGB3_PACKED, RGB3_PLANAR, TENSOR_IN, kClasses };
+enum Class { SURF, RGB, SCALED_SURF, SCALED_RGB, SIZED_SURF, SIZED_RGB, RGB3_PACKED, RGB3_PLANAR, TENSOR_IN, HWC_IN, kClasses };
 
 struct IngestPlan {
     SurfaceJob surf[3];
@@ -172,15 +208,16 @@ struct IngestPlan {
     SizedRgbJob sized_rgb[1];
     Rgb3Job rgb3[1];                         // of RGB3_PACKED or of RGB3_PLANAR, by its kind
     TensorInJob tensor[1];
-    int n[kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // records per class: a surface brings those of ONE class, a PACKED picture none
+    int n[kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // records per class: a surface brings those of ONE class, a PACKED picture none
     // what the step needs to pick its kernels' forms and grids
-    bool wide[kClasses] = {true, true, true, true, true, true, true, true, true}; // every record of the class allows the wide form (io_jobs.h: *_job_wide)
+    bool wide[kClasses] = {true, true, true, true, true, true, true, true, true, true}; // every record of the class allows the wide form (io_jobs.h: *_job_wide)
     int scaled_row_bytes = 0; // SCALED_SURF: the most bytes a source row of a record holds
     int scaled_rgb_sw = 0;    // SCALED_RGB: the source's width
+    HwcInJob hwc[1];          // (behind every member a plan had before it)
 };
 // the room a picture's records take in the step's table arena at most: they are some of its plan's arrays
 constexpr size_t kPlanRecordBytes = 3 * sizeof(SurfaceJob) + sizeof(RgbJob) + 3 * sizeof(ScaledSurfaceJob) + sizeof(ScaledRgbJob) +
-                                    3 * sizeof(SizedSurfaceJob) + sizeof(SizedRgbJob) + sizeof(Rgb3Job) + sizeof(TensorInJob);
+                                    3 * sizeof(SizedSurfaceJob) + sizeof(SizedRgbJob) + sizeof(Rgb3Job) + sizeof(TensorInJob) + sizeof(HwcInJob);
 
 // f: the encoder's bordered source planes (dframe_alloc's: its format and plane sizes are the encoder's), which the records write; s: an
 // accepted source
@@ -194,7 +231,13 @@ inline IngestPlan plan_ingest(const DFrame &f, const Source &s)
     const int hs = DSV_FORMAT_H_SHIFT(f.format), vs = DSV_FORMAT_V_SHIFT(f.format);
     const bool semi = s.kind == Source::SEMI;
     const int scw = (s.src_w + (1 << hs) - 1) >> hs, sch = (s.src_h + (1 << vs) - 1) >> vs; // dsv_mk_frame's chroma planes, of the SOURCE
-    if (s.kind == Source::TENSOR) { // (the plain route alone)
+    if (s.kind == Source::HWC) { // (the plain route alone)
+        HwcInJob &j = p.hwc[p.n[HWC_IN]++];
+        j = HwcInJob{s.plane[0], s.pitch[0], {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride, dp[0].w, dp[0].h, hs, vs, s.dtype,
+                     rgb_job_coefs(s.layout), // (memory order is byte order, as for a packed Rgb3Job)
+                     {s.scale[0], s.scale[1], s.scale[2]}, {s.bias[0], s.bias[1], s.bias[2]}};
+        p.wide[HWC_IN] = hwc_in_job_wide(j);
+    } else if (s.kind == Source::TENSOR) { // (the plain route alone)
         TensorInJob &j = p.tensor[p.n[TENSOR_IN]++];
         j = TensorInJob{{s.plane[0], s.plane[1], s.plane[2]}, {s.pitch[0], s.pitch[1], s.pitch[2]}, {dp[0].data, dp[1].data, dp[2].data}, dp[0].stride, dp[1].stride,
                         dp[0].w, dp[0].h, hs, vs, s.dtype,

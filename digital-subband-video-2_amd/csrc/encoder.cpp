@@ -1519,7 +1519,7 @@ static std::atomic<long> g_list_growths{0}; // pictures that had more symbols th
 // pyramids and source pre-pass still enqueued on the stream)
 static std::atomic<int> g_fail_next_step{0};
 // steps whose ingest of a launch class ran in the wide / the general form: [2 * class + (wide ? 0 : 1)] (dsv2hip_enc_surface_stats,
-// _rgb_stats, _scale_stats, _resize_stats, _rgb3_stats, _tensor_stats, each over its one or two classes)
+// _rgb_stats, _scale_stats, _resize_stats, _rgb3_stats, _tensor_stats, _hwc_stats, each over its one or two classes)
 static std::atomic<unsigned long long> g_ingest_steps[2 * enc_ingest::kClasses];
 
 // workgroups per (picture, plane) of the entropy coder's chunk kernels; each walks its share of the plane's 1 024-symbol chunks
@@ -1713,9 +1713,10 @@ struct Ingest {
     Tab<SizedRgbJob> sized_rgb;
     Tab<Rgb3Job> rgb3[2];
     Tab<TensorInJob> tensor;
-    size_t room[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // entries the step's plans need of each table
-    int n[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    bool wide[enc_ingest::kClasses] = {true, true, true, true, true, true, true, true, true}; // IngestPlan's, over the step
+    Tab<HwcInJob> hwc;
+    size_t room[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // entries the step's plans need of each table
+    int n[enc_ingest::kClasses] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool wide[enc_ingest::kClasses] = {true, true, true, true, true, true, true, true, true, true}; // IngestPlan's, over the step
     int scaled_row_bytes = 0, scaled_rgb_sw = 0;
     void count(const std::vector<enc_ingest::IngestPlan> &plans)
     {
@@ -1737,6 +1738,7 @@ struct Ingest {
         rgb3[0] = Tab<Rgb3Job>(tabs, room[RGB3_PACKED]);
         rgb3[1] = Tab<Rgb3Job>(tabs, room[RGB3_PLANAR]);
         tensor = Tab<TensorInJob>(tabs, room[TENSOR_IN]);
+        hwc = Tab<HwcInJob>(tabs, room[HWC_IN]);
     }
     template <class T> void append(Tab<T> &t, int cl, const T *jobs, const enc_ingest::IngestPlan &p)
     {
@@ -1756,6 +1758,7 @@ struct Ingest {
         append(rgb3[0], RGB3_PACKED, p.rgb3, p);
         append(rgb3[1], RGB3_PLANAR, p.rgb3, p);
         append(tensor, TENSOR_IN, p.tensor, p);
+        append(hwc, HWC_IN, p.hwc, p);
         scaled_row_bytes = std::max(scaled_row_bytes, p.scaled_row_bytes);
         scaled_rgb_sw = std::max(scaled_rgb_sw, p.scaled_rgb_sw);
     }
@@ -1796,6 +1799,9 @@ struct Ingest {
         }
         if (ran(TENSOR_IN)) {
             ingest_tensor_batch(bs, tensor.d, n[TENSOR_IN], h, wide[TENSOR_IN]);
+        }
+        if (ran(HWC_IN)) {
+            ingest_hwc_batch(bs, hwc.d, n[HWC_IN], h, wide[HWC_IN]);
         }
     }
 };
@@ -2751,6 +2757,12 @@ static bool accept_tensor(const DSV_ENCODER *enc, const dsv2hip_in_tensor &t, en
     return enc_ingest::accept_tensor(enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, uyvy_input, t, out);
 }
 
+static bool accept_hwc(const DSV_ENCODER *enc, const dsv2hip_in_hwc &t, enc_ingest::Source *out)
+{
+    const bool uyvy_input = enc->ref && ((const EncImpl *) enc->ref)->input_uyvy;
+    return enc_ingest::accept_hwc(enc->vidmeta.width, enc->vidmeta.height, enc->vidmeta.subsamp, uyvy_input, t, out);
+}
+
 /* dsv2hip_enc_batch for pictures that accept_k(k, &source) admits: surfaces or tensors, read during the call only.  Refused as a whole
  * with -1, nothing touched, for what dsv2hip_enc_batch refuses, a missing argument (have_args) or an entry accept_k does not pass. */
 extern "C++" { // (templates: this stretch of the file has C linkage)
@@ -2812,6 +2824,16 @@ int dsv2hip_enc_batch_tensor(int n, DSV_ENCODER **encs, const dsv2hip_in_tensor 
 int dsv2hip_enc_tensor_frame(DSV_ENCODER *enc, const dsv2hip_in_tensor *t, DSV_BUF *bufs)
 {
     return source_frame(enc, t != NULL, bufs, [&](enc_ingest::Source *out) { return accept_tensor(enc, *t, out); });
+}
+
+/* the interleaved tensor calls (include/dsv2_hip.h: INTERLEAVED RGB FLOAT TENSORS AS ENCODER INPUT): the same steps again */
+int dsv2hip_enc_batch_hwc(int n, DSV_ENCODER **encs, const dsv2hip_in_hwc *t, DSV_BUF *bufs, int *nbufs)
+{
+    return source_batch(n, encs, t != NULL, bufs, nbufs, [&](int k, enc_ingest::Source *out) { return accept_hwc(encs[k], t[k], out); });
+}
+int dsv2hip_enc_hwc_frame(DSV_ENCODER *enc, const dsv2hip_in_hwc *t, DSV_BUF *bufs)
+{
+    return source_frame(enc, t != NULL, bufs, [&](enc_ingest::Source *out) { return accept_hwc(enc, *t, out); });
 }
 
 int dsv2hip_enc_batch_surface(int n, DSV_ENCODER **encs, const dsv2hip_surface *surf, DSV_BUF *bufs, int *nbufs)
@@ -2883,6 +2905,7 @@ void dsv2hip_enc_scale_stats(unsigned long long *out4, int reset) { ingest_stats
 void dsv2hip_enc_resize_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::SIZED_SURF, 2, out4, reset); }
 void dsv2hip_enc_rgb3_stats(unsigned long long *out4, int reset) { ingest_stats(enc_ingest::RGB3_PACKED, 2, out4, reset); }
 void dsv2hip_enc_tensor_stats(unsigned long long *out2, int reset) { ingest_stats(enc_ingest::TENSOR_IN, 1, out2, reset); }
+void dsv2hip_enc_hwc_stats(unsigned long long *out2, int reset) { ingest_stats(enc_ingest::HWC_IN, 1, out2, reset); }
 
 /* the same with the pictures in HOST memory (packed planar Y, U, V).  host_planar[k]: stream k's picture of this
  * step; host_next (may be NULL, entries may be NULL): the picture stream k will bring to the NEXT call -- it is

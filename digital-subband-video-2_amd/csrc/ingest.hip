@@ -1,5 +1,5 @@
 // ingest.hip -- the kernels a caller's device picture enters the encoder through: pitched planar / semiplanar surfaces, packed and
-// planar RGB surfaces and float tensors converted on the way in, each at the encoder's size, at half / quarter / eighth size or
+// planar RGB surfaces and planar and interleaved float tensors converted on the way in, each at the encoder's size, at half / quarter / eighth size or
 // at any larger size.  The records are io_jobs.h's, planned per picture by enc_ingest.h; what a thread does is in the body headers
 // ingest_*.h, which the check programs under tools/ run on the CPU.  (The packed and the UYVY pictures of the host path enter
 // through frame.hip.)
@@ -10,6 +10,7 @@
 #include "ingest_rgb.h"
 #include "ingest_rgb3.h"
 #include "ingest_tensor.h"
+#include "ingest_hwc.h"
 #include "ingest_scale.h"
 #include "ingest_resize.h"
 #include "prio.h"
@@ -177,6 +178,30 @@ void ingest_tensor_batch(hipStream_t s, const TensorInJob *d_jobs, int n, int h,
     }
     const dim3 grid((h + kSurfaceRows - 1) / kSurfaceRows, n), block(64, 4);
     DSV2_LAUNCH_FORM(wide, k_ingest_tensor<true>, k_ingest_tensor<false>, grid, block, 0, s, d_jobs);
+}
+
+// ---- interleaved RGB float tensors (dsv2hip_in_hwc: [h, w, 3] of binary16, bfloat16, binary32; R G B or B G R) --------------------
+// One HwcInJob per picture, fetched by value and pinned to scalar registers as above -- the six constants too; the thread's work is
+// ingest_hwc.h's ingest_hwc_rows (which tools/ingest_hwc_check.cpp runs on the CPU), k_ingest_rgb3's decomposition with another
+// fetch.  Element type and order are data of the job; a launch may hold jobs of all of them.
+template <bool WIDE> __global__ __launch_bounds__(256) void k_ingest_hwc(const HwcInJob *__restrict__ tab)
+{
+    DSV2_KERNEL_PRIO();
+    const HwcInJob j = pin(job_of(tab, blockIdx.y));
+    const int y0 = ((int) blockIdx.x * 4 + uni((int) threadIdx.y)) * 4;
+    if (y0 >= j.h) {
+        return;
+    }
+    ingest_hwc_rows<WIDE>(j, y0, (int) threadIdx.x * 4, 64 * 4);
+}
+
+void ingest_hwc_batch(hipStream_t s, const HwcInJob *d_jobs, int n, int h, bool wide)
+{
+    if (n <= 0) {
+        return;
+    }
+    const dim3 grid((h + kSurfaceRows - 1) / kSurfaceRows, n), block(64, 4);
+    DSV2_LAUNCH_FORM(wide, k_ingest_hwc<true>, k_ingest_hwc<false>, grid, block, 0, s, d_jobs);
 }
 
 // ---- half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled) ---------------------------------------------------

@@ -130,6 +130,25 @@ inline bool tensor_in_job_wide(const TensorInJob &j)
     }
     return (bits & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
 }
+struct HwcInJob { // one picture that is a caller's interleaved [h, w, 3] float tensor (dsv2hip_in_hwc: binary16, bfloat16 or binary32 elements,
+                  // R G B or B G R) on its way into the three bordered source planes: element k of a pixel taken through the job's
+                  // scale[k] and bias[k], clamped and rounded to byte k of the pixel's dword, then converted as a three-byte surface is
+                  // (ingest_hwc.h, ingest.hip: k_ingest_hwc); 120 bytes.  It shares Rgb3Job's destination side.  (A uint8 one is an Rgb3Job.)
+    const uint8_t *src;    // device memory, element aligned: pixel x of row y at src + y * pitch + 3 * x * elem, 3 * w elements of a row read
+    size_t pitch;          // bytes, a multiple of the element size
+    uint8_t *dst[3];       // Y, U, V planes from dframe_alloc
+    int ystride, cstride;  // RgbJob's, as w, h, hs, vs and the quads
+    int w, h;
+    int hs, vs;
+    int dtype;             // kTensorF16, kTensorBF16, kTensorF32
+    RgbInCoefs csc;        // the packed kind's: memory order is byte order, so B G R and R G B differ only in these quads
+    float scale[3], bias[3]; // of element k of every pixel, in memory order: TensorInJob's formula with k for c
+};
+// pointer and pitch multiples of four elements and w of 4: a thread's twelve elements of a row arrive as three vector loads
+inline bool hwc_in_job_wide(const HwcInJob &j)
+{
+    return ((((uintptr_t) j.src) | (uintptr_t) j.pitch) & (uintptr_t) (4 * tensor_elem(j.dtype) - 1)) == 0 && (j.w & 3) == 0;
+}
 struct ScaleOutJob { // one plane of a decoded picture on its way out at half, quarter or eighth size (dsv2hip_out_surface, DSV2HIP_SCALE_*): the box
                      // average of include/dsv2_hip.h (egress_scale.h, egress.hip: k_egress_scale) into a plane of the caller's surface, or into the
                      // decoder's staging picture that k_egress_uv / k_egress_rgb then read; 40 bytes
@@ -212,6 +231,9 @@ inline bool rgb3_job_wide(const Rgb3Job &j)
 // n float tensors of h rows (TensorInJob above; the element types may differ from job to job); wide: every job's plane pointers and
 // pitches are multiples of four elements and w of 4 (tensor_in_job_wide)
 void ingest_tensor_batch(hipStream_t s, const TensorInJob *d_jobs, int n, int h, bool wide);
+// n interleaved float tensors of h rows (HwcInJob above; element types and orders may differ from job to job); wide: every job's
+// pointer and pitch are multiples of four elements and w of 4 (hwc_in_job_wide)
+void ingest_hwc_batch(hipStream_t s, const HwcInJob *d_jobs, int n, int h, bool wide);
 // Half, quarter and eighth-size ingest (dsv2hip_enc_batch_surface_scaled): the records of k_ingest_surface_scaled and
 // k_ingest_rgb_scaled (ingest.hip, ingest_scale.h), in tables of their own behind the two above.
 struct ScaledSurfaceJob { // one SOURCE plane of a caller's surface, box-averaged (the decoder's REDUCTION, include/dsv2_hip.h) on its way into a
@@ -306,6 +328,7 @@ DSV2_IO_RECORD(SurfaceJob, 48);
 DSV2_IO_RECORD(RgbJob, 88);
 DSV2_IO_RECORD(Rgb3Job, 128);
 DSV2_IO_RECORD(TensorInJob, 152);
+DSV2_IO_RECORD(HwcInJob, 120);
 DSV2_IO_RECORD(ScaledSurfaceJob, 48);
 DSV2_IO_RECORD(ScaledRgbJob, 96);
 DSV2_IO_RECORD(SizedSurfaceJob, 64);
@@ -316,9 +339,10 @@ DSV2_IO_RECORD(RgbOutJob, 144);
 DSV2_IO_RECORD(ScaleOutJob, 40);
 DSV2_IO_RECORD(ResizeOutJob, 72);
 #undef DSV2_IO_RECORD
-static_assert(offsetof(RgbJob, csc) == 64 && offsetof(Rgb3Job, csc) == 100 && offsetof(TensorInJob, csc) == 100 && offsetof(ScaledRgbJob, csc) == 68 &&
+static_assert(offsetof(RgbJob, csc) == 64 && offsetof(Rgb3Job, csc) == 100 && offsetof(TensorInJob, csc) == 100 && offsetof(HwcInJob, csc) == 68 &&
+                  offsetof(ScaledRgbJob, csc) == 68 &&
                   offsetof(SizedRgbJob, csc) == 112,
-              "the ingest quads stay where the six words were");
+              "the ingest quads stay where the six words were (HwcInJob: new with DESIGN 5.26)");
 static_assert(offsetof(RgbOutJob, layout) + 4 == offsetof(RgbOutJob, dst) && offsetof(RgbOutJob, dtype) == 116,
               "what every layout reads first, the tensors' words behind it");
 

@@ -922,7 +922,7 @@ void dsv2hip_dec_tensor_stats(unsigned long long *out2, int reset);
  * MEMORY: as an RGB surface's -- a drawn-on or sharpened picture stages its luma, a sized one its resampled planes.
  * Out of scope: a fourth channel (the BGRA / RGBA surfaces are that); the DSV2HIP_SCALE_* presets (a size covers them where it
  * divides); interleaved tensors together with surfaces or planar tensors in one call; enlargement; out420p; host memory; any change to
- * what the surface or planar-tensor calls accept; the encoder's float interleaved input.
+ * what the surface or planar-tensor calls accept.  (The way back in: INTERLEAVED RGB FLOAT TENSORS AS ENCODER INPUT below.)
  * dsv2hip_dec_hwc_stats: out2[0] / out2[1] = device rounds of this process whose interleaved conversion ran in the wide form (data and
  * pitch of every interleaved tensor of the round multiples of four elements and the delivered width a multiple of 4 -- any contiguous
  * torch [h, w, 3] or channels_last [1, 3, h, w] tensor with w % 4 == 0: a thread's twelve elements of a row leave as whole vector
@@ -979,7 +979,7 @@ void dsv2hip_dec_hwc_stats(unsigned long long *out2, int reset);
  * RGB layout (an encoder with dsv2hip_enc_set_uyvy_input on, a stream format outside the five, encoders of different step keys ...);
  * an unknown dtype; a csc bit outside the two; a NULL plane; a plane pointer or a pitch that is not a multiple of the element size; a
  * pitch below w * elem; a scale[c] or bias[c] that is not finite (float dtypes only).
- * Out of scope: interleaved [h, w, 3] float tensors; the scaled and the sized route (they remain the surface calls' own, as for
+ * Out of scope: interleaved [h, w, 3] float tensors (they have the calls of INTERLEAVED RGB FLOAT TENSORS AS ENCODER INPUT below); the scaled and the sized route (they remain the surface calls' own, as for
  * three-byte and planar RGB); tensors and surfaces in one call; 10-bit; host memory; any change to what the surface calls accept.
  * dsv2hip_enc_tensor_stats: out2[0] / out2[1] = lockstep steps of this process whose float tensor ingest ran in the wide form (every
  * plane pointer and pitch of every float tensor of the step a multiple of four elements and w a multiple of 4 -- any contiguous torch
@@ -995,6 +995,60 @@ typedef struct dsv2hip_in_tensor {
 int  dsv2hip_enc_batch_tensor(int n, DSV_ENCODER **encs, const dsv2hip_in_tensor *t, DSV_BUF *bufs, int *nbufs);
 int  dsv2hip_enc_tensor_frame(DSV_ENCODER *enc, const dsv2hip_in_tensor *t, DSV_BUF *bufs);
 void dsv2hip_enc_tensor_stats(unsigned long long *out2, int reset);   /* steps in the wide / in the general form */
+/* INTERLEAVED RGB FLOAT TENSORS AS ENCODER INPUT, f16 / bf16 / f32 -- a torch channels_last model output, a float NHWC picture from JAX
+ * or TF, a renderer's RGB float framebuffer, an OpenCV GpuMat of CV_32FC3 / CV_16FC3, the decoder's own INTERLEAVED RGB TENSORS after a
+ * model has touched them.  The encoder reads it in place: no permute(2, 0, 1).contiguous() of the caller's in front of the planar
+ * tensor call, which is a second pass as large as the ingest.  The counterpart of dsv2hip_dec_batch_hwc; the vocabulary is
+ * dsv2hip_out_hwc's, the element types are the tensors' enum.
+ * A contiguous torch [h, w, 3] tensor is data = data_ptr, pitch = 3 * w * elem (elem = 2, 2, 4).  A channels_last [n, 3, h, w] tensor
+ * is [n, h, w, 3] in memory: n descriptors, data = data_ptr + i * h * w * 3 * elem, pitch = 3 * w * elem.  An OpenCV GpuMat of
+ * CV_32FC3 / CV_16FC3 is data = mat.data, pitch = mat.step, order DSV2HIP_SURFACE_BGR.  A crop is data at its first pixel under the
+ * parent's pitch.
+ * Semantics are those of dsv2hip_enc_batch_tensor / dsv2hip_enc_tensor_frame: 4 buffer slots per stream, their return values, t[k]
+ * copied by value.  The tensor is only read, and only inside its rows -- the 3 * w elements of each of the h rows; no byte of padding,
+ * no byte behind the last row; it is never written.  The picture has the encoder's size.  One step may mix element types, orders,
+ * presets, constants and tensor geometries; a refused call touches nothing: no encoder, buffer, nbufs or tensor.
+ * THE CONTRACT.  Element k (k = 0, 1, 2 in memory order) of pixel (x, y), widened EXACTLY to binary32, gives
+ *
+ *   g = fl32( fl32( e * scale[k] ) + bias[k] )
+ *   v = 0                              where g is a NaN
+ *       rint( min( max(g, 0), 255 ) )  else, ties to even, as a byte
+ *
+ * which is THE CONTRACT of the planar tensor word for word -- two binary32 operations, NOT fused, nothing flushed to zero -- with
+ * constants that belong to MEMORY POSITIONS as dsv2hip_out_hwc's do: under DSV2HIP_SURFACE_BGR scale[0] / bias[0] are blue's.  The
+ * packets are exactly those of dsv2hip_enc_batch_surface on a DSV2HIP_SURFACE_RGB | csc or DSV2HIP_SURFACE_BGR | csc surface that
+ * holds the bytes v at the same positions; equivalently those of dsv2hip_enc_batch_tensor on the de-interleaved planes, with the
+ * constants permuted by the order.
+ * The inverse of the decoder's constants is scale'[k] = 1 / scale[k], bias'[k] = -bias[k] / scale[k] position by position; a BGR
+ * consumer of torchvision's Normalize(mean, std) passes 255 * std and 255 * mean in B, G, R order.  ROUND TRIP: an element delivered by
+ * dsv2hip_dec_batch_hwc under scale = 1 / 255, bias = 0 or under the ImageNet constants, in either order, comes back as the byte it
+ * was made from under these inverse constants, for F32, F16 and BF16 alike -- checked for all 256 bytes at every position
+ * (tests/test_ingest_hwc_cpu.py).  A checked fact about these constants, NOT a theorem, as for the planar tensor.
+ * DSV2HIP_TENSOR_U8 is accepted and IS the three-byte surface: the same record and kernel as order | csc through
+ * dsv2hip_enc_batch_surface, scale and bias ignored (they may hold anything); it counts in dsv2hip_enc_rgb3_stats, not in
+ * dsv2hip_enc_hwc_stats.
+ * Refused as a whole (the batch call returns -1, the one-frame call 0 packets): everything dsv2hip_enc_batch_tensor refuses for an
+ * RGB layout (UYVY input on, a stream format outside the five, encoders of different step keys ...); an unknown dtype; an order that
+ * is not exactly DSV2HIP_SURFACE_RGB or DSV2HIP_SURFACE_BGR (0x22, the four-byte layouts and CSC bits in `order` included); a csc bit
+ * outside the two; a NULL data; data or pitch not a multiple of the element size; pitch / elem < 3 * w; a scale[k] or bias[k] that is
+ * not finite (float dtypes only).
+ * Out of scope: the scaled and the sized route; interleaved tensors together with surfaces or planar tensors in one call; a fourth
+ * channel (the BGRA / RGBA surfaces are that); 10-bit; host memory; any change to what the other calls accept.
+ * dsv2hip_enc_hwc_stats: out2[0] / out2[1] = lockstep steps of this process whose interleaved float ingest ran in the wide form (data
+ * and pitch of every such tensor of the step multiples of four elements and w a multiple of 4 -- any contiguous torch [h, w, 3] or
+ * channels_last tensor with w % 4 == 0: a thread's twelve elements of a row arrive as three 8 / 16-byte loads) / in the general form
+ * so far; reset != 0 clears the counts afterwards. */
+typedef struct dsv2hip_in_hwc {
+    const void *data;   /* device memory: pixel (x, y) at data + y * pitch + 3 * x * elem */
+    size_t pitch;       /* bytes from one row to the next */
+    int    dtype;       /* DSV2HIP_TENSOR_* */
+    int    order;       /* DSV2HIP_SURFACE_RGB: elements R G B;  DSV2HIP_SURFACE_BGR: B G R */
+    int    csc;         /* any subset of DSV2HIP_CSC_BT709 | DSV2HIP_CSC_FULL_RANGE */
+    float  scale[3], bias[3];  /* for ELEMENT k of every pixel, in memory order; ignored for U8 */
+} dsv2hip_in_hwc;
+int  dsv2hip_enc_batch_hwc(int n, DSV_ENCODER **encs, const dsv2hip_in_hwc *t, DSV_BUF *bufs, int *nbufs);
+int  dsv2hip_enc_hwc_frame(DSV_ENCODER *enc, const dsv2hip_in_hwc *t, DSV_BUF *bufs);
+void dsv2hip_enc_hwc_stats(unsigned long long *out2, int reset);      /* steps in the wide / in the general form */
 /* -postsharp of the reference CLI (dsv_main.c:1058-1060, :1084-1089) inside the decoder: the luma of every picture handed out from
  * now on -- by dsv_dec, dsv2hip_dec_batch and the device deliveries alike -- has dsv_post_process (bmc.c:340) applied, last: behind
  * the 4:2:0 conversion and the draw_info overlay, as the CLI gets it by calling it on the frame dsv_dec returned.  Chroma and the
