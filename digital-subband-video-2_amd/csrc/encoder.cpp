@@ -55,7 +55,14 @@ struct EncImpl {
     size_t h_pack_bytes = 0;
     std::vector<uint8_t> big_bytes;   // plane sections of a picture too large for the pinned mirror of the GPU entropy coder
     bool input_uyvy = false;          // packed pictures arrive as interleaved UYVY rows (de-interleaved by the ingest kernel)
+    // dsv2hip_seam_set_field (tests): a field and the search's four sums that replace the next searched picture's own
+    std::vector<DSV_MV> seam_field;
+    int seam_ints[4] = {0, 0, 0, 0};
+    bool seam_pending = false;
 };
+
+// P pictures for which k_side_info itself set info[0] (dsv2hip_enc_side_flag_count)
+std::atomic<long> g_side_flags;
 
 inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 inline int sar(int v, int s) { return v < 0 ? ~(~v >> s) : v >> s; }
@@ -1222,6 +1229,12 @@ void phase_h1a(Job &jb)
             jb.failed = dv.h_counters[7] == 1 ? 1 : 2;
             return;
         }
+        if (im->seam_pending) { // (the device counters and the field were replaced behind the search: search_under_token)
+            if (im->seam_field.size() == nb) {
+                memcpy(dv.h_counters, im->seam_ints, sizeof(im->seam_ints));
+            }
+            im->seam_pending = false;
+        }
         int nintra = dv.h_counters[0], ndiff = dv.h_counters[1], eligible = dv.h_counters[2]; // hme.c:1825-1832, 2015
         unsigned total_err = (unsigned) dv.h_counters[3];
         enc->curr_scblocks = ndiff * 100 / (eligible ? eligible : 1);
@@ -1313,6 +1326,9 @@ void phase_h1b(Job &jb)
     bs.put_bit(0);
     bs.align();
     static const bool side_fallback = env_int("DSV2_SIDE_FORCE_FALLBACK", 0) != 0; // (tests)
+    if (isP && jb.side_out && jb.side_info[0] != 0) {
+        g_side_flags++;
+    }
     if (isP && jb.side_out && jb.side_info[0] == 0 && !side_fallback) {
         // the six sub-streams arrive coded (k_side_info); what stays here of encode_stable_blocks (dsv_encoder.c:797) is the
         // stability accumulator of the temporal AQ, which the next intra picture reads on the host
@@ -2001,6 +2017,16 @@ static void search_under_token(Step &st)
         st.prof.begin(bs, ST_HME);
         int nfronts = hme_run_batch(bs, st.hf.data(), st.hp.data(), nsearch, sc.h_hme, sc.d_hme, &st.prof, HME_LEVELS);
         st.prof.end(bs, ST_HME, nsearch, nfronts); // launches = the per-level search kernels
+        for (int q = 0; q < nsearch; q++) { // dsv2hip_seam_set_field: a queued field and its four sums over the search's
+            EncImpl *im = st.jobs[st.searched[q]].im;
+            if (im->seam_pending && im->seam_field.size() == im->dev.nblocks()) {
+                HIPCHK(hipMemcpyAsync(im->dev.d_mvf[0], im->seam_field.data(), im->seam_field.size() * sizeof(DSV_MV), hipMemcpyHostToDevice, bs));
+                HIPCHK(hipMemcpyAsync(im->dev.d_counters, im->seam_ints, sizeof(im->seam_ints), hipMemcpyHostToDevice, bs));
+            } else if (im->seam_pending) { // queued before the encoder knew its geometry: said aloud, not passed over
+                fprintf(stderr, "dsv2hip_seam_set_field: a field of %zu blocks was queued, the encoder has %zu: dropped, the search's own field is used\n",
+                        im->seam_field.size(), im->dev.nblocks());
+            }
+        }
         HIPCHK(hipMemsetAsync(sc.d_bstats, 0, (size_t) st.n_bsj * BS_WORDS * sizeof(int), bs));
         block_stats_batch(bs, st.bsj.d, st.n_bsj, st.nbh, st.nbv);
         HIPCHK(hipMemcpyAsync(sc.h_bstats, sc.d_bstats, (size_t) st.n_bsj * BS_WORDS * sizeof(int), hipMemcpyDeviceToHost, bs));
@@ -2680,7 +2706,31 @@ long dsv2hip_enc_ent_flag_count(int flag)
     }
     return -1;
 }
+long dsv2hip_enc_side_flag_count(void) { return g_side_flags.load(); }
 long dsv2hip_arena_fallbacks(void) { return dsv2::arena_fallbacks(); }
+
+int dsv2hip_seam_set_field(DSV_ENCODER *enc, const DSV_MV *field, int nblocks, int nintra, int ndiff, int eligible, unsigned total_err)
+{
+    if (!enc || nblocks < 0 || (field && nblocks == 0)) {
+        return -1;
+    }
+    if (!enc->ref) {
+        enc->ref = new EncImpl();
+    }
+    EncImpl *im = (EncImpl *) enc->ref;
+    if (field && im->ready && (size_t) nblocks != im->dev.nblocks()) {
+        return -1;
+    }
+    im->seam_pending = field != nullptr;
+    if (field) {
+        im->seam_field.assign(field, field + nblocks);
+        im->seam_ints[0] = nintra;
+        im->seam_ints[1] = ndiff;
+        im->seam_ints[2] = eligible;
+        im->seam_ints[3] = (int) total_err;
+    }
+    return 0;
+}
 
 void dsv2hip_enc_queue_stats(unsigned long long *out4, int reset)
 {

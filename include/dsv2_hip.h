@@ -1090,6 +1090,20 @@ long dsv2hip_enc_ent_flag_count(int flag);
  * where a damaged section makes the parse run on further than that, the device parser reads zeros where the other two read the
  * caller's bytes.) */
 int dsv2hip_seam_set_gpu_entropy(int on);
+/* Test seam behind the motion search: queues `field` (nblocks = nblocks_h * nblocks_v records, copied) for the NEXT picture of
+ * `enc` that is searched.  The search still runs; behind it, and before the controller's sums are taken (k_block_stats_b), the
+ * field replaces the level-0 field in device memory and nintra / ndiff / eligible / total_err replace the search's own four sums
+ * (intra_pct = nintra * 100 / nb, scblocks = ndiff * 100 / max(eligible, 1), avg_err = total_err / nb: hme.c:1825-1832, :2015) on
+ * the device and on the host.  Everything behind that -- scene-change test, rate control, votes, side information, prediction --
+ * is the production path on that field.  A legal record is one the reference's dsv_hme can store (tests/field_cases.py).
+ * field == NULL drops a queued field.  0 on success, -1 for a NULL encoder or a block count that is not the encoder's.  An encoder
+ * that has not coded a picture yet does not know its block count: a field queued then is taken as it is, and one of the wrong size
+ * is dropped at the next searched picture with a line on stderr -- that picture is coded from the search's own field. */
+int dsv2hip_seam_set_field(DSV_ENCODER *enc, const DSV_MV *field, int nblocks, int nintra, int ndiff, int eligible, unsigned total_err);
+/* The side-information coder (csrc/sideinfo.hip) hands a P picture to the host coders when a sub-stream outgrows its image or a
+ * code the 15-pair form of the exp-Golomb code; the packets are the same.  Number of P pictures of this process for which the
+ * kernel ITSELF decided so; the tests' forced fall-back (DSV2_SIDE_FORCE_FALLBACK) is not counted. */
+long dsv2hip_enc_side_flag_count(void);
 /* Device allocations that did not fit their instance's one-block arena (the block's size is an estimate): 0 unless the estimate has
  * drifted from the allocations it stands for. */
 long dsv2hip_arena_fallbacks(void);

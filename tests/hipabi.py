@@ -57,6 +57,8 @@ def _prototypes():
         "dsv2hip_enc_list_growths": (None, C.c_long),
         "dsv2hip_enc_ent_flag_count": ([i], C.c_long),
         "dsv2hip_seam_set_gpu_entropy": ([i], i),
+        "dsv2hip_seam_set_field": ([ENC, vp, i, i, i, i, C.c_uint], i),
+        "dsv2hip_enc_side_flag_count": ([], C.c_long),
         "dsv2hip_host_alloc": ([sz], vp),
         "dsv2hip_host_free": ([vp],),
         # decoder

@@ -427,18 +427,25 @@ class _Bits:
         return n
 
 
-def motion_substream_lengths(packet):
-    """(blk_w, blk_h, [bytes of the mode, x, y, sub-block-mask and EPRM sub-streams]) of a P picture packet, read as the
-    reference's decoder reads it (dsv_decoder.c: the picture header, the stability section, decode_motion)"""
+def side_substream_lengths(packet):
+    """(blk_w, blk_h, (stable, mode, EPRM inversion bits), [bytes of the stability, mode, x, y, sub-block-mask and EPRM
+    sub-streams]) of a P picture packet, read as the reference's decoder reads it (dsv_decoder.c: the picture header, the
+    stability section, decode_motion)"""
     assert packet[5] & 4 and packet[5] & 1, "no P picture"
     bs = _Bits(packet, 14)  # DSV_PACKET_HDR_SIZE
     bs.bits(32)             # frame number
     bs.align()
     bw, bh = 16 << bs.ueg(), 16 << bs.ueg()
     bs.align()
-    bs.bits(3 + 1 + 12)     # three statistics bits, the filter flag, the quantiser
+    inv = (bs.bit(), bs.bit(), bs.bit())  # the three statistics bits
+    bs.bits(1 + 12)         # the filter flag, the quantiser
     if bs.bit():
         bs.bits(15)
     bs.align()
-    bs.section()            # stability blocks
-    return bw, bh, [bs.section() for _ in range(5)]
+    return bw, bh, inv, [bs.section() for _ in range(6)]
+
+
+def motion_substream_lengths(packet):
+    """(blk_w, blk_h, [bytes of the mode, x, y, sub-block-mask and EPRM sub-streams]) of a P picture packet"""
+    bw, bh, _, lengths = side_substream_lengths(packet)
+    return bw, bh, lengths[1:]

@@ -16,7 +16,7 @@ import long_motion as L
 import mixed_steps as M
 from codec_run import encode_stream
 from hme_common import assert_fields_equal
-from hipabi import PARSE_IDS, parse_mode
+from hipabi import PARSE_IDS, bind, parse_mode
 from test_oracle_bmc import clone
 
 pytestmark = [pytest.mark.gpu]  # (a GPU box without oracle/_ref FAILS these tests: conftest.py)
@@ -163,5 +163,8 @@ def test_side_information_overflows_on_its_own():
     so k_side_info itself raises the flag that hands the picture to the host -- no DSV2_SIDE_FORCE_FALLBACK"""
     assert "DSV2_SIDE_FORCE_FALLBACK" not in os.environ
     want = L.reference_jitter_stream()
-    pk, stats = encode_stream(A.load_hip(), list(L.jitter_frames()), L.SIDE_W, L.SIDE_H, A.SUBSAMP_420, eos=False, **L.SIDE_CFG)
+    hip = bind(A.load_hip())
+    before = hip.dsv2hip_enc_side_flag_count()
+    pk, stats = encode_stream(hip, list(L.jitter_frames()), L.SIDE_W, L.SIDE_H, A.SUBSAMP_420, eos=False, **L.SIDE_CFG)
     M.assert_same([want], ([pk], [stats]), "jitter")
+    assert hip.dsv2hip_enc_side_flag_count() - before == L.SIDE_FRAMES - 1  # every P picture, by the kernel's own verdict
